@@ -2,7 +2,7 @@
 """Headline benchmark of the DINOSeg hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks 12] [--batch 32] [--res 480]
-                    [--precision fp16|bf16|bf16x3] [--no-cpu-baseline] [--dry-run]
+                    [--precision fp16|bf16|bf16x3] [--no-cpu-baseline] [--dry-run] [--dump-outputs DIR]
                     [--config headline|parity|960|vitb|finetune]     (the other BASELINE.json configs, one JSON line each)
 
 Metric (BASELINE.json): frames/sec of DINOSeg inference -- ViT-S/8 (12 blocks) + MLP head, 480x480 frames,
@@ -26,6 +26,8 @@ The JSON line also carries
   configs      : BASELINE.json configs [2] (@960 batch 8), [4] (ViT-B/8, batch 16 per GPU) and [3] (3-block fine-tune step, batch 8 per GPU)
                  as compact records (value, ms_per_step, dominant-kernel roofline, parity / gradient_parity), each measured by a child
                  `python bench.py --config ...` after the headline (N=1 only; --no-configs skips them).
+  dump_outputs : with --dump-outputs DIR, where the last timed step's outputs went (dump_outputs(): log-probs and argmax map;
+                 --mode finetune: the loss and the updated parameters), for comparing two builds output for output.
   cpu_baseline : the oracle (oracle/dinoseg_oracle.py = CPU fp32 restatement of the reference path, kind "port")
                  timed on this box's host cores on a bounded sample of the same workload (rank 0, N=1 only); --mode finetune:
                  the oracle's forward + loss + autograd backward of one frame.
@@ -205,6 +207,38 @@ def golden_grad_check(precision, dev):
             "worst_norm_ratio_error": float(f"{worst_norm:.3e}"), "worst_sampled_relative_error": float(f"{worst_rel:.3e}"), "tensors": 48}
 
 
+DUMP_BYTES = 64 << 20       # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: what the timed path's last step returned, as out_dir/<name>.npy (float64 for 0-d / scalar results, float32
+    otherwise).  Past DUMP_BYTES in all, every array is cut to the same fixed, seeded sample of its flattened entries (sorted indices;
+    the indices go to <name>.index.npy), so two builds of the project still compare entry for entry.  Returns the record for the
+    JSON line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        host[name] = x.astype(np.float64) if x.ndim == 0 or x.size == 1 else x.astype(np.float32)
+    frac = 1.0
+    if sum(x.nbytes for x in host.values()) > DUMP_BYTES:
+        # a sampled entry costs its value and its float64 index
+        frac = 0.99 * DUMP_BYTES / sum(x.size * (x.itemsize + 8) for x in host.values())
+    rec = {"dir": os.path.abspath(out_dir), "sampled": frac < 1.0, "arrays": {}}
+    for name, x in host.items():
+        shape = list(x.shape)
+        if frac < 1.0 and x.size > 1:
+            flat = x.reshape(-1)
+            k = max(1, int(flat.size * frac))
+            idx = np.sort(np.random.default_rng(seed).choice(flat.size, size=k, replace=False))
+            x = flat[idx]
+            np.save(os.path.join(out_dir, f"{name}.index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), x)
+        rec["arrays"][name] = {"shape": shape, "dtype": str(x.dtype), "saved": int(x.size)}
+    return rec
+
+
 def bench_finetune(a, world, rank, dev, rehearsal=False):
     """Fine-tune step throughput: ViT-S/8 truncated to 3 blocks + MLP head, all 48 tensors trainable, Adam lr 1e-3
     (run_experiment.py:135-136), 480x480 frames, batch 8 per GPU (global 64 at 8 GPUs), bf16 operands unless
@@ -241,6 +275,13 @@ def bench_finetune(a, world, rank, dev, rehearsal=False):
         dist.barrier()
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # what the caller of the step gets: the loss, and the parameters the step updated in place (taken before the profile pass
+        # below steps them again)
+        res = {"loss": loss}
+        res.update({f"param.{k}": p for k, p in model.named_parameters()})
+        dumped = dump_outputs(a.dump_outputs, res)
     cdev = torch.device("cpu") if rehearsal else dev
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -290,6 +331,7 @@ def bench_finetune(a, world, rank, dev, rehearsal=False):
             "model_mfma_frac": round(fps / world * 3 * fl["total"] / 1e12 / MFMA_PEAK_TFLOPS[a.precision], 4),
             "roofline": roof, "gradient_parity": grad_parity,
             "cpu_baseline": cpu_baseline_finetune(cfg, sd, a.res) if world == 1 and not rehearsal and not a.no_cpu_baseline else None,
+            **({"dump_outputs": dumped} if dumped is not None else {}),
         }), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -323,9 +365,14 @@ def parse_args(argv=None):
                     help="0 = the library default (2: a batch of >= 8 frames runs as two half-batches on two streams); 1 / 2 force it")
     ap.add_argument("--collective", default="allreduce", choices=["allreduce", "rs_ag"],
                     help="--mode finetune: one all-reduce per gradient bucket, or reduce-scatter + all-gather (dino_amd/parallel.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed, seeded sample beyond that); inputs are the same from run to run")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous check only: no model, no GPU (gloo); prints the JSON line with value 0")
     a = ap.parse_args(argv)
+    if a.steps < 1 and not a.dry_run:
+        ap.error("--steps must be at least 1")
     if a.config == "parity":
         a.precision = a.precision or "fp16x3"
     elif a.config == "960":
@@ -540,6 +587,8 @@ def main():
     torch.cuda.synchronize()
     elapsed, (logp, amax) = timed(a.steps)
     seen = ranks_seen(dist, world, dev if not rehearsal else torch.device("cpu"))
+    # (forward_frames returns fresh tensors: the later passes do not touch the last timed step's outputs)
+    dumped = dump_outputs(a.dump_outputs, {"logp": logp, "argmax": amax}) if a.dump_outputs and rank == 0 else None
 
     # per-kernel timing (HIP events on the forward's stream, recorded by the library) in a SEPARATE untimed pass right after
     # the timed one, on ONE stream: with two half-batches sharing the chip a launch's duration is not the kernel's own, and the
@@ -663,6 +712,8 @@ def main():
         }
         if one_stream is not None:
             out["one_stream"] = one_stream
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         out["parity"] = parity      # the timed precision / dispatch against the reference fixture (computed before the timed loop)
         def sub_mode(prec):
             """the same configuration in another precision: its own short timing (library defaults) and its parity record"""
