@@ -107,6 +107,7 @@ SIGNATURES = {
     "dinoseg_op_pos_resample": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _vp]),
     "dinoseg_op_patch_gather": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
     "dinoseg_op_head_final": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _fp, _fp, _i32, _fp, _fp, _vp]),
+    "dinoseg_op_head_wide": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _fp, _i32, _fp, _fp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -88,7 +88,7 @@ extern "C" int dinoseg_create(const dinoseg_config* cfg, dinoseg_handle** out) {
         return -1;
     }
     if (cfg->embed_dim % 128 != 0 || cfg->embed_dim > 1024 || cfg->num_heads * 64 != cfg->embed_dim || cfg->patch != 8 ||
-        cfg->n_blocks < 0 || cfg->n_classes < 1 || cfg->n_classes > 32 || cfg->mlp_ratio < 1 || cfg->pos_grid < 1 ||
+        cfg->n_blocks < 0 || cfg->n_classes < 1 || cfg->n_classes > HEAD_WIDE_MAX_C || cfg->mlp_ratio < 1 || cfg->pos_grid < 1 ||
         (cfg->precision != DINOSEG_BF16 && cfg->precision != DINOSEG_BF16X3 && cfg->precision != DINOSEG_FP16 &&
          cfg->precision != DINOSEG_FP16X3) ||
         (cfg->head_kind != DINOSEG_HEAD_MLP && cfg->head_kind != DINOSEG_HEAD_LINEAR)) {
@@ -242,6 +242,12 @@ static std::vector<LinSpec> linear_specs(const dinoseg_handle* h) {
     if (c.head_kind == DINOSEG_HEAD_MLP) {
         v.push_back({"clf.layer_1.weight", "clf.layer_1.bias", 200, D, 256, D, head_planes(), split_fmt(h)});
         v.push_back({"clf.layer_2.weight", "clf.layer_2.bias", 100, 200, 128, 256, head_planes(), split_fmt(h)});
+    }
+    // more than 32 classes: the classifier as hi+lo planes [round_up(C, 32)][ld] for the wide kernel (head_wide.hip)
+    if (c.n_classes > HEAD_FINAL_MAX_C) {
+        const bool mlp = c.head_kind == DINOSEG_HEAD_MLP;
+        v.push_back({mlp ? "clf.layer_3.weight" : "clf.layer_1.weight", mlp ? "clf.layer_3.bias" : "clf.layer_1.bias", c.n_classes,
+                     mlp ? 100 : D, (c.n_classes + 31) / 32 * 32, mlp ? 128 : D, head_planes(), split_fmt(h)});
     }
     return v;
 }
@@ -458,7 +464,10 @@ static WsLayout make_layout(const dinoseg_handle* h, int B, int r) {
     L.ctx_plane = (long)L.M * D;
     L.CTX = take((size_t)P * L.ctx_plane * 2);
     L.hb_plane = (long)L.M * F;
-    L.HB = take((size_t)P * L.hb_plane * 2);
+    {   // HB also hosts the log-probabilities when the caller asks for the argmax only (dinoseg_forward with logp_out == nullptr)
+        const size_t hb_bytes = (size_t)P * L.hb_plane * 2, lp_bytes = (size_t)L.Mp * c.n_classes * 4;
+        L.HB = take(hb_bytes > lp_bytes ? hb_bytes : lp_bytes);
+    }
     L.feat_plane = (long)L.Mp * D;
     L.FEAT = take((size_t)HP * L.feat_plane * 2);
     L.h1_plane = (long)L.Mp * 256;
@@ -873,10 +882,12 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
             DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_gemm(g, s)));
         }
         DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_head_final(H2, L.h2_plane, 128, L.Mp, 100, W(h, "clf.layer_3.weight"), W(h, "clf.layer_3.bias"),
-                                   c.n_classes, logp_out ? logp_out : reinterpret_cast<float*>(ws + L.HB), argmax_out, s, SF)));
+                                   c.n_classes, logp_out ? logp_out : reinterpret_cast<float*>(ws + L.HB), argmax_out, s, SF,
+                                   wide_clf(h).w, wide_clf(h).plane)));
     } else {
         DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_head_final(FEAT, L.feat_plane, D, L.Mp, D, W(h, "clf.layer_1.weight"), W(h, "clf.layer_1.bias"),
-                                   c.n_classes, logp_out ? logp_out : reinterpret_cast<float*>(ws + L.HB), argmax_out, s, SF)));
+                                   c.n_classes, logp_out ? logp_out : reinterpret_cast<float*>(ws + L.HB), argmax_out, s, SF,
+                                   wide_clf(h).w, wide_clf(h).plane)));
     }
     return 0;
 }
@@ -1443,4 +1454,10 @@ extern "C" int dinoseg_op_head_final(const void* in, int64_t in_plane, int32_t l
                                      const float* b, int32_t C, float* logp, int32_t* argmax, void* stream) {
     return launch_head_final(reinterpret_cast<const bf16_t*>(in), in_plane, ld, M, K, Wc, b, C, logp, argmax,
                              reinterpret_cast<hipStream_t>(stream), options().op_fmt);
+}
+
+extern "C" int dinoseg_op_head_wide(const void* in, int64_t in_plane, int32_t ld, int32_t M, int32_t K, const void* Wp, int64_t w_plane,
+                                    const float* b, int32_t C, float* logp, int32_t* argmax, void* stream) {
+    return launch_head_wide(reinterpret_cast<const bf16_t*>(in), in_plane, ld, M, K, reinterpret_cast<const bf16_t*>(Wp), w_plane, b, C,
+                            logp, argmax, reinterpret_cast<hipStream_t>(stream), options().op_fmt);
 }

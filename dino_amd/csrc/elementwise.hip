@@ -442,8 +442,10 @@ __global__ __launch_bounds__(256) void head_final_kernel(const bf16_t* __restric
 }
 
 int launch_head_final(const bf16_t* in, long in_plane, int ld, int M, int K, const float* W, const float* b, int C,
-                      float* logp, int32_t* argmax, hipStream_t s, int fmt) {
+                      float* logp, int32_t* argmax, hipStream_t s, int fmt, const bf16_t* Wp, long w_plane) {
     if (M <= 0) return 0;
+    if (C > HEAD_FINAL_MAX_C && C <= HEAD_WIDE_MAX_C)        // wider heads: the MFMA kernel on the packed classifier (head_wide.hip)
+        return launch_head_wide(in, in_plane, ld, M, K, Wp, w_plane, b, C, logp, argmax, s, fmt);
     if (C < 1 || C > 32 || ld % 8 != 0 || K > ld || (long)C * ld > 16384) {
         dinoseg_set_error("head_final: need 1 <= C <= 32, K <= ld, ld %% 8 == 0 and C * ld <= 16384 (C=%d K=%d ld=%d)", C, K, ld);
         return -1;
@@ -649,14 +651,42 @@ __global__ __launch_bounds__(256) void confusion_kernel(const int32_t* __restric
         if (h[i]) atomicAdd(cm + i, (unsigned long long)h[i]);
 }
 
+// C > 32: a C x C u32 histogram (256 KiB at C = 256) does not fit a CU's 160 KiB of LDS.  Workgroup (x, y) keeps the slab of ground-truth
+// rows 32y .. 32y+31 (32 x C u32, <= 32 KiB) and counts only the patches whose label falls in it; every slab reads the labels again
+// (<= 8 passes over 12 bytes per patch).  Counts are exact: u32 in LDS, int64 atomics on the way out.
+constexpr int CONF_SLAB = 32;
+__global__ __launch_bounds__(256) void confusion_slab_kernel(const int32_t* __restrict__ pred, const int64_t* __restrict__ gt, long n,
+                                                             int C, unsigned long long* __restrict__ cm) {
+    __shared__ unsigned int h[CONF_SLAB * 256];
+    const int g0 = blockIdx.y * CONF_SLAB;
+    for (int i = threadIdx.x; i < CONF_SLAB * C; i += 256) h[i] = 0;
+    __syncthreads();
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const long g = gt[i] - g0;
+        const int pr = pred[i];
+        if (g >= 0 && g < CONF_SLAB && g0 + g < C && pr >= 0 && pr < C) atomicAdd(&h[g * C + pr], 1u);
+    }
+    __syncthreads();
+    const int rows = C - g0 < CONF_SLAB ? C - g0 : CONF_SLAB;
+    for (int i = threadIdx.x; i < rows * C; i += 256)
+        if (h[i]) atomicAdd(cm + (long)g0 * C + i, (unsigned long long)h[i]);
+}
+
 int launch_confusion(const int32_t* pred, const int64_t* gt, long n, int C, int64_t* cm, hipStream_t s) {
-    if (C < 1 || C > 32) {
-        dinoseg_set_error("confusion: need 1 <= C <= 32");
+    if (C < 1 || C > HEAD_WIDE_MAX_C) {
+        dinoseg_set_error("confusion: need 1 <= C <= %d", HEAD_WIDE_MAX_C);
         return -1;
     }
     int grid = (int)((n + 255) / 256);
     if (grid > 1024) grid = 1024;
     if (grid < 1) grid = 1;
+    if (C > 32) {
+        const int slabs = (C + CONF_SLAB - 1) / CONF_SLAB;
+        const int gx = grid > 256 ? 256 : grid;
+        hipLaunchKernelGGL(confusion_slab_kernel, dim3(gx, slabs), dim3(256), 0, s, pred, gt, n, C, reinterpret_cast<unsigned long long*>(cm));
+        DSEG_CHECK_HIP(hipGetLastError());
+        return 0;
+    }
     hipLaunchKernelGGL(confusion_kernel, dim3(grid), dim3(256), 0, s, pred, gt, n, C, reinterpret_cast<unsigned long long*>(cm));
     DSEG_CHECK_HIP(hipGetLastError());
     return 0;

@@ -158,6 +158,12 @@ static inline int patch_planes(const dinoseg_handle* h) { return (h->fmt == FMT_
 static inline int split_fmt(const dinoseg_handle* h) { return h->planes == 2 ? h->fmt : (int)FMT_BF16; }
 // format of the patch-embedding operands: the mode's own when it runs on the mode's planes, the split format otherwise
 static inline int patch_fmt(const dinoseg_handle* h) { return patch_planes(h) == h->planes ? h->fmt : split_fmt(h); }   // the classifier head always runs in split precision (it is tiny)
+// the classifier packed for the wide head kernel (n_classes > 32, dinoseg_refresh_weights); empty below that
+static inline PackedLinear wide_clf(const dinoseg_handle* h) {
+    if (h->cfg.n_classes <= HEAD_FINAL_MAX_C) return PackedLinear();
+    auto it = h->packed.find(h->cfg.head_kind == DINOSEG_HEAD_MLP ? "clf.layer_3.weight" : "clf.layer_1.weight");
+    return it == h->packed.end() ? PackedLinear() : it->second;
+}
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline const float* W(const dinoseg_handle* h, const std::string& k) { return h->bound.at(k).ptr; }
 static inline void norm_consts(float mean255[3], float inv255[3]) {

@@ -250,9 +250,14 @@ int launch_cls_rows(float* X, const float* cls, const float* pos, int B, int nto
 // Bicubic (A=-0.75, align_corners=False, scale_factor rule) resample of the patch pos-embed grid.
 int launch_pos_resample(const float* pos_embed, int g, int D, int o, float* out, hipStream_t s);
 
-// Final classifier layer + log_softmax + argmax.  in: bf16 hi/lo planes [2][M][ld]; W fp32 [C][K]; C <= 32.
+// Final classifier layer + log_softmax + argmax.  in: bf16 hi/lo planes [2][M][ld]; W fp32 [C][K].  C <= 32 runs head_final_kernel;
+// 33 <= C <= HEAD_WIDE_MAX_C runs the wide MFMA kernel on Wp, the classifier packed as hi+lo planes [round_up(C, 32)][ld].
+constexpr int HEAD_FINAL_MAX_C = 32, HEAD_WIDE_MAX_C = 256;
 int launch_head_final(const bf16_t* in, long in_plane, int ld, int M, int K, const float* W, const float* b, int C,
-                      float* logp, int32_t* argmax, hipStream_t s, int fmt = 0);
+                      float* logp, int32_t* argmax, hipStream_t s, int fmt = 0, const bf16_t* Wp = nullptr, long w_plane = 0);
+// the wide kernel alone (head_wide.hip), any 1 <= C <= HEAD_WIDE_MAX_C; needs ld % 32 == 0
+int launch_head_wide(const bf16_t* in, long in_plane, int ld, int M, int K, const bf16_t* Wp, long w_plane, const float* b, int C,
+                     float* logp, int32_t* argmax, hipStream_t s, int fmt);
 
 // materialised softmax(q k^T) of one block, fp32 [B,H,ntok,ntok] (get_last_selfattention; visualisation only)
 int launch_attn_probs(const bf16_t* q, const bf16_t* k, long plane, int planes, int B, int heads, int ntok, int npad, float* out,

@@ -220,6 +220,56 @@ __global__ __launch_bounds__(256) void logsoftmax_bwd_kernel(const float* __rest
     }
 }
 
+// The same arithmetic for C > 32, one row per 16-lane group (a thread walking a whole row touched 64 rows per store instruction): lane
+// `sub` owns the column pairs 2 (sub + 16 i), so a group's loads and its 4-byte stores of both planes are contiguous runs of the row.
+// (The autograd path's row sum runs in another order than the narrow kernel's; with nll_loss's d logp -- one nonzero per row -- every
+// order gives the same value, so the fused step and F.nll_loss(...).backward() stay bit-identical here too.)
+__global__ __launch_bounds__(256) void logsoftmax_bwd_wide_kernel(const float* __restrict__ logp, const float* __restrict__ dlogp,
+                                                                  const int64_t* __restrict__ labels, const float* __restrict__ acc,
+                                                                  int M, int C, float* __restrict__ loss, bf16_t* __restrict__ dz,
+                                                                  long dz_plane, int ldz) {
+    const int sub = threadIdx.x & 15;
+    const long m = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
+    if (labels && m == 0 && sub == 0) *loss = acc[1] > 0.f ? acc[0] / acc[1] : __builtin_nanf("");
+    if (m >= M) return;                 // (whole 16-lane groups leave together: the shuffles below stay inside live groups)
+    const float* lp = logp + m * C;
+    const float* dl = dlogp ? dlogp + m * C : nullptr;
+    float rowsum = 0.f, own = 0.f;
+    int y = -1;
+    if (labels) {
+        const long yy = labels[m];
+        if (yy >= 0 && yy < C) {
+            y = (int)yy;
+            own = -1.0f / acc[1];
+            rowsum = own;
+        }
+    } else {
+        for (int c = sub; c < C; c += 16) rowsum += dl[c];
+        rowsum += __shfl_xor(rowsum, 1, 16);
+        rowsum += __shfl_xor(rowsum, 2, 16);
+        rowsum += __shfl_xor(rowsum, 4, 16);
+        rowsum += __shfl_xor(rowsum, 8, 16);
+    }
+    uint32_t* dh = reinterpret_cast<uint32_t*>(dz + m * ldz);
+    uint32_t* dlo = reinterpret_cast<uint32_t*>(dz + dz_plane + m * ldz);
+    for (int p = sub; p < ldz / 2; p += 16) {
+        float g[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int c = 2 * p + e;
+            g[e] = 0.f;
+            if (c < C) {
+                const float d = labels ? (c == y ? own : 0.f) : dl[c];
+                g[e] = d - expf(lp[c]) * rowsum;
+            }
+        }
+        uint32_t hi, lo;
+        split_bf16x2(g[0], g[1], hi, lo);
+        dh[p] = hi;
+        dlo[p] = lo;
+    }
+}
+
 int launch_nll_loss_grad(const float* logp, const int64_t* labels, const float* dlogp, int M, int C, float* acc, int* flags,
                          float* loss, bf16_t* dz, long dz_plane, int ldz, hipStream_t s) {
     if (labels) {
@@ -233,8 +283,17 @@ int launch_nll_loss_grad(const float* logp, const int64_t* labels, const float* 
         hipLaunchKernelGGL(nll_reduce_kernel, dim3(nb), dim3(256), 0, s, logp, labels, M, C, acc, flags, det);
         if (det) DSEG_TRY_RC(launch_det_finalize(det, nb, 2, 2, acc, s));
     }
-    hipLaunchKernelGGL(logsoftmax_bwd_kernel, dim3((M + 255) / 256), dim3(256), 0, s, logp, dlogp, labels, acc, M, C, loss, dz, dz_plane,
-                       ldz);
+    if (C > 32) {
+        if (ldz % 2 != 0 || dz_plane % 2 != 0 || ldz < C) {
+            dinoseg_set_error("nll_loss: d logits planes need an even width >= C (C=%d ldz=%d)", C, ldz);
+            return -1;
+        }
+        hipLaunchKernelGGL(logsoftmax_bwd_wide_kernel, dim3((M + 15) / 16), dim3(256), 0, s, logp, dlogp, labels, acc, M, C, loss, dz,
+                           dz_plane, ldz);
+    } else {
+        hipLaunchKernelGGL(logsoftmax_bwd_kernel, dim3((M + 255) / 256), dim3(256), 0, s, logp, dlogp, labels, acc, M, C, loss, dz, dz_plane,
+                           ldz);
+    }
     DSEG_CHECK_HIP(hipGetLastError());
     return 0;
 }

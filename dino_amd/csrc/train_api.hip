@@ -24,6 +24,9 @@ inline int splitk_budget() {
     return v < 1 ? 1 : v > SPLITK_TILES ? SPLITK_TILES : v;
 }
 
+// width of the d logits planes DZ: the classes rounded up to the 64-column k-step of the head's dgrad GEMM (launch_gemm_small: K % 64)
+static int dz_ld(int C) { return (C + 63) / 64 * 64; }
+
 struct TrainLayout {
     int n, ntok, npad, M, Mp, Mpad, Mppad, Cmax;
     // per block (offsets are for block 0; block l adds l * blk_stride)
@@ -82,7 +85,7 @@ TrainLayout make_train_layout(const dinoseg_handle* h, int B, int r) {
     L.h2_plane = (long)L.Mp * 128;
     L.H2 = take((size_t)HP * L.h2_plane * 2);
     L.LOGP = take((size_t)L.Mp * c.n_classes * 4);
-    L.dz_plane = (long)L.Mp * 64;
+    L.dz_plane = (long)L.Mp * dz_ld(c.n_classes);
     L.DZ = take((size_t)HP * L.dz_plane * 2);
     // backward scratch
     L.dX = take((size_t)L.M * D * 4);
@@ -127,9 +130,9 @@ std::vector<TLin> transposed_specs(const dinoseg_handle* h) {
     if (c.head_kind == DINOSEG_HEAD_MLP) {
         v.push_back({"clf.layer_1.weight", 200, D, 256, D, HP});
         v.push_back({"clf.layer_2.weight", 100, 200, 128, 256, HP});
-        v.push_back({"clf.layer_3.weight", C, 100, 64, 128, HP});
+        v.push_back({"clf.layer_3.weight", C, 100, dz_ld(C), 128, HP});
     } else {
-        v.push_back({"clf.layer_1.weight", C, D, 64, D, HP});
+        v.push_back({"clf.layer_1.weight", C, D, dz_ld(C), D, HP});
     }
     return v;
 }
@@ -395,10 +398,10 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
             DSEG_TRY(launch_gemm(g, s));
         }
         DSEG_TRY(launch_head_final(H2, L.h2_plane, 128, L.Mp, 100, W(h, "clf.layer_3.weight"), W(h, "clf.layer_3.bias"), C, LOGP,
-                                   nullptr, s));
+                                   nullptr, s, FMT_BF16, wide_clf(h).w, wide_clf(h).plane));
     } else {
         DSEG_TRY(launch_head_final(FEAT, L.feat_plane, D, L.Mp, D, W(h, "clf.layer_1.weight"), W(h, "clf.layer_1.bias"), C, LOGP,
-                                   nullptr, s));
+                                   nullptr, s, FMT_BF16, wide_clf(h).w, wide_clf(h).plane));
     }
     if (logp_out) DSEG_CHECK_HIP(hipMemcpyAsync(logp_out, LOGP, (size_t)L.Mp * C * 4, hipMemcpyDeviceToDevice, s));
     h->tr_B = B;
@@ -656,8 +659,9 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
     };
 
     // ---- loss and d logits (pl_torch_modules.py:264-265)
+    const int ldz = dz_ld(C);
     DSEG_TRY(launch_nll_loss_grad(LOGP, labels, dlogp, L.Mp, C, F32(L.ACC), h->bad_label_flag, loss_out, DZ,
-                                  L.dz_plane, 64, s));
+                                  L.dz_plane, ldz, s));
     const long tpl = L.t_plane;
     float* dX = F32(L.dX);
     float* dA = F32(L.dA);
@@ -665,10 +669,10 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
     if (mlp_head) {
         // layer_3: z = h2 W3^T + b3      (weight and bias gradients straight from the row-major planes: gemm_tn.hip; h2 / h1 are stored
         // 128 / 256 wide, zero beyond their 100 / 200 columns)
-        DSEG_TRY(wgrad_tn(DZ, L.dz_plane, 64, H2, L.h2_plane, 128, L.Mp, C, 100, HP, grad("clf.layer_3.weight"), grad("clf.layer_3.bias"), s, 128));
+        DSEG_TRY(wgrad_tn(DZ, L.dz_plane, ldz, H2, L.h2_plane, 128, L.Mp, C, 100, HP, grad("clf.layer_3.weight"), grad("clf.layer_3.bias"), s, 128));
         bf16_t* dH2 = G;                         // [HP][Mp][128]
         const long dh2_plane = (long)L.Mp * 128;
-        DSEG_TRY(dgrad(DZ, L.dz_plane, 64, L.Mp, 64, tw.at("clf.layer_3.weight"), 128, HP, EPI_DRELU, nullptr, dH2, dh2_plane, H2, L.h2_plane));
+        DSEG_TRY(dgrad(DZ, L.dz_plane, ldz, L.Mp, ldz, tw.at("clf.layer_3.weight"), 128, HP, EPI_DRELU, nullptr, dH2, dh2_plane, H2, L.h2_plane));
         // layer_2
         DSEG_TRY(wgrad_tn(dH2, dh2_plane, 128, H1, L.h1_plane, 256, L.Mp, 100, 200, HP, grad("clf.layer_2.weight"), grad("clf.layer_2.bias"), s, 256));
         bf16_t* dH1 = B16(L.dCTX);               // [HP][Mp][256] fits: Mp*256 <= M*D
@@ -687,15 +691,15 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
             DSEG_TRY(dgrad(dH1, dh1_plane, 256, L.Mp, 256, tw.at("clf.layer_1.weight"), D, HP, EPI_PLAIN, dA, nullptr, 0, nullptr, 0));
     } else {
         if (D % 128 == 0) {
-            DSEG_TRY(wgrad_tn(DZ, L.dz_plane, 64, FEAT, L.feat_plane, D, L.Mp, C, D, HP, grad("clf.layer_1.weight"), grad("clf.layer_1.bias"), s, D));
+            DSEG_TRY(wgrad_tn(DZ, L.dz_plane, ldz, FEAT, L.feat_plane, D, L.Mp, C, D, HP, grad("clf.layer_1.weight"), grad("clf.layer_1.bias"), s, D));
         } else {
-            DSEG_TRY(launch_transpose_planes(nullptr, DZ, L.dz_plane, 64, L.Mp, C, T1, tpl, 128, L.Mppad, nullptr, 0, 0,
+            DSEG_TRY(launch_transpose_planes(nullptr, DZ, L.dz_plane, ldz, L.Mp, C, T1, tpl, pad128(C), L.Mppad, nullptr, 0, 0,
                                              grad("clf.layer_1.bias"), HP, 0, 0, s));
             DSEG_TRY(launch_transpose_planes(nullptr, FEAT, L.feat_plane, D, L.Mp, D, T2, tpl, pad128(D), L.Mppad, nullptr, 0, 0, nullptr, HP, 0, 0, s));
             DSEG_TRY(wgrad(T1, T2, tpl, L.Mppad, C, pad128(D), D, HP, grad("clf.layer_1.weight")));
         }
         if (backbone)
-            DSEG_TRY(dgrad(DZ, L.dz_plane, 64, L.Mp, 64, tw.at("clf.layer_1.weight"), D, HP, EPI_PLAIN, dA, nullptr, 0, nullptr, 0));
+            DSEG_TRY(dgrad(DZ, L.dz_plane, ldz, L.Mp, ldz, tw.at("clf.layer_1.weight"), D, HP, EPI_PLAIN, dA, nullptr, 0, nullptr, 0));
     }
     DSEG_TRY(stage_mark(0));
     if (!backbone) return 0;      // frozen backbone (freeze_bb, pl_torch_modules.py:434-436): only the head trains

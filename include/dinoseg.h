@@ -52,7 +52,7 @@ typedef struct dinoseg_config {
     int32_t n_blocks;     /* transformer blocks kept (dino.blocks[:n_blocks], :177)              */
     int32_t patch;        /* 8                                                                   */
     int32_t mlp_ratio;    /* 4                                                                   */
-    int32_t n_classes;    /* <= 32                                                               */
+    int32_t n_classes;    /* 1 .. 256 (33 and up: the wide MFMA head kernel; above 256: rejected)  */
     int32_t head_kind;    /* DINOSEG_HEAD_*  (pl_torch_modules.py:219-222)                       */
     int32_t pos_grid;     /* 28: stored pos_embed is [1, 28*28+1, D]                             */
     float   ln_eps;       /* 1e-6 (vision_transformer.py:303)                                    */
@@ -117,7 +117,7 @@ int dinoseg_features(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B
 int dinoseg_op_resize_u8(const uint8_t* src, int32_t sh, int32_t sw, uint8_t* dst, int32_t dh, int32_t dw, void* stream);
 
 /* Confusion matrix for the validation metrics (validation_epoch_end, pl_torch_modules.py:310-332):
- * cm[gt][pred] += 1 over n patches; cm int64 [n_classes, n_classes] on device (zero it first). */
+ * cm[gt][pred] += 1 over n patches; cm int64 [n_classes, n_classes] on device (zero it first); 1 <= n_classes <= 256. */
 int dinoseg_op_confusion(const int32_t* pred, const int64_t* gt, int64_t n, int32_t n_classes, int64_t* cm, void* stream);
 
 /* ---- fine-tune step (replaces DINOSeg.training_step + autograd + optimizer.step, pl_torch_modules.py:258-268) ---- */
@@ -372,9 +372,14 @@ int dinoseg_op_pos_resample(const float* pos_embed, int32_t g, int32_t D, int32_
 int dinoseg_op_patch_gather(const void* x, int32_t x_kind, int32_t B, int32_t r, void* out, int64_t out_plane,
                             int32_t planes, void* stream);
 
-/* last Linear + log_softmax + argmax (pl_torch_modules.py:122-123,:294); in: hi/lo planes [2][M][ld] */
+/* last Linear + log_softmax + argmax (pl_torch_modules.py:122-123,:294); in: hi/lo planes [2][M][ld]; C <= 32 */
 int dinoseg_op_head_final(const void* in, int64_t in_plane, int32_t ld, int32_t M, int32_t K, const float* W,
                           const float* b, int32_t C, float* logp, int32_t* argmax, void* stream);
+/* The same on MFMAs (the kernel the model runs for 33 <= n_classes <= 256), any 1 <= C <= 256: Wp = the classifier as hi/lo planes
+ * [2][round_up(C, 32)][ld] (dinoseg_op_pack, zero padded; w_plane = their stride), b fp32 [C]; ld % 32 == 0, K <= ld.
+ * Operand format: option op_fmt. */
+int dinoseg_op_head_wide(const void* in, int64_t in_plane, int32_t ld, int32_t M, int32_t K, const void* Wp, int64_t w_plane,
+                         const float* b, int32_t C, float* logp, int32_t* argmax, void* stream);
 
 /* flash-attention backward: q,k,v as the forward; dO, O: ctx-layout planes [planes][B*ntok][heads*64]; lse from the
  * forward; scratch: 2*B*heads*npad floats; dqkv out: planes [planes][B*ntok][3*heads*64] (gradient of the qkv

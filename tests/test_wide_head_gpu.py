@@ -1,0 +1,284 @@
+"""Segmentation heads with 33 .. 256 classes on the GPU (-m gpu): the wide MFMA classifier tail (head_wide.hip) as an op against fp64
+on its own operands, the model's forward / predict / fine-tune step at 150 classes against the CPU oracle, and the confusion matrix
+beyond 32 classes."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import dino_amd
+from dino_amd import DINOSeg, ViTConfig, capi, procedural_state_dict
+from dino_amd.weights import synthetic_frames, synthetic_labels
+from oracle import dinoseg_oracle as O
+from tests.gpu_util import seeded
+
+pytestmark = pytest.mark.gpu
+S = capi.stream_ptr
+FMTS = {"bf16": (0, torch.bfloat16, 2.0 ** -16), "fp16": (1, torch.float16, 2.0 ** -22)}
+
+
+def _pack(x, fmt, rows_pad, cols_pad):
+    """fp32 [rows, cols] -> hi+lo planes [2, rows_pad, cols_pad] in the op format (zero padded)."""
+    out = torch.empty((2, rows_pad, cols_pad), dtype=torch.int16, device="cuda")
+    capi.check(capi.lib().dinoseg_op_pack(x.contiguous().data_ptr(), x.shape[0], x.shape[1], out.data_ptr(), rows_pad * cols_pad,
+                                          rows_pad, cols_pad, 2, S()))
+    return out
+
+
+def _quant(x, dt):
+    """What the kernel multiplies: hi(x) + lo(x), each rounded to the 16-bit operand type."""
+    hi = x.to(dt).to(torch.float32)
+    return hi + (x - hi).to(dt).to(torch.float32)
+
+
+def _wide_case(C, K, ld, M, fmt, seed):
+    code, dt, _ = FMTS[fmt]
+    x = torch.zeros((M, ld), device="cuda")
+    x[:, :K] = torch.relu(seeded((M, K), seed)) if K == 100 else seeded((M, K), seed)
+    Wc = seeded((C, K), seed + 1) * (1.5 / K ** 0.5)
+    b = seeded((C,), seed + 2)
+    cp = (C + 31) // 32 * 32
+    capi.check(capi.lib().dinoseg_set_option(b"op_fmt", code))
+    try:
+        xp = _pack(x, fmt, M, ld)
+        wp = _pack(Wc, fmt, cp, ld)
+        logp = torch.full((M, C), float("nan"), device="cuda")
+        am = torch.full((M,), -1, dtype=torch.int32, device="cuda")
+        capi.check(capi.lib().dinoseg_op_head_wide(xp.data_ptr(), M * ld, ld, M, K, wp.data_ptr(), cp * ld, b.data_ptr(), C,
+                                                   logp.data_ptr(), am.data_ptr(), S()))
+        torch.cuda.synchronize()
+    finally:
+        capi.check(capi.lib().dinoseg_set_option(b"op_fmt", 0))
+    return x, Wc, b, xp, logp, am
+
+
+@pytest.mark.parametrize("fmt", ["bf16", "fp16"])
+@pytest.mark.parametrize("K,ld", [(100, 128), (384, 384), (768, 768)])
+@pytest.mark.parametrize("C", [1, 7, 33, 64, 150, 171, 256])
+def test_head_wide_op_against_fp64(cuda, fmt, K, ld, C):
+    _, dt, eps = FMTS[fmt]
+    for M in (1, 333, 3601):
+        x, Wc, b, xp, logp, am = _wide_case(C, K, ld, M, fmt, seed=7 * C + M + K)
+        xq = _quant(x[:, :K], dt).double()
+        wq = _quant(Wc, dt).double()
+        z = xq @ wq.t() + b.double()
+        ref = torch.log_softmax(z, dim=1)
+        # Bound from the operand width: the three MFMA products drop lo*lo (relative eps = 2^-16 bf16 / 2^-22 fp16 per product) and
+        # accumulate K terms in fp32 (K * 2^-24 at worst), both relative to sum_k |x_k w_ck|; a logit error enters log_softmax
+        # twice (the logit and the log-sum-exp).
+        mag = float((xq.abs() @ wq.abs().t()).max())
+        bound = 2.0 * (eps + K * 2.0 ** -24) * mag + 1e-5
+        err = float((logp.double() - ref).abs().max())
+        assert torch.isfinite(logp).all() and err <= bound, (M, err, bound)
+        top2 = ref.topk(2, dim=1).values if C > 1 else torch.cat([ref, ref - 1.0], dim=1)
+        clear = (top2[:, 0] - top2[:, 1]) > 2 * bound
+        want = ref.argmax(dim=1)
+        assert torch.equal(am.long()[clear], want[clear]), M
+        if C == 7:
+            # the narrow kernel (head_final_kernel: fp32 classifier) on the same activation planes
+            code = FMTS[fmt][0]
+            lp0 = torch.full((M, C), float("nan"), device="cuda")
+            am0 = torch.full((M,), -1, dtype=torch.int32, device="cuda")
+            capi.check(capi.lib().dinoseg_set_option(b"op_fmt", code))
+            try:
+                capi.check(capi.lib().dinoseg_op_head_final(xp.data_ptr(), M * ld, ld, M, K, Wc.data_ptr(), b.data_ptr(), C,
+                                                            lp0.data_ptr(), am0.data_ptr(), S()))
+                torch.cuda.synchronize()
+            finally:
+                capi.check(capi.lib().dinoseg_set_option(b"op_fmt", 0))
+            # (the narrow kernel multiplies the fp32 classifier: the wide one's classifier rounding, eps relative, comes on top)
+            assert float((lp0 - logp).abs().max()) <= bound + 2.0 * eps * mag
+            assert torch.equal(am0[clear], am[clear])
+
+
+def test_head_final_still_refuses_wide_heads_without_packed_weights(cuda):
+    M, ld, K, C = 64, 128, 100, 40
+    x = torch.zeros((2, M, ld), dtype=torch.int16, device="cuda")
+    Wc, b = torch.zeros((C, K), device="cuda"), torch.zeros((C,), device="cuda")
+    logp = torch.zeros((M, C), device="cuda")
+    am = torch.zeros((M,), dtype=torch.int32, device="cuda")
+    rc = capi.lib().dinoseg_op_head_final(x.data_ptr(), M * ld, ld, M, K, Wc.data_ptr(), b.data_ptr(), C, logp.data_ptr(), am.data_ptr(), S())
+    assert rc == -1 and "head_wide" in capi.last_error()
+
+
+# ------------------------------------------------------------------------------------------------ the model at 150 classes
+def _model(head, precision, n_blocks=3, C=150):
+    cfg = ViTConfig(n_blocks=n_blocks, n_classes=C, head=head)
+    sd = procedural_state_dict(cfg)
+    m = DINOSeg(head=head, n_blocks=n_blocks, n_classes=C, precision=precision, arch=cfg, optimizer=torch.optim.Adam, lr=1e-3)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    return m.to("cuda:0"), sd, cfg
+
+
+@pytest.mark.parametrize("head", ["linear", "mlp"])
+def test_forward_and_predict_at_150_classes(cuda, head):
+    m, sd, cfg = _model(head, "fp16x3")
+    frames = synthetic_frames(2, 64, seed=21)
+    with torch.no_grad():
+        ref64 = O.dinoseg_forward(O.preprocess(frames).double(), {k: v.double() for k, v in O.to_torch(sd).items()}, cfg.num_heads)
+    top2 = ref64.topk(2, dim=1).values
+    margin = top2[:, 0] - top2[:, 1]
+    want = ref64.argmax(dim=1)
+    assert int(want.max()) >= 32, "the fixture should exercise classes beyond the narrow kernel's 32"
+    for prec, bar in (("fp16x3", 1e-3), ("bf16x3", 1e-3), ("fp16", 0.1), ("bf16", 0.5)):
+        m.set_precision(prec)
+        lp, am = m.forward_frames(torch.from_numpy(frames).cuda())
+        lp, am = lp.cpu().double(), am.cpu().long()
+        err = float((lp - ref64).abs().max())
+        flips = am != want
+        print(f"{head} C=150 {prec}: max|dlogp| {err:.3e}, argmax flips {int(flips.sum())} / {flips.numel()}")
+        assert lp.shape == (2 * 64, 150) and torch.isfinite(lp).all()
+        assert err <= bar, (prec, err)
+        if bar <= 1e-3:     # the parity bar: with |dlogp| <= 1e-3 only a top-2 gap below 2e-3 can flip
+            assert not bool((flips & (margin > 2e-3)).any()), prec
+        # the argmax-only call (log-probabilities kept in the workspace) agrees with the full one
+        lp2, am2 = m.forward_frames(torch.from_numpy(frames).cuda(), want_logp=False)
+        assert lp2 is None and torch.equal(am2.cpu().long(), am)
+    m.set_precision("fp16x3")
+    m.set_resolution(64)
+    low_ok = margin.reshape(2, 8, 8)[0] > 2e-3
+    want_map = np.kron(want.reshape(2, 8, 8)[0].numpy(), np.ones((60, 60), dtype=int))
+    ok_map = np.kron(low_ok.numpy().astype(int), np.ones((60, 60), dtype=int)).astype(bool)
+    for _ in range(2):          # the second call replays the captured graph
+        pred = m.predict(frames[0])
+        assert pred.shape == (480, 480) and pred.max() <= 149
+        assert np.array_equal(pred[ok_map], want_map[ok_map])
+
+
+def test_two_stream_forward_at_150_classes(cuda):
+    """The two half-batches of dinoseg_forward (option streams = 2) write their log-probabilities at offset B0 * n * C."""
+    m, _, _ = _model("mlp", "bf16x3", n_blocks=2)
+    m.set_resolution(64)
+    frames = torch.from_numpy(synthetic_frames(16, 64, seed=9)).cuda()
+    dino_amd.set_option("streams", 1)
+    try:
+        ref, ram = (t.clone() for t in m.forward_frames(frames))
+        dino_amd.set_option("streams", 2)           # (16 frames: above the default split_min of 8)
+        out, am = m.forward_frames(frames)
+    finally:
+        dino_amd.set_option("streams", 2)
+    assert torch.equal(out, ref) and torch.equal(am, ram)
+
+
+def _labels(B, n, C, seed):
+    y = synthetic_labels(B, n, C, seed=seed)
+    y[0, :5] = -100                         # ignored patches
+    y[1, 3] = C - 1
+    y[1, 4] = 40
+    return torch.from_numpy(y).cuda()
+
+
+@pytest.mark.parametrize("frozen", [True, False])
+def test_train_step_at_150_classes_vs_oracle_autograd(cuda, frozen):
+    m, sd, cfg = _model("mlp", "bf16x3", n_blocks=1)
+    m.freeze_bb() if frozen else m.unfreeze_bb()
+    frames = synthetic_frames(2, 64, seed=31)
+    labels = _labels(2, 64, 150, seed=32)
+    # Patches with a head pre-activation within 1e-4 of the ReLU kink are ignored: there the bf16x3 step and the fp32 oracle may take
+    # different branches (seed 31 has one at -2.0e-5 in layer_2; its flipped mask moves one row of layer_2's weight gradient by 0.0129,
+    # 2.6e-3 of the norm), which is the input's conditioning, not the kernels'.
+    with torch.no_grad():
+        W64 = {k: v.double() for k, v in O.to_torch(sd).items()}
+        t = O.vit_forward(O.preprocess(frames).double(), W64, cfg.num_heads)[:, 1:].reshape(-1, cfg.embed_dim)
+        p1 = t @ W64["clf.layer_1.weight"].t() + W64["clf.layer_1.bias"]
+        p2 = torch.relu(p1) @ W64["clf.layer_2.weight"].t() + W64["clf.layer_2.bias"]
+        kink = ((p1.abs() < 1e-4).any(dim=1) | (p2.abs() < 1e-4).any(dim=1)).reshape(2, 64).cuda()
+    labels = torch.where(kink, torch.full_like(labels, -100), labels)
+    out = m.fused_training_step((torch.from_numpy(frames).cuda(), labels), 0)
+    W = O.to_torch(sd, requires_grad=True)
+    loss = O.nll_loss(O.dinoseg_forward(O.preprocess(frames), W, cfg.num_heads), labels.cpu())
+    loss.backward()
+    assert abs(float(out["loss"]) - float(loss)) <= 2e-4
+    checked = 0
+    for k, p in m.named_parameters():
+        if frozen and not k.startswith("clf."):
+            assert p.grad is None, k
+            continue
+        gn = float(W[k].grad.norm())
+        assert float((p.grad.cpu() - W[k].grad).abs().max()) <= 2e-3 * gn + 1e-7, k
+        checked += 1
+    assert checked == (6 if frozen else len(sd))
+    m.check_labels()
+    bad = labels.clone()
+    bad[0, 7] = 150
+    m.fused_training_step((torch.from_numpy(frames).cuda(), bad), 0)
+    with pytest.raises(IndexError):
+        m.check_labels()
+
+
+@pytest.mark.parametrize("head", ["linear", "mlp"])
+def test_autograd_equals_fused_step_at_150_classes(cuda, head):
+    m, _, _ = _model(head, "bf16x3", n_blocks=1)
+    m.unfreeze_bb()
+    frames = synthetic_frames(2, 64, seed=41)
+    labels = _labels(2, 64, 150, seed=42)
+    x = O.preprocess(frames).cuda()
+    fused = m.fused_training_step((x, labels), 0)
+    want = {k: p.grad.clone() for k, p in m.named_parameters()}
+    for p in m.parameters():
+        p.grad = None
+    loss = torch.nn.functional.nll_loss(m(x), labels.reshape(-1))
+    loss.backward()
+    assert abs(float(loss) - float(fused["loss"])) <= 1e-6
+    for k, p in m.named_parameters():
+        scale = float(want[k].abs().max()) + 1e-12
+        assert float((p.grad - want[k]).abs().max()) <= 2e-5 * scale, k
+    clf_w = "clf.layer_3.weight" if head == "mlp" else "clf.layer_1.weight"
+    assert torch.equal(m.get_parameter(clf_w).grad, want[clf_w])      # same d logits bit for bit
+
+
+def test_deterministic_step_at_150_classes(cuda):
+    frames = torch.from_numpy(synthetic_frames(2, 64, seed=51)).cuda()
+    labels = _labels(2, 64, 150, seed=52)
+
+    def run():
+        m = _model("linear", "bf16x3", n_blocks=1)[0]
+        m.unfreeze_bb()
+        out = m.fused_training_step((frames, labels), 0)
+        m.fused_adam_step()
+        out2 = m.fused_training_step((frames, labels), 1)
+        return out["loss"].clone(), out2["loss"].clone(), {k: p.grad.clone() for k, p in m.named_parameters()}
+    dino_amd.set_option("deterministic", 1)
+    try:
+        a, b = run(), run()
+    finally:
+        dino_amd.set_option("deterministic", 0)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    for k in a[2]:
+        assert torch.equal(a[2][k], b[2][k]), k
+
+
+@pytest.mark.parametrize("C", [33, 150, 256])
+def test_confusion_beyond_32_classes(cuda, C):
+    rng = np.random.default_rng(C)
+    n = 100003
+    gt = rng.integers(0, C, n).astype(np.int64)
+    pred = rng.integers(0, C, n).astype(np.int32)
+    gt[::97] = -100                         # ignore_index
+    gt[5::211] = C + 1                      # out of range labels
+    pred[::89] = -1                         # out of range predictions
+    pred[3::101] = C
+    pred[7::53] = pred[7::53] // 7          # a few heavy cells
+    cm = torch.zeros((C, C), dtype=torch.int64, device="cuda")
+    pred_d, gt_d = torch.from_numpy(pred).cuda(), torch.from_numpy(gt).cuda()
+    capi.check(capi.lib().dinoseg_op_confusion(pred_d.data_ptr(), gt_d.data_ptr(), n, C, cm.data_ptr(), S()))
+    torch.cuda.synchronize()
+    keep = (gt >= 0) & (gt < C) & (pred >= 0) & (pred < C)
+    want = np.bincount(gt[keep] * C + pred[keep], minlength=C * C).reshape(C, C)
+    assert np.array_equal(cm.cpu().numpy(), want)
+
+
+def test_fit_one_epoch_at_150_classes(cuda, tmp_path):
+    cfg = ViTConfig(embed_dim=128, num_heads=2, n_blocks=1, n_classes=150, head="mlp")
+    m = DINOSeg(arch=cfg, head="mlp", n_blocks=1, n_classes=150, lr=1e-3, optimizer=torch.optim.Adam, freeze_backbone=True,
+                max_epochs=1, write_path=str(tmp_path), precision="bf16x3").to("cuda")
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in procedural_state_dict(cfg).items()})
+    m.set_resolution(64)
+    frames = torch.from_numpy(synthetic_frames(6, 64, seed=3))
+    lab = torch.from_numpy(synthetic_labels(6, 64, 150, seed=4))
+    out = m.fit(train_dataloader=[(frames[0:2], lab[0:2]), (frames[2:4], lab[2:4])], val_dataloader=[(frames[4:6], lab[4:6])])
+    assert len(out["history"]) == 1 and np.isfinite(out["history"][0]["train_loss"])
+    assert m.best_ck and os.path.exists(m.best_ck)
+    m2 = DINOSeg.load_from_checkpoint(m.best_ck, arch=cfg, precision="bf16x3")
+    assert m2.n_classes == 150 and tuple(m2.clf.layer_3.weight.shape) == (150, 100)
