@@ -108,6 +108,17 @@ SIGNATURES = {
     "dinoseg_op_patch_gather": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
     "dinoseg_op_head_final": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _fp, _fp, _i32, _fp, _fp, _vp]),
     "dinoseg_op_head_wide": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _fp, _i32, _fp, _fp, _vp]),
+    # non-square frames: the `r` entries above with H, W in place of r
+    "dinoseg_prepare_resolution_hw": (C.c_int, [_vp, _i32, _i32, _vp]),
+    "dinoseg_forward_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _fp, _fp, _i32, _fp, _vp]),
+    "dinoseg_last_selfattention_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _fp, _vp]),
+    "dinoseg_forward_mask_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _fp, _i32, _fp, _fp, _vp]),
+    "dinoseg_features_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _fp, _vp]),
+    "dinoseg_train_forward_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _fp, _vp]),
+    "dinoseg_train_step_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _vp]),
+    "dinoseg_workspace_bytes_hw": (_i64, [_vp, _i32, _i32, _i32]),
+    "dinoseg_op_pos_resample_hw": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _fp, _vp]),
+    "dinoseg_op_patch_gather_hw": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

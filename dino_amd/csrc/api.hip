@@ -119,7 +119,7 @@ static void release_workspaces(dinoseg_handle* h) {
     h->bw_ev.clear();
     h->ws = h->ws2 = nullptr;
     h->ws_bytes = h->ws2_bytes = 0;
-    h->ws_B = h->ws_r = h->ws2_B = h->ws2_r = -1;
+    h->ws_B = h->ws_H = h->ws_W = h->ws2_B = h->ws2_H = h->ws2_W = -1;
     h->aux_stream = nullptr;
     h->ev_fork = h->ev_join = nullptr;
 }
@@ -189,9 +189,9 @@ extern "C" int dinoseg_bind_weight(dinoseg_handle* h, const char* name, const vo
                 h->prof_recs.clear();
                 for (auto& e : h->prof_pool) (void)hipEventDestroy(e);
                 h->prof_pool.clear();
-                h->wbuf = nullptr; h->pos_cache = nullptr; h->pos_r = -1;
+                h->wbuf = nullptr; h->pos_cache = nullptr; h->pos_hp = h->pos_wp = -1;
                 h->wbuf_bytes = h->pos_cap = 0;
-                h->tws_B = h->tws_r = h->tr_B = -1;
+                h->tws_B = h->tws_H = h->tws_W = h->tr_B = -1;
                 h->packed.clear();
                 h->packed_slab.clear();
                 h->packed_mlp.clear();
@@ -390,20 +390,23 @@ extern "C" int dinoseg_refresh_weights(dinoseg_handle* h, void* stream) {
     h->weights_ready = true;
     // pos_embed may have changed in place (load_state_dict into the same storage, an optimizer step on an unfrozen backbone).  A
     // captured forward contains no resample launch and never calls dinoseg_prepare_resolution, so "resample on the next forward"
-    // (pos_r = -1 alone) would let a replay read the OLD rows next to freshly packed linears: resample here, in stream order with
+    // (pos_hp = -1 alone) would let a replay read the OLD rows next to freshly packed linears: resample here, in stream order with
     // the packs, into the SAME buffer: like the re-packed linears, the captured pointers stay valid and the replay reads new rows.
-    if (h->pos_r > 0 && h->pos_cache != nullptr && h->bound.count("dino.pos_embed")) {
-        DSEG_TRY(launch_pos_resample(W(h, "dino.pos_embed"), h->cfg.pos_grid, h->cfg.embed_dim, h->pos_r / 8, h->pos_cache, s));
+    if (h->pos_hp > 0 && h->pos_cache != nullptr && h->bound.count("dino.pos_embed")) {
+        DSEG_TRY(launch_pos_resample(W(h, "dino.pos_embed"), h->cfg.pos_grid, h->cfg.embed_dim, h->pos_hp, h->pos_wp, h->pos_cache, s));
     } else {
-        h->pos_r = -1;      // (nothing cached: the next forward resamples, and dinoseg_prepare_resolution counts a new generation)
+        h->pos_hp = h->pos_wp = -1;      // (nothing cached: the next forward resamples, and dinoseg_prepare_resolution counts a new generation)
     }
     h->pos_stale = false;
     return 0;
 }
 
-extern "C" int dinoseg_prepare_resolution(dinoseg_handle* h, int32_t r, void* stream) {
+// H x W frames: both multiples of 8 (the reference's message, pl_torch_modules.py:271-272)
+static bool frame_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0; }
+
+extern "C" int dinoseg_prepare_resolution_hw(dinoseg_handle* h, int32_t Hf, int32_t Wf, void* stream) {
     if (!h) return -1;
-    if (r <= 0 || r % 8 != 0) {
+    if (!frame_ok(Hf, Wf)) {
         dinoseg_set_error("Resolution should be a multiple of 8.");
         return -1;
     }
@@ -411,22 +414,27 @@ extern "C" int dinoseg_prepare_resolution(dinoseg_handle* h, int32_t r, void* st
         dinoseg_set_error("dinoseg_prepare_resolution: dino.pos_embed not bound");
         return -3;
     }
-    if (h->pos_r == r && !h->pos_stale) return 0;
+    const int hp = Hf / 8, wp = Wf / 8, D = h->cfg.embed_dim;
+    if (h->pos_hp == hp && h->pos_wp == wp && !h->pos_stale) return 0;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     DeviceGuard guard(h);
-    const int o = r / 8, D = h->cfg.embed_dim;
-    ++h->generation;        // (the cache holds ONE resolution: a captured forward of another one would read this one's rows)
-    const size_t need = ((size_t)o * o + 1) * D * sizeof(float);
+    ++h->generation;        // (the cache holds ONE patch grid: a captured forward of another one would read this one's rows)
+    const size_t need = ((size_t)hp * wp + 1) * D * sizeof(float);
     if (need > h->pos_cap) {
         if (h->pos_cache) DSEG_CHECK_HIP(hipFree(h->pos_cache));
         h->pos_cache = nullptr;
         DSEG_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&h->pos_cache), need));
         h->pos_cap = need;
     }
-    DSEG_TRY(launch_pos_resample(W(h, "dino.pos_embed"), h->cfg.pos_grid, D, o, h->pos_cache, s));
-    h->pos_r = r;
+    DSEG_TRY(launch_pos_resample(W(h, "dino.pos_embed"), h->cfg.pos_grid, D, hp, wp, h->pos_cache, s));
+    h->pos_hp = hp;
+    h->pos_wp = wp;
     h->pos_stale = false;
     return 0;
+}
+
+extern "C" int dinoseg_prepare_resolution(dinoseg_handle* h, int32_t r, void* stream) {
+    return dinoseg_prepare_resolution_hw(h, r, r, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ workspace
@@ -436,11 +444,11 @@ struct WsLayout {
     int n, ntok, npad, M, Mp;
 };
 
-static WsLayout make_layout(const dinoseg_handle* h, int B, int r) {
+static WsLayout make_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
     const dinoseg_config& c = h->cfg;
     const int D = c.embed_dim, F = D * c.mlp_ratio, P = h->planes, HP = head_planes();
     WsLayout L;
-    L.n = (r / 8) * (r / 8);
+    L.n = (Hf / 8) * (Wf / 8);
     L.ntok = L.n + 1;
     L.npad = (L.ntok + 63) / 64 * 64;
     L.M = B * L.ntok;
@@ -480,17 +488,26 @@ static WsLayout make_layout(const dinoseg_handle* h, int B, int r) {
 
 extern "C" int64_t dinoseg_state_generation(const dinoseg_handle* h) { return h ? h->generation : -1; }
 
+extern "C" int64_t dinoseg_workspace_bytes_hw(const dinoseg_handle* h, int32_t B, int32_t H, int32_t W) {
+    if (!h || B <= 0) return -1;
+    if (!frame_ok(H, W)) {
+        dinoseg_set_error("Resolution should be a multiple of 8.");
+        return -1;
+    }
+    return (int64_t)(make_layout(h, B, H, W).total + h->wbuf_bytes);
+}
+
 extern "C" int64_t dinoseg_workspace_bytes(const dinoseg_handle* h, int32_t B, int32_t r) {
-    if (!h || B <= 0 || r <= 0 || r % 8 != 0) return -1;
-    return (int64_t)(make_layout(h, B, r).total + h->wbuf_bytes);
+    return dinoseg_workspace_bytes_hw(h, B, r, r);
 }
 
 // slot 0: the caller's stream; slot 1: the second half-batch of a split forward (its own buffer, the handle's internal stream)
-static int ensure_workspace(dinoseg_handle* h, int slot, const WsLayout& L, int B, int r, hipStream_t s) {
+static int ensure_workspace(dinoseg_handle* h, int slot, const WsLayout& L, int B, int Hf, int Wf, hipStream_t s) {
     char*& ws = slot ? h->ws2 : h->ws;
     size_t& bytes = slot ? h->ws2_bytes : h->ws_bytes;
     int& wB = slot ? h->ws2_B : h->ws_B;
-    int& wr = slot ? h->ws2_r : h->ws_r;
+    int& wH = slot ? h->ws2_H : h->ws_H;
+    int& wW = slot ? h->ws2_W : h->ws_W;
     if (L.total > bytes) {
         ++h->generation;
         if (ws) {
@@ -503,14 +520,15 @@ static int ensure_workspace(dinoseg_handle* h, int slot, const WsLayout& L, int 
         bytes = L.total;
         wB = -1;
     }
-    if (wB != B || wr != r) {
+    if (wB != B || wH != Hf || wW != Wf) {
         // key/value pad rows beyond ntok must be finite: zero Q/K/V once per layout (never written afterwards).  A layout change is a
         // new state generation: a forward captured under the OLD layout holds no memset node, and another layout's launches have since
         // written other things (fp32 residual rows ...) where its pad rows live -- the owner of the graph must capture again.
         DSEG_CHECK_HIP(hipMemsetAsync(ws + L.Q, 0, L.CTX - L.Q, s));
         ++h->generation;
         wB = B;
-        wr = r;
+        wH = Hf;
+        wW = Wf;
     }
     return 0;
 }
@@ -566,14 +584,14 @@ static int ensure_mlp_packs(dinoseg_handle* h, hipStream_t s) {
     return 0;
 }
 
-static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* logp_out,
+static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t Hf, int32_t Wf, float* logp_out,
                         int32_t* argmax_out, int32_t tap_block, float* tap_out, float* attn_out, void* stream,
                         const MaskRequest* mreq = nullptr, int slot = 0, int disp_B = 0) {
     if (!h || !x || B <= 0) {
         dinoseg_set_error("dinoseg_forward: bad argument");
         return -1;
     }
-    if (r <= 0 || r % 8 != 0) {
+    if (!frame_ok(Hf, Wf)) {
         dinoseg_set_error("Resolution should be a multiple of 8.");
         return -1;
     }
@@ -588,12 +606,12 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     DeviceGuard guard(h);
     DSEG_TRY(check_stream_device(h, s));
-    DSEG_TRY(dinoseg_prepare_resolution(h, r, stream));
+    DSEG_TRY(dinoseg_prepare_resolution_hw(h, Hf, Wf, stream));
 
     const dinoseg_config& c = h->cfg;
     const int D = c.embed_dim, F = D * c.mlp_ratio, P = h->planes, HP = head_planes(), H = c.num_heads, FM = h->fmt, SF = split_fmt(h);
-    const WsLayout L = make_layout(h, B, r);
-    DSEG_TRY(ensure_workspace(h, slot, L, B, r, s));
+    const WsLayout L = make_layout(h, B, Hf, Wf);
+    DSEG_TRY(ensure_workspace(h, slot, L, B, Hf, Wf, s));
     // every size-dependent kernel choice below is made for the rows of the WHOLE call: the half-batches of a split forward (disp_B =
     // the call's batch) then take the routes -- and the summation order -- the unsplit batch takes, so the split changes no bit
     const int dB = disp_B > 0 ? disp_B : B;
@@ -635,7 +653,7 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
     norm_consts(mean255, inv255);
     const long pg_plane = (long)L.Mp * 192;
     const int PP = patch_planes(h);
-    DSEG_PROF(DINOSEG_PROF_PATCH, DSEG_TRY(launch_patch_gather(x, x_kind, B, r, mean255, inv255, A, pg_plane, PP, s, patch_fmt(h))));
+    DSEG_PROF(DINOSEG_PROF_PATCH, DSEG_TRY(launch_patch_gather(x, x_kind, B, Hf, Wf, mean255, inv255, A, pg_plane, PP, s, patch_fmt(h))));
     {
         const PackedLinear& pk = h->packed.at("dino.patch_embed.proj.weight");
         GemmParams g = {};
@@ -906,27 +924,27 @@ int ensure_aux_stream(dinoseg_handle* h) {
 // semantics and stays capturable).  Frames are independent (pl_torch_modules.py:253 flattens them); kernels of different
 // layers of the two halves overlap: one half's attention fills the CUs the other half's GEMM tail rounds and memory phases
 // leave idle (measured: +4.5 % frames/s at B = 32; four quarter-batches: -5 %).  The two workspaces together are the size of one.
-extern "C" int dinoseg_forward(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* logp_out,
-                               int32_t* argmax_out, int32_t tap_block, float* tap_out, void* stream) {
+extern "C" int dinoseg_forward_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, float* logp_out,
+                                  int32_t* argmax_out, int32_t tap_block, float* tap_out, void* stream) {
     const bool split = h && x && options().streams >= 2 && B >= options().split_min && B >= 2 && tap_block < 0 && !tap_out &&
-                       r > 0 && r % 8 == 0 && (x_kind == DINOSEG_INPUT_U8_HWC || x_kind == DINOSEG_INPUT_F32_CHW) && h->weights_ready;
-    if (!split) return forward_impl(h, x, x_kind, B, r, logp_out, argmax_out, tap_block, tap_out, nullptr, stream);
+                       frame_ok(H, W) && (x_kind == DINOSEG_INPUT_U8_HWC || x_kind == DINOSEG_INPUT_F32_CHW) && h->weights_ready;
+    if (!split) return forward_impl(h, x, x_kind, B, H, W, logp_out, argmax_out, tap_block, tap_out, nullptr, stream);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     DeviceGuard guard(h);
     DSEG_TRY(check_stream_device(h, s));
     DSEG_TRY(ensure_aux_stream(h));
-    DSEG_TRY(dinoseg_prepare_resolution(h, r, stream));      // the resampled position embedding: before the fork, both halves read it
+    DSEG_TRY(dinoseg_prepare_resolution_hw(h, H, W, stream));      // the resampled position embedding: before the fork, both halves read it
     const int B0 = (B + 1) / 2, B1 = B - B0;
-    const long n = (long)(r / 8) * (r / 8);
-    const size_t frame_bytes = x_kind == DINOSEG_INPUT_U8_HWC ? (size_t)r * r * 3 : (size_t)r * r * 3 * sizeof(float);
+    const long n = (long)(H / 8) * (W / 8);
+    const size_t frame_bytes = x_kind == DINOSEG_INPUT_U8_HWC ? (size_t)H * W * 3 : (size_t)H * W * 3 * sizeof(float);
     const void* x1 = reinterpret_cast<const char*>(x) + (size_t)B0 * frame_bytes;
     const long ntok_ = n + 1;
     if (mlp_fuse_wanted(h, B * ntok_)) DSEG_TRY(ensure_mlp_packs(h, s));   // before the fork: both halves read them
     DSEG_CHECK_HIP(hipEventRecord(h->ev_fork, s));
     DSEG_CHECK_HIP(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
     h->in_split = true;
-    const int rc0 = forward_impl(h, x, x_kind, B0, r, logp_out, argmax_out, -1, nullptr, nullptr, stream, nullptr, 0, B);
-    const int rc1 = forward_impl(h, x1, x_kind, B1, r, logp_out ? logp_out + (size_t)B0 * n * h->cfg.n_classes : nullptr,
+    const int rc0 = forward_impl(h, x, x_kind, B0, H, W, logp_out, argmax_out, -1, nullptr, nullptr, stream, nullptr, 0, B);
+    const int rc1 = forward_impl(h, x1, x_kind, B1, H, W, logp_out ? logp_out + (size_t)B0 * n * h->cfg.n_classes : nullptr,
                                  argmax_out ? argmax_out + (size_t)B0 * n : nullptr, -1, nullptr, nullptr, h->aux_stream, nullptr, 1, B);
     h->in_split = false;
     // join even after an error: the caller's stream must not run ahead of work already queued on the internal one
@@ -935,37 +953,57 @@ extern "C" int dinoseg_forward(dinoseg_handle* h, const void* x, int32_t x_kind,
     return rc0 ? rc0 : rc1;
 }
 
-extern "C" int dinoseg_last_selfattention(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* attn_out,
-                                          void* stream) {
+extern "C" int dinoseg_forward(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* logp_out,
+                               int32_t* argmax_out, int32_t tap_block, float* tap_out, void* stream) {
+    return dinoseg_forward_hw(h, x, x_kind, B, r, r, logp_out, argmax_out, tap_block, tap_out, stream);
+}
+
+extern "C" int dinoseg_last_selfattention_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W,
+                                             float* attn_out, void* stream) {
     if (!attn_out || !h || h->cfg.n_blocks < 1) {
         dinoseg_set_error("dinoseg_last_selfattention: needs an output buffer and at least one block");
         return -1;
     }
-    return forward_impl(h, x, x_kind, B, r, nullptr, nullptr, -1, nullptr, attn_out, stream);
+    return forward_impl(h, x, x_kind, B, H, W, nullptr, nullptr, -1, nullptr, attn_out, stream);
 }
 
-extern "C" int dinoseg_forward_mask(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t r, const float* cls_mask,
-                                    int32_t n_masks, float* emb_out, float* attn_out, void* stream) {
+extern "C" int dinoseg_last_selfattention(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* attn_out,
+                                          void* stream) {
+    return dinoseg_last_selfattention_hw(h, x, x_kind, B, r, r, attn_out, stream);
+}
+
+extern "C" int dinoseg_forward_mask_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t H, int32_t W, const float* cls_mask,
+                                       int32_t n_masks, float* emb_out, float* attn_out, void* stream) {
     if (!h || h->cfg.n_blocks < 1 || !cls_mask || n_masks < 1 || (!emb_out && !attn_out)) {
         dinoseg_set_error("dinoseg_forward_mask: needs at least one block, n_masks >= 1 masks and one output buffer");
         return -1;
     }
-    if (r > 0 && r % 8 == 0 && n_masks >= (r / 8) * (r / 8) + 1) {
-        dinoseg_set_error("dinoseg_forward_mask: n_masks=%d must be smaller than the token count %d", n_masks, (r / 8) * (r / 8) + 1);
+    if (frame_ok(H, W) && n_masks >= (H / 8) * (W / 8) + 1) {
+        dinoseg_set_error("dinoseg_forward_mask: n_masks=%d must be smaller than the token count %d", n_masks, (H / 8) * (W / 8) + 1);
         return -1;
     }
     const MaskRequest mr = {cls_mask, n_masks, emb_out, attn_out, nullptr, 0};
-    return forward_impl(h, x, x_kind, 1, r, nullptr, nullptr, -1, nullptr, nullptr, stream, &mr);
+    return forward_impl(h, x, x_kind, 1, H, W, nullptr, nullptr, -1, nullptr, nullptr, stream, &mr);
 }
 
-extern "C" int dinoseg_features(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, int32_t n_blocks,
-                                float* tokens_out, void* stream) {
+extern "C" int dinoseg_forward_mask(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t r, const float* cls_mask,
+                                    int32_t n_masks, float* emb_out, float* attn_out, void* stream) {
+    return dinoseg_forward_mask_hw(h, x, x_kind, r, r, cls_mask, n_masks, emb_out, attn_out, stream);
+}
+
+extern "C" int dinoseg_features_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t n_blocks,
+                                   float* tokens_out, void* stream) {
     if (!h || !tokens_out || n_blocks < 0 || n_blocks > h->cfg.n_blocks) {
         dinoseg_set_error("dinoseg_features: needs an output buffer and 0 <= n_blocks <= %d", h ? h->cfg.n_blocks : 0);
         return -1;
     }
     const MaskRequest mr = {nullptr, 0, nullptr, nullptr, tokens_out, n_blocks};
-    return forward_impl(h, x, x_kind, B, r, nullptr, nullptr, -1, nullptr, nullptr, stream, &mr);
+    return forward_impl(h, x, x_kind, B, H, W, nullptr, nullptr, -1, nullptr, nullptr, stream, &mr);
+}
+
+extern "C" int dinoseg_features(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, int32_t n_blocks,
+                                float* tokens_out, void* stream) {
+    return dinoseg_features_hw(h, x, x_kind, B, r, r, n_blocks, tokens_out, stream);
 }
 
 extern "C" int dinoseg_op_resize_u8(const uint8_t* src, int32_t sh, int32_t sw, uint8_t* dst, int32_t dh, int32_t dw, void* stream) {
@@ -1434,20 +1472,33 @@ extern "C" int dinoseg_op_layernorm(const float* x, const float* gamma, const fl
                             drop_cls, ntok, reinterpret_cast<hipStream_t>(stream), options().op_fmt);
 }
 
-extern "C" int dinoseg_op_pos_resample(const float* pos_embed, int32_t g, int32_t D, int32_t o, float* out, void* stream) {
-    return launch_pos_resample(pos_embed, g, D, o, out, reinterpret_cast<hipStream_t>(stream));
+extern "C" int dinoseg_op_pos_resample_hw(const float* pos_embed, int32_t g, int32_t D, int32_t oh, int32_t ow, float* out, void* stream) {
+    if (!pos_embed || !out || g <= 0 || D <= 0 || oh <= 0 || ow <= 0) {
+        dinoseg_set_error("dinoseg_op_pos_resample: bad argument");
+        return -1;
+    }
+    return launch_pos_resample(pos_embed, g, D, oh, ow, out, reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" int dinoseg_op_patch_gather(const void* x, int32_t x_kind, int32_t B, int32_t r, void* out, int64_t out_plane,
-                                       int32_t planes, void* stream) {
-    if (r <= 0 || r % 8 != 0) {
+extern "C" int dinoseg_op_pos_resample(const float* pos_embed, int32_t g, int32_t D, int32_t o, float* out, void* stream) {
+    return dinoseg_op_pos_resample_hw(pos_embed, g, D, o, o, out, stream);
+}
+
+extern "C" int dinoseg_op_patch_gather_hw(const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, void* out, int64_t out_plane,
+                                          int32_t planes, void* stream) {
+    if (!frame_ok(H, W)) {
         dinoseg_set_error("Resolution should be a multiple of 8.");
         return -1;
     }
     float mean255[3], inv255[3];
     norm_consts(mean255, inv255);
-    return launch_patch_gather(x, x_kind, B, r, mean255, inv255, reinterpret_cast<bf16_t*>(out), out_plane, planes,
+    return launch_patch_gather(x, x_kind, B, H, W, mean255, inv255, reinterpret_cast<bf16_t*>(out), out_plane, planes,
                                reinterpret_cast<hipStream_t>(stream), planes == 2 ? options().op_fmt : FMT_BF16);
+}
+
+extern "C" int dinoseg_op_patch_gather(const void* x, int32_t x_kind, int32_t B, int32_t r, void* out, int64_t out_plane,
+                                       int32_t planes, void* stream) {
+    return dinoseg_op_patch_gather_hw(x, x_kind, B, r, r, out, out_plane, planes, stream);
 }
 
 extern "C" int dinoseg_op_head_final(const void* in, int64_t in_plane, int32_t ld, int32_t M, int32_t K, const float* Wc,

@@ -202,27 +202,28 @@ int launch_layernorm(const float* x, const float* gamma, const float* beta, floa
 
 // ------------------------------------------------------------------------------------------------
 // Patch gather for Conv2d(3, D, kernel 8, stride 8) as a GEMM (vision_transformer.py:153,157):
-// out[b*n + py*o + px][c*64 + ky*8 + kx] = pixel(b, c, py*8+ky, px*8+kx).
+// out[b*n + py*wp + px][c*64 + ky*8 + kx] = pixel(b, c, py*8+ky, px*8+kx) for H x W frames, hp = H/8, wp = W/8, n = hp*wp
+// (PatchEmbed's flatten(2).transpose(1, 2): patches row-major over (hp, wp); square frames are H == W).
 // kind 0: uint8 HWC frames, with albumentations' Normalize fused: (u8 - 255*mean[c]) * (1 / (255*std[c]))
 //         (pl_torch_modules.py:37) -- frames stay uint8 on the wire (691 KB instead of 2.76 MB @480).
 // kind 1: fp32 CHW tensor as handed to DINOSeg.forward (pl_torch_modules.py:239).
-__global__ __launch_bounds__(256) void patch_gather_kernel(const void* __restrict__ xin, int kind, int B, int r,
+__global__ __launch_bounds__(256) void patch_gather_kernel(const void* __restrict__ xin, int kind, int B, int H, int W,
                                                            f32x4 mean255, f32x4 inv255, bf16_t* __restrict__ out,
                                                            long out_plane, int planes, int fmt) {
-    const int o = r >> 3;
-    const long total = (long)B * o * o * 8;   // one work item = (patch, ky): 8 pixels x 3 channels
+    const int hp = H >> 3, wp = W >> 3;
+    const long total = (long)B * hp * wp * 8;   // one work item = (patch, ky): 8 pixels x 3 channels
     for (long w = (long)blockIdx.x * blockDim.x + threadIdx.x; w < total; w += (long)gridDim.x * blockDim.x) {
         const int ky = (int)(w & 7);
         const long patch = w >> 3;
-        const int px = (int)(patch % o);
-        const int py = (int)((patch / o) % o);
-        const int b = (int)(patch / ((long)o * o));
+        const int px = (int)(patch % wp);
+        const int py = (int)((patch / wp) % hp);
+        const int b = (int)(patch / ((long)hp * wp));
         float v[3][8];
         if (kind == 0) {
-            const uint8_t* src = reinterpret_cast<const uint8_t*>(xin) + (((long)b * r + py * 8 + ky) * r + px * 8) * 3;
+            const uint8_t* src = reinterpret_cast<const uint8_t*>(xin) + (((long)b * H + py * 8 + ky) * W + px * 8) * 3;
             uint32_t raw[6];
 #pragma unroll
-            for (int i = 0; i < 6; ++i) raw[i] = reinterpret_cast<const uint32_t*>(src)[i];   // 24 B, 8-byte aligned
+            for (int i = 0; i < 6; ++i) raw[i] = reinterpret_cast<const uint32_t*>(src)[i];   // 24 B, 8-byte aligned (W % 8 == 0)
 #pragma unroll
             for (int kx = 0; kx < 8; ++kx)
 #pragma unroll
@@ -235,7 +236,7 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const void* __restric
             const float* src = reinterpret_cast<const float*>(xin);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float* s = src + (((long)b * 3 + c) * r + py * 8 + ky) * r + px * 8;
+                const float* s = src + (((long)b * 3 + c) * H + py * 8 + ky) * W + px * 8;
                 const f32x4 a = *reinterpret_cast<const f32x4*>(s), bq = *reinterpret_cast<const f32x4*>(s + 4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -265,13 +266,13 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const void* __restric
     }
 }
 
-int launch_patch_gather(const void* x, int kind, int B, int r, const float* mean255, const float* inv_std255,
+int launch_patch_gather(const void* x, int kind, int B, int H, int W, const float* mean255, const float* inv_std255,
                         bf16_t* out, long out_plane, int planes, hipStream_t s, int fmt) {
-    const long total = (long)B * (r / 8) * (r / 8) * 8;
+    const long total = (long)B * (H / 8) * (W / 8) * 8;
     int grid = (int)((total + 255) / 256);
     if (grid > 4096) grid = 4096;
     f32x4 m = {mean255[0], mean255[1], mean255[2], 0.f}, iv = {inv_std255[0], inv_std255[1], inv_std255[2], 0.f};
-    hipLaunchKernelGGL(patch_gather_kernel, dim3(grid), dim3(256), 0, s, x, kind, B, r, m, iv, out, out_plane, planes, fmt);
+    hipLaunchKernelGGL(patch_gather_kernel, dim3(grid), dim3(256), 0, s, x, kind, B, H, W, m, iv, out, out_plane, planes, fmt);
     DSEG_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -294,8 +295,10 @@ int launch_cls_rows(float* X, const float* cls, const float* pos, int B, int nto
 
 // ------------------------------------------------------------------------------------------------
 // Pos-embed resample (vision_transformer.py:202-222): bicubic, A = -0.75, align_corners=False, source
-// coordinate (dst + 0.5) * (g / (o + 0.1)) - 0.5 (torch uses the GIVEN scale factor), taps clamped to the
-// border.  Parameter-only: run once per resolution and cached by the caller.  out: [o*o + 1, D], row 0 = class pos.
+// coordinate (dst + 0.5) * (g / (o + 0.1)) - 0.5 per axis (torch uses the GIVEN scale factor), taps clamped to the
+// border.  An hp x wp grid has one scale per axis: rows (g / (hp + 0.1)), columns (g / (wp + 0.1)) -- scale_factor=(w0/g, h0/g)
+// with w0 = H/8 + 0.1 from x.shape[2], h0 = W/8 + 0.1 from x.shape[3] (:224-225).  Parameter-only: run once per grid and cached by
+// the caller.  out: [hp*wp + 1, D], row 0 = class pos.
 __device__ __forceinline__ void cubic_w(float t, float w[4]) {
     const float A = -0.75f;
     const float x0 = t + 1.f, x1 = t, x2 = 1.f - t, x3 = 2.f - t;
@@ -305,9 +308,9 @@ __device__ __forceinline__ void cubic_w(float t, float w[4]) {
     w[3] = ((A * x3 - 5.f * A) * x3 + 8.f * A) * x3 - 4.f * A;
 }
 
-__global__ void pos_resample_kernel(const float* __restrict__ pe, int g, int D, int o, float scale,
+__global__ void pos_resample_kernel(const float* __restrict__ pe, int g, int D, int oh, int ow, float scale_y, float scale_x,
                                     float* __restrict__ out) {
-    const long total = ((long)o * o + 1) * D;
+    const long total = ((long)oh * ow + 1) * D;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int d = (int)(i % D);
         const long tokn = i / D;
@@ -315,8 +318,8 @@ __global__ void pos_resample_kernel(const float* __restrict__ pe, int g, int D, 
             out[i] = pe[d];
             continue;
         }
-        const int y = (int)((tokn - 1) / o), x = (int)((tokn - 1) % o);
-        const float sy = (y + 0.5f) * scale - 0.5f, sx = (x + 0.5f) * scale - 0.5f;
+        const int y = (int)((tokn - 1) / ow), x = (int)((tokn - 1) % ow);
+        const float sy = (y + 0.5f) * scale_y - 0.5f, sx = (x + 0.5f) * scale_x - 0.5f;
         const float fy = floorf(sy), fx = floorf(sx);
         float wy[4], wx[4];
         cubic_w(sy - fy, wy);
@@ -340,17 +343,20 @@ __global__ void pos_resample_kernel(const float* __restrict__ pe, int g, int D, 
     }
 }
 
-int launch_pos_resample(const float* pos_embed, int g, int D, int o, float* out, hipStream_t s) {
-    const long total = ((long)o * o + 1) * D;
-    if (o == g) {   // the reference returns the stored pos_embed untouched (vision_transformer.py:205-206)
+int launch_pos_resample(const float* pos_embed, int g, int D, int oh, int ow, float* out, hipStream_t s) {
+    const long total = ((long)oh * ow + 1) * D;
+    // the reference returns the stored pos_embed untouched only for npatch == g*g and w == h (vision_transformer.py:205-206): a
+    // rectangle with one side of g (or with hp*wp == g*g, 128x392) is resampled, at scale g / (g + 0.1) on that axis too
+    if (oh == g && ow == g) {
         DSEG_CHECK_HIP(hipMemcpyAsync(out, pos_embed, (size_t)total * sizeof(float), hipMemcpyDeviceToDevice, s));
         return 0;
     }
     int grid = (int)((total + 255) / 256);
     if (grid > 4096) grid = 4096;
     // torch: scale_factor = (o + 0.1) / g in double; ATen uses (float)(1.0 / scale_factor) for source coordinates
-    const float scale = (float)(1.0 / (((double)o + 0.1) / (double)g));
-    hipLaunchKernelGGL(pos_resample_kernel, dim3(grid), dim3(256), 0, s, pos_embed, g, D, o, scale, out);
+    const float scale_y = (float)(1.0 / (((double)oh + 0.1) / (double)g));
+    const float scale_x = (float)(1.0 / (((double)ow + 0.1) / (double)g));
+    hipLaunchKernelGGL(pos_resample_kernel, dim3(grid), dim3(256), 0, s, pos_embed, g, D, oh, ow, scale_y, scale_x, out);
     DSEG_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -55,17 +55,17 @@ struct dinoseg_handle {
     int64_t generation = 0;     // dinoseg_state_generation: bumped when an address or cached content a captured forward bakes in changes
     // pos-embed cache
     float* pos_cache = nullptr;
-    int pos_r = -1;             // resolution the cache holds (-1: nothing)
+    int pos_hp = -1, pos_wp = -1;   // patch grid (rows, columns) the cache holds (-1: nothing)
     bool pos_stale = false;     // dino.pos_embed was (re)bound since the cache was filled
     size_t pos_cap = 0;
     // activation workspace (library-owned)
     char* ws = nullptr;
     size_t ws_bytes = 0;
-    int ws_B = -1, ws_r = -1;
+    int ws_B = -1, ws_H = -1, ws_W = -1;
     // second half-batch of a split forward (option "streams" = 2): its own workspace, an internal stream, fork / join events
     char* ws2 = nullptr;
     size_t ws2_bytes = 0;
-    int ws2_B = -1, ws2_r = -1;
+    int ws2_B = -1, ws2_H = -1, ws2_W = -1;
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool in_split = false;                 // a split forward is being queued (both halves' launches share the chip)
@@ -74,8 +74,8 @@ struct dinoseg_handle {
     std::map<std::string, float*> grads;   // bound gradient buffers (absent / null = frozen tensor)
     char* tws = nullptr;                   // training workspace: saved activations + backward scratch
     size_t tws_bytes = 0;
-    int tws_B = -1, tws_r = -1;
-    int tr_B = -1, tr_r = -1;              // batch / resolution of the saved forward dinoseg_backward will differentiate
+    int tws_B = -1, tws_H = -1, tws_W = -1;
+    int tr_B = -1, tr_H = -1, tr_W = -1;   // batch / frame size of the saved forward dinoseg_backward will differentiate
     int* bad_label_flag = nullptr;         // sticky "a label outside [0, C) other than -100 was seen" (device int, owned by the handle:
                                            // it must survive the training workspace being re-laid out for another batch shape)
     // gradient-stage events of the last backward (dinoseg_stream_wait_grad_stage): stage 0 = head, 1 + k = final norm and block

@@ -240,15 +240,15 @@ int launch_layernorm(const float* x, const float* gamma, const float* beta, floa
                      bf16_t* out, long out_plane, int planes, float* out_f32, int drop_cls, int ntok, hipStream_t s, int fmt = 0);
 
 // Patch gather ("im2col") for the 8x8/stride-8 patch embedding. k index = c*64 + ky*8 + kx.
-// kind 0: uint8 HWC frames [B,r,r,3] with the ImageNet normalisation fused; kind 1: fp32 CHW [B,3,r,r] as is.
-int launch_patch_gather(const void* x, int kind, int B, int r, const float* mean255, const float* inv_std255,
+// kind 0: uint8 HWC frames [B,H,W,3] with the ImageNet normalisation fused; kind 1: fp32 CHW [B,3,H,W] as is.  H, W multiples of 8.
+int launch_patch_gather(const void* x, int kind, int B, int H, int W, const float* mean255, const float* inv_std255,
                         bf16_t* out, long out_plane, int planes, hipStream_t s, int fmt = 0);
 
 // X[b*ntok + 0, :] = cls[:] + pos[0, :]
 int launch_cls_rows(float* X, const float* cls, const float* pos, int B, int ntok, int D, hipStream_t s);
 
-// Bicubic (A=-0.75, align_corners=False, scale_factor rule) resample of the patch pos-embed grid.
-int launch_pos_resample(const float* pos_embed, int g, int D, int o, float* out, hipStream_t s);
+// Bicubic (A=-0.75, align_corners=False, scale_factor rule) resample of the g x g patch pos-embed grid to oh x ow (one scale per axis).
+int launch_pos_resample(const float* pos_embed, int g, int D, int oh, int ow, float* out, hipStream_t s);
 
 // Final classifier layer + log_softmax + argmax.  in: bf16 hi/lo planes [2][M][ld]; W fp32 [C][K].  C <= 32 runs head_final_kernel;
 // 33 <= C <= HEAD_WIDE_MAX_C runs the wide MFMA kernel on Wp, the classifier packed as hi+lo planes [round_up(C, 32)][ld].
@@ -310,7 +310,7 @@ DetScratch& det_scratch();
 int launch_det_finalize(const float* part, int nparts, int width, int ld, float* dst, hipStream_t s);
 int launch_splitk_reduce(const float* part, int ks, long stride, int rows, int ld_part, float* out, int ldo, int cols, hipStream_t s);
 int launch_batch_sum_rows(const float* X, int B, int ntok, int D, float* out, hipStream_t s);
-int launch_pos_resample_bwd(const float* dpos, int g, int D, int o, float* dpe, float* scratch /* g*o*D floats */, hipStream_t s);
+int launch_pos_resample_bwd(const float* dpos, int g, int D, int oh, int ow, float* dpe, float* scratch /* g*ow*D floats */, hipStream_t s);
 constexpr int MULTI_MAX = 64;       // tensors per multi-tensor launch (table passed as a kernel argument)
 int launch_multi_adam(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long* n, float lr,
                       float b1, float b2, float eps, float wd, int decoupled, int step, float gscale, hipStream_t s);

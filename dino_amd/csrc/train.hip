@@ -705,29 +705,31 @@ __device__ __forceinline__ float tap_weight(int y, int yy, int g, float scale) {
     }
     return acc;
 }
-__device__ __forceinline__ void tap_range(int yy, int g, int o, float scale, int& lo, int& hi) {
+__device__ __forceinline__ void tap_range(int yy, int g, int o, float scale, int& lo, int& hi) {      // (o, scale: the axis' own)
     // outputs y whose taps can reach yy: floor(sy) in [yy - 2, yy + 1] (all smaller / larger ones too at the clamped borders)
     lo = (int)floorf(((float)(yy - 2) + 0.5f) / scale - 0.5f) - 1;
     hi = (int)ceilf(((float)(yy + 2) + 0.5f) / scale - 0.5f) + 1;
     if (yy == 0 || lo < 0) lo = 0;
     if (yy == g - 1 || hi > o - 1) hi = o - 1;
 }
-// separable: pass 1 sums the rows (tmp[yy][x][d] = sum_y Wy(y, yy) dpos[y][x][d]), pass 2 the columns into the stored gradient
-__global__ void pos_resample_bwd_rows_kernel(const float* __restrict__ dpos, int g, int D, int o, float scale, float* __restrict__ tmp) {
-    const long total = (long)g * o * D;
+// separable: pass 1 sums the oh rows (tmp[yy][x][d] = sum_y Wy(y, yy) dpos[y][x][d], scale_y), pass 2 the ow columns (scale_x)
+// into the stored gradient; tmp is [g][ow][D]
+__global__ void pos_resample_bwd_rows_kernel(const float* __restrict__ dpos, int g, int D, int oh, int ow, float scale_y,
+                                             float* __restrict__ tmp) {
+    const long total = (long)g * ow * D;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int d = (int)(i % D);
         const long t = i / D;
-        const int x = (int)(t % o), yy = (int)(t / o);
+        const int x = (int)(t % ow), yy = (int)(t / ow);
         int ylo, yhi;
-        tap_range(yy, g, o, scale, ylo, yhi);
+        tap_range(yy, g, oh, scale_y, ylo, yhi);
         float acc = 0.f;
-        for (int y = ylo; y <= yhi; ++y) acc = fmaf(tap_weight(y, yy, g, scale), dpos[(1 + (long)y * o + x) * D + d], acc);
+        for (int y = ylo; y <= yhi; ++y) acc = fmaf(tap_weight(y, yy, g, scale_y), dpos[(1 + (long)y * ow + x) * D + d], acc);
         tmp[i] = acc;
     }
 }
-__global__ void pos_resample_bwd_cols_kernel(const float* __restrict__ dpos, const float* __restrict__ tmp, int g, int D, int o,
-                                             float scale, float* __restrict__ dpe) {
+__global__ void pos_resample_bwd_cols_kernel(const float* __restrict__ dpos, const float* __restrict__ tmp, int g, int D, int ow,
+                                             float scale_x, float* __restrict__ dpe) {
     const long total = ((long)g * g + 1) * D;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int d = (int)(i % D);
@@ -738,9 +740,9 @@ __global__ void pos_resample_bwd_cols_kernel(const float* __restrict__ dpos, con
         }
         const int yy = (int)((tokn - 1) / g), xx = (int)((tokn - 1) % g);
         int xlo, xhi;
-        tap_range(xx, g, o, scale, xlo, xhi);
+        tap_range(xx, g, ow, scale_x, xlo, xhi);
         float acc = 0.f;
-        for (int x = xlo; x <= xhi; ++x) acc = fmaf(tap_weight(x, xx, g, scale), tmp[((long)yy * o + x) * D + d], acc);
+        for (int x = xlo; x <= xhi; ++x) acc = fmaf(tap_weight(x, xx, g, scale_x), tmp[((long)yy * ow + x) * D + d], acc);
         dpe[i] += acc;
     }
 }
@@ -748,21 +750,22 @@ __global__ void pos_identity_bwd_kernel(const float* __restrict__ dpos, long tot
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) dpe[i] += dpos[i];
 }
 
-// scratch: g * o * D floats (the row pass)
-int launch_pos_resample_bwd(const float* dpos, int g, int D, int o, float* dpe, float* scratch, hipStream_t s) {
-    const float scale = (float)(1.0 / (((double)o + 0.1) / (double)g));
-    if (o == g) {      // identity grid
+// scratch: g * ow * D floats (the row pass)
+int launch_pos_resample_bwd(const float* dpos, int g, int D, int oh, int ow, float* dpe, float* scratch, hipStream_t s) {
+    const float scale_y = (float)(1.0 / (((double)oh + 0.1) / (double)g));
+    const float scale_x = (float)(1.0 / (((double)ow + 0.1) / (double)g));
+    if (oh == g && ow == g) {      // identity grid (square frames only: launch_pos_resample)
         const long total = ((long)g * g + 1) * D;
         hipLaunchKernelGGL(pos_identity_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dpos, total, dpe);
         DSEG_CHECK_HIP(hipGetLastError());
         return 0;
     }
-    const long t1 = (long)g * o * D, t2 = ((long)g * g + 1) * D;
+    const long t1 = (long)g * ow * D, t2 = ((long)g * g + 1) * D;
     int g1 = (int)((t1 + 255) / 256), g2 = (int)((t2 + 255) / 256);
     if (g1 > 8192) g1 = 8192;
     if (g2 > 8192) g2 = 8192;
-    hipLaunchKernelGGL(pos_resample_bwd_rows_kernel, dim3(g1), dim3(256), 0, s, dpos, g, D, o, scale, scratch);
-    hipLaunchKernelGGL(pos_resample_bwd_cols_kernel, dim3(g2), dim3(256), 0, s, dpos, scratch, g, D, o, scale, dpe);
+    hipLaunchKernelGGL(pos_resample_bwd_rows_kernel, dim3(g1), dim3(256), 0, s, dpos, g, D, oh, ow, scale_y, scratch);
+    hipLaunchKernelGGL(pos_resample_bwd_cols_kernel, dim3(g2), dim3(256), 0, s, dpos, scratch, g, D, ow, scale_x, dpe);
     DSEG_CHECK_HIP(hipGetLastError());
     return 0;
 }

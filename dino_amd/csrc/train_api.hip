@@ -36,14 +36,15 @@ struct TrainLayout {
     size_t zero_begin, zero_end;      // Q/K/V of every block (pad rows must be zero)
     size_t total;
     long a_plane, qkv_plane, f_plane, feat_plane, h1_plane, h2_plane, dz_plane, patch_plane, g_plane, t_plane;
+    size_t t2_bytes;
 };
 
-TrainLayout make_train_layout(const dinoseg_handle* h, int B, int r) {
+TrainLayout make_train_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
     const dinoseg_config& c = h->cfg;
     const int D = c.embed_dim, F = D * c.mlp_ratio, P = h->planes, HP = head_planes();
     TrainLayout L;
     memset(&L, 0, sizeof(L));
-    L.n = (r / 8) * (r / 8);
+    L.n = (Hf / 8) * (Wf / 8);
     L.ntok = L.n + 1;
     L.npad = (L.ntok + 63) / 64 * 64;
     L.M = B * L.ntok;
@@ -99,7 +100,12 @@ TrainLayout make_train_layout(const dinoseg_handle* h, int B, int r) {
     }
     L.t_plane = (long)L.Cmax * L.Mpad;
     L.T1 = take((size_t)2 * L.t_plane * 2);
-    L.T2 = take((size_t)2 * L.t_plane * 2);
+    {   // ... T2 also hosts the row pass of the pos-embed gradient, [pos_grid][W/8][D] floats: a strip a few patches high (8 x 480)
+        // has fewer token rows than that (on every frame of at least 7 x 7 patches the planes are the larger)
+        const size_t t_bytes = (size_t)2 * L.t_plane * 2, pos_bytes = (size_t)c.pos_grid * (Wf / 8) * D * sizeof(float);
+        L.T2 = take(t_bytes > pos_bytes ? t_bytes : pos_bytes);
+        L.t2_bytes = t_bytes > pos_bytes ? t_bytes : pos_bytes;
+    }
     L.NLSE = take((size_t)B * c.num_heads * L.npad * 4);
     L.NDEL = take((size_t)B * c.num_heads * L.npad * 4);
     L.DPOS = take((size_t)L.ntok * D * 4);
@@ -221,12 +227,13 @@ extern "C" int dinoseg_op_layernorm_bwd(const float* dy, const float* x, const f
 // ------------------------------------------------------------------------------------------------ the step
 // Forward with saved activations (DINOSeg.forward under autograd, pl_torch_modules.py:239-256).  The saved state stays valid
 // until the next call; train_backward_impl consumes it.
-static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* logp_out, hipStream_t s) {
+static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t Hf, int32_t Wf, float* logp_out,
+                              hipStream_t s) {
     if (!h || !x || B <= 0) {
         dinoseg_set_error("dinoseg_train_forward: bad argument");
         return -1;
     }
-    if (r <= 0 || r % 8 != 0) {
+    if (Hf <= 0 || Wf <= 0 || Hf % 8 != 0 || Wf % 8 != 0) {
         dinoseg_set_error("Resolution should be a multiple of 8.");
         return -1;
     }
@@ -244,12 +251,12 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
     }
     h->tr_B = -1;       // no valid saved forward until this one has been enqueued completely
     DSEG_TRY(check_stream_device(h, s));
-    DSEG_TRY(dinoseg_prepare_resolution(h, r, reinterpret_cast<void*>(s)));
+    DSEG_TRY(dinoseg_prepare_resolution_hw(h, Hf, Wf, reinterpret_cast<void*>(s)));
     const dinoseg_config& c = h->cfg;
     const int D = c.embed_dim, F = D * c.mlp_ratio, P = h->planes, HP = head_planes(), H = c.num_heads, C = c.n_classes;
     const int NB = c.n_blocks;
     const bool mlp_head = c.head_kind == DINOSEG_HEAD_MLP;
-    const TrainLayout L = make_train_layout(h, B, r);
+    const TrainLayout L = make_train_layout(h, B, Hf, Wf);
 
     // ---- workspace
     if (!h->bad_label_flag) {       // (its own allocation: a change of batch shape re-lays the workspace, the latched flag must survive it)
@@ -268,12 +275,13 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
         h->tws_B = -1;
     }
     char* ws = h->tws;
-    if (h->tws_B != B || h->tws_r != r) {
+    if (h->tws_B != B || h->tws_H != Hf || h->tws_W != Wf) {
         for (int l = 0; l < NB; ++l)   // Q/K/V pad rows must be zero (never written afterwards)
             DSEG_CHECK_HIP(hipMemsetAsync(ws + L.Q + l * L.blk_stride, 0, L.LSE - L.Q, s));
         DSEG_CHECK_HIP(hipMemsetAsync(ws + L.ACC, 0, 256, s));
         h->tws_B = B;
-        h->tws_r = r;
+        h->tws_H = Hf;
+        h->tws_W = Wf;
     }
     auto F32 = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
     auto B16 = [&](size_t o) { return reinterpret_cast<bf16_t*>(ws + o); };
@@ -282,7 +290,7 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
     float mean255[3], inv255[3];
     norm_consts(mean255, inv255);
     bf16_t* PATCH = B16(L.PATCH);
-    DSEG_TRY(launch_patch_gather(x, x_kind, B, r, mean255, inv255, PATCH, L.patch_plane, P, s));
+    DSEG_TRY(launch_patch_gather(x, x_kind, B, Hf, Wf, mean255, inv255, PATCH, L.patch_plane, P, s));
     float* X0 = NB > 0 ? F32(L.Xin) : F32(L.Xfin);
     {
         const PackedLinear& pk = h->packed.at("dino.patch_embed.proj.weight");
@@ -405,7 +413,8 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
     }
     if (logp_out) DSEG_CHECK_HIP(hipMemcpyAsync(logp_out, LOGP, (size_t)L.Mp * C * 4, hipMemcpyDeviceToDevice, s));
     h->tr_B = B;
-    h->tr_r = r;
+    h->tr_H = Hf;
+    h->tr_W = Wf;
     return 0;
 }
 
@@ -426,12 +435,12 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
         dinoseg_set_error("dinoseg_backward: weights were re-bound after the forward; run the forward again");
         return -3;
     }
-    const int B = h->tr_B, r = h->tr_r;
+    const int B = h->tr_B, oh = h->tr_H / 8, ow = h->tr_W / 8;
     const dinoseg_config& c = h->cfg;
     const int D = c.embed_dim, F = D * c.mlp_ratio, P = h->planes, HP = head_planes(), H = c.num_heads, C = c.n_classes;
     const int NB = c.n_blocks;
     const bool mlp_head = c.head_kind == DINOSEG_HEAD_MLP;
-    const TrainLayout L = make_train_layout(h, B, r);
+    const TrainLayout L = make_train_layout(h, B, h->tr_H, h->tr_W);
     char* ws = h->tws;
     auto F32 = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
     auto B16 = [&](size_t o) { return reinterpret_cast<bf16_t*>(ws + o); };
@@ -785,14 +794,13 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
     DSEG_TRY(launch_batch_sum_rows(dX, B, L.ntok, D, dpos, s));
     if (grad("dino.cls_token"))
         DSEG_CHECK_HIP(hipMemcpyAsync(grad("dino.cls_token"), dpos, (size_t)D * 4, hipMemcpyDeviceToDevice, s));
-    // (scratch: the T2 transpose buffer, idle until the patch-embed gradient below; [pos_grid][r/8][D] floats fit its >= Mppad x 256 bf16)
+    // (scratch: the T2 transpose buffer, idle until the patch-embed gradient below; make_train_layout sizes it for [pos_grid][W/8][D] floats)
     if (grad("dino.pos_embed")) {
-        // (T2 is allocated with two planes whatever the precision: make_train_layout)
-        if ((size_t)c.pos_grid * (r / 8) * D * sizeof(float) > (size_t)2 * L.t_plane * sizeof(bf16_t)) {
-            dinoseg_set_error("dinoseg_backward: pos-embed scratch does not fit (pos_grid %d, grid %d)", c.pos_grid, r / 8);
+        if ((size_t)c.pos_grid * ow * D * sizeof(float) > L.t2_bytes) {
+            dinoseg_set_error("dinoseg_backward: pos-embed scratch does not fit (pos_grid %d, grid %d x %d)", c.pos_grid, oh, ow);
             return -1;
         }
-        DSEG_TRY(launch_pos_resample_bwd(dpos, c.pos_grid, D, r / 8, grad("dino.pos_embed"), reinterpret_cast<float*>(T2), s));
+        DSEG_TRY(launch_pos_resample_bwd(dpos, c.pos_grid, D, oh, ow, grad("dino.pos_embed"), reinterpret_cast<float*>(T2), s));
     }
     DSEG_TRY(launch_transpose_planes(dX, nullptr, 0, D, L.Mp, D, T1, tpl, pad128(D), L.Mppad, nullptr, 0, 0,
                                      grad("dino.patch_embed.proj.bias"), P, 1, L.ntok, s));
@@ -803,10 +811,15 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
     return stage_mark(NB + 1);
 }
 
+extern "C" int dinoseg_train_forward_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W,
+                                        float* logp_out, void* stream) {
+    DeviceGuard guard(h);
+    return train_forward_impl(h, x, x_kind, B, H, W, logp_out, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int dinoseg_train_forward(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* logp_out,
                                      void* stream) {
-    DeviceGuard guard(h);
-    return train_forward_impl(h, x, x_kind, B, r, logp_out, reinterpret_cast<hipStream_t>(stream));
+    return dinoseg_train_forward_hw(h, x, x_kind, B, r, r, logp_out, stream);
 }
 
 // The backward forks weight-gradient kernels onto the handle's side stream (option train_streams = 2) and joins them before it
@@ -826,16 +839,21 @@ extern "C" int dinoseg_backward(dinoseg_handle* h, const float* dlogp, void* str
     return backward_joined(h, nullptr, dlogp, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" int dinoseg_train_step(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r,
-                                  const int64_t* labels, float* loss_out, float* logp_out, void* stream) {
+extern "C" int dinoseg_train_step_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W,
+                                     const int64_t* labels, float* loss_out, float* logp_out, void* stream) {
     if (!labels || !loss_out) {
         dinoseg_set_error("dinoseg_train_step: bad argument");
         return -1;
     }
     DeviceGuard guard(h);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    DSEG_TRY(train_forward_impl(h, x, x_kind, B, r, logp_out, s));
+    DSEG_TRY(train_forward_impl(h, x, x_kind, B, H, W, logp_out, s));
     return backward_joined(h, labels, nullptr, loss_out, s);
+}
+
+extern "C" int dinoseg_train_step(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r,
+                                  const int64_t* labels, float* loss_out, float* logp_out, void* stream) {
+    return dinoseg_train_step_hw(h, x, x_kind, B, r, r, labels, loss_out, logp_out, stream);
 }
 
 extern "C" int dinoseg_grad_stages(const dinoseg_handle* h) { return h ? h->cfg.n_blocks + 2 : -1; }

@@ -155,7 +155,7 @@ class _ViTParams(nn.Module):
         return state
 
     def forward(self, x: torch.Tensor, all: bool = True, intermediate=False) -> torch.Tensor:
-        """VisionTransformer.forward (vision_transformer.py:237-248): fp32 [B,3,r,r] -> final-norm tokens [B, N, D]
+        """VisionTransformer.forward (vision_transformer.py:237-248): fp32 [B,3,H,W] -> final-norm tokens [B, N, D]
         (``all=False``: the CLS row [B, D]); ``intermediate=k`` returns ``norm(x)`` of ALL tokens after block k, whatever ``all``
         says (:241-242) -- unless k is past the last block, where the loop never exits early and ``all`` applies (:243-248)."""
         owner = self._owner()
@@ -200,8 +200,8 @@ class _DinoSegFunction(torch.autograd.Function):
     backward = dinoseg_backward(d loss / d logp).  The parameters are inputs only so that autograd routes their gradients."""
 
     @staticmethod
-    def forward(ctx, model, x, kind, B, r, *params):
-        logp = model._autograd_forward(x, kind, B, r)
+    def forward(ctx, model, x, kind, B, H, W, *params):
+        logp = model._autograd_forward(x, kind, B, H, W)
         ctx.model = model
         ctx.epoch = model._fwd_epoch
         ctx.params = params
@@ -210,7 +210,7 @@ class _DinoSegFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogp):
         grads = ctx.model._autograd_backward(dlogp, ctx.epoch, ctx.params)
-        return (None, None, None, None, None) + grads
+        return (None, None, None, None, None, None) + grads
 
 
 # --------------------------------------------------------------------------- the model
@@ -447,54 +447,55 @@ class DINOSeg(nn.Module):
         self.transforms = get_transforms(resolution)
         self.resolution = resolution
 
-    def _run(self, x: torch.Tensor, kind: int, B: int, r: int, want_logp: bool = True, want_argmax: bool = False,
+    def _run(self, x: torch.Tensor, kind: int, B: int, H: int, W: int, want_logp: bool = True, want_argmax: bool = False,
              tap_block: int = -1):
         self._sync_weights()
-        n = (r // 8) ** 2
+        n = (H // 8) * (W // 8)
         dev = x.device
         logp = torch.empty((B * n, self.cfg.n_classes), dtype=torch.float32, device=dev) if want_logp else None
         amax = torch.empty((B * n,), dtype=torch.int32, device=dev) if want_argmax else None
         tap = (torch.empty((B * (n + 1), self.cfg.embed_dim), dtype=torch.float32, device=dev)
                if tap_block >= 0 else None)
-        capi.check(capi.lib().dinoseg_forward(self._handle, x.data_ptr(), kind, B, r, capi.ptr(logp), capi.ptr(amax),
-                                              tap_block, capi.ptr(tap), self._stream()))
+        capi.check(capi.lib().dinoseg_forward_hw(self._handle, x.data_ptr(), kind, B, H, W, capi.ptr(logp), capi.ptr(amax),
+                                                 tap_block, capi.ptr(tap), self._stream()))
         return logp, amax, tap
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """fp32 [B,3,r,r] (normalised) -> fp32 [B*(r/8)^2, n_classes] log-probabilities (pl_torch_modules.py:239-256).
+        """fp32 [B,3,H,W] (normalised; H, W multiples of 8) -> fp32 [B*(H/8)*(W/8), n_classes] log-probabilities, patches row-major
+        (pl_torch_modules.py:239-256; the ViT takes H x W frames, vision_transformer.py:202-235).
         With grad enabled and at least one trainable parameter the result carries an autograd graph: its backward calls
         ``dinoseg_backward`` and hands d loss / d parameter to torch (x itself gets no gradient: the reference never asks)."""
         self._require_gpu()
-        x, kind, B, r = self._prep_batch(x)
+        x, kind, B, H, W = self._prep_batch(x)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            return _DinoSegFunction.apply(self, x, kind, B, r, *self.parameters())
-        logp, _, _ = self._run(x, kind, B, r)
+            return _DinoSegFunction.apply(self, x, kind, B, H, W, *self.parameters())
+        logp, _, _ = self._run(x, kind, B, H, W)
         return logp
 
     def features(self, x: torch.Tensor, n_blocks: int = 0) -> torch.Tensor:
         """``model.dino(x)``: final-norm tokens fp32 [B, N, D] after `n_blocks` blocks (0 = all), CLS token first
         (VisionTransformer.forward, vision_transformer.py:237-248).  Inference only (no autograd graph)."""
         self._require_gpu()
-        x, kind, B, r = self._prep_batch(x)
+        x, kind, B, H, W = self._prep_batch(x)
         if not 0 <= n_blocks <= self.cfg.n_blocks:
             raise ValueError(f"intermediate must be in [0, {self.cfg.n_blocks}]")
         self._sync_weights()
-        out = torch.empty((B, (r // 8) ** 2 + 1, self.cfg.embed_dim), dtype=torch.float32, device=self.device)
-        capi.check(capi.lib().dinoseg_features(self._handle, x.data_ptr(), kind, B, r, n_blocks, out.data_ptr(), self._stream()))
+        out = torch.empty((B, (H // 8) * (W // 8) + 1, self.cfg.embed_dim), dtype=torch.float32, device=self.device)
+        capi.check(capi.lib().dinoseg_features_hw(self._handle, x.data_ptr(), kind, B, H, W, n_blocks, out.data_ptr(),
+                                                  self._stream()))
         return out
 
     @torch.no_grad()
     def forward_frames(self, frames_u8: torch.Tensor, want_logp: bool = True):
-        """uint8 [B,r,r,3] device frames -> (log-probs or None, int32 argmax [B*(r/8)^2]).
+        """uint8 [B,H,W,3] device frames -> (log-probs or None, int32 argmax [B*(H/8)*(W/8)]).
         The batched form of predict(): normalisation is fused into the patch gather on device."""
         self._require_gpu()
-        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 \
-                or frames_u8.shape[1] != frames_u8.shape[2]:
-            raise ValueError(f"expected uint8 [B,r,r,3], got {frames_u8.dtype} {tuple(frames_u8.shape)}")
-        if frames_u8.shape[1] % 8 != 0:
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+            raise ValueError(f"expected uint8 [B,H,W,3], got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+        if frames_u8.shape[1] % 8 != 0 or frames_u8.shape[2] % 8 != 0:
             raise ValueError("Resolution should be a multiple of 8.")
         frames_u8 = frames_u8.to(self.device).contiguous()
-        logp, amax, _ = self._run(frames_u8, capi.INPUT_U8_HWC, frames_u8.shape[0], frames_u8.shape[1],
+        logp, amax, _ = self._run(frames_u8, capi.INPUT_U8_HWC, frames_u8.shape[0], frames_u8.shape[1], frames_u8.shape[2],
                                   want_logp=want_logp, want_argmax=True)
         return logp, amax
 
@@ -569,47 +570,47 @@ class DINOSeg(nn.Module):
     def debug_tokens(self, x: torch.Tensor, block: int) -> torch.Tensor:
         """Token matrix [B, N, D] after prepare_tokens (block=0) or after transformer block `block`."""
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
-        _, _, tap = self._run(x, capi.INPUT_F32_CHW, x.shape[0], x.shape[2], tap_block=block)
+        _, _, tap = self._run(x, capi.INPUT_F32_CHW, x.shape[0], x.shape[2], x.shape[3], tap_block=block)
         return tap.reshape(x.shape[0], -1, self.cfg.embed_dim)
 
     def _mask_request(self, x: torch.Tensor, cls_mask: torch.Tensor, want_emb: bool, want_attn: bool):
         self._require_gpu()
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
-        if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] % 8 != 0:
-            raise ValueError(f"expected a single frame [1,3,r,r] with r % 8 == 0, got {tuple(x.shape)}")
-        r = x.shape[2]
-        n = (r // 8) ** 2
+        if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 3 or x.shape[2] % 8 != 0 or x.shape[3] % 8 != 0:
+            raise ValueError(f"expected a single frame [1,3,H,W] with H % 8 == W % 8 == 0, got {tuple(x.shape)}")
+        H, W = x.shape[2], x.shape[3]
+        n = (H // 8) * (W // 8)
         m = cls_mask.to(device=self.device, dtype=torch.float32).reshape(cls_mask.shape[0], -1).contiguous()
         if m.shape[1] != n:
-            raise ValueError(f"cls_mask must be [n_masks, {r // 8}, {r // 8}], got {tuple(cls_mask.shape)}")
+            raise ValueError(f"cls_mask must be [n_masks, {H // 8}, {W // 8}], got {tuple(cls_mask.shape)}")
         self._sync_weights()
         emb = torch.empty((m.shape[0], self.cfg.embed_dim), dtype=torch.float32, device=x.device) if want_emb else None
         att = torch.empty((1, self.cfg.num_heads, m.shape[0], n + 1), dtype=torch.float32, device=x.device) if want_attn else None
-        capi.check(capi.lib().dinoseg_forward_mask(self._handle, x.data_ptr(), capi.INPUT_F32_CHW, r, m.data_ptr(), m.shape[0],
-                                                   capi.ptr(emb), capi.ptr(att), self._stream()))
+        capi.check(capi.lib().dinoseg_forward_mask_hw(self._handle, x.data_ptr(), capi.INPUT_F32_CHW, H, W, m.data_ptr(), m.shape[0],
+                                                      capi.ptr(emb), capi.ptr(att), self._stream()))
         return emb, att
 
     def forward_mask(self, x: torch.Tensor, cls_mask: torch.Tensor) -> torch.Tensor:
         """One embedding per mask, [n_masks, embed_dim]: ``model.dino.forward_mask(x, cls_mask)`` of the reference
-        (vision_transformer.py:250-271).  x: one frame fp32 [1,3,r,r]; cls_mask [n_masks, r/8, r/8]."""
+        (vision_transformer.py:250-271).  x: one frame fp32 [1,3,H,W]; cls_mask [n_masks, H/8, W/8]."""
         return self._mask_request(x, cls_mask, True, False)[0]
 
     def get_last_selfattention(self, x: torch.Tensor, cls_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Attention probabilities [B, heads, N, N] of the last block (reference: ``model.dino.get_last_selfattention(x)``,
-        vision_transformer.py:273-280; used by visualize_attention.py:46).  x: fp32 [B,3,r,r].  With cls_mask
-        [n_masks, r/8, r/8]: the masked CLS attention [1, heads, n_masks, N] of one frame."""
+        vision_transformer.py:273-280; used by visualize_attention.py:46).  x: fp32 [B,3,H,W], N = (H/8)*(W/8) + 1.  With
+        cls_mask [n_masks, H/8, W/8]: the masked CLS attention [1, heads, n_masks, N] of one frame."""
         if cls_mask is not None:
             return self._mask_request(x, cls_mask, False, True)[1]
         self._require_gpu()
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] % 8 != 0:
-            raise ValueError(f"expected [B,3,r,r] with r % 8 == 0, got {tuple(x.shape)}")
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 8 != 0 or x.shape[3] % 8 != 0:
+            raise ValueError(f"expected [B,3,H,W] with H % 8 == W % 8 == 0, got {tuple(x.shape)}")
         self._sync_weights()
-        B, r = x.shape[0], x.shape[2]
-        N = (r // 8) ** 2 + 1
+        B, H, W = x.shape[0], x.shape[2], x.shape[3]
+        N = (H // 8) * (W // 8) + 1
         out = torch.empty((B, self.cfg.num_heads, N, N), dtype=torch.float32, device=x.device)
-        capi.check(capi.lib().dinoseg_last_selfattention(self._handle, x.data_ptr(), capi.INPUT_F32_CHW, B, r, out.data_ptr(),
-                                                         self._stream()))
+        capi.check(capi.lib().dinoseg_last_selfattention_hw(self._handle, x.data_ptr(), capi.INPUT_F32_CHW, B, H, W, out.data_ptr(),
+                                                            self._stream()))
         return out
 
     # ---- validation metrics (pl_torch_modules.py:302-345) ------------------------------------------
@@ -617,8 +618,8 @@ class DINOSeg(nn.Module):
         """Reference: probs = self(x); pred = argmax.  Here the per-batch confusion matrix is accumulated on device."""
         x, y = batch
         with torch.no_grad():
-            xx, kind, B, r = self._prep_batch(x)
-            logp, amax, _ = self._run(xx, kind, B, r, want_logp=True, want_argmax=True)
+            xx, kind, B, H, W = self._prep_batch(x)
+            logp, amax, _ = self._run(xx, kind, B, H, W, want_logp=True, want_argmax=True)
             y = y.to(self.device).reshape(-1).long().contiguous()
             cm = torch.zeros((self.cfg.n_classes, self.cfg.n_classes), dtype=torch.int64, device=self.device)
             capi.check(capi.lib().dinoseg_op_confusion(amax.data_ptr(), y.data_ptr(), y.numel(), self.cfg.n_classes,
@@ -710,20 +711,21 @@ class DINOSeg(nn.Module):
         return bk
 
     def _prep_batch(self, x: torch.Tensor):
+        """uint8 [B,H,W,3] or fp32 [B,3,H,W] -> (contiguous tensor on the model's device, input kind, B, H, W)."""
         dev = self.device
         if x.dtype == torch.uint8:
-            if x.dim() != 4 or x.shape[3] != 3 or x.shape[1] != x.shape[2]:
-                raise ValueError(f"expected uint8 [B,r,r,3], got {tuple(x.shape)}")
-            kind, B, r = capi.INPUT_U8_HWC, x.shape[0], x.shape[1]
+            if x.dim() != 4 or x.shape[3] != 3:
+                raise ValueError(f"expected uint8 [B,H,W,3], got {tuple(x.shape)}")
+            kind, B, H, W = capi.INPUT_U8_HWC, x.shape[0], x.shape[1], x.shape[2]
             x = x.to(dev).contiguous()
         else:
-            if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
-                raise ValueError(f"expected [B,3,r,r], got {tuple(x.shape)}")
-            kind, B, r = capi.INPUT_F32_CHW, x.shape[0], x.shape[2]
+            if x.dim() != 4 or x.shape[1] != 3:
+                raise ValueError(f"expected [B,3,H,W], got {tuple(x.shape)}")
+            kind, B, H, W = capi.INPUT_F32_CHW, x.shape[0], x.shape[2], x.shape[3]
             x = x.to(device=dev, dtype=torch.float32).contiguous()
-        if r % 8 != 0:
+        if H % 8 != 0 or W % 8 != 0:
             raise ValueError("Resolution should be a multiple of 8.")
-        return x, kind, B, r
+        return x, kind, B, H, W
 
     def check_labels(self) -> None:
         """Raise IndexError if a training step since the last check saw a label outside [0, n_classes) other than the
@@ -751,29 +753,30 @@ class DINOSeg(nn.Module):
     def fused_training_step(self, batch, batch_idx=0):
         """zero_grad + forward + F.nll_loss + backward in one native call (``dinoseg_train_step``): on return every trainable
         parameter's ``.grad`` holds d loss / d parameter of THIS call (overwritten), so ``fused_adam_step`` -- or any torch
-        optimiser -- can follow.  x: fp32 [B,3,r,r] (normalised) or uint8 [B,r,r,3]; y: int [B, (r/8)^2] (-100 = ignored)."""
+        optimiser -- can follow.  x: fp32 [B,3,H,W] (normalised) or uint8 [B,H,W,3]; y: int [B, (H/8)*(W/8)] (-100 = ignored)."""
         x, y = batch
         self._require_gpu()
         self._sync_weights(train=True)
         self._sync_grads("grad")
-        x, kind, B, r = self._prep_batch(x)
+        x, kind, B, H, W = self._prep_batch(x)
         dev = self.device
-        n = (r // 8) ** 2
+        n = (H // 8) * (W // 8)
         y = y.to(dev).reshape(-1).long().contiguous()
         if y.numel() != B * n:
-            raise ValueError(f"labels must have B*(r/8)^2 = {B * n} entries, got {y.numel()}")
+            raise ValueError(f"labels must have B*(H/8)*(W/8) = {B * n} entries, got {y.numel()}")
         loss = torch.zeros((), dtype=torch.float32, device=dev)
         logp = torch.empty((B * n, self.cfg.n_classes), dtype=torch.float32, device=dev)
-        capi.check(capi.lib().dinoseg_train_step(self._handle, x.data_ptr(), kind, B, r, y.data_ptr(), loss.data_ptr(),
-                                                 logp.data_ptr(), self._stream()))
+        capi.check(capi.lib().dinoseg_train_step_hw(self._handle, x.data_ptr(), kind, B, H, W, y.data_ptr(), loss.data_ptr(),
+                                                    logp.data_ptr(), self._stream()))
         self._fwd_epoch = getattr(self, "_fwd_epoch", 0) + 1
         return {"loss": loss, "pred": logp.argmax(dim=-1).detach(), "gt": y, "probs": logp}
 
-    def _autograd_forward(self, x: torch.Tensor, kind: int, B: int, r: int) -> torch.Tensor:
+    def _autograd_forward(self, x: torch.Tensor, kind: int, B: int, H: int, W: int) -> torch.Tensor:
         self._sync_weights(train=True)
-        n = (r // 8) ** 2
+        n = (H // 8) * (W // 8)
         logp = torch.empty((B * n, self.cfg.n_classes), dtype=torch.float32, device=self.device)
-        capi.check(capi.lib().dinoseg_train_forward(self._handle, x.data_ptr(), kind, B, r, logp.data_ptr(), self._stream()))
+        capi.check(capi.lib().dinoseg_train_forward_hw(self._handle, x.data_ptr(), kind, B, H, W, logp.data_ptr(),
+                                                       self._stream()))
         self._fwd_epoch = getattr(self, "_fwd_epoch", 0) + 1
         return logp
 
@@ -892,7 +895,7 @@ class DINOSeg(nn.Module):
         main phase; each phase tracks its own best ``val_acc`` (the reference builds a fresh ``ModelCheckpoint`` per phase), the
         main phase's best is what ``best_ck`` names.  The dataset / augmentation pipeline is out of scope,
         so the dataloaders are arguments (or the ``train_dataloader() / val_dataloader() / test_dataloader()`` hooks of a
-        subclass): any iterables of ``(x, y)`` batches with x uint8 [B,r,r,3] or fp32 [B,3,r,r] and y int [B,(r/8)^2].
+        subclass): any iterables of ``(x, y)`` batches with x uint8 [B,H,W,3] or fp32 [B,3,H,W] and y int [B,(H/8)*(W/8)].
         Returns {'history': [per-epoch metrics of the main phase], 'sim_history': [...] or None, 'test': test metrics or None}."""
         import os
 

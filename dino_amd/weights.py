@@ -16,6 +16,7 @@ from __future__ import annotations
 import zlib
 from collections import OrderedDict
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 
@@ -155,8 +156,13 @@ def procedural_state_dict(cfg: ViTConfig = VIT_S8, salt: int = 0) -> "OrderedDic
     return out
 
 
-def synthetic_frames(B: int, r: int, seed: int = 0, smooth: bool = False) -> np.ndarray:
-    """uint8 [B, r, r, 3] frames already at r x r (resize = identity)."""
+def synthetic_frames(B: int, r: int, seed: int = 0, smooth: bool = False, w: Optional[int] = None) -> np.ndarray:
+    """uint8 [B, r, r, 3] frames already at r x r (resize = identity).  With ``w``: uniform noise frames of
+    r rows and w columns, [B, r, w, 3] (the same draw as the square call when w == r)."""
+    if w is not None and w != r:
+        if smooth:
+            raise ValueError("smooth frames are square")
+        return np.random.default_rng(seed).integers(0, 256, (B, r, w, 3), dtype=np.uint8)
     if not smooth:
         return np.random.default_rng(seed).integers(0, 256, (B, r, r, 3), dtype=np.uint8)
     yy, xx = np.meshgrid(np.arange(r, dtype=np.float32), np.arange(r, dtype=np.float32), indexing="ij")

@@ -79,6 +79,29 @@ int dinoseg_refresh_weights(dinoseg_handle* h, void* stream);
  * resample for an (r/8)x(r/8) grid (vision_transformer.py:202-222), cached per resolution.  r % 8 != 0 -> -1. */
 int dinoseg_prepare_resolution(dinoseg_handle* h, int32_t r, void* stream);
 
+/* ---- non-square frames.  The reference takes H x W inputs: prepare_tokens reads `B, nc, w, h = x.shape`, and
+ * interpolate_pos_encoding resamples the g x g grid with one scale per axis, scale_factor = ((H/8 + 0.1)/g, (W/8 + 0.1)/g)
+ * (vision_transformer.py:202-233); forward_mask takes (1, 3, H, W) frames and (N, H/8, W/8) masks (:250-265).  Each `_hw`
+ * entry below is its `r` sibling with the frame given as H rows x W columns (both multiples of 8, else -1 and
+ * "Resolution should be a multiple of 8."), hp = H/8, wp = W/8 patches per column / row, n = hp*wp tokens per frame ordered
+ * row-major over (hp, wp) (PatchEmbed's flatten(2).transpose(1, 2), :153-157); the `r` entry is H = W = r.  The stored
+ * pos_embed is returned untouched only when H == W and hp == g (:205): a side of g on one axis of a rectangle still
+ * resamples that axis at g / (g + 0.1).  The position cache holds one (hp, wp) grid. */
+int dinoseg_prepare_resolution_hw(dinoseg_handle* h, int32_t H, int32_t W, void* stream);
+/* dinoseg_forward at H x W (vision_transformer.py:224-248): logp_out [B*n, n_classes], argmax_out [B*n], tap_out [B*(n+1), D] */
+int dinoseg_forward_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, float* logp_out,
+                       int32_t* argmax_out, int32_t tap_block, float* tap_out, void* stream);
+/* dinoseg_last_selfattention at H x W (vision_transformer.py:273-280): attn_out [B, heads, n+1, n+1] */
+int dinoseg_last_selfattention_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W,
+                                  float* attn_out, void* stream);
+/* dinoseg_forward_mask at H x W (vision_transformer.py:250-271): cls_mask [n_masks, hp*wp] (the (N, H/8, W/8) masks, row-major),
+ * n_masks <= hp*wp; attn_out [heads, n_masks, n+1] */
+int dinoseg_forward_mask_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t H, int32_t W, const float* cls_mask,
+                            int32_t n_masks, float* emb_out, float* attn_out, void* stream);
+/* dinoseg_features at H x W (vision_transformer.py:237-248): tokens_out [B, n+1, embed_dim] */
+int dinoseg_features_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t n_blocks,
+                        float* tokens_out, void* stream);
+
 /* Replaces DINOSeg.forward (pl_torch_modules.py:239-256) and the argmax of predict() (:294):
  *   x        : B frames at r x r, layout per x_kind
  *   logp_out : fp32 [B*(r/8)^2, n_classes] log-probabilities (may be NULL)
@@ -141,6 +164,12 @@ int dinoseg_train_step(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t
  * dinoseg_train_forward / dinoseg_train_step on this handle.  dinoseg_train_step(labels) == train_forward + nll_loss +
  * backward, through the same kernels (same d logits bit for bit). */
 int dinoseg_train_forward(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* logp_out, void* stream);
+/* The two at H x W frames (vision_transformer.py:202-233; see dinoseg_prepare_resolution_hw): labels / logp_out have B*(H/8)*(W/8)
+ * rows; the pos_embed gradient is the transpose of the two-axis resample. */
+int dinoseg_train_step_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, const int64_t* labels,
+                          float* loss_out, float* logp_out, void* stream);
+int dinoseg_train_forward_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, float* logp_out,
+                             void* stream);
 int dinoseg_backward(dinoseg_handle* h, const float* dlogp, void* stream);
 
 /* Gradient stages of the backward, for overlapping the data-parallel all-reduce with it (no reference
@@ -218,6 +247,8 @@ int dinoseg_set_option(const char* key, int32_t value);
 
 /* Bytes of library-owned device memory a (B, r) forward needs (activations + packed weights). */
 int64_t dinoseg_workspace_bytes(const dinoseg_handle* h, int32_t B, int32_t r);
+/* ... of a (B, H x W) forward (vision_transformer.py:224-233: hp*wp + 1 tokens per frame) */
+int64_t dinoseg_workspace_bytes_hw(const dinoseg_handle* h, int32_t B, int32_t H, int32_t W);
 /* Counts the events that invalidate device addresses or cached contents a CAPTURED dinoseg_forward has baked in: a re-allocation of
  * the activation workspace or of the packed weights, a re-computation of the resampled position embedding (another resolution).
  * A caller that replays a HIP graph of the forward compares it with the value read after the capture and re-captures on a change
@@ -367,10 +398,16 @@ int dinoseg_op_layernorm(const float* x, const float* gamma, const float* beta, 
 
 /* interpolate_pos_encoding (vision_transformer.py:202-222): pos_embed fp32 [g*g+1, D] -> out fp32 [o*o+1, D] */
 int dinoseg_op_pos_resample(const float* pos_embed, int32_t g, int32_t D, int32_t o, float* out, void* stream);
+/* interpolate_pos_encoding with one scale per axis (vision_transformer.py:202-233): out fp32 [oh*ow+1, D]; rows at
+ * g / (oh + 0.1), columns at g / (ow + 0.1); the copy only when oh == ow == g (:205) */
+int dinoseg_op_pos_resample_hw(const float* pos_embed, int32_t g, int32_t D, int32_t oh, int32_t ow, float* out, void* stream);
 
 /* patch gather (+ fused Normalize for uint8 input) -> bf16 planes [planes][B*(r/8)^2][192] */
 int dinoseg_op_patch_gather(const void* x, int32_t x_kind, int32_t B, int32_t r, void* out, int64_t out_plane,
                             int32_t planes, void* stream);
+/* ... of H x W frames (PatchEmbed, vision_transformer.py:153-157): [planes][B*(H/8)*(W/8)][192], patches row-major */
+int dinoseg_op_patch_gather_hw(const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, void* out, int64_t out_plane,
+                               int32_t planes, void* stream);
 
 /* last Linear + log_softmax + argmax (pl_torch_modules.py:122-123,:294); in: hi/lo planes [2][M][ld]; C <= 32 */
 int dinoseg_op_head_final(const void* in, int64_t in_plane, int32_t ld, int32_t M, int32_t K, const float* W,
