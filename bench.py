@@ -2,13 +2,18 @@
 """Headline benchmark of the DINOSeg hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks 12] [--batch 32] [--res 480]
-                    [--precision fp16|bf16|bf16x3] [--no-cpu-baseline] [--dry-run] [--dump-outputs DIR]
+                    [--precision fp16|bf16|bf16x3] [--full] [--no-cpu-baseline] [--dry-run] [--dump-outputs DIR]
                     [--config headline|parity|960|vitb|finetune]     (the other BASELINE.json configs, one JSON line each)
+
+A plain run does what the headline figure needs and no more: it builds the model, runs one untimed forward of the timed
+batch (workspaces, packed weights and the resolution cache exist before the warm-up starts; with --full the parity check
+below is that forward), the W warm-up steps and the K timed steps, writes --dump-outputs, and prints the JSON line.
+`--full` (off by default) adds everything else the line can carry, listed below.
 
 Metric (BASELINE.json): frames/sec of DINOSeg inference -- ViT-S/8 (12 blocks) + MLP head, 480x480 frames,
 batch 32 per GPU, 16-bit MFMA operands / fp32 accumulation -- whole job over all N GPUs.  Default precision (round 4): fp16
 operands for the linears and Q.K^T (v_mfma_f32_32x32x16_f16: the bf16 instruction's rate and the same 2.5 PFLOP/s dense peak),
-bf16 for the probabilities and V -- same speed as the all-bf16 mode, ~6x closer to the fp32 reference; the line carries the all-bf16
+bf16 for the probabilities and V -- same speed as the all-bf16 mode, ~6x closer to the fp32 reference; the --full line carries the all-bf16
 mode's own frames/s and parity as `bf16_mode`, and `--precision bf16` times that mode as the headline.  One "step" = one forward
 of the hot path (uint8 frames resident in HBM -> log-probs + argmax map) over one batch.  Frames are
 independent, so N GPUs run N data-parallel replicas with no data-path collective ("weak" scaling); the
@@ -16,21 +21,27 @@ barrier + max-over-ranks timing follows the driver's contract.  `python bench.py
 WORLD_SIZE in the environment starts the N ranks itself (a `python -m torch.distributed.run` child, before anything
 touches the GPU); under torchrun it is one of the ranks.  The line records `ranks_seen` = an all-reduce of ones.
 
-The JSON line also carries
+Every line carries the headline fields (metric, value, unit, ms_per_step, higher_is_better, dtype), the config, outputs_valid,
+model_mfma_frac, and
+  dump_outputs : with --dump-outputs DIR, where the last timed step's outputs went (dump_outputs(): log-probs and argmax map;
+                 --mode finetune: the loss and the updated parameters), for comparing two builds output for output.
+
+With --full it also carries
   roofline     : the dominant kernel (fused attention, 61 % of the FLOPs) -- algorithmic FLOPs per launch /
                  its mean launch duration measured with HIP events on the forward's stream, in an untimed pass of the
-                 same steps right after the timed loop (no event records inside the timed region).
+                 same steps right after the timed loop (no event records inside the timed region); kernel_ms_per_step =
+                 every kernel class of that pass; one_stream = the same batch timed on one stream (--no-two-stream skips it).
+                 --mode finetune: the attention backward kernels, timed the same way.
   parity       : "mask argmax match vs ref": the golden fixture's frame through the timed precision (argmax_match,
                  max_abs_dlogp against the reference's log-probabilities); parity_mode = the same config in bf16x3
-                 (the mode that meets argmax-identical / 1e-3) with its own frames/s and match; bf16_mode = the same in bf16.
+                 (the mode that meets argmax-identical / 1e-3) with its own frames/s and match; bf16_mode = the same in bf16
+                 (--no-parity-mode skips both).  --mode finetune: gradient_parity, the step's gradients against fixture G12.
   configs      : BASELINE.json configs [2] (@960 batch 8), [4] (ViT-B/8, batch 16 per GPU) and [3] (3-block fine-tune step, batch 8 per GPU)
                  as compact records (value, ms_per_step, dominant-kernel roofline, parity / gradient_parity), each measured by a child
                  `python bench.py --config ...` after the headline (N=1 only; --no-configs skips them).
-  dump_outputs : with --dump-outputs DIR, where the last timed step's outputs went (dump_outputs(): log-probs and argmax map;
-                 --mode finetune: the loss and the updated parameters), for comparing two builds output for output.
   cpu_baseline : the oracle (oracle/dinoseg_oracle.py = CPU fp32 restatement of the reference path, kind "port")
                  timed on this box's host cores on a bounded sample of the same workload (rank 0, N=1 only); --mode finetune:
-                 the oracle's forward + loss + autograd backward of one frame.
+                 the oracle's forward + loss + autograd backward of one frame (--no-cpu-baseline skips it).
 """
 import argparse
 import json
@@ -294,7 +305,7 @@ def bench_finetune(a, world, rank, dev, rehearsal=False):
     # HIP events by the library in an untimed pass of the same steps; algorithmic work = the five products of the backward
     # (S, dP, dV, dK, dQ: 10 N^2 d per head; the two kernels recompute S and dP each -- 7 products issued -- which is not counted)
     roof = None
-    if not rehearsal:
+    if a.full and not rehearsal:
         model.profile(2)
         psteps = max(2, a.steps // 3)
         for _ in range(psteps):
@@ -316,8 +327,7 @@ def bench_finetune(a, world, rank, dev, rehearsal=False):
                     "note": "algorithmic FLOPs (5 products); the kernels issue 7 products' worth of MFMAs"
                             + (" x 3 (hi+lo planes)" if a.precision == "bf16x3" else "")}
     if rank == 0:
-        grad_parity = None if rehearsal else golden_grad_check(a.precision, dev)
-        print(json.dumps({
+        out = {
             "metric": "frames/sec (480x480, ViT-S/8 x3 blocks) DINOSeg fine-tune step", "value": round(fps, 2),
             "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
@@ -329,10 +339,14 @@ def bench_finetune(a, world, rank, dev, rehearsal=False):
                        "precision": a.precision, "collective": a.collective,
                        "parallelism": f"dp{world} (RCCL gradient {'all-reduce' if a.collective == 'allreduce' else 'reduce-scatter + all-gather'}, 22.1 MiB fp32)"},
             "model_mfma_frac": round(fps / world * 3 * fl["total"] / 1e12 / MFMA_PEAK_TFLOPS[a.precision], 4),
-            "roofline": roof, "gradient_parity": grad_parity,
-            "cpu_baseline": cpu_baseline_finetune(cfg, sd, a.res) if world == 1 and not rehearsal and not a.no_cpu_baseline else None,
-            **({"dump_outputs": dumped} if dumped is not None else {}),
-        }), flush=True)
+        }
+        if a.full:
+            out["roofline"] = roof
+            out["gradient_parity"] = None if rehearsal else golden_grad_check(a.precision, dev)
+            out["cpu_baseline"] = cpu_baseline_finetune(cfg, sd, a.res) if world == 1 and not rehearsal and not a.no_cpu_baseline else None
+        if dumped is not None:
+            out["dump_outputs"] = dumped
+        print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
 
@@ -348,6 +362,10 @@ def parse_args(argv=None):
     ap.add_argument("--arch", default="vit_small", choices=["vit_small", "vit_base"])
     ap.add_argument("--precision", default=None, choices=["fp16", "bf16", "bf16x3", "fp16x3"],
                     help="default: fp16 for inference (see the module docstring), bf16 for --mode finetune (fp16 is inference-only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: reference parity, the roofline and per-kernel "
+                         "times (an untimed profiled pass), the one-stream and other-precision sub-records, the CPU baseline and "
+                         "the other BASELINE.json configs (the --no-* options below skip parts of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--profile-all", action="store_true", help="(kept for compatibility: kernel_ms_per_step is always emitted)")
     ap.add_argument("--option", action="append", default=[], help="library tuning knob key=int (dinoseg_set_option)")
@@ -396,7 +414,7 @@ def other_configs(a):
     recs = {}
     for name in ("960", "vitb", "finetune"):
         cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(max(5, a.steps // 2)), "--warmup", "3",
-               "--no-cpu-baseline", "--no-parity-mode", "--no-two-stream", "--no-configs"]
+               "--full", "--no-cpu-baseline", "--no-parity-mode", "--no-two-stream", "--no-configs"]
         t0 = time.time()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
@@ -474,6 +492,81 @@ def ranks_seen(dist, world, dev):
     t = torch.ones(1, dtype=torch.float32, device=dev)
     dist.all_reduce(t)
     return int(round(float(t.item())))
+
+
+def attention_roofline(a, cfg, dev, prof, fl):
+    """--full: the `roofline` record of the inference line -- the dominant kernel (fused attention) as launched by the untimed
+    one-stream pass, its algorithmic FLOPs per launch over its mean launch time from `prof` (model.profile_read())."""
+    import torch
+    peak = MFMA_PEAK_TFLOPS[a.precision]
+    att_ms, att_n = prof["attention"]
+    att_avg_ms = att_ms / max(att_n, 1)
+    att_flops = fl["attention"] * a.batch           # algorithmic FLOPs of one attention launch (the whole batch: one stream)
+    achieved = att_flops / (att_avg_ms * 1e-3) / 1e12 if att_n else None
+
+    traffic = None
+    clock = None
+    measured_peak = None
+    tpath = os.path.join(ROOT, "profiles", "attention_traffic.json")
+    if os.path.exists(tpath):
+        # HBM bytes per attention launch from the committed rocprofv3 PMC passes of this same command
+        # (tools/profile_bench.sh + tools/summarize_profile.py); only quoted when the workload matches
+        tj = json.load(open(tpath))
+        if (tj.get("batch"), tj.get("resolution"), tj.get("precision")) == (a.batch, a.res, a.precision) \
+                and a.arch == "vit_small":
+            traffic = tj["hbm_bytes_per_launch"]
+            clock = tj.get("clock_ghz_under_load")
+        measured_peak = (tj.get("measured_mfma_peak_tflops") or {}).get("random_operands") if a.precision in ("bf16", "fp16") else None
+
+    # the instantiation the one-stream roofline pass launches (attention_z.hip's rule: 256-query workgroups from one round of
+    # 128-query ones on)
+    heads_ = 6 if a.arch == "vit_small" else 12
+    wgs4 = (a.batch * heads_ + 7) // 8 * 8 * (((a.res // 8) ** 2 + 1 + 127) // 128)
+    nw = 8 if wgs4 >= 4 * torch.cuda.get_device_properties(dev).multi_processor_count else 4
+    # (kernels.h Options::attn_variant: from four rounds of workgroups on, bit 10 = the assembly tile loop, bit 16 = 64 queries per wave)
+    av = next((int(kv.split("=")[1]) for kv in a.option if kv.startswith("attn_variant=")), 11 | 1024 | 65536)
+    fmt_note = "; fp16 Q.K^T, bf16 P.V" if a.precision == "fp16" else ""
+    f16 = 1 if a.precision in ("fp16", "fp16x3") else 0
+    ncu_ = torch.cuda.get_device_properties(dev).multi_processor_count
+    if nw == 8 and (av & 1024) and not (av & 64):
+        z_symbol = (f"dseg::attn_fwd_za_kernel<{f16}, {2 if av & 65536 else 1}, 0, false> (attention_za.hip: fused "
+                    f"QK^T-softmax-PV, head_dim 64, zero-reference softmax, tile loop = generated assembly pipeline, "
+                    f"{64 if av & 65536 else 32} queries per wave{fmt_note})")
+    else:
+        z_symbol = (f"dseg::attn_fwd_z_kernel<1, 4, {nw}, {f16}> (attention_z.hip: fused QK^T-softmax-PV, "
+                    f"head_dim 64, zero-reference softmax{fmt_note})")
+    # hi + lo planes (attention_z.hip: attention_x3_za): from two rounds of 256-query workgroups on, the assembly body with three
+    # MFMAs per product (attention_za.hip, X3); below that the reference-based kernel of attention.hip
+    wgs256 = (a.batch * heads_ + 7) // 8 * 8 * (((a.res // 8) ** 2 + 1 + 255) // 256)
+    if (av & 1024) and not (av & 64) and ((av & 2048) or wgs256 >= 2 * ncu_):
+        x3_symbol = (f"dseg::attn_fwd_za_kernel<{f16}, 1, 0, true> (attention_za.hip: fused QK^T-softmax-PV, head_dim 64, hi+lo planes = "
+                     f"three MFMAs per product, zero-reference softmax, tile loop = generated assembly pipeline"
+                     f"{'; Q / K / ctx fp16 hi+lo, P and V bf16 hi+lo' if f16 else ''})")
+    else:
+        x3_symbol = (f"dseg::attn_fwd_kernel<2, 4, false, 3, {f16}> (attention.hip: fused QK^T-softmax-PV, head_dim 64, hi+lo planes)")
+    attn_symbol = z_symbol if a.precision in ("bf16", "fp16") else x3_symbol
+    return {"bound": "mfma", "kernel": attn_symbol,
+            "achieved": None if achieved is None else round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
+            "frac": None if achieved is None else round(achieved / peak, 4),
+            "measured_how": "HIP events around every launch on the forward's stream, in an untimed pass of the same steps on "
+                            "ONE stream (exclusive launches) right after the timed loop; `value` above is timed with the "
+                            "library default (two half-batches on two streams from 8 frames on)",
+            "peak_note": "peak = dense bf16 / fp16 MFMA at the nominal 2.4 GHz (MI355X_MICROARCH.md: one rate).  clock_ghz_under_load = what "
+                         "this kernel was measured to hold (rocprofv3 PMC GRBM_GUI_ACTIVE / 8 / duration, committed in "
+                         "profiles/attention_traffic.json); peak_at_measured_clock scales the peak by it",
+            "clock_ghz_under_load": clock,
+            "peak_at_measured_clock": None if clock is None else round(peak * clock / 2.4, 1),
+            "frac_at_measured_clock": None if (clock is None or achieved is None) else round(achieved / (peak * clock / 2.4), 4),
+            # what a register-only MFMA loop sustains on this chip with non-trivial operand bits (tools/mfma_peak.py):
+            # the power-limited ceiling of ANY bf16 MFMA kernel here, 79 % of the nominal peak
+            "measured_mfma_peak": measured_peak,
+            "frac_of_measured_mfma_peak": None if (measured_peak is None or achieved is None) else round(achieved / measured_peak, 4),
+            "traffic": traffic,
+            "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, profiles/attention_traffic.json)",
+            "algorithmic_bytes_per_launch": 4 * a.batch * cfg.num_heads * ((a.res // 8) ** 2 + 1) * 64 * 2
+            * (2 if a.precision in ("bf16x3", "fp16x3") else 1),
+            "launches_timed": att_n, "avg_launch_ms": round(att_avg_ms, 4),
+            "gflop_per_launch": round(att_flops / 1e9, 1)}
 
 
 def main():
@@ -579,9 +672,14 @@ def main():
             el = float(t.item())
         return el, out
 
-    # "mask argmax match vs ref" first: the fixture's frame through the timed precision and dispatch (a validation pass of the freshly
-    # built model -- workspaces, packed weights and the resolution cache exist before the warm-up steps start)
-    parity = golden_check(model, a.arch, a.blocks, a.res, a.batch) if rank == 0 else None
+    if a.full:
+        # "mask argmax match vs ref" first: the fixture's frame through the timed precision and dispatch (a validation pass of the freshly
+        # built model -- workspaces, packed weights and the resolution cache exist before the warm-up steps start)
+        parity = golden_check(model, a.arch, a.blocks, a.res, a.batch) if rank == 0 else None
+    else:
+        # the same first, untimed forward of the freshly built model without the fixture: the warm-up steps start from the state
+        # they start from with --full
+        step()
     for _ in range(a.warmup):
         step()
     torch.cuda.synchronize()
@@ -590,84 +688,40 @@ def main():
     # (forward_frames returns fresh tensors: the later passes do not touch the last timed step's outputs)
     dumped = dump_outputs(a.dump_outputs, {"logp": logp, "argmax": amax}) if a.dump_outputs and rank == 0 else None
 
-    # per-kernel timing (HIP events on the forward's stream, recorded by the library) in a SEPARATE untimed pass right after
-    # the timed one, on ONE stream: with two half-batches sharing the chip a launch's duration is not the kernel's own, and the
-    # roofline object is defined on exclusive launches.  The timed loop has no event records in it.
-    capi.check(lib.dinoseg_set_option(b"streams", 1))
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    model.profile(2)
-    prof_steps = max(3, a.steps // 2)
-    for _ in range(prof_steps):
-        lp1, am1 = step()
-    torch.cuda.synchronize()
-    prof = model.profile_read()
-    model.profile(0)
     one_stream = None
-    if split and not a.no_two_stream:
-        # the same batch on one stream (what the roofline pass launches), timed for reference
-        t1 = time.perf_counter()
+    if a.full:
+        # per-kernel timing (HIP events on the forward's stream, recorded by the library) in a SEPARATE untimed pass right after
+        # the timed one, on ONE stream: with two half-batches sharing the chip a launch's duration is not the kernel's own, and the
+        # roofline object is defined on exclusive launches.  The timed loop has no event records in it.
+        capi.check(lib.dinoseg_set_option(b"streams", 1))
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+        model.profile(2)
+        prof_steps = max(3, a.steps // 2)
         for _ in range(prof_steps):
             lp1, am1 = step()
         torch.cuda.synchronize()
-        tel = time.perf_counter() - t1
-        one_stream = {"value": round(a.batch * prof_steps / tel, 2), "unit": "frames/s (this rank)", "steps": prof_steps,
-                      "ms_per_step": round(tel / prof_steps * 1e3, 4),
-                      "outputs_identical_to_two_streams": bool(torch.equal(lp1, logp) and torch.equal(am1, amax))}
-    capi.check(lib.dinoseg_set_option(b"streams", streams))
+        prof = model.profile_read()
+        model.profile(0)
+        if split and not a.no_two_stream:
+            # the same batch on one stream (what the roofline pass launches), timed for reference
+            t1 = time.perf_counter()
+            for _ in range(prof_steps):
+                lp1, am1 = step()
+            torch.cuda.synchronize()
+            tel = time.perf_counter() - t1
+            one_stream = {"value": round(a.batch * prof_steps / tel, 2), "unit": "frames/s (this rank)", "steps": prof_steps,
+                          "ms_per_step": round(tel / prof_steps * 1e3, 4),
+                          "outputs_identical_to_two_streams": bool(torch.equal(lp1, logp) and torch.equal(am1, amax))}
+        capi.check(lib.dinoseg_set_option(b"streams", streams))
 
     ok = bool(torch.isfinite(logp).all().item()) and bool(torch.equal(amax.long(), logp.argmax(1)))
     fl = flops_per_frame(cfg.embed_dim, cfg.num_heads, a.blocks, a.res)
     fps = a.batch * a.steps * world / elapsed
     peak = MFMA_PEAK_TFLOPS[a.precision]
-    att_ms, att_n = prof["attention"]
-    att_avg_ms = att_ms / max(att_n, 1)
-    att_flops = fl["attention"] * a.batch           # algorithmic FLOPs of one attention launch (the whole batch: one stream)
-    achieved = att_flops / (att_avg_ms * 1e-3) / 1e12 if att_n else None
-
-    traffic = None
-    clock = None
-    measured_peak = None
-    tpath = os.path.join(ROOT, "profiles", "attention_traffic.json")
-    if os.path.exists(tpath):
-        # HBM bytes per attention launch from the committed rocprofv3 PMC passes of this same command
-        # (tools/profile_bench.sh + tools/summarize_profile.py); only quoted when the workload matches
-        tj = json.load(open(tpath))
-        if (tj.get("batch"), tj.get("resolution"), tj.get("precision")) == (a.batch, a.res, a.precision) \
-                and a.arch == "vit_small":
-            traffic = tj["hbm_bytes_per_launch"]
-            clock = tj.get("clock_ghz_under_load")
-        measured_peak = (tj.get("measured_mfma_peak_tflops") or {}).get("random_operands") if a.precision in ("bf16", "fp16") else None
 
     if rank == 0:
-        # the instantiation the one-stream roofline pass launches (attention_z.hip's rule: 256-query workgroups from one round of
-        # 128-query ones on)
-        heads_ = 6 if a.arch == "vit_small" else 12
-        wgs4 = (a.batch * heads_ + 7) // 8 * 8 * (((a.res // 8) ** 2 + 1 + 127) // 128)
-        nw = 8 if wgs4 >= 4 * torch.cuda.get_device_properties(dev).multi_processor_count else 4
-        # (kernels.h Options::attn_variant: from four rounds of workgroups on, bit 10 = the assembly tile loop, bit 16 = 64 queries per wave)
-        av = next((int(kv.split("=")[1]) for kv in a.option if kv.startswith("attn_variant=")), 11 | 1024 | 65536)
-        fmt_note = "; fp16 Q.K^T, bf16 P.V" if a.precision == "fp16" else ""
-        f16 = 1 if a.precision in ("fp16", "fp16x3") else 0
-        ncu_ = torch.cuda.get_device_properties(dev).multi_processor_count
-        if nw == 8 and (av & 1024) and not (av & 64):
-            z_symbol = (f"dseg::attn_fwd_za_kernel<{f16}, {2 if av & 65536 else 1}, 0, false> (attention_za.hip: fused "
-                        f"QK^T-softmax-PV, head_dim 64, zero-reference softmax, tile loop = generated assembly pipeline, "
-                        f"{64 if av & 65536 else 32} queries per wave{fmt_note})")
-        else:
-            z_symbol = (f"dseg::attn_fwd_z_kernel<1, 4, {nw}, {f16}> (attention_z.hip: fused QK^T-softmax-PV, "
-                        f"head_dim 64, zero-reference softmax{fmt_note})")
-        # hi + lo planes (attention_z.hip: attention_x3_za): from two rounds of 256-query workgroups on, the assembly body with three
-        # MFMAs per product (attention_za.hip, X3); below that the reference-based kernel of attention.hip
-        wgs256 = (a.batch * heads_ + 7) // 8 * 8 * (((a.res // 8) ** 2 + 1 + 255) // 256)
-        if (av & 1024) and not (av & 64) and ((av & 2048) or wgs256 >= 2 * ncu_):
-            x3_symbol = (f"dseg::attn_fwd_za_kernel<{f16}, 1, 0, true> (attention_za.hip: fused QK^T-softmax-PV, head_dim 64, hi+lo planes = "
-                         f"three MFMAs per product, zero-reference softmax, tile loop = generated assembly pipeline"
-                         f"{'; Q / K / ctx fp16 hi+lo, P and V bf16 hi+lo' if f16 else ''})")
-        else:
-            x3_symbol = (f"dseg::attn_fwd_kernel<2, 4, false, 3, {f16}> (attention.hip: fused QK^T-softmax-PV, head_dim 64, hi+lo planes)")
-        attn_symbol = z_symbol if a.precision in ("bf16", "fp16") else x3_symbol
         metric_text = (f"frames/sec ({a.res}x{a.res}, ViT-{'S' if a.arch == 'vit_small' else 'B'}/8"
                        f"{'' if a.blocks == 12 else f' x{a.blocks} blocks'}) DINOSeg inference")
         out = {
@@ -685,79 +739,60 @@ def main():
             "outputs_valid": ok,
             "model_gflop_per_frame": round(fl["total"] / 1e9, 2),
             "model_mfma_frac": round(fps / world * fl["total"] / 1e12 / peak, 4),
-            "roofline": {"bound": "mfma", "kernel": attn_symbol,
-                         "achieved": None if achieved is None else round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
-                         "frac": None if achieved is None else round(achieved / peak, 4),
-                         "measured_how": "HIP events around every launch on the forward's stream, in an untimed pass of the same steps on "
-                                         "ONE stream (exclusive launches) right after the timed loop; `value` above is timed with the "
-                                         "library default (two half-batches on two streams from 8 frames on)",
-                         "peak_note": "peak = dense bf16 / fp16 MFMA at the nominal 2.4 GHz (MI355X_MICROARCH.md: one rate).  clock_ghz_under_load = what "
-                                      "this kernel was measured to hold (rocprofv3 PMC GRBM_GUI_ACTIVE / 8 / duration, committed in "
-                                      "profiles/attention_traffic.json); peak_at_measured_clock scales the peak by it",
-                         "clock_ghz_under_load": clock,
-                         "peak_at_measured_clock": None if clock is None else round(peak * clock / 2.4, 1),
-                         "frac_at_measured_clock": None if (clock is None or achieved is None) else round(achieved / (peak * clock / 2.4), 4),
-                         # what a register-only MFMA loop sustains on this chip with non-trivial operand bits (tools/mfma_peak.py):
-                         # the power-limited ceiling of ANY bf16 MFMA kernel here, 79 % of the nominal peak
-                         "measured_mfma_peak": measured_peak,
-                         "frac_of_measured_mfma_peak": None if (measured_peak is None or achieved is None) else round(achieved / measured_peak, 4),
-                         "traffic": traffic,
-                         "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, profiles/attention_traffic.json)",
-                         "algorithmic_bytes_per_launch": 4 * a.batch * cfg.num_heads * ((a.res // 8) ** 2 + 1) * 64 * 2
-                         * (2 if a.precision in ("bf16x3", "fp16x3") else 1),
-                         "launches_timed": att_n, "avg_launch_ms": round(att_avg_ms, 4),
-                         "gflop_per_launch": round(att_flops / 1e9, 1)},
-            # every kernel class of one forward, same untimed one-stream pass (fc1_gemm holds the fused MLP launch when it applies)
-            "kernel_ms_per_step": {k: round(v[0] / prof_steps, 4) for k, v in prof.items()},
         }
-        if one_stream is not None:
-            out["one_stream"] = one_stream
+        if a.full:
+            out["roofline"] = attention_roofline(a, cfg, dev, prof, fl)
+            # every kernel class of one forward, same untimed one-stream pass (fc1_gemm holds the fused MLP launch when it applies)
+            out["kernel_ms_per_step"] = {k: round(v[0] / prof_steps, 4) for k, v in prof.items()}
+            if one_stream is not None:
+                out["one_stream"] = one_stream
         if dumped is not None:
             out["dump_outputs"] = dumped
-        out["parity"] = parity      # the timed precision / dispatch against the reference fixture (computed before the timed loop)
-        def sub_mode(prec):
-            """the same configuration in another precision: its own short timing (library defaults) and its parity record"""
-            pm = DINOSeg(head="mlp", n_blocks=a.blocks, precision=prec, arch=cfg)
-            pm.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-            pm.to(dev)
-            pm.set_resolution(a.res)
-            for _ in range(2):
-                pm.forward_frames(frames, want_logp=True)
-            torch.cuda.synchronize()
-            psteps = max(3, a.steps // 2)
-            t1 = time.perf_counter()
-            for _ in range(psteps):
-                pm.forward_frames(frames, want_logp=True)
-            torch.cuda.synchronize()
-            pel = time.perf_counter() - t1
-            pfps = a.batch * psteps / pel
-            rec = {"precision": prec, "value": round(pfps, 2), "unit": "frames/s (this rank)", "steps": psteps,
-                   "ms_per_step": round(pel / psteps * 1e3, 4), "streams": 2 if split else 1,
-                   "parity": golden_check(pm, a.arch, a.blocks, a.res, a.batch)}
-            del pm
-            return rec, pfps
-        if a.precision in ("bf16", "fp16") and not a.no_parity_mode:
-            # north_star's bar (argmax identical, |dlogp| <= 1e-3) is met by the hi+lo modes: same config, own timing.  fp16x3 =
-            # fp16 hi+lo planes (~22 bits, round 4): the parity mode with margin; bf16x3 = rounds 1-3's (~16 bits)
-            for key, prec, text in (("parity_mode", "fp16x3", "fp16x3 (fp16 hi+lo operand planes, 3 MFMAs per product, fp32 accumulate)"),
-                                    ("parity_mode_bf16x3", "bf16x3", "bf16x3 (bf16 hi+lo operand planes, 3 MFMAs per product, fp32 accumulate)")):
-                rec, pfps = sub_mode(prec)
-                rec["precision"] = text
-                rec["mfma_issue_frac"] = round(3 * pfps * fl["total"] / 1e12 / peak, 4)
-                out[key] = rec
-        if a.precision == "fp16" and not a.no_parity_mode:
-            # BASELINE.json names bf16: the all-bf16 mode's own numbers next to the fp16-operand headline (same kernels, same rate)
-            out["bf16_mode"] = sub_mode("bf16")[0]
-        if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cfg, sd, a.res)
-        # (never under a profiler: the children would inherit its preload, write into the same output names and mix their kernels
-        #  into the statistics this line's roofline is read from -- ADVICE r5)
-        profiled = bool(os.environ.get("ROCP_TOOL_LIBRARIES")) or "rocprofiler" in os.environ.get("LD_PRELOAD", "") \
-            or bool(os.environ.get("ROCPROFILER_REGISTER_FORCE_LOAD")) or bool(os.environ.get("ROCPROF_OUTPUT_PATH"))
-        if world == 1 and not a.no_configs and not profiled and a.config in (None, "headline") and a.arch == "vit_small" and a.res == 480 and a.batch == 32:
-            del model
-            torch.cuda.empty_cache()
-            out["configs"] = other_configs(a)
+        if a.full:
+            out["parity"] = parity      # the timed precision / dispatch against the reference fixture (computed before the timed loop)
+            def sub_mode(prec):
+                """the same configuration in another precision: its own short timing (library defaults) and its parity record"""
+                pm = DINOSeg(head="mlp", n_blocks=a.blocks, precision=prec, arch=cfg)
+                pm.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+                pm.to(dev)
+                pm.set_resolution(a.res)
+                for _ in range(2):
+                    pm.forward_frames(frames, want_logp=True)
+                torch.cuda.synchronize()
+                psteps = max(3, a.steps // 2)
+                t1 = time.perf_counter()
+                for _ in range(psteps):
+                    pm.forward_frames(frames, want_logp=True)
+                torch.cuda.synchronize()
+                pel = time.perf_counter() - t1
+                pfps = a.batch * psteps / pel
+                rec = {"precision": prec, "value": round(pfps, 2), "unit": "frames/s (this rank)", "steps": psteps,
+                       "ms_per_step": round(pel / psteps * 1e3, 4), "streams": 2 if split else 1,
+                       "parity": golden_check(pm, a.arch, a.blocks, a.res, a.batch)}
+                del pm
+                return rec, pfps
+            if a.precision in ("bf16", "fp16") and not a.no_parity_mode:
+                # north_star's bar (argmax identical, |dlogp| <= 1e-3) is met by the hi+lo modes: same config, own timing.  fp16x3 =
+                # fp16 hi+lo planes (~22 bits, round 4): the parity mode with margin; bf16x3 = rounds 1-3's (~16 bits)
+                for key, prec, text in (("parity_mode", "fp16x3", "fp16x3 (fp16 hi+lo operand planes, 3 MFMAs per product, fp32 accumulate)"),
+                                        ("parity_mode_bf16x3", "bf16x3", "bf16x3 (bf16 hi+lo operand planes, 3 MFMAs per product, fp32 accumulate)")):
+                    rec, pfps = sub_mode(prec)
+                    rec["precision"] = text
+                    rec["mfma_issue_frac"] = round(3 * pfps * fl["total"] / 1e12 / peak, 4)
+                    out[key] = rec
+            if a.precision == "fp16" and not a.no_parity_mode:
+                # BASELINE.json names bf16: the all-bf16 mode's own numbers next to the fp16-operand headline (same kernels, same rate)
+                out["bf16_mode"] = sub_mode("bf16")[0]
+            if world == 1 and not a.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(cfg, sd, a.res)
+            # (never under a profiler: the children would inherit its preload, write into the same output names and mix their kernels
+            #  into the statistics this line's roofline is read from -- ADVICE r5)
+            profiled = bool(os.environ.get("ROCP_TOOL_LIBRARIES")) or "rocprofiler" in os.environ.get("LD_PRELOAD", "") \
+                or bool(os.environ.get("ROCPROFILER_REGISTER_FORCE_LOAD")) or bool(os.environ.get("ROCPROF_OUTPUT_PATH"))
+            if world == 1 and not a.no_configs and not profiled and a.config in (None, "headline") and a.arch == "vit_small" and a.res == 480 and a.batch == 32:
+                del model
+                torch.cuda.empty_cache()
+                out["configs"] = other_configs(a)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

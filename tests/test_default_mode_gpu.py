@@ -1,7 +1,7 @@
 """The class DEFAULT (`precision="auto"`: inference runs fp16x3 -- what `DINOSeg.load_from_checkpoint(path).predict / forward_frames` give a
 user, pl_torch_modules.py:276-300) at the BASELINE.json batch shapes, against the fixtures captured from the reference (-m gpu).
 
-bench.py prints the same comparison as `parity_mode.parity`; here it is asserted: |dlogp| <= 3e-4 (the north-star bar is 1e-3), argmax
+`bench.py --full` prints the same comparison as `parity_mode.parity`; here it is asserted: |dlogp| <= 3e-4 (the north-star bar is 1e-3), argmax
 identical to the reference (a tie of the reference itself excepted at 14 400 patches, as tests/test_fp16_gpu.py), and every copy of the
 frame in the batch bit-identical -- the batch goes through the large-batch dispatch (fused projection + MLP launch on hi + lo planes,
 persistent GEMMs, assembly attention, two streams) that a single frame never sees."""

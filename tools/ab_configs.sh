@@ -7,7 +7,7 @@ for r in $(seq $R); do
   for c in "$@"; do
     for lib in "" "$BASE"; do
       if [ -z "$lib" ]; then unset DINOSEG_LIB; tag=tree; else export DINOSEG_LIB=$lib; tag=$NAME; fi
-      timeout -k 10 300 python bench.py --config $c --no-cpu-baseline --no-configs --no-parity-mode 2>/dev/null | tail -1 | python -c "
+      timeout -k 10 300 python bench.py --full --config $c --no-cpu-baseline --no-configs --no-parity-mode 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$tag', '$c', d['value'], d['ms_per_step'], (d.get('parity') or d.get('gradient_parity') or {}).get('max_abs_dlogp'))"
     done
   done

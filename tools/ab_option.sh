@@ -8,7 +8,7 @@ for i in $(seq 1 $R); do
   for spec in "$@"; do
     label=${spec%%=*}; opts=""
     if [ "$spec" != "$label" ]; then for kv in $(echo ${spec#*=} | tr ',' ' '); do opts="$opts --option $kv"; done; fi
-    python bench.py $EXTRA $opts 2>/dev/null | tail -1 | python -c "
+    python bench.py --full $EXTRA $opts 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d.get('kernel_ms_per_step',{})
 print('$label', d['value'], 'one_stream', (d.get('one_stream') or {}).get('value'), 'attn_us', round(d['roofline']['avg_launch_ms']*1e3,1), 'qkv', k.get('qkv_gemm'), 'mlp', k.get('fc1_gemm'))"
   done

@@ -11,7 +11,7 @@ unset DINOSEG_LIB
 for r in 1 2; do
   for o in "" $2; do
     opt=""; [ -n "$o" ] && opt="--option $o"
-    timeout -k 10 300 python bench.py --config parity --no-cpu-baseline --steps 10 --warmup 3 $opt 2>/dev/null | tail -1 | python -c "
+    timeout -k 10 300 python bench.py --full --config parity --no-cpu-baseline --steps 10 --warmup 3 $opt 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('parity [$o]', d['value'], 'one stream', d['one_stream']['value'], 'fused ms', d['kernel_ms_per_step']['fc1_gemm'])"
   done
 done

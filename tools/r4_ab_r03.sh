@@ -9,6 +9,6 @@ import json,sys; d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_step']; prin
 }
 for i in 1 2 3; do
   one r03_bf16 build/r03_tree
-  one r04_bf16 . --precision bf16
-  one r04_fp16 .
+  one r04_bf16 . --full --precision bf16
+  one r04_fp16 . --full
 done 2>&1 | tee gpurun_out/r4_ab_r03.log
