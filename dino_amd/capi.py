@@ -69,6 +69,15 @@ SIGNATURES = {
                                            _i32, _i32, _f32, _vp]),
     "dinoseg_op_attention_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _fp, _fp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dinoseg_op_layernorm_bwd": (C.c_int, [_fp, _fp, _fp, _f32, _i32, _i32, _fp, _i32, _fp, _fp, _i32, _i32, _vp]),
+    "dinoseg_op_layernorm_bwd2": (C.c_int, [_fp, _fp, _fp, _f32, _i32, _i32, _fp, _i32, _fp, _fp, _i32, _i32, _vp, _i64, _i32, _fp,
+                                            _vp]),
+    "dinoseg_op_gemm_tn": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _i32, _i32, _fp, _vp]),
+    "dinoseg_op_gemm_bwd": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _fp, _i32, _vp, _i64, _i32, _vp, _i64,
+                                      _vp]),
+    "dinoseg_op_wgrad_nt": (C.c_int, [_fp, _vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64,
+                                      _i32, _fp, _fp, _fp, _vp]),
+    "dinoseg_op_nll_loss_grad": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _fp, _fp, _fp, _vp, _i64, _i32, _vp]),
+    "dinoseg_op_pos_resample_bwd_hw": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _fp, _fp, _vp]),
     "dinoseg_set_option": (C.c_int, [C.c_char_p, _i32]),
     "dinoseg_profile": (C.c_int, [_vp, _i32]),
     "dinoseg_profile_read": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(_i32)]),

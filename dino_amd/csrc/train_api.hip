@@ -148,6 +148,37 @@ struct TW {
     long plane;
 };
 
+// batch slices of the narrow-layer weight gradient below: as many as the split-K budget allows, at least two k-steps each
+int wgrad_nt_slices(int n_rows, int k_pad128, int m_pad) {
+    const int tiles = ((n_rows + 127) / 128) * (k_pad128 / 128), nk = m_pad / 64;
+    int ks = splitk_budget() / tiles;
+    if (ks > nk / 2) ks = nk / 2;
+    return ks < 1 ? 1 : ks;
+}
+
+// dW[n_rows, k_cols] += dY^T . X  from transposed planes T_dy [n_pad][m_pad], T_x [k_pad128][m_pad] (NT kernel, the batch rows as
+// the contraction).  ks == 1: fp32 atomics straight into dW; ks > 1: slices of the batch write partial tiles to `part` (plain
+// stores), one pass sums the slices that own k-steps into dW.
+int wgrad_nt(const bf16_t* Tdy, const bf16_t* Tx, long tplane, int m_pad, int n_rows, int k_pad128, int k_cols, int planes, int ks,
+             float* part, float* dW, hipStream_t s) {
+    GemmParams g = {};
+    g.A = Tdy; g.a_plane = tplane; g.lda = m_pad; g.W = Tx; g.w_plane = tplane;
+    g.M = n_rows; g.N = k_pad128; g.K = m_pad; g.planes = planes;
+    if (ks == 1) {
+        g.epi = EPI_ATOMIC;
+        g.out_f32 = dW; g.ldo_f32 = k_cols; g.n_valid = k_cols;
+        g.ksplit = 1;
+        return launch_gemm_small(g, s);
+    }
+    const int nk = m_pad / 64, row_tiles = (n_rows + 127) / 128;
+    const int per = (nk + ks - 1) / ks, used = (nk + per - 1) / per;       // slices that own k-steps (gemm.hip)
+    g.epi = EPI_PLAIN;
+    g.out_f32 = part; g.ldo_f32 = k_pad128; g.ksplit = ks;
+    g.split_stride = (long)row_tiles * 128 * k_pad128;
+    DSEG_TRY(launch_gemm_small(g, s));
+    return launch_splitk_reduce(part, used, g.split_stride, n_rows, k_pad128, dW, k_cols, k_cols, s);
+}
+
 }  // namespace
 
 int dinoseg_train_release(dinoseg_handle* h) {
@@ -222,6 +253,103 @@ extern "C" int dinoseg_op_layernorm_bwd(const float* dy, const float* x, const f
                                         int32_t ntok, void* stream) {
     return launch_layernorm_bwd(dy, x, gamma, eps, M, D, dx, accumulate, dgamma, dbeta, drop_cls, ntok,
                                 reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_layernorm_bwd2(const float* dy, const float* x, const float* gamma, float eps, int32_t M, int32_t D, float* dx,
+                                         int32_t accumulate, float* dgamma, float* dbeta, int32_t drop_cls, int32_t ntok, void* dxp,
+                                         int64_t dxp_plane, int32_t planes, float* colsum, void* stream) {
+    if (dxp && planes != 1 && planes != 2) {
+        dinoseg_set_error("dinoseg_op_layernorm_bwd2: planes must be 1 or 2 (got %d)", planes);
+        return -1;
+    }
+    return launch_layernorm_bwd(dy, x, gamma, eps, M, D, dx, accumulate, dgamma, dbeta, drop_cls, ntok,
+                                reinterpret_cast<hipStream_t>(stream), (bf16_t*)dxp, dxp_plane, planes, colsum);
+}
+
+// the step's wgrad_tn with the caller's slice count: gemm_tn, then the reduce over the slices that own batch rows
+extern "C" int dinoseg_op_gemm_tn(const void* Y, int64_t y_plane, int32_t ldy, const void* X, int64_t x_plane, int32_t ldx, int32_t M,
+                                  int32_t N, int32_t Kc, int32_t planes, int32_t ksplit, float* part, float* dW, int32_t ldw,
+                                  int32_t k_cols, float* colsum, void* stream) {
+    if (!part) {        // (the kernel always writes its partial tiles there, also when only the column sums are wanted)
+        dinoseg_set_error("dinoseg_op_gemm_tn: part is required");
+        return -1;
+    }
+    if (dW && (k_cols < 1 || k_cols > Kc || ldw < k_cols)) {
+        dinoseg_set_error("dinoseg_op_gemm_tn: bad output columns (k_cols=%d Kc=%d ldw=%d)", k_cols, Kc, ldw);
+        return -1;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    TnParams g = {};
+    g.Y = (const bf16_t*)Y; g.y_plane = y_plane; g.ldy = ldy; g.X = (const bf16_t*)X; g.x_plane = x_plane; g.ldx = ldx;
+    g.M = M; g.N = N; g.Kc = Kc; g.planes = planes;
+    g.part = part; g.ld_part = Kc; g.split_stride = (long)((N + 127) / 128) * 128 * Kc; g.ksplit = ksplit;
+    g.colsum = colsum;
+    DSEG_TRY(launch_gemm_tn(g, s));
+    if (!dW) return 0;
+    const int nchunks = (M + 31) / 32, per = (nchunks + ksplit - 1) / ksplit, used = (nchunks + per - 1) / per;
+    return launch_splitk_reduce(part, used, g.split_stride, N, Kc, dW, ldw, k_cols, s);
+}
+
+// the step's dgrad: dX[M, N] = dY[M, K] . W^T[N, K]^T through the 128x128 kernel with a backward epilogue
+extern "C" int dinoseg_op_gemm_bwd(const void* A, int64_t a_plane, int32_t lda, const void* Wt, int64_t w_plane, int32_t M, int32_t N,
+                                   int32_t K, int32_t planes, int32_t epi, float* out_f32, int32_t ldo_f32, void* out_bf16,
+                                   int64_t out_plane, int32_t ldo, const void* aux_in, int64_t aux_plane, void* stream) {
+    if (epi != EPI_PLAIN && epi != EPI_BF16 && epi != EPI_DGELU && epi != EPI_DRELU) {
+        dinoseg_set_error("dinoseg_op_gemm_bwd: epi %d is not a backward epilogue (0, 6, 8, 9)", epi);
+        return -1;
+    }
+    if ((epi == EPI_DGELU || epi == EPI_DRELU) && !aux_in) {
+        dinoseg_set_error("dinoseg_op_gemm_bwd: epi %d needs aux_in", epi);
+        return -1;
+    }
+    GemmParams g = {};
+    g.A = (const bf16_t*)A; g.a_plane = a_plane; g.lda = lda; g.W = (const bf16_t*)Wt; g.w_plane = w_plane;
+    g.M = M; g.N = N; g.K = K; g.planes = planes; g.epi = epi;
+    g.out_f32 = out_f32; g.ldo_f32 = ldo_f32;
+    g.out_bf16 = (bf16_t*)out_bf16; g.out_plane = out_plane; g.ldo = ldo; g.aux_in = (const bf16_t*)aux_in; g.aux_plane = aux_plane;
+    return launch_gemm_small(g, reinterpret_cast<hipStream_t>(stream));
+}
+
+// the step's narrow-layer weight gradient (k_cols % 128 != 0: the patch embedding): dY [M][N] (fp32 rows, or bf16 planes) and X
+// planes [M][K] transposed into T1 / T2 (+ the bias column sums of dY, drop_cls), then the NT kernel over the batch rows with ksplit
+// slices (1: fp32 atomics into dW; else partial tiles in `part` + the reduce).  dW [N][K], row stride K.
+extern "C" int dinoseg_op_wgrad_nt(const float* dy_f32, const void* dy, int64_t dy_plane, int32_t ldy, const void* x, int64_t x_plane,
+                                   int32_t ldx, int32_t M, int32_t N, int32_t K, int32_t planes, int32_t drop_cls, int32_t ntok,
+                                   int32_t ksplit, void* T1, void* T2, int64_t t_plane, int32_t m_pad, float* part, float* dW,
+                                   float* colsum, void* stream) {
+    const int n_pad = (N + 127) / 128 * 128, k_pad = (K + 127) / 128 * 128;
+    if ((dy_f32 == nullptr) == (dy == nullptr) || ksplit < 1 || M < 1 || (long)n_pad * m_pad > t_plane ||
+        (long)k_pad * m_pad > t_plane || (ksplit > 1 && !part)) {
+        dinoseg_set_error("dinoseg_op_wgrad_nt: bad argument (M=%d N=%d K=%d m_pad=%d ksplit=%d)", M, N, K, m_pad, ksplit);
+        return -1;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    bf16_t *t1 = (bf16_t*)T1, *t2 = (bf16_t*)T2;
+    DSEG_TRY(launch_transpose_planes(dy_f32, (const bf16_t*)dy, dy_plane, ldy, M, N, t1, t_plane, n_pad, m_pad, nullptr, 0, 0, colsum,
+                                     planes, drop_cls, ntok, s));
+    DSEG_TRY(launch_transpose_planes(nullptr, (const bf16_t*)x, x_plane, ldx, M, K, t2, t_plane, k_pad, m_pad, nullptr, 0, 0, nullptr,
+                                     planes, 0, 0, s));
+    if (!dW) return 0;
+    return wgrad_nt(t1, t2, t_plane, m_pad, N, k_pad, K, planes, ksplit, part, dW, s);
+}
+
+extern "C" int dinoseg_op_nll_loss_grad(const float* logp, const int64_t* labels, const float* dlogp, int32_t M, int32_t C, float* acc,
+                                        int32_t* flags, float* loss, void* dz, int64_t dz_plane, int32_t ldz, void* stream) {
+    if ((labels == nullptr) == (dlogp == nullptr) || (labels && (!acc || !flags || !loss)) || M < 1 || C < 1 || ldz < C) {
+        dinoseg_set_error("dinoseg_op_nll_loss_grad: needs exactly one of labels (+ acc, flags, loss) and dlogp, ldz >= C");
+        return -1;
+    }
+    return launch_nll_loss_grad(logp, labels, dlogp, M, C, acc, flags, loss, (bf16_t*)dz, dz_plane, ldz,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_pos_resample_bwd_hw(const float* dpos, int32_t g, int32_t D, int32_t oh, int32_t ow, float* dpe, float* scratch,
+                                              void* stream) {
+    if (g < 1 || D < 1 || oh < 1 || ow < 1) {
+        dinoseg_set_error("dinoseg_op_pos_resample_bwd_hw: bad shape g=%d D=%d oh=%d ow=%d", g, D, oh, ow);
+        return -1;
+    }
+    return launch_pos_resample_bwd(dpos, g, D, oh, ow, dpe, scratch, reinterpret_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------------------------------------ the step
@@ -590,27 +718,8 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
     auto wgrad = [&](const bf16_t* Tdy, const bf16_t* Tx, long tplane, int m_pad, int n_rows, int k_pad128, int k_cols, int planes,
                      float* dW) -> int {
         if (!dW) return 0;
-        GemmParams g = {};
-        g.A = Tdy; g.a_plane = tplane; g.lda = m_pad; g.W = Tx; g.w_plane = tplane;
-        g.M = n_rows; g.N = k_pad128; g.K = m_pad; g.planes = planes;
-        const int row_tiles = (n_rows + 127) / 128, tiles = row_tiles * (k_pad128 / 128), nk = m_pad / 64;
-        int ks = splitk_budget() / tiles;
-        if (ks > nk / 2) ks = nk / 2;
-        if (ks < 1) ks = 1;
-        if (ks == 1) {
-            g.epi = EPI_ATOMIC;
-            g.out_f32 = dW; g.ldo_f32 = k_cols; g.n_valid = k_cols;
-            g.ksplit = 1;
-            return launch_gemm_small(g, s);
-        }
-        // slices of the batch dimension write partial tiles (plain stores), one pass sums them into dW
-        const int per = (nk + ks - 1) / ks, used = (nk + per - 1) / per;       // slices that own k-steps (gemm.hip)
-        float* part = F32(L.SPLITK);
-        g.epi = EPI_PLAIN;
-        g.out_f32 = part; g.ldo_f32 = k_pad128; g.ksplit = ks;
-        g.split_stride = (long)row_tiles * 128 * k_pad128;
-        DSEG_TRY(launch_gemm_small(g, s));
-        return launch_splitk_reduce(part, used, g.split_stride, n_rows, k_pad128, dW, k_cols, k_cols, s);
+        return wgrad_nt(Tdy, Tx, tplane, m_pad, n_rows, k_pad128, k_cols, planes, wgrad_nt_slices(n_rows, k_pad128, m_pad),
+                        F32(L.SPLITK), dW, s);
     };
     auto pad128 = [](int v) { return (v + 127) / 128 * 128; };
     // weight gradient straight from the row-major dY and layer-input planes (gemm_tn.hip): no operand transposes

@@ -428,6 +428,43 @@ int dinoseg_op_attention_bwd(const void* q, const void* k, const void* v, int64_
 /* native_layer_norm_backward: dx (+)= ..., dgamma += ..., dbeta += ... (atomics; zero them first) */
 int dinoseg_op_layernorm_bwd(const float* dy, const float* x, const float* gamma, float eps, int32_t M, int32_t D, float* dx,
                              int32_t accumulate, float* dgamma, float* dbeta, int32_t drop_cls, int32_t ntok, void* stream);
+/* ... with the by-products the fine-tune step uses: the final dx rows as bf16 planes dxp [planes][M][D] (plane stride dxp_plane; null =
+ * none) and colsum[D] += their column sums (null = none) */
+int dinoseg_op_layernorm_bwd2(const float* dy, const float* x, const float* gamma, float eps, int32_t M, int32_t D, float* dx,
+                              int32_t accumulate, float* dgamma, float* dbeta, int32_t drop_cls, int32_t ntok, void* dxp,
+                              int64_t dxp_plane, int32_t planes, float* colsum, void* stream);
+
+/* Weight gradient on row-major planes (the step's route for every layer whose input width is a multiple of 128):
+ * dW[n][k] += sum_m Y[m][n] X[m][k] for n < N, k < k_cols; Y planes [planes][M][ldy], X planes [planes][M][ldx], Kc % 128 == 0
+ * columns of X multiplied.  ksplit slices of the batch write partial tiles to part (required: ksplit * ceil(N/128)*128 * Kc floats), then
+ * the slices that own rows are summed into dW (row stride ldw; dW == null: column sums only).  colsum[N] += the column sums of Y
+ * (null = none).  Zero dW and colsum first. */
+int dinoseg_op_gemm_tn(const void* Y, int64_t y_plane, int32_t ldy, const void* X, int64_t x_plane, int32_t ldx, int32_t M, int32_t N,
+                       int32_t Kc, int32_t planes, int32_t ksplit, float* part, float* dW, int32_t ldw, int32_t k_cols, float* colsum,
+                       void* stream);
+/* Input gradient of a linear layer: acc[M][N] = A[M][K] . Wt[N][K]^T (bf16 planes, N % 128 == 0, K % 64 == 0) with a backward
+ * epilogue: epi 0 = fp32 out_f32[M][ldo_f32] (no bias), 6 = bf16 planes out_bf16 [planes][M][ldo], 8 = acc * gelu'(aux_in),
+ * 9 = acc * (aux_in > 0) into out_bf16 (aux_in: planes [planes][M][ldo], plane stride aux_plane) */
+int dinoseg_op_gemm_bwd(const void* A, int64_t a_plane, int32_t lda, const void* Wt, int64_t w_plane, int32_t M, int32_t N, int32_t K,
+                        int32_t planes, int32_t epi, float* out_f32, int32_t ldo_f32, void* out_bf16, int64_t out_plane, int32_t ldo,
+                        const void* aux_in, int64_t aux_plane, void* stream);
+/* Weight gradient of a narrow layer (input width not a multiple of 128: the patch embedding): dY (fp32 rows dy_f32 [*][ldy], or bf16
+ * planes dy [planes][*][ldy]; drop_cls: logical row j is physical row b*ntok + t + 1) and X planes [planes][M][ldx] are transposed
+ * into T1 / T2 ([planes][round_up(., 128)][m_pad] each, plane stride t_plane, m_pad % 64 == 0, >= M), colsum[N] += the column sums
+ * of dY; then dW[N][K] += dY^T X over the batch rows: ksplit == 1 by fp32 atomics, else ksplit slices of partial tiles in part
+ * (ksplit * ceil(N/128)*128 * round_up(K, 128) floats) and a reduce. */
+int dinoseg_op_wgrad_nt(const float* dy_f32, const void* dy, int64_t dy_plane, int32_t ldy, const void* x, int64_t x_plane, int32_t ldx,
+                        int32_t M, int32_t N, int32_t K, int32_t planes, int32_t drop_cls, int32_t ntok, int32_t ksplit, void* T1,
+                        void* T2, int64_t t_plane, int32_t m_pad, float* part, float* dW, float* colsum, void* stream);
+/* F.nll_loss (mean, ignore_index -100) + the backward of log_softmax.  Exactly one of labels [M] and dlogp [M][C] (fp32).  labels:
+ * acc (2 floats), *loss = the mean, flags[0] |= 1 on a label outside [0, C) and not -100 (the row is ignored).  dz: d logits as bf16
+ * hi + lo planes [2][M][ldz] (plane stride dz_plane), columns >= C zero; C > 32 needs an even ldz. */
+int dinoseg_op_nll_loss_grad(const float* logp, const int64_t* labels, const float* dlogp, int32_t M, int32_t C, float* acc,
+                             int32_t* flags, float* loss, void* dz, int64_t dz_plane, int32_t ldz, void* stream);
+/* Backward of dinoseg_op_pos_resample_hw: dpe [g*g+1][D] += the transpose of the resample applied to dpos [oh*ow+1][D];
+ * scratch: g * ow * D floats */
+int dinoseg_op_pos_resample_bwd_hw(const float* dpos, int32_t g, int32_t D, int32_t oh, int32_t ow, float* dpe, float* scratch,
+                                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,39 @@ def test_library_exports_every_header_symbol():
     assert lib.dinoseg_version() >= 100
 
 
+def test_backward_op_entries_refuse_bad_shapes_without_gpu():
+    """The stand-alone backward entries check their shapes before they touch the device (no pointer is dereferenced)."""
+    lib = capi.lib()
+    fake = 256      # never dereferenced: every call below is refused on the host
+    # gemm_tn multiplies whole 128-column tiles of X
+    assert lib.dinoseg_op_gemm_tn(fake, 0, 64, fake, 0, 128, 33, 7, 100, 1, 1, fake, fake, 100, 100, None, None) == -1
+    assert "gemm_tn: bad shape M=33 N=7 Kc=100 ksplit=1 planes=1" in capi.last_error()
+    assert lib.dinoseg_op_gemm_tn(fake, 0, 64, fake, 0, 128, 33, 7, 128, 1, 0, fake, fake, 128, 128, None, None) == -1
+    assert "gemm_tn: bad shape" in capi.last_error()
+    assert lib.dinoseg_op_gemm_tn(fake, 0, 64, fake, 0, 128, 33, 7, 128, 1, 1, fake, fake, 99, 100, None, None) == -1
+    assert "bad output columns (k_cols=100 Kc=128 ldw=99)" in capi.last_error()
+    assert lib.dinoseg_op_gemm_tn(fake, 0, 64, fake, 0, 128, 33, 7, 128, 1, 1, None, fake, 128, 128, None, None) == -1
+    assert "dinoseg_op_gemm_tn: part is required" in capi.last_error()
+    # the wide log-softmax backward stores column pairs: an odd d-logits width is refused
+    assert lib.dinoseg_op_nll_loss_grad(fake, None, fake, 4, 33, None, None, None, fake, 4 * 65, 65, None) == -1
+    assert "nll_loss: d logits planes need an even width >= C (C=33 ldz=65)" in capi.last_error()
+    assert lib.dinoseg_op_nll_loss_grad(fake, fake, fake, 4, 7, fake, fake, fake, fake, 4 * 64, 64, None) == -1
+    assert "needs exactly one of labels" in capi.last_error()
+    # the backward GEMM takes the backward epilogues only; the activation derivatives need their saved operand
+    assert lib.dinoseg_op_gemm_bwd(fake, 0, 64, fake, 0, 33, 128, 64, 1, 2, None, 0, fake, 0, 128, fake, 0, None) == -1
+    assert "epi 2 is not a backward epilogue" in capi.last_error()
+    assert lib.dinoseg_op_gemm_bwd(fake, 0, 64, fake, 0, 33, 128, 64, 1, 8, None, 0, fake, 0, 128, None, 0, None) == -1
+    assert "epi 8 needs aux_in" in capi.last_error()
+    assert lib.dinoseg_op_gemm_bwd(fake, 0, 64, fake, 0, 33, 100, 64, 1, 6, None, 0, fake, 0, 128, None, 0, None) == -1
+    assert "gemm: unsupported shape M=33 N=100 K=64" in capi.last_error()
+    # the narrow-layer route: the transposed planes must hold round_up(N, 128) x m_pad
+    assert lib.dinoseg_op_wgrad_nt(None, fake, 0, 384, fake, 0, 192, 100, 384, 192, 1, 0, 0, 1, fake, fake, 384 * 64, 128,
+                                   None, fake, None, None) == -1
+    assert "dinoseg_op_wgrad_nt: bad argument (M=100 N=384 K=192 m_pad=128 ksplit=1)" in capi.last_error()
+    assert lib.dinoseg_op_pos_resample_bwd_hw(fake, 28, 384, 0, 60, fake, fake, None) == -1
+    assert "bad shape g=28 D=384 oh=0 ow=60" in capi.last_error()
+
+
 def test_handle_lifecycle_and_errors_without_gpu():
     lib = capi.lib()
     h = ctypes.c_void_p()
