@@ -141,6 +141,19 @@ extern "C" int dinoseg_destroy(dinoseg_handle* h) {
     return 0;
 }
 
+// forget every packed copy (they point into wbuf): a refresh lays out only the copies its options ask for
+static void clear_packs(dinoseg_handle* h) {
+    h->packed.clear();
+    h->packed_slab.clear();
+    h->packed_mlp.clear();
+    h->packed_proj.clear();
+    h->packed_qkvf.clear();
+    h->packed_mlp3.clear();
+    h->packed_mlp4.clear();
+    h->packed_rs.clear();
+    h->packed_rs_bias.clear();
+}
+
 extern "C" int dinoseg_bind_weight(dinoseg_handle* h, const char* name, const void* dev_ptr, const int64_t* shape,
                                    int32_t ndim) {
     if (!h || !name || !dev_ptr || !shape) {
@@ -192,17 +205,7 @@ extern "C" int dinoseg_bind_weight(dinoseg_handle* h, const char* name, const vo
                 h->wbuf = nullptr; h->pos_cache = nullptr; h->pos_hp = h->pos_wp = -1;
                 h->wbuf_bytes = h->pos_cap = 0;
                 h->tws_B = h->tws_H = h->tws_W = h->tr_B = -1;
-                h->packed.clear();
-                h->packed_slab.clear();
-                h->packed_mlp.clear();
-                h->packed_proj.clear();
-                h->packed_qkvf.clear();
-                h->packed_mlp3.clear();
-    h->packed_mlp4.clear();
-    h->packed_rs_bias.clear();
-                h->packed_mlp4.clear();
-                h->packed_rs_bias.clear();
-                h->packed_rs.clear();
+                clear_packs(h);
                 h->bound.clear();
                 h->grads.clear();
             }
@@ -254,6 +257,29 @@ static std::vector<LinSpec> linear_specs(const dinoseg_handle* h) {
 
 static int ensure_mlp_packs(dinoseg_handle* h, hipStream_t s);
 
+// the gemm_rs option bit of a block linear: 1 mlp.fc1, 2 attn.qkv, 4 attn.proj and mlp.fc2
+static int rs_bit(const std::string& wname) {
+    return wname.find("mlp.fc1.weight") != std::string::npos ? 1 : wname.find("attn.qkv.weight") != std::string::npos ? 2 : 4;
+}
+
+// does gemm_rs.hip take this block linear (with the LayerNorm inside: ln)?  gemm_rs_supported on the shape and strides the forward
+// fills in; the addresses are placeholders it never reads
+static bool rs_shape_supported(const dinoseg_handle* h, const LinSpec& sp, bool ln) {
+    static float placeholder[1];
+    float* f = placeholder;
+    bf16_t* b = reinterpret_cast<bf16_t*>(placeholder);
+    const int bit = rs_bit(sp.wname);
+    GemmParams g = {};
+    g.A = b; g.lda = sp.K; g.W = b;
+    g.M = 1; g.N = sp.N; g.K = sp.K; g.planes = 1; g.fmt = sp.fmt; g.epi = bit == 1 ? EPI_GELU : bit == 2 ? EPI_QKV : EPI_RESID;
+    g.bias = f;
+    g.out_f32 = f; g.ldo_f32 = sp.N;        // attn.proj / mlp.fc2: the fp32 residual rows, N = embed_dim wide
+    g.out_bf16 = b; g.ldo = sp.N;           // mlp.fc1: the hidden rows
+    g.q = g.k = g.v = b; g.heads = h->cfg.num_heads; g.dmodel = h->cfg.embed_dim;
+    if (ln) { g.ln_x = f; g.ln_eps = h->cfg.ln_eps; }
+    return gemm_rs_supported(g);
+}
+
 extern "C" int dinoseg_refresh_weights(dinoseg_handle* h, void* stream) {
     if (!h) return -1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -264,9 +290,17 @@ extern "C" int dinoseg_refresh_weights(dinoseg_handle* h, void* stream) {
             dinoseg_set_error("dinoseg_refresh_weights: missing key '%s' (strict load)", kv.first.c_str());
             return -3;
         }
-    // the process-wide option is read ONCE per refresh: the packs below and every forward until the next refresh use this value
-    // (a later dinoseg_set_option on a live handle takes effect with the next refresh, never between a pack and its GEMM)
+    // the process-wide options that decide which copies exist are read ONCE per refresh: the packs below and every forward until the
+    // next refresh use these values (a later dinoseg_set_option on a live handle takes effect with the next refresh, never between a
+    // pack and its GEMM; mlp_fused4 and gemm_rs can also switch their route off in between: kernels.h Options)
     h->fp16_patch_planes_snap = options().fp16_patch_planes;
+    h->mlp_fused4_snap = options().mlp_fused4;
+    h->gemm_rs_snap = options().gemm_rs;
+    h->gemm_rs_ln_snap = options().gemm_rs_ln;
+    // every copy of the previous refresh is dropped: only those these options ask for are laid out again (a copy left over from
+    // another layout would be re-packed over, or read from, whatever lives at its old offset now)
+    clear_packs(h);
+    h->weights_ready = false;
     const std::vector<LinSpec> specs = linear_specs(h);
     auto ln_fed = [&](const LinSpec& sp) {        // qkv / fc1: also kept slab-major for the LayerNorm-fused kernel
         const bool qkv = sp.wname.find("attn.qkv.weight") != std::string::npos;
@@ -283,18 +317,16 @@ extern "C" int dinoseg_refresh_weights(dinoseg_handle* h, void* stream) {
     const int Dm = h->cfg.embed_dim, Fh = h->cfg.embed_dim * h->cfg.mlp_ratio;
     const bool mlp_fusable = mlp_fused_supported(Dm, Fh, h->planes);
     const bool mlp3_fusable = mlp_fused3_supported(Dm, Fh, h->planes);
-    const bool mlp4_fusable = options().mlp_fused4 && mlp_fused4_supported(Dm, Fh, h->planes);      // (read at refresh time: a fine-tune step re-packs what exists)
-    // one-plane modes of the wide model: fragment-order copies of the four block linears for the row-stationary GEMMs (gemm_rs.hip)
+    const bool mlp4_fusable = h->mlp_fused4_snap && mlp_fused4_supported(Dm, Fh, h->planes);      // (a fine-tune step re-packs what exists)
+    // one-plane modes of the wide model: fragment-order copies of the four block linears for the row-stationary GEMMs (gemm_rs.hip),
+    // for the linears whose gemm_rs bit is set and whose shape gemm_rs.hip takes (kind 0: qkv / fc1, kind 1: proj / fc2)
     auto rs_kind = [&](const LinSpec& sp) -> int {
-        if (!options().gemm_rs || h->planes != 1 || Dm != 768 || sp.wname.rfind("dino.blocks.", 0) != 0) return -1;      // (read at refresh time)
-        const int bit = sp.wname.find("mlp.fc1.weight") != std::string::npos ? 1 : sp.wname.find("attn.qkv.weight") != std::string::npos ? 2 : 4;
-        if (!(options().gemm_rs & bit)) return -1;                                                                              // (bit set: 1 fc1, 2 qkv, 4 proj + fc2)
-        if (sp.K == 768 && (sp.wname.find("attn.qkv.weight") != std::string::npos || sp.wname.find("mlp.fc1.weight") != std::string::npos)) return 0;
-        if (sp.N == 768 && sp.K % 192 == 0 && (sp.wname.find("attn.proj.weight") != std::string::npos || sp.wname.find("mlp.fc2.weight") != std::string::npos)) return 1;
-        return -1;
+        if (h->planes != 1 || Dm != 768 || sp.wname.rfind("dino.blocks.", 0) != 0 || !(h->gemm_rs_snap & rs_bit(sp.wname))) return -1;
+        const int kind = rs_bit(sp.wname) == 4 ? 1 : 0;
+        return rs_shape_supported(h, sp, kind == 0 && h->gemm_rs_ln_snap) ? kind : -1;
     };
-    // (kind 0 with option gemm_rs_ln, read here: the copy carries the LayerNorm in front of the linear -- norm1 for qkv, norm2 for fc1 -- and a folded bias)
-    auto rs_ln = [&](const LinSpec& sp) -> bool { return rs_kind(sp) == 0 && options().gemm_rs_ln; };
+    // (kind 0 with option gemm_rs_ln: the copy carries the LayerNorm in front of the linear -- norm1 for qkv, norm2 for fc1 -- and a folded bias)
+    auto rs_ln = [&](const LinSpec& sp) -> bool { return rs_kind(sp) == 0 && h->gemm_rs_ln_snap; };
     for (const LinSpec& sp : specs)
         if (rs_kind(sp) >= 0) total += align_up((size_t)sp.N * sp.K * sizeof(bf16_t), 256) + (rs_ln(sp) ? align_up((size_t)sp.N * sizeof(float), 256) : 0);
     if (mlp3_fusable) total += (size_t)h->cfg.n_blocks * align_up((size_t)mlp_fused3_pack_elems(Dm, Fh) * sizeof(bf16_t), 256);
@@ -311,43 +343,40 @@ extern "C" int dinoseg_refresh_weights(dinoseg_handle* h, void* stream) {
         h->wbuf_bytes = total;
     }
     size_t off = 0;
+    std::vector<dinoseg_handle::WbufEntry> layout;
+    auto carve = [&](const std::string& what, size_t bytes) -> char* {      // the next copy, 256-byte aligned, recorded in the layout
+        char* p = h->wbuf + off;
+        layout.push_back({what, off, bytes});
+        off += align_up(bytes, 256);
+        return p;
+    };
     std::vector<PackJob> jobs;
     for (const LinSpec& sp : specs) {
         PackedLinear pk;
-        pk.w = reinterpret_cast<bf16_t*>(h->wbuf + off);
+        pk.w = reinterpret_cast<bf16_t*>(carve(sp.wname, (size_t)sp.planes * sp.n_pad * sp.k_pad * sizeof(bf16_t)));
         pk.plane = (long)sp.n_pad * sp.k_pad;
         pk.n_pad = sp.n_pad;
         pk.k_pad = sp.k_pad;
-        off += align_up((size_t)sp.planes * sp.n_pad * sp.k_pad * sizeof(bf16_t), 256);
         jobs.push_back({W(h, sp.wname), pk.w, pk.plane, sp.N, sp.K, sp.n_pad, sp.k_pad, sp.planes, 0, sp.fmt});
         if (sp.n_pad != sp.N) {
-            pk.bias_pad = reinterpret_cast<float*>(h->wbuf + off);
-            off += align_up((size_t)sp.n_pad * sizeof(float), 256);
+            pk.bias_pad = reinterpret_cast<float*>(carve("bias_pad " + sp.bname, (size_t)sp.n_pad * sizeof(float)));
             DSEG_CHECK_HIP(hipMemsetAsync(pk.bias_pad, 0, (size_t)sp.n_pad * sizeof(float), s));
             DSEG_CHECK_HIP(hipMemcpyAsync(pk.bias_pad, W(h, sp.bname), (size_t)sp.N * sizeof(float),
                                           hipMemcpyDeviceToDevice, s));
         }
         h->packed[sp.wname] = pk;
         if (ln_fed(sp)) {
-            bf16_t* slab = reinterpret_cast<bf16_t*>(h->wbuf + off);
-            off += align_up((size_t)gemm_ln_slab_elems(sp.N, sp.K, sp.planes) * sizeof(bf16_t), 256);
+            bf16_t* slab = reinterpret_cast<bf16_t*>(carve("slab " + sp.wname, (size_t)gemm_ln_slab_elems(sp.N, sp.K, sp.planes) * sizeof(bf16_t)));
             DSEG_TRY(launch_pack_slabs(W(h, sp.wname), sp.N, sp.K, sp.planes, slab, s, sp.fmt));
             h->packed_slab[sp.wname] = slab;
         }
     }
     DSEG_TRY(launch_multi_pack(jobs.data(), (int)jobs.size(), s));
-    h->packed_mlp.clear();
-    h->packed_proj.clear();
-    h->packed_qkvf.clear();
-    h->packed_mlp3.clear();
-    h->packed_rs.clear();
     for (const LinSpec& sp : specs)
         if (rs_kind(sp) >= 0) {
-            bf16_t* dst = reinterpret_cast<bf16_t*>(h->wbuf + off);
-            off += align_up((size_t)sp.N * sp.K * sizeof(bf16_t), 256);
+            bf16_t* dst = reinterpret_cast<bf16_t*>(carve("rs " + sp.wname, (size_t)sp.N * sp.K * sizeof(bf16_t)));
             if (rs_ln(sp)) {
-                float* fb = reinterpret_cast<float*>(h->wbuf + off);
-                off += align_up((size_t)sp.N * sizeof(float), 256);
+                float* fb = reinterpret_cast<float*>(carve("rs_bias " + sp.wname, (size_t)sp.N * sizeof(float)));
                 const std::string blk = sp.wname.substr(0, sp.wname.find(sp.wname.find("attn.qkv") != std::string::npos ? "attn.qkv" : "mlp.fc1"));
                 const std::string nrm = blk + (sp.wname.find("attn.qkv") != std::string::npos ? "norm1" : "norm2");
                 DSEG_TRY(launch_pack_rs_ln(W(h, sp.wname), W(h, nrm + ".weight"), W(h, nrm + ".bias"), W(h, sp.bname), sp.N, sp.K, dst, fb, s, sp.fmt));
@@ -359,29 +388,28 @@ extern "C" int dinoseg_refresh_weights(dinoseg_handle* h, void* stream) {
         }
     if (mlp3_fusable)
         for (int i = 0; i < h->cfg.n_blocks; ++i) {
-            h->packed_mlp3["dino.blocks." + std::to_string(i) + "."] = reinterpret_cast<bf16_t*>(h->wbuf + off);
-            off += align_up((size_t)mlp_fused3_pack_elems(Dm, Fh) * sizeof(bf16_t), 256);
+            const std::string b = "dino.blocks." + std::to_string(i) + ".";
+            h->packed_mlp3[b] = reinterpret_cast<bf16_t*>(carve("mlp3 " + b, (size_t)mlp_fused3_pack_elems(Dm, Fh) * sizeof(bf16_t)));
         }
     if (mlp4_fusable)
         for (int i = 0; i < h->cfg.n_blocks; ++i) {
-            h->packed_mlp4["dino.blocks." + std::to_string(i) + "."] = reinterpret_cast<bf16_t*>(h->wbuf + off);
-            off += align_up((size_t)mlp_fused4_pack_elems(Dm, Fh) * sizeof(bf16_t), 256);
+            const std::string b = "dino.blocks." + std::to_string(i) + ".";
+            h->packed_mlp4[b] = reinterpret_cast<bf16_t*>(carve("mlp4 " + b, (size_t)mlp_fused4_pack_elems(Dm, Fh) * sizeof(bf16_t)));
         }
     if (mlp_fusable)
         for (int i = 0; i < h->cfg.n_blocks; ++i) {
             const std::string b = "dino.blocks." + std::to_string(i) + ".";
-            bf16_t* dst = reinterpret_cast<bf16_t*>(h->wbuf + off);
-            off += align_up((size_t)mlp_fused_pack_elems(Dm, Fh) * sizeof(bf16_t), 256);
-            h->packed_mlp[b] = dst;
-            if (mlp_fused_proj_pack_elems(Dm) > 0) {
-                h->packed_proj[b] = reinterpret_cast<bf16_t*>(h->wbuf + off);
-                off += align_up((size_t)mlp_fused_proj_pack_elems(Dm) * sizeof(bf16_t), 256);
-            }
-            if (i > 0 && mlp_fused_qkv_pack_elems(Dm) > 0) {      // (block 0's qkv has no fused kernel in front of it)
-                h->packed_qkvf[b] = reinterpret_cast<bf16_t*>(h->wbuf + off);
-                off += align_up((size_t)mlp_fused_qkv_pack_elems(Dm) * sizeof(bf16_t), 256);
-            }
+            h->packed_mlp[b] = reinterpret_cast<bf16_t*>(carve("mlp " + b, (size_t)mlp_fused_pack_elems(Dm, Fh) * sizeof(bf16_t)));
+            if (mlp_fused_proj_pack_elems(Dm) > 0)
+                h->packed_proj[b] = reinterpret_cast<bf16_t*>(carve("proj " + b, (size_t)mlp_fused_proj_pack_elems(Dm) * sizeof(bf16_t)));
+            if (i > 0 && mlp_fused_qkv_pack_elems(Dm) > 0)      // (block 0's qkv has no fused kernel in front of it)
+                h->packed_qkvf[b] = reinterpret_cast<bf16_t*>(carve("qkvf " + b, (size_t)mlp_fused_qkv_pack_elems(Dm) * sizeof(bf16_t)));
         }
+    // a captured forward bakes in the address and the format of every copy it reads: another layout in the same buffer (a copy
+    // that changed size, appeared or left) is a new state generation, like a new buffer; the same layout is not (an in-place weight
+    // update replays the captured forward, which reads the re-packed copies)
+    if (layout != h->wbuf_layout) ++h->generation;
+    h->wbuf_layout = std::move(layout);
     // Always packed here, in stream order with the other packs: a forward captured in a graph contains no pack kernels, so a
     // deferred pack (round 3 skipped these while gradient buffers were bound) would let a replay after a fine-tune step read stale
     // fused-kernel weights next to fresh ones.  Three small launches per block.
@@ -616,26 +644,6 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
     // the call's batch) then take the routes -- and the summation order -- the unsplit batch takes, so the split changes no bit
     const int dB = disp_B > 0 ? disp_B : B;
     const int disp_M = dB * L.ntok, disp_Mp = dB * L.n;
-    // a block linear through the row-stationary streaming kernels (gemm_rs.hip) where a fragment-order copy exists and the batch fills the chip
-    // ... and with the LayerNorm in front of it in its prologue (qkv / fc1 of the wide model: no LayerNorm launch, no 16-bit A round trip)
-    auto rs_takes_ln = [&](const std::string& wname) -> bool {
-        return options().gemm_rs && options().gemm_rs_ln && disp_M >= options().gemm_rs_min_rows && h->packed_rs_bias.count(wname) && P == 1 &&
-               !(mreq && mreq->cls_mask);
-    };
-    auto gemm_any = [&](GemmParams& g, const std::string& wname) -> int {
-        // (a copy that carries the LayerNorm serves only the launch with the LayerNorm inside)
-        if (options().gemm_rs && disp_M >= options().gemm_rs_min_rows && h->packed_rs.count(wname) && (g.ln_x != nullptr) == (h->packed_rs_bias.count(wname) != 0)) {
-            GemmParams r = g;
-            r.W = h->packed_rs.at(wname);
-            if (g.ln_x) r.bias = h->packed_rs_bias.at(wname);
-            if (gemm_rs_supported(r)) return launch_gemm_rs(r, s);
-        }
-        if (g.ln_x) {      // (rs_takes_ln said the LayerNorm runs inside: no normalised A exists for another kernel)
-            dinoseg_set_error("internal: %s was routed to gemm_rs with its LayerNorm inside, which does not take it", wname.c_str());
-            return -1;
-        }
-        return launch_gemm(g, s);
-    };
     char* ws = slot ? h->ws2 : h->ws;
     float* X = reinterpret_cast<float*>(ws + L.X);
     bf16_t* A = reinterpret_cast<bf16_t*>(ws + L.A);
@@ -647,6 +655,26 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
     bf16_t* FEAT = reinterpret_cast<bf16_t*>(ws + L.FEAT);
     bf16_t* H1 = reinterpret_cast<bf16_t*>(ws + L.H1);
     bf16_t* H2 = reinterpret_cast<bf16_t*>(ws + L.H2);
+    // a block linear through the row-stationary streaming kernels (gemm_rs.hip): its copy exists (the linear's gemm_rs bit was set at
+    // the last refresh), the bit is still set, the batch fills the chip and the kernel takes the parameters.  A copy that carries the
+    // LayerNorm in front of qkv / fc1 (gemm_rs_ln at that refresh) runs with the LayerNorm inside -- no LayerNorm launch, no 16-bit A
+    // round trip -- and only so.  The one predicate for both the LayerNorm launch and the GEMM; *r = the kernel's parameters.
+    auto rs_route = [&](const GemmParams& g, const std::string& wname, GemmParams* r) -> bool {
+        const auto w = h->packed_rs.find(wname);
+        if (w == h->packed_rs.end() || !(options().gemm_rs & h->gemm_rs_snap & rs_bit(wname)) || disp_M < options().gemm_rs_min_rows) return false;
+        *r = g;
+        r->W = w->second;
+        const auto fb = h->packed_rs_bias.find(wname);
+        if (fb != h->packed_rs_bias.end()) {
+            if (mreq && mreq->cls_mask) return false;
+            r->ln_x = X; r->ln_eps = c.ln_eps; r->bias = fb->second;
+        }
+        return gemm_rs_supported(*r);
+    };
+    auto gemm_any = [&](const GemmParams& g, const std::string& wname) -> int {
+        GemmParams r;
+        return rs_route(g, wname, &r) ? launch_gemm_rs(r, s) : launch_gemm(g, s);
+    };
 
     // ---- prepare_tokens (vision_transformer.py:224-235) ----
     float mean255[3], inv255[3];
@@ -703,14 +731,8 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
             g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.dmodel = D; g.qscale = qscale; g.fmt = FM;
             DSEG_PROF(DINOSEG_PROF_QKV, DSEG_TRY(launch_gemm_ln(g, D, P, s)));
         } else {
-        const bool ln_inside = rs_takes_ln(b + "attn.qkv.weight");
-        if (!ln_inside)
-        DSEG_PROF(DINOSEG_PROF_LN, DSEG_TRY(launch_layernorm(X, W(h, b + "norm1.weight"), W(h, b + "norm1.bias"), c.ln_eps, L.M, D, A, L.a_plane, P,
-                                  nullptr, 0, L.ntok, s, FM)));
-        {
             const PackedLinear& pk = h->packed.at(b + "attn.qkv.weight");
             GemmParams g = {};
-            if (ln_inside) { g.ln_x = X; g.ln_eps = c.ln_eps; }
             g.A = A; g.a_plane = L.a_plane; g.lda = D;
             g.W = pk.w; g.w_plane = pk.plane;
             g.M = L.M; g.N = 3 * D; g.K = D; g.planes = P; g.fmt = FM; g.epi = EPI_QKV; g.dispatch_rows = disp_M;
@@ -718,8 +740,12 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
             g.bias = W(h, b + "attn.qkv.bias");
             g.q = Q; g.k = Kb; g.v = V; g.qkv_plane = L.qkv_plane;
             g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.dmodel = D; g.qscale = qscale;
-            DSEG_PROF(DINOSEG_PROF_QKV, DSEG_TRY(gemm_any(g, b + "attn.qkv.weight")));
-        }
+            GemmParams r;
+            const bool rs = rs_route(g, b + "attn.qkv.weight", &r);
+            if (!rs || !r.ln_x)
+                DSEG_PROF(DINOSEG_PROF_LN, DSEG_TRY(launch_layernorm(X, W(h, b + "norm1.weight"), W(h, b + "norm1.bias"), c.ln_eps, L.M, D, A, L.a_plane,
+                                                                     P, nullptr, 0, L.ntok, s, FM)));
+            DSEG_PROF(DINOSEG_PROF_QKV, DSEG_TRY(rs ? launch_gemm_rs(r, s) : launch_gemm(g, s)));
         }
         if (attn_out && i == c.n_blocks - 1)      // get_last_selfattention: probabilities of the last block, then stop
             return launch_attn_probs(Q, Kb, L.qkv_plane, P, B, H, L.ntok, L.npad, attn_out, s, FM);
@@ -795,7 +821,7 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
                 }
             }
             DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(launch_mlp_fused3(g, s)));
-        } else if (fuse_mlp && fuse_proj && options().mlp_fused4 && !options().qkv_fused && h->packed_mlp4.count(b)) {
+        } else if (fuse_mlp && fuse_proj && options().mlp_fused4 && h->mlp_fused4_snap && !options().qkv_fused && h->packed_mlp4.count(b)) {
             DSEG_TRY(ensure_mlp_packs(h, s));
             // the same launch with one wave per SIMD (mlp_fused4.hip)
             MlpFused3Params g = {};
@@ -837,21 +863,19 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
             g.out_bf16 = HB; g.out_plane = L.hb_plane; g.ldo = F;
             DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(launch_gemm_ln(g, D, P, s)));
         } else {
-        const bool ln_inside = rs_takes_ln(b + "mlp.fc1.weight");
-        if (!ln_inside)
-        DSEG_PROF(DINOSEG_PROF_LN, DSEG_TRY(launch_layernorm(X, W(h, b + "norm2.weight"), W(h, b + "norm2.bias"), c.ln_eps, L.M, D, A, L.a_plane, P,
-                                  nullptr, 0, L.ntok, s, FM)));
-        {
             const PackedLinear& pk = h->packed.at(b + "mlp.fc1.weight");
             GemmParams g = {};
-            if (ln_inside) { g.ln_x = X; g.ln_eps = c.ln_eps; }
             g.A = A; g.a_plane = L.a_plane; g.lda = D;
             g.W = pk.w; g.w_plane = pk.plane;
             g.M = L.M; g.N = F; g.K = D; g.planes = P; g.fmt = FM; g.epi = EPI_GELU; g.dispatch_rows = disp_M;
             g.bias = W(h, b + "mlp.fc1.bias");
             g.out_bf16 = HB; g.out_plane = L.hb_plane; g.ldo = F;
-            DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(gemm_any(g, b + "mlp.fc1.weight")));
-        }
+            GemmParams r;
+            const bool rs = rs_route(g, b + "mlp.fc1.weight", &r);
+            if (!rs || !r.ln_x)
+                DSEG_PROF(DINOSEG_PROF_LN, DSEG_TRY(launch_layernorm(X, W(h, b + "norm2.weight"), W(h, b + "norm2.bias"), c.ln_eps, L.M, D, A, L.a_plane,
+                                                                     P, nullptr, 0, L.ntok, s, FM)));
+            DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(rs ? launch_gemm_rs(r, s) : launch_gemm(g, s)));
         }
         {
             const PackedLinear& pk = h->packed.at(b + "mlp.fc2.weight");

@@ -44,7 +44,7 @@ struct dinoseg_handle {
     std::map<std::string, bf16_t*> packed_mlp;      // per block ("dino.blocks.i."): fc1 + fc2 in MFMA fragment order (mlp_fused2.hip)
     std::map<std::string, bf16_t*> packed_proj;     // per block: attn.proj.weight in the same fragment order (mlp_fused2.hip, PROJ)
     std::map<std::string, bf16_t*> packed_rs;       // per Linear weight name, one-plane modes at embed_dim 768: the fragment-order copy gemm_rs.hip streams
-    std::map<std::string, float*> packed_rs_bias;   // ... those of them that carry the LayerNorm in front of the linear (qkv / fc1, option gemm_rs_ln at refresh): the folded bias
+    std::map<std::string, float*> packed_rs_bias;   // ... those of them that carry the LayerNorm in front of the linear (qkv / fc1, gemm_rs_ln_snap): the folded bias
     std::map<std::string, bf16_t*> packed_mlp4;     // per block, one-plane modes: attn.proj + fc1 + fc2 as the slot stream of mlp_fused4.hip
     std::map<std::string, bf16_t*> packed_mlp3;     // per block, hi + lo modes: attn.proj + fc1 + fc2 as the slot stream of mlp_fused3.hip
     std::map<std::string, bf16_t*> packed_qkvf;     // per block: attn.qkv.weight in fragment order (mlp_fused2.hip, QKV tail of the block before)
@@ -52,6 +52,15 @@ struct dinoseg_handle {
                                            // step refreshes the weights every step and never runs the fused MLP kernel)
     bool weights_ready = false;
     int fp16_patch_planes_snap = 1;        // option fp16_patch_planes as of the last dinoseg_refresh_weights (what the packs were made for)
+    int mlp_fused4_snap = 0;               // ... mlp_fused4, gemm_rs and gemm_rs_ln likewise (kernels.h Options: which of them a forward reads)
+    int gemm_rs_snap = 0;
+    int gemm_rs_ln_snap = 0;
+    struct WbufEntry {                     // one packed copy in wbuf: what it is, where it starts, how long it is
+        std::string what;
+        size_t off, bytes;
+        bool operator==(const WbufEntry& o) const { return what == o.what && off == o.off && bytes == o.bytes; }
+    };
+    std::vector<WbufEntry> wbuf_layout;    // the copies of the last refresh, in wbuf order (a change of layout is a new generation)
     int64_t generation = 0;     // dinoseg_state_generation: bumped when an address or cached content a captured forward bakes in changes
     // pos-embed cache
     float* pos_cache = nullptr;

@@ -151,7 +151,13 @@ long mlp_fused4_pack_elems(int D, int F);       // 16-bit elements of the packed
 int launch_pack_mlp4(const MlpFused3Weights& w, int D, int F, bf16_t* dst, hipStream_t s, int fmt);
 int launch_mlp_fused4(const MlpFused3Params& p, hipStream_t s);
 
-// tuning knobs (dinoseg_set_option): see api.hip
+// tuning knobs (dinoseg_set_option): see api.hip.  A handle's forward reads them as it runs, except four that decide which packed
+// copies dinoseg_refresh_weights lays out (every load_state_dict, in-place weight update and fine-tune step refreshes):
+// fp16_patch_planes and gemm_rs_ln are refresh-only, mlp_fused4 and the gemm_rs bits switch-off-only (below).  Every forward
+// equals, bit for bit, the same forward of a fresh handle whose first refresh saw fp16_patch_planes and gemm_rs_ln at their values
+// of the last refresh, mlp_fused4 and gemm_rs at (value at the last refresh) AND (current value), and every other option at its
+// current value (tests/test_refresh_routes_gpu.py).  A refresh that
+// changes which copies exist, or their offsets or sizes, bumps dinoseg_state_generation; one that keeps them does not.
 struct Options {
     int gemm_ln = 1;         // qkv / fc1 through the LayerNorm-fused kernel (gemm_ln.hip): 0 never, 2 wherever it applies, 1 = by measurement (api.hip)
     int gemm_big = 1;        // use gemm_big.hip where it applies
@@ -168,15 +174,21 @@ struct Options {
     int mlp_fused4 = 0;      // one-plane modes: 1 = the fused projection + MLP launch with ONE wave per SIMD (mlp_fused4.hip) instead of mlp_fused2.hip's two
                              // (no qkv tail: only while qkv_fused is 0).  The launch 354-360 against 359-371 us, the headline +0.3-0.4 % (profiles/r06_mlp_fused4.md):
                              // inside the boxes' spread, so the older kernel stays the default.
-                             // Read when the weights are packed (dinoseg_refresh_weights) and at every forward
+                             // Switch-off-only: read when the weights are packed (dinoseg_refresh_weights: its copies exist only if it was
+                             // on then) and at every forward; the route runs while it was on at the last refresh AND is on now -- setting it
+                             // between two refreshes can switch the route off, never on
     int qkv_fused4 = 1;      // ... with LayerNorm1 + qkv of the NEXT block at its end (as qkv_fused3 for the hi + lo launch)
     int qkv_fused3 = 1;      // hi + lo planes (mlp_fused3.hip): 1 = LayerNorm1 + qkv of the NEXT block at the end of the fused projection + MLP launch
     int gemm_rs = 3;         // the row-stationary streaming GEMMs (gemm_rs.hip; embed_dim 768, one plane, >= gemm_rs_min_rows rows), a bit per linear:
                              // 1 = mlp.fc1 (its GELU epilogue rides in the MFMA gaps: 329 against gemm_big's 357 us at 57 616 rows), 2 = attn.qkv
                              // (-3 % on the launch), 4 = attn.proj and mlp.fc2 (slower); 0 = never.  configs.vitb on one box: 850 / 865 / 873
-                             // frames/s with 0 / 1 / 3 (profiles/r06_gemm_rs.md).  Read when the weights are packed and at every forward
+                             // frames/s with 0 / 1 / 3 (profiles/r06_gemm_rs.md).  Switch-off-only, bit by bit, like mlp_fused4: a linear gets its
+                             // copy at refresh only if its bit is set and gemm_rs.hip takes its shape (else LayerNorm + the regular GEMM), and
+                             // runs on it while the bit was set at the last refresh AND is set at the forward
     int gemm_rs_min_rows = 24000;
-    int gemm_rs_ln = 1;      // ... with the LayerNorm in front of qkv / fc1 computed in the kernel's prologue (no LayerNorm launch, no 16-bit A round trip)
+    int gemm_rs_ln = 1;      // ... with the LayerNorm in front of qkv / fc1 computed in the kernel's prologue (no LayerNorm launch, no 16-bit A round trip).
+                             // Refresh-only: the copy carries the LayerNorm or not as this was at the last refresh; setting it in between
+                             // changes nothing until the next refresh
     int proj_fused = 1;      // 1: the block's attention output projection runs inside the fused MLP launch
     int streams = 2;         // 2: dinoseg_forward runs a batch of >= split_min frames as two half-batches on two streams (api.hip)
     int split_min = 8;       // (8 frames @480: +6 %, 12: +16 %, 16: +12 %; 6 frames and fewer: slower split)
@@ -185,7 +197,7 @@ struct Options {
                              // gradient GEMM's split count not rounded to a multiple of 8 (its XCD-aware grid off: train_api.hip, gemm_tn.hip)
     int fp16_patch_planes = 1;      // precision fp16: 1 = the patch embedding on one fp16 plane like the rest of the mode (2466 -> 2486 frames/s,
                                     // 0.0263 / 8 flips -> 0.0218 / 5 on the G3 fixture), 2 = on bf16 hi+lo planes (round 4's first build).
-                                    // Read when the weights are packed: set it before the first forward
+                                    // Refresh-only: read when the weights are packed (the next dinoseg_refresh_weights), never in between
     int op_v_bf16 = 0;       // dinoseg_op_attention: AttnParams::v_bf16 (tests)
     int op_fmt = 0;          // operand format (FMT_BF16 / FMT_FP16) of the single-plane stand-alone ops (dinoseg_op_*: tests, tools); a
                              // handle's forward follows its own precision instead

@@ -219,7 +219,7 @@ class DINOSeg(nn.Module):
 
     Constructor keywords follow the reference (pl_torch_modules.py:144-147); two extra
     keyword-only arguments select what the reference hard-codes or cannot express:
-    ``arch`` ('vit_small' | 'vit_base' | a ViTConfig giving embed_dim/num_heads) and ``precision``: 'auto' (default: 'fp16x3'
+    ``arch`` ('vit_small' | 'vit_base' | a ViTConfig giving embed_dim/num_heads/mlp_ratio) and ``precision``: 'auto' (default: 'fp16x3'
     for inference calls, 'bf16x3' when a gradient is requested), 'fp16x3' / 'bf16x3' (parity modes: hi + lo operand planes),
     'fp16' / 'bf16' (benchmark modes: one plane).
     """
@@ -236,7 +236,7 @@ class DINOSeg(nn.Module):
         if precision != "auto" and precision not in _PRECISIONS:
             raise ValueError(f"precision must be 'auto' or one of {sorted(_PRECISIONS)}")
         base = arch if isinstance(arch, ViTConfig) else {"vit_small": VIT_S8, "vit_base": VIT_B8}[arch]
-        self.cfg = ViTConfig(embed_dim=base.embed_dim, num_heads=base.num_heads, n_blocks=int(n_blocks),
+        self.cfg = ViTConfig(embed_dim=base.embed_dim, num_heads=base.num_heads, mlp_ratio=base.mlp_ratio, n_blocks=int(n_blocks),
                              n_classes=int(n_classes), head=head)
         self.arch = arch
         self.precision = precision

@@ -101,6 +101,11 @@ def test_state_dict_keys_match_reference_schema():
         assert got == dict(want)
     assert len(DINOSeg(head="mlp", n_blocks=3).state_dict()) == 48      # 48 tensors for L=3
     assert sum(v.numel() for v in DINOSeg(head="mlp", n_blocks=3).state_dict().values()) == 5797903
+    # an arch given as a ViTConfig keeps its MLP width (the native handle is created from self.cfg)
+    wide = ViTConfig(embed_dim=768, num_heads=12, mlp_ratio=6, n_blocks=2)
+    m = DINOSeg(head="mlp", n_blocks=2, arch=wide)
+    assert m.cfg.mlp_ratio == 6
+    assert {k: tuple(v.shape) for k, v in m.state_dict().items()} == dict(tensor_shapes(wide))
 
 
 def test_set_resolution_and_no_cpu_fallback():
