@@ -128,6 +128,8 @@ SIGNATURES = {
     "dinoseg_workspace_bytes_hw": (_i64, [_vp, _i32, _i32, _i32]),
     "dinoseg_op_pos_resample_hw": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _fp, _vp]),
     "dinoseg_op_patch_gather_hw": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
+    # the gather at either patch size (8 or 16): H, W, patch
+    "dinoseg_op_patch_gather_p": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -167,7 +169,8 @@ def check(rc: int) -> None:
     if rc != 0:
         msg = last_error()
         # the reference raises ValueError for a bad resolution (pl_torch_modules.py:271-272)
-        if msg == "Resolution should be a multiple of 8.":
+        # (a patch-16 handle names its own patch size)
+        if msg in ("Resolution should be a multiple of 8.", "Resolution should be a multiple of 16."):
             raise ValueError(msg)
         raise DinosegError(f"dinoseg error {rc}: {msg}")
 

@@ -74,6 +74,20 @@ def load_checkpoint(cls, path, map_location=None, **overrides):
         kwargs["head"] = "mlp" if "clf.layer_2.weight" in sd else "linear"
     if "arch" not in kwargs and "dino.cls_token" in sd:
         kwargs["arch"] = "vit_base" if sd["dino.cls_token"].shape[-1] == 768 else "vit_small"
+    # the patch size and the stored position grid, from the tensors (patch-8 checkpoints carry neither among their hyper-parameters)
+    pw, pe = sd.get("dino.patch_embed.proj.weight"), sd.get("dino.pos_embed")
+    if "patch_size" in allowed and "patch_size" not in kwargs and not hasattr(kwargs.get("arch"), "patch") and pw is not None:
+        p = int(pw.shape[-1])
+        g = int(round((pe.shape[-2] - 1) ** 0.5)) if pe is not None else 224 // p
+        if p != 8 or g != 224 // p:
+            if g == 224 // p:
+                kwargs["patch_size"] = p
+            else:       # a position grid other than 224 / patch: only a ViTConfig says it (width and MLP ratio from the tensors too)
+                from .weights import ViTConfig
+                D = int(pw.shape[0])
+                fc1 = sd.get("dino.blocks.0.mlp.fc1.weight")
+                kwargs["arch"] = ViTConfig(embed_dim=D, num_heads=D // 64, mlp_ratio=int(fc1.shape[0]) // D if fc1 is not None else 4,
+                                           patch=p, pos_grid=g)
     model = cls(**kwargs)
     model.load_state_dict(OrderedDict((k, v.to(torch.float32)) for k, v in sd.items()), strict=True)
     return model

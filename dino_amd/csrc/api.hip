@@ -87,12 +87,13 @@ extern "C" int dinoseg_create(const dinoseg_config* cfg, dinoseg_handle** out) {
         dinoseg_set_error("dinoseg_create: null argument");
         return -1;
     }
-    if (cfg->embed_dim % 128 != 0 || cfg->embed_dim > 1024 || cfg->num_heads * 64 != cfg->embed_dim || cfg->patch != 8 ||
+    if (cfg->embed_dim % 128 != 0 || cfg->embed_dim > 1024 || cfg->num_heads * 64 != cfg->embed_dim ||
+        (cfg->patch != 8 && cfg->patch != 16) ||
         cfg->n_blocks < 0 || cfg->n_classes < 1 || cfg->n_classes > HEAD_WIDE_MAX_C || cfg->mlp_ratio < 1 || cfg->pos_grid < 1 ||
         (cfg->precision != DINOSEG_BF16 && cfg->precision != DINOSEG_BF16X3 && cfg->precision != DINOSEG_FP16 &&
          cfg->precision != DINOSEG_FP16X3) ||
         (cfg->head_kind != DINOSEG_HEAD_MLP && cfg->head_kind != DINOSEG_HEAD_LINEAR)) {
-        dinoseg_set_error("dinoseg_create: unsupported config (embed_dim=%d heads=%d patch=%d blocks=%d classes=%d)",
+        dinoseg_set_error("dinoseg_create: unsupported config (embed_dim=%d heads=%d patch=%d blocks=%d classes=%d; patch must be 8 or 16)",
                           cfg->embed_dim, cfg->num_heads, cfg->patch, cfg->n_blocks, cfg->n_classes);
         return -1;
     }
@@ -234,7 +235,7 @@ static std::vector<LinSpec> linear_specs(const dinoseg_handle* h) {
     const int D = c.embed_dim, F = c.embed_dim * c.mlp_ratio, P = h->planes, FM = h->fmt;
     std::vector<LinSpec> v;
     // (fp16 mode: the patch embedding runs split like the head -- 0.13 % of the FLOPs, and its operands are raw pixels)
-    v.push_back({"dino.patch_embed.proj.weight", "dino.patch_embed.proj.bias", D, 3 * c.patch * c.patch, D, 192, patch_planes(h), patch_fmt(h)});
+    v.push_back({"dino.patch_embed.proj.weight", "dino.patch_embed.proj.bias", D, 3 * c.patch * c.patch, D, 3 * c.patch * c.patch, patch_planes(h), patch_fmt(h)});
     for (int i = 0; i < c.n_blocks; ++i) {
         const std::string b = "dino.blocks." + std::to_string(i) + ".";
         v.push_back({b + "attn.qkv.weight", b + "attn.qkv.bias", 3 * D, D, 3 * D, D, P, FM});
@@ -429,20 +430,18 @@ extern "C" int dinoseg_refresh_weights(dinoseg_handle* h, void* stream) {
     return 0;
 }
 
-// H x W frames: both multiples of 8 (the reference's message, pl_torch_modules.py:271-272)
-static bool frame_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0; }
 
 extern "C" int dinoseg_prepare_resolution_hw(dinoseg_handle* h, int32_t Hf, int32_t Wf, void* stream) {
     if (!h) return -1;
-    if (!frame_ok(Hf, Wf)) {
-        dinoseg_set_error("Resolution should be a multiple of 8.");
+    if (!frame_ok(Hf, Wf, h->cfg.patch)) {
+        set_resolution_error(h->cfg.patch);
         return -1;
     }
     if (!h->bound.count("dino.pos_embed")) {
         dinoseg_set_error("dinoseg_prepare_resolution: dino.pos_embed not bound");
         return -3;
     }
-    const int hp = Hf / 8, wp = Wf / 8, D = h->cfg.embed_dim;
+    const int hp = Hf / h->cfg.patch, wp = Wf / h->cfg.patch, D = h->cfg.embed_dim;
     if (h->pos_hp == hp && h->pos_wp == wp && !h->pos_stale) return 0;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     DeviceGuard guard(h);
@@ -476,7 +475,7 @@ static WsLayout make_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
     const dinoseg_config& c = h->cfg;
     const int D = c.embed_dim, F = D * c.mlp_ratio, P = h->planes, HP = head_planes();
     WsLayout L;
-    L.n = (Hf / 8) * (Wf / 8);
+    L.n = (Hf / c.patch) * (Wf / c.patch);
     L.ntok = L.n + 1;
     L.npad = (L.ntok + 63) / 64 * 64;
     L.M = B * L.ntok;
@@ -488,9 +487,9 @@ static WsLayout make_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
         return o;
     };
     L.X = take((size_t)L.M * D * 4);
-    L.a_plane = (long)L.M * D;                 // LN output; also hosts the patch-gather matrix: patch_planes x [Mp, 192]
+    L.a_plane = (long)L.M * D;                 // LN output; also hosts the patch-gather matrix: patch_planes x [Mp, 3 p^2]
     {
-        const size_t ln_bytes = (size_t)P * L.a_plane * 2, pg_bytes = (size_t)patch_planes(h) * L.Mp * 192 * 2;
+        const size_t ln_bytes = (size_t)P * L.a_plane * 2, pg_bytes = (size_t)patch_planes(h) * L.Mp * (3 * c.patch * c.patch) * 2;
         L.A = take(ln_bytes > pg_bytes ? ln_bytes : pg_bytes);
     }
     L.qkv_plane = (long)B * c.num_heads * L.npad * 64;
@@ -518,8 +517,8 @@ extern "C" int64_t dinoseg_state_generation(const dinoseg_handle* h) { return h 
 
 extern "C" int64_t dinoseg_workspace_bytes_hw(const dinoseg_handle* h, int32_t B, int32_t H, int32_t W) {
     if (!h || B <= 0) return -1;
-    if (!frame_ok(H, W)) {
-        dinoseg_set_error("Resolution should be a multiple of 8.");
+    if (!frame_ok(H, W, h->cfg.patch)) {
+        set_resolution_error(h->cfg.patch);
         return -1;
     }
     return (int64_t)(make_layout(h, B, H, W).total + h->wbuf_bytes);
@@ -619,8 +618,8 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
         dinoseg_set_error("dinoseg_forward: bad argument");
         return -1;
     }
-    if (!frame_ok(Hf, Wf)) {
-        dinoseg_set_error("Resolution should be a multiple of 8.");
+    if (!frame_ok(Hf, Wf, h->cfg.patch)) {
+        set_resolution_error(h->cfg.patch);
         return -1;
     }
     if (x_kind != DINOSEG_INPUT_U8_HWC && x_kind != DINOSEG_INPUT_F32_CHW) {
@@ -679,15 +678,16 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
     // ---- prepare_tokens (vision_transformer.py:224-235) ----
     float mean255[3], inv255[3];
     norm_consts(mean255, inv255);
-    const long pg_plane = (long)L.Mp * 192;
+    const int KP = 3 * c.patch * c.patch;       // the conv's fan-in: 192 at patch 8, 768 at patch 16
+    const long pg_plane = (long)L.Mp * KP;
     const int PP = patch_planes(h);
-    DSEG_PROF(DINOSEG_PROF_PATCH, DSEG_TRY(launch_patch_gather(x, x_kind, B, Hf, Wf, mean255, inv255, A, pg_plane, PP, s, patch_fmt(h))));
+    DSEG_PROF(DINOSEG_PROF_PATCH, DSEG_TRY(launch_patch_gather(x, x_kind, B, Hf, Wf, mean255, inv255, A, pg_plane, PP, s, patch_fmt(h), c.patch)));
     {
         const PackedLinear& pk = h->packed.at("dino.patch_embed.proj.weight");
         GemmParams g = {};
-        g.A = A; g.a_plane = pg_plane; g.lda = 192;
+        g.A = A; g.a_plane = pg_plane; g.lda = KP;
         g.W = pk.w; g.w_plane = pk.plane;
-        g.M = L.Mp; g.N = D; g.K = 192; g.planes = PP; g.fmt = patch_fmt(h); g.epi = EPI_PATCH; g.dispatch_rows = disp_Mp;
+        g.M = L.Mp; g.N = D; g.K = KP; g.planes = PP; g.fmt = patch_fmt(h); g.epi = EPI_PATCH; g.dispatch_rows = disp_Mp;
         g.bias = W(h, "dino.patch_embed.proj.bias");
         g.out_f32 = X; g.ldo_f32 = D;
         g.pos = h->pos_cache; g.n_patches = L.n;
@@ -951,7 +951,7 @@ int ensure_aux_stream(dinoseg_handle* h) {
 extern "C" int dinoseg_forward_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, float* logp_out,
                                   int32_t* argmax_out, int32_t tap_block, float* tap_out, void* stream) {
     const bool split = h && x && options().streams >= 2 && B >= options().split_min && B >= 2 && tap_block < 0 && !tap_out &&
-                       frame_ok(H, W) && (x_kind == DINOSEG_INPUT_U8_HWC || x_kind == DINOSEG_INPUT_F32_CHW) && h->weights_ready;
+                       frame_ok(H, W, patch_of(h)) && (x_kind == DINOSEG_INPUT_U8_HWC || x_kind == DINOSEG_INPUT_F32_CHW) && h->weights_ready;
     if (!split) return forward_impl(h, x, x_kind, B, H, W, logp_out, argmax_out, tap_block, tap_out, nullptr, stream);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     DeviceGuard guard(h);
@@ -959,7 +959,7 @@ extern "C" int dinoseg_forward_hw(dinoseg_handle* h, const void* x, int32_t x_ki
     DSEG_TRY(ensure_aux_stream(h));
     DSEG_TRY(dinoseg_prepare_resolution_hw(h, H, W, stream));      // the resampled position embedding: before the fork, both halves read it
     const int B0 = (B + 1) / 2, B1 = B - B0;
-    const long n = (long)(H / 8) * (W / 8);
+    const long n = (long)(H / h->cfg.patch) * (W / h->cfg.patch);
     const size_t frame_bytes = x_kind == DINOSEG_INPUT_U8_HWC ? (size_t)H * W * 3 : (size_t)H * W * 3 * sizeof(float);
     const void* x1 = reinterpret_cast<const char*>(x) + (size_t)B0 * frame_bytes;
     const long ntok_ = n + 1;
@@ -1002,8 +1002,9 @@ extern "C" int dinoseg_forward_mask_hw(dinoseg_handle* h, const void* x, int32_t
         dinoseg_set_error("dinoseg_forward_mask: needs at least one block, n_masks >= 1 masks and one output buffer");
         return -1;
     }
-    if (frame_ok(H, W) && n_masks >= (H / 8) * (W / 8) + 1) {
-        dinoseg_set_error("dinoseg_forward_mask: n_masks=%d must be smaller than the token count %d", n_masks, (H / 8) * (W / 8) + 1);
+    const int32_t pz = h->cfg.patch;
+    if (frame_ok(H, W, pz) && n_masks >= (H / pz) * (W / pz) + 1) {
+        dinoseg_set_error("dinoseg_forward_mask: n_masks=%d must be smaller than the token count %d", n_masks, (H / pz) * (W / pz) + 1);
         return -1;
     }
     const MaskRequest mr = {cls_mask, n_masks, emb_out, attn_out, nullptr, 0};
@@ -1518,6 +1519,28 @@ extern "C" int dinoseg_op_patch_gather_hw(const void* x, int32_t x_kind, int32_t
     norm_consts(mean255, inv255);
     return launch_patch_gather(x, x_kind, B, H, W, mean255, inv255, reinterpret_cast<bf16_t*>(out), out_plane, planes,
                                reinterpret_cast<hipStream_t>(stream), planes == 2 ? options().op_fmt : FMT_BF16);
+}
+
+// the gather at either patch size (8: the entry above; 16: rows 768 wide); both plane counts in the op_fmt format
+extern "C" int dinoseg_op_patch_gather_p(const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t patch, void* out,
+                                         int64_t out_plane, int32_t planes, void* stream) {
+    if (patch != 8 && patch != 16) {
+        dinoseg_set_error("dinoseg_op_patch_gather_p: patch=%d must be 8 or 16", patch);
+        return -1;
+    }
+    if (!frame_ok(H, W, patch)) {
+        set_resolution_error(patch);
+        return -1;
+    }
+    if (!x || !out || B <= 0 || (planes != 1 && planes != 2) || (x_kind != DINOSEG_INPUT_U8_HWC && x_kind != DINOSEG_INPUT_F32_CHW) ||
+        (planes == 2 && out_plane < (int64_t)B * (H / patch) * (W / patch) * 3 * patch * patch)) {
+        dinoseg_set_error("dinoseg_op_patch_gather_p: bad argument");
+        return -1;
+    }
+    float mean255[3], inv255[3];
+    norm_consts(mean255, inv255);
+    return launch_patch_gather(x, x_kind, B, H, W, mean255, inv255, reinterpret_cast<bf16_t*>(out), out_plane, planes,
+                               reinterpret_cast<hipStream_t>(stream), options().op_fmt, patch);
 }
 
 extern "C" int dinoseg_op_patch_gather(const void* x, int32_t x_kind, int32_t B, int32_t r, void* out, int64_t out_plane,

@@ -266,8 +266,103 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const void* __restric
     }
 }
 
+// The same gather for Conv2d(3, D, kernel 16, stride 16) (ViT-S/16, ViT-B/16): hp = H/16, wp = W/16, rows 768 wide,
+// out[b*n + py*wp + px][c*256 + ky*16 + kx] = pixel(b, c, py*16+ky, px*16+kx).  One work item = (patch, ky): 16 pixels x 3 channels
+// -- 48 contiguous bytes of a uint8 frame, 16-byte aligned (W % 16 == 0), or 64 bytes of each fp32 channel row -- and two 16-byte
+// chunks per channel and plane on the way out.  Consecutive lanes take consecutive ky of one patch, then consecutive px: the
+// sixteen lanes of a patch cover its 3 x 512 contiguous bytes with each pair of store instructions (one instruction writes every
+// other 16-byte chunk), and a wave's four patches read four neighbouring 48-byte (64-byte) segments of each of sixteen frame rows.
+__global__ __launch_bounds__(256) void patch_gather16_kernel(const void* __restrict__ xin, int kind, int B, int H, int W,
+                                                             f32x4 mean255, f32x4 inv255, bf16_t* __restrict__ out,
+                                                             long out_plane, int planes, int fmt) {
+    const int hp = H >> 4, wp = W >> 4;
+    const long total = (long)B * hp * wp * 16;
+    for (long w = (long)blockIdx.x * blockDim.x + threadIdx.x; w < total; w += (long)gridDim.x * blockDim.x) {
+        const int ky = (int)(w & 15);
+        const long patch = w >> 4;
+        const int px = (int)(patch % wp);
+        const int py = (int)((patch / wp) % hp);
+        const int b = (int)(patch / ((long)hp * wp));
+        float v[3][16];
+        if (kind == 0) {
+            const uint8_t* src = reinterpret_cast<const uint8_t*>(xin) + (((long)b * H + py * 16 + ky) * W + px * 16) * 3;
+            uint32_t raw[12];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const uint4 q = reinterpret_cast<const uint4*>(src)[i];
+                raw[4 * i] = q.x; raw[4 * i + 1] = q.y; raw[4 * i + 2] = q.z; raw[4 * i + 3] = q.w;
+            }
+#pragma unroll
+            for (int kx = 0; kx < 16; ++kx)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int byte = kx * 3 + c;
+                    const float u = (float)((raw[byte >> 2] >> ((byte & 3) * 8)) & 0xFF);
+                    v[c][kx] = (u - mean255[c]) * inv255[c];
+                }
+        } else {
+            const float* src = reinterpret_cast<const float*>(xin);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float* s = src + (((long)b * 3 + c) * H + py * 16 + ky) * W + px * 16;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 a = *reinterpret_cast<const f32x4*>(s + 4 * q);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[c][4 * q + e] = a[e];
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            bf16_t* dst = out + patch * 768 + c * 256 + ky * 16;
+#pragma unroll
+            for (int hlf = 0; hlf < 2; ++hlf) {
+                const float* u = &v[c][8 * hlf];
+                uint4 hi, lo;
+                if (fmt == FMT_FP16) {      // (uniform; pixels are bounded: no saturation needed)
+                    split2<FMT_FP16>(u[0], u[1], hi.x, lo.x);
+                    split2<FMT_FP16>(u[2], u[3], hi.y, lo.y);
+                    split2<FMT_FP16>(u[4], u[5], hi.z, lo.z);
+                    split2<FMT_FP16>(u[6], u[7], hi.w, lo.w);
+                } else {
+                    split_bf16x2(u[0], u[1], hi.x, lo.x);
+                    split_bf16x2(u[2], u[3], hi.y, lo.y);
+                    split_bf16x2(u[4], u[5], hi.z, lo.z);
+                    split_bf16x2(u[6], u[7], hi.w, lo.w);
+                }
+                *reinterpret_cast<uint4*>(dst + 8 * hlf) = hi;
+                if (planes == 2) *reinterpret_cast<uint4*>(dst + out_plane + 8 * hlf) = lo;
+            }
+        }
+    }
+}
+
 int launch_patch_gather(const void* x, int kind, int B, int H, int W, const float* mean255, const float* inv_std255,
-                        bf16_t* out, long out_plane, int planes, hipStream_t s, int fmt) {
+                        bf16_t* out, long out_plane, int planes, hipStream_t s, int fmt, int patch) {
+    if (patch == 16) {
+        if (B <= 0 || H <= 0 || W <= 0 || H % 16 != 0 || W % 16 != 0) {
+            dinoseg_set_error("patch_gather: a patch-16 frame must be a positive multiple of 16 (B=%d H=%d W=%d)", B, H, W);
+            return -1;
+        }
+        // 16-byte loads and stores: W % 16 == 0 aligns every offset, the base pointers and the plane stride must be aligned too
+        if (reinterpret_cast<uintptr_t>(x) % 16 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0 || (planes == 2 && out_plane % 8 != 0)) {
+            dinoseg_set_error("patch_gather: patch 16 needs 16-byte aligned frames and output planes (x %p, out %p, out_plane %ld)", x,
+                              (void*)out, out_plane);
+            return -1;
+        }
+        const long total16 = (long)B * (H / 16) * (W / 16) * 16;
+        int grid16 = (int)((total16 + 255) / 256);
+        if (grid16 > 4096) grid16 = 4096;
+        f32x4 m16 = {mean255[0], mean255[1], mean255[2], 0.f}, iv16 = {inv_std255[0], inv_std255[1], inv_std255[2], 0.f};
+        hipLaunchKernelGGL(patch_gather16_kernel, dim3(grid16), dim3(256), 0, s, x, kind, B, H, W, m16, iv16, out, out_plane, planes, fmt);
+        DSEG_CHECK_HIP(hipGetLastError());
+        return 0;
+    }
+    if (patch != 8) {
+        dinoseg_set_error("patch_gather: patch=%d must be 8 or 16", patch);
+        return -1;
+    }
     const long total = (long)B * (H / 8) * (W / 8) * 8;
     int grid = (int)((total + 255) / 256);
     if (grid > 4096) grid = 4096;

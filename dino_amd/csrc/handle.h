@@ -182,4 +182,12 @@ static inline void norm_consts(float mean255[3], float inv255[3]) {
         inv255[c] = 1.0f / (sd[c] * 255.0f);    // reciprocal of std * max_pixel_value (fp32)
     }
 }
+// H x W frames: both positive multiples of the patch size, 8 or 16.  The ONE copy of the check and of its two messages (the
+// reference's text at patch 8, pl_torch_modules.py:271-272; a patch-16 handle names 16): dino_amd/capi.py maps exactly these
+// strings to ValueError.
+static inline bool frame_ok(int32_t H, int32_t W, int32_t p = 8) { return H > 0 && W > 0 && H % p == 0 && W % p == 0; }
+static inline void set_resolution_error(int32_t p) {
+    dinoseg_set_error(p == 16 ? "Resolution should be a multiple of 16." : "Resolution should be a multiple of 8.");
+}
+static inline int32_t patch_of(const dinoseg_handle* h) { return h ? h->cfg.patch : 8; }
 int dinoseg_train_release(dinoseg_handle* h);   // train_api.hip: frees the training workspace

@@ -253,8 +253,9 @@ int launch_layernorm(const float* x, const float* gamma, const float* beta, floa
 
 // Patch gather ("im2col") for the 8x8/stride-8 patch embedding. k index = c*64 + ky*8 + kx.
 // kind 0: uint8 HWC frames [B,H,W,3] with the ImageNet normalisation fused; kind 1: fp32 CHW [B,3,H,W] as is.  H, W multiples of 8.
+// patch = 16: the 16x16/stride-16 embedding, k index = c*256 + ky*16 + kx, rows 768 wide, H, W multiples of 16.
 int launch_patch_gather(const void* x, int kind, int B, int H, int W, const float* mean255, const float* inv_std255,
-                        bf16_t* out, long out_plane, int planes, hipStream_t s, int fmt = 0);
+                        bf16_t* out, long out_plane, int planes, hipStream_t s, int fmt = 0, int patch = 8);
 
 // X[b*ntok + 0, :] = cls[:] + pos[0, :]
 int launch_cls_rows(float* X, const float* cls, const float* pos, int B, int ntok, int D, hipStream_t s);

@@ -89,6 +89,10 @@ int launch_transpose_planes(const float* src_f32, const bf16_t* src_pl, long src
         dinoseg_set_error("transpose_planes: bad padding (M=%d C=%d m_pad=%d c_pad=%d)", M, C, m_pad, c_pad);
         return -1;
     }
+    if (T && planes > 1 && (long)c_pad * m_pad > t_plane) {      // (the planes would run into each other, the last one past the buffer)
+        dinoseg_set_error("transpose_planes: %d x %d transposed elements do not fit the plane stride %ld", c_pad, m_pad, t_plane);
+        return -1;
+    }
     float* det = nullptr;
     if (colsum && det_scratch().ptr) {
         // (a launch on the weight-gradient side stream must not share the caller's stream's region: both streams run at once)

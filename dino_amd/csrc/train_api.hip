@@ -44,7 +44,7 @@ TrainLayout make_train_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
     const int D = c.embed_dim, F = D * c.mlp_ratio, P = h->planes, HP = head_planes();
     TrainLayout L;
     memset(&L, 0, sizeof(L));
-    L.n = (Hf / 8) * (Wf / 8);
+    L.n = (Hf / c.patch) * (Wf / c.patch);
     L.ntok = L.n + 1;
     L.npad = (L.ntok + 63) / 64 * 64;
     L.M = B * L.ntok;
@@ -77,7 +77,7 @@ TrainLayout make_train_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
     L.blk_stride = off - b0;
     off = b0 + L.blk_stride * (c.n_blocks > 0 ? c.n_blocks : 1);
     L.Xfin = take((size_t)L.M * D * 4);
-    L.patch_plane = (long)L.Mp * 192;
+    L.patch_plane = (long)L.Mp * (3 * c.patch * c.patch);      // the gather matrix: rows 192 wide at patch 8, 768 at patch 16
     L.PATCH = take((size_t)P * L.patch_plane * 2);
     L.feat_plane = (long)L.Mp * D;
     L.FEAT = take((size_t)HP * L.feat_plane * 2);
@@ -98,11 +98,15 @@ TrainLayout make_train_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
         const size_t e = (size_t)L.a_plane > (size_t)L.Mp * 256 ? (size_t)L.a_plane : (size_t)L.Mp * 256;
         L.dCTX = take(2 * e * 2);
     }
-    L.t_plane = (long)L.Cmax * L.Mpad;
+    {   // a transposed plane holds the widest operand of a weight gradient: a block linear (Cmax rows), or the patch matrix, whose
+        // round_up(3 p^2, 128) rows exceed Cmax only for a narrow model at patch 16 (768 rows against 512 at embed_dim 128)
+        const int patch_rows = (3 * c.patch * c.patch + 127) / 128 * 128;
+        L.t_plane = (long)(L.Cmax > patch_rows ? L.Cmax : patch_rows) * L.Mpad;
+    }
     L.T1 = take((size_t)2 * L.t_plane * 2);
-    {   // ... T2 also hosts the row pass of the pos-embed gradient, [pos_grid][W/8][D] floats: a strip a few patches high (8 x 480)
+    {   // ... T2 also hosts the row pass of the pos-embed gradient, [pos_grid][W/patch][D] floats: a strip a few patches high (8 x 480)
         // has fewer token rows than that (on every frame of at least 7 x 7 patches the planes are the larger)
-        const size_t t_bytes = (size_t)2 * L.t_plane * 2, pos_bytes = (size_t)c.pos_grid * (Wf / 8) * D * sizeof(float);
+        const size_t t_bytes = (size_t)2 * L.t_plane * 2, pos_bytes = (size_t)c.pos_grid * (Wf / c.patch) * D * sizeof(float);
         L.T2 = take(t_bytes > pos_bytes ? t_bytes : pos_bytes);
         L.t2_bytes = t_bytes > pos_bytes ? t_bytes : pos_bytes;
     }
@@ -361,8 +365,8 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
         dinoseg_set_error("dinoseg_train_forward: bad argument");
         return -1;
     }
-    if (Hf <= 0 || Wf <= 0 || Hf % 8 != 0 || Wf % 8 != 0) {
-        dinoseg_set_error("Resolution should be a multiple of 8.");
+    if (!frame_ok(Hf, Wf, h->cfg.patch)) {
+        set_resolution_error(h->cfg.patch);
         return -1;
     }
     if (x_kind != DINOSEG_INPUT_U8_HWC && x_kind != DINOSEG_INPUT_F32_CHW) {
@@ -418,14 +422,14 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
     float mean255[3], inv255[3];
     norm_consts(mean255, inv255);
     bf16_t* PATCH = B16(L.PATCH);
-    DSEG_TRY(launch_patch_gather(x, x_kind, B, Hf, Wf, mean255, inv255, PATCH, L.patch_plane, P, s));
+    DSEG_TRY(launch_patch_gather(x, x_kind, B, Hf, Wf, mean255, inv255, PATCH, L.patch_plane, P, s, FMT_BF16, c.patch));
     float* X0 = NB > 0 ? F32(L.Xin) : F32(L.Xfin);
     {
         const PackedLinear& pk = h->packed.at("dino.patch_embed.proj.weight");
         GemmParams g = {};
-        g.A = PATCH; g.a_plane = L.patch_plane; g.lda = 192;
+        g.A = PATCH; g.a_plane = L.patch_plane; g.lda = 3 * c.patch * c.patch;
         g.W = pk.w; g.w_plane = pk.plane;
-        g.M = L.Mp; g.N = D; g.K = 192; g.planes = P; g.epi = EPI_PATCH;
+        g.M = L.Mp; g.N = D; g.K = 3 * c.patch * c.patch; g.planes = P; g.epi = EPI_PATCH;
         g.bias = W(h, "dino.patch_embed.proj.bias");
         g.out_f32 = X0; g.ldo_f32 = D;
         g.pos = h->pos_cache; g.n_patches = L.n;
@@ -563,7 +567,7 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
         dinoseg_set_error("dinoseg_backward: weights were re-bound after the forward; run the forward again");
         return -3;
     }
-    const int B = h->tr_B, oh = h->tr_H / 8, ow = h->tr_W / 8;
+    const int B = h->tr_B, oh = h->tr_H / h->cfg.patch, ow = h->tr_W / h->cfg.patch;
     const dinoseg_config& c = h->cfg;
     const int D = c.embed_dim, F = D * c.mlp_ratio, P = h->planes, HP = head_planes(), H = c.num_heads, C = c.n_classes;
     const int NB = c.n_blocks;
@@ -903,7 +907,7 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
     DSEG_TRY(launch_batch_sum_rows(dX, B, L.ntok, D, dpos, s));
     if (grad("dino.cls_token"))
         DSEG_CHECK_HIP(hipMemcpyAsync(grad("dino.cls_token"), dpos, (size_t)D * 4, hipMemcpyDeviceToDevice, s));
-    // (scratch: the T2 transpose buffer, idle until the patch-embed gradient below; make_train_layout sizes it for [pos_grid][W/8][D] floats)
+    // (scratch: the T2 transpose buffer, idle until the patch-embed gradient below; make_train_layout sizes it for [pos_grid][W/patch][D] floats)
     if (grad("dino.pos_embed")) {
         if ((size_t)c.pos_grid * ow * D * sizeof(float) > L.t2_bytes) {
             dinoseg_set_error("dinoseg_backward: pos-embed scratch does not fit (pos_grid %d, grid %d x %d)", c.pos_grid, oh, ow);
@@ -914,8 +918,13 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
     DSEG_TRY(launch_transpose_planes(dX, nullptr, 0, D, L.Mp, D, T1, tpl, pad128(D), L.Mppad, nullptr, 0, 0,
                                      grad("dino.patch_embed.proj.bias"), P, 1, L.ntok, s));
     if (grad("dino.patch_embed.proj.weight")) {
-        DSEG_TRY(launch_transpose_planes(nullptr, PATCH, L.patch_plane, 192, L.Mp, 192, T2, tpl, 256, L.Mppad, nullptr, 0, 0, nullptr, P, 0, 0, s));
-        DSEG_TRY(wgrad(T1, T2, tpl, L.Mppad, D, 256, 192, P, grad("dino.patch_embed.proj.weight")));
+        const int kp = 3 * c.patch * c.patch;       // 192 columns in 256 transposed rows at patch 8; 768 in 768 at patch 16
+        if ((long)pad128(kp) * L.Mppad > tpl) {
+            dinoseg_set_error("dinoseg_backward: the transposed patch matrix (%d x %d) does not fit its plane (%ld)", pad128(kp), L.Mppad, tpl);
+            return -1;
+        }
+        DSEG_TRY(launch_transpose_planes(nullptr, PATCH, L.patch_plane, kp, L.Mp, kp, T2, tpl, pad128(kp), L.Mppad, nullptr, 0, 0, nullptr, P, 0, 0, s));
+        DSEG_TRY(wgrad(T1, T2, tpl, L.Mppad, D, pad128(kp), kp, P, grad("dino.patch_embed.proj.weight")));
     }
     return stage_mark(NB + 1);
 }

@@ -18,7 +18,7 @@ from torch import nn
 
 from . import capi
 from .preprocess import resize_linear_u8
-from .weights import VIT_B8, VIT_S8, ViTConfig
+from .weights import VIT_B8, VIT_B16, VIT_S8, VIT_S16, ViTConfig
 
 _IMAGENET_MEAN = (0.485, 0.456, 0.406)
 _IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -217,9 +217,11 @@ class _DinoSegFunction(torch.autograd.Function):
 class DINOSeg(nn.Module):
     """DINO ViT + per-patch segmentation head on MI355X.
 
-    Constructor keywords follow the reference (pl_torch_modules.py:144-147); two extra
+    Constructor keywords follow the reference (pl_torch_modules.py:144-147); three extra
     keyword-only arguments select what the reference hard-codes or cannot express:
-    ``arch`` ('vit_small' | 'vit_base' | a ViTConfig giving embed_dim/num_heads/mlp_ratio) and ``precision``: 'auto' (default: 'fp16x3'
+    ``arch`` ('vit_small' | 'vit_base' | a ViTConfig giving embed_dim/num_heads/mlp_ratio/patch/pos_grid), ``patch_size`` (8 or 16,
+    the reference's ``get_dino(patch_size=8)``; None: the ViTConfig's own, 8 for a named arch; at 16 the stored position grid is
+    14 x 14 and every frame side is a multiple of 16) and ``precision``: 'auto' (default: 'fp16x3'
     for inference calls, 'bf16x3' when a gradient is requested), 'fp16x3' / 'bf16x3' (parity modes: hi + lo operand planes),
     'fp16' / 'bf16' (benchmark modes: one plane).
     """
@@ -227,7 +229,7 @@ class DINOSeg(nn.Module):
     def __init__(self, data_path=None, write_path=None, class_names=None, head="linear", n_blocks=1,
                  batch_size=1, lr=1e-6, optimizer=torch.optim.AdamW, freeze_backbone=True, max_epochs=200,
                  patience=10, grayscale=False, n_classes=7, pretrain_on_sim=False, comet_logger=None,
-                 augmented=True, random_init=False, backbone="vit", *, arch="vit_small", precision="auto"):
+                 augmented=True, random_init=False, backbone="vit", *, arch="vit_small", patch_size=None, precision="auto"):
         super().__init__()
         if backbone != "vit":
             raise NotImplementedError("only backbone='vit' is on the MI355X hot path (SURVEY.md §2 row 7)")
@@ -235,9 +237,20 @@ class DINOSeg(nn.Module):
             raise ValueError(f"unknown head {head!r}")
         if precision != "auto" and precision not in _PRECISIONS:
             raise ValueError(f"precision must be 'auto' or one of {sorted(_PRECISIONS)}")
-        base = arch if isinstance(arch, ViTConfig) else {"vit_small": VIT_S8, "vit_base": VIT_B8}[arch]
+        if patch_size is not None and patch_size not in (8, 16):
+            raise ValueError(f"patch_size must be 8 or 16 (the published DINO sizes), got {patch_size!r}")
+        if isinstance(arch, ViTConfig):
+            base = arch
+            if patch_size is not None and int(patch_size) != base.patch:
+                raise ValueError(f"patch_size={patch_size} contradicts arch.patch={base.patch}")
+        else:
+            base = {("vit_small", 8): VIT_S8, ("vit_base", 8): VIT_B8, ("vit_small", 16): VIT_S16,
+                    ("vit_base", 16): VIT_B16}[(arch, 8 if patch_size is None else int(patch_size))]
+        if base.patch not in (8, 16):
+            raise ValueError(f"arch.patch must be 8 or 16 (the published DINO sizes), got {base.patch}")
         self.cfg = ViTConfig(embed_dim=base.embed_dim, num_heads=base.num_heads, mlp_ratio=base.mlp_ratio, n_blocks=int(n_blocks),
-                             n_classes=int(n_classes), head=head)
+                             n_classes=int(n_classes), head=head, patch=base.patch, pos_grid=base.pos_grid)
+        self.patch_size = self.cfg.patch
         self.arch = arch
         self.precision = precision
         self.n_blocks = n_blocks
@@ -440,17 +453,21 @@ class DINOSeg(nn.Module):
         except Exception:
             pass
 
+    def _resolution_message(self) -> str:
+        # patch 8: the reference's text (pl_torch_modules.py:271-272), byte for byte
+        return "Resolution should be a multiple of 16." if self.cfg.patch == 16 else "Resolution should be a multiple of 8."
+
     # ---- reference API ----------------------------------------------------------------------
     def set_resolution(self, resolution=480):
-        if resolution % 8 != 0:
-            raise ValueError("Resolution should be a multiple of 8.")
+        if resolution % self.cfg.patch != 0:
+            raise ValueError(self._resolution_message())
         self.transforms = get_transforms(resolution)
         self.resolution = resolution
 
     def _run(self, x: torch.Tensor, kind: int, B: int, H: int, W: int, want_logp: bool = True, want_argmax: bool = False,
              tap_block: int = -1):
         self._sync_weights()
-        n = (H // 8) * (W // 8)
+        n = (H // self.cfg.patch) * (W // self.cfg.patch)
         dev = x.device
         logp = torch.empty((B * n, self.cfg.n_classes), dtype=torch.float32, device=dev) if want_logp else None
         amax = torch.empty((B * n,), dtype=torch.int32, device=dev) if want_argmax else None
@@ -480,7 +497,7 @@ class DINOSeg(nn.Module):
         if not 0 <= n_blocks <= self.cfg.n_blocks:
             raise ValueError(f"intermediate must be in [0, {self.cfg.n_blocks}]")
         self._sync_weights()
-        out = torch.empty((B, (H // 8) * (W // 8) + 1, self.cfg.embed_dim), dtype=torch.float32, device=self.device)
+        out = torch.empty((B, (H // self.cfg.patch) * (W // self.cfg.patch) + 1, self.cfg.embed_dim), dtype=torch.float32, device=self.device)
         capi.check(capi.lib().dinoseg_features_hw(self._handle, x.data_ptr(), kind, B, H, W, n_blocks, out.data_ptr(),
                                                   self._stream()))
         return out
@@ -492,8 +509,8 @@ class DINOSeg(nn.Module):
         self._require_gpu()
         if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
             raise ValueError(f"expected uint8 [B,H,W,3], got {frames_u8.dtype} {tuple(frames_u8.shape)}")
-        if frames_u8.shape[1] % 8 != 0 or frames_u8.shape[2] % 8 != 0:
-            raise ValueError("Resolution should be a multiple of 8.")
+        if frames_u8.shape[1] % self.cfg.patch != 0 or frames_u8.shape[2] % self.cfg.patch != 0:
+            raise ValueError(self._resolution_message())
         frames_u8 = frames_u8.to(self.device).contiguous()
         logp, amax, _ = self._run(frames_u8, capi.INPUT_U8_HWC, frames_u8.shape[0], frames_u8.shape[1], frames_u8.shape[2],
                                   want_logp=want_logp, want_argmax=True)
@@ -535,7 +552,8 @@ class DINOSeg(nn.Module):
     def predict(self, x) -> np.ndarray:
         """Run inference on a single image (PIL.Image or HxWx3 uint8 array); returns the int64 map the
         reference returns: np.kron of the (r/8)x(r/8) argmax map with a (480//(r/8))^2 block of ones
-        (pl_torch_modules.py:276-300, including the non-480 sizes it yields when 480 % (r/8) != 0)."""
+        (pl_torch_modules.py:276-300, including the non-480 sizes it yields when 480 % (r/8) != 0).  A patch-16 model follows the
+        same rule with 16 in place of 8: o = r // 16, blocks of 480 // o."""
         with torch.no_grad():
             raw = np.asarray(x)
             if raw.dtype != np.uint8 or not raw.flags.c_contiguous:
@@ -560,7 +578,7 @@ class DINOSeg(nn.Module):
                 amax = ent["out"]
             else:
                 _, amax = self.forward_frames(frames.to(self.device), want_logp=False)
-            output_size = self.resolution // 8
+            output_size = self.resolution // self.cfg.patch
             low_res = amax.cpu().numpy().astype(np.int64).reshape((output_size, output_size))
             high_res_patch_size = 480 // output_size
             # == np.kron(low_res, np.ones((k, k), dtype=int)) of the reference (:297-298), 4x cheaper on the host
@@ -576,13 +594,13 @@ class DINOSeg(nn.Module):
     def _mask_request(self, x: torch.Tensor, cls_mask: torch.Tensor, want_emb: bool, want_attn: bool):
         self._require_gpu()
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
-        if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 3 or x.shape[2] % 8 != 0 or x.shape[3] % 8 != 0:
-            raise ValueError(f"expected a single frame [1,3,H,W] with H % 8 == W % 8 == 0, got {tuple(x.shape)}")
+        if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 3 or x.shape[2] % self.cfg.patch != 0 or x.shape[3] % self.cfg.patch != 0:
+            raise ValueError(f"expected a single frame [1,3,H,W] with H % {self.cfg.patch} == W % {self.cfg.patch} == 0, got {tuple(x.shape)}")
         H, W = x.shape[2], x.shape[3]
-        n = (H // 8) * (W // 8)
+        n = (H // self.cfg.patch) * (W // self.cfg.patch)
         m = cls_mask.to(device=self.device, dtype=torch.float32).reshape(cls_mask.shape[0], -1).contiguous()
         if m.shape[1] != n:
-            raise ValueError(f"cls_mask must be [n_masks, {H // 8}, {W // 8}], got {tuple(cls_mask.shape)}")
+            raise ValueError(f"cls_mask must be [n_masks, {H // self.cfg.patch}, {W // self.cfg.patch}], got {tuple(cls_mask.shape)}")
         self._sync_weights()
         emb = torch.empty((m.shape[0], self.cfg.embed_dim), dtype=torch.float32, device=x.device) if want_emb else None
         att = torch.empty((1, self.cfg.num_heads, m.shape[0], n + 1), dtype=torch.float32, device=x.device) if want_attn else None
@@ -603,11 +621,11 @@ class DINOSeg(nn.Module):
             return self._mask_request(x, cls_mask, False, True)[1]
         self._require_gpu()
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 8 != 0 or x.shape[3] % 8 != 0:
-            raise ValueError(f"expected [B,3,H,W] with H % 8 == W % 8 == 0, got {tuple(x.shape)}")
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % self.cfg.patch != 0 or x.shape[3] % self.cfg.patch != 0:
+            raise ValueError(f"expected [B,3,H,W] with H % {self.cfg.patch} == W % {self.cfg.patch} == 0, got {tuple(x.shape)}")
         self._sync_weights()
         B, H, W = x.shape[0], x.shape[2], x.shape[3]
-        N = (H // 8) * (W // 8) + 1
+        N = (H // self.cfg.patch) * (W // self.cfg.patch) + 1
         out = torch.empty((B, self.cfg.num_heads, N, N), dtype=torch.float32, device=x.device)
         capi.check(capi.lib().dinoseg_last_selfattention_hw(self._handle, x.data_ptr(), capi.INPUT_F32_CHW, B, H, W, out.data_ptr(),
                                                             self._stream()))
@@ -723,8 +741,8 @@ class DINOSeg(nn.Module):
                 raise ValueError(f"expected [B,3,H,W], got {tuple(x.shape)}")
             kind, B, H, W = capi.INPUT_F32_CHW, x.shape[0], x.shape[2], x.shape[3]
             x = x.to(device=dev, dtype=torch.float32).contiguous()
-        if H % 8 != 0 or W % 8 != 0:
-            raise ValueError("Resolution should be a multiple of 8.")
+        if H % self.cfg.patch != 0 or W % self.cfg.patch != 0:
+            raise ValueError(self._resolution_message())
         return x, kind, B, H, W
 
     def check_labels(self) -> None:
@@ -760,10 +778,10 @@ class DINOSeg(nn.Module):
         self._sync_grads("grad")
         x, kind, B, H, W = self._prep_batch(x)
         dev = self.device
-        n = (H // 8) * (W // 8)
+        n = (H // self.cfg.patch) * (W // self.cfg.patch)
         y = y.to(dev).reshape(-1).long().contiguous()
         if y.numel() != B * n:
-            raise ValueError(f"labels must have B*(H/8)*(W/8) = {B * n} entries, got {y.numel()}")
+            raise ValueError(f"labels must have B*(H/{self.cfg.patch})*(W/{self.cfg.patch}) = {B * n} entries, got {y.numel()}")
         loss = torch.zeros((), dtype=torch.float32, device=dev)
         logp = torch.empty((B * n, self.cfg.n_classes), dtype=torch.float32, device=dev)
         capi.check(capi.lib().dinoseg_train_step_hw(self._handle, x.data_ptr(), kind, B, H, W, y.data_ptr(), loss.data_ptr(),
@@ -773,7 +791,7 @@ class DINOSeg(nn.Module):
 
     def _autograd_forward(self, x: torch.Tensor, kind: int, B: int, H: int, W: int) -> torch.Tensor:
         self._sync_weights(train=True)
-        n = (H // 8) * (W // 8)
+        n = (H // self.cfg.patch) * (W // self.cfg.patch)
         logp = torch.empty((B * n, self.cfg.n_classes), dtype=torch.float32, device=self.device)
         capi.check(capi.lib().dinoseg_train_forward_hw(self._handle, x.data_ptr(), kind, B, H, W, logp.data_ptr(),
                                                        self._stream()))

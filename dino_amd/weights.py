@@ -45,6 +45,9 @@ class ViTConfig:
 
 VIT_S8 = ViTConfig()
 VIT_B8 = ViTConfig(embed_dim=768, num_heads=12)   # vit_base, vision_transformer.py:307-311
+# patch 16 (the factories' own default, vision_transformer.py:293-311): pos_embed is [1, 14*14+1, D] (img_size=[224] / 16)
+VIT_S16 = ViTConfig(patch=16, pos_grid=14)
+VIT_B16 = ViTConfig(embed_dim=768, num_heads=12, patch=16, pos_grid=14)
 
 
 def tensor_shapes(cfg: ViTConfig) -> "OrderedDict[str, tuple]":

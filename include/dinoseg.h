@@ -45,16 +45,27 @@ enum { DINOSEG_INPUT_U8_HWC = 0,      /* uint8 [B,r,r,3] frames; ImageNet normal
 
 /* Architecture = the reference ctor arguments that shape the path.
  * DINOSeg.__init__(head, n_blocks, n_classes, backbone='vit')   dt_segmentation/src/pl_torch_modules.py:144-222
- * vit_small / vit_base(patch_size=8)                             dt_segmentation/src/vision_transformer.py:300-311 */
+ * vit_small / vit_base(patch_size=8)                             dt_segmentation/src/vision_transformer.py:300-311
+ *
+ * Patch size.  `patch` is 8 or 16, the published DINO sizes (anything else: dinoseg_create returns -1).  Every comment below
+ * is written for patch 8; on a patch-16 handle read `patch` wherever it says 8 in a frame size: H and W must be multiples of
+ * 16 (else -1 and "Resolution should be a multiple of 16."; a patch-8 handle keeps "... multiple of 8."), hp = H/16, wp = W/16,
+ * masks, labels and outputs have (H/16)*(W/16) rows per frame, dino.patch_embed.proj.weight is [D, 3, 16, 16] and, with
+ * pos_grid = 14, dino.pos_embed is [1, 197, D] and is returned unresampled for 224 x 224 frames only.
+ * Alignment at patch 16: the gather reads frames with 16-byte loads, so the frame pointer x of every entry that takes frames
+ * (dinoseg_forward*, dinoseg_features*, dinoseg_last_selfattention*, dinoseg_forward_mask*, dinoseg_train_forward*,
+ * dinoseg_train_step*) must be 16-byte aligned -- W % 16 == 0 keeps every row and frame offset aligned behind it; a whole
+ * allocation or a slice of whole frames is.  A misaligned pointer is refused (-1), never read.  (Patch 8 reads uint8 frames with
+ * 4-byte loads and fp32 frames with 16-byte loads, as before.) */
 typedef struct dinoseg_config {
     int32_t embed_dim;    /* 384 (ViT-S) / 768 (ViT-B); multiple of 128                         */
     int32_t num_heads;    /* embed_dim / 64                                                      */
     int32_t n_blocks;     /* transformer blocks kept (dino.blocks[:n_blocks], :177)              */
-    int32_t patch;        /* 8                                                                   */
+    int32_t patch;        /* 8 or 16                                                             */
     int32_t mlp_ratio;    /* 4                                                                   */
     int32_t n_classes;    /* 1 .. 256 (33 and up: the wide MFMA head kernel; above 256: rejected)  */
     int32_t head_kind;    /* DINOSEG_HEAD_*  (pl_torch_modules.py:219-222)                       */
-    int32_t pos_grid;     /* 28: stored pos_embed is [1, 28*28+1, D]                             */
+    int32_t pos_grid;     /* 28 (patch 8) / 14 (patch 16): stored pos_embed is [1, g*g+1, D]     */
     float   ln_eps;       /* 1e-6 (vision_transformer.py:303)                                    */
     int32_t precision;    /* DINOSEG_BF16 / DINOSEG_BF16X3 / DINOSEG_FP16 / DINOSEG_FP16X3       */
 } dinoseg_config;
@@ -408,6 +419,13 @@ int dinoseg_op_patch_gather(const void* x, int32_t x_kind, int32_t B, int32_t r,
 /* ... of H x W frames (PatchEmbed, vision_transformer.py:153-157): [planes][B*(H/8)*(W/8)][192], patches row-major */
 int dinoseg_op_patch_gather_hw(const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, void* out, int64_t out_plane,
                                int32_t planes, void* stream);
+/* ... at either patch size, patch = 8 or 16 (anything else -> -1): [planes][B*(H/patch)*(W/patch)][3*patch*patch], column
+ * c*patch*patch + ky*patch + kx.  H and W must be multiples of `patch` (-1, "Resolution should be a multiple of 8." / "... of 16.").
+ * One plane is the rounded value, two planes are hi + lo at out and out + out_plane (out_plane >= rows * 3*patch*patch elements);
+ * both in the format of option "op_fmt".  At patch 16, x and out must be 16-byte aligned and out_plane a multiple of 8 elements
+ * (16-byte loads and stores; else -1).  The two entries above keep their meaning: patch 8. */
+int dinoseg_op_patch_gather_p(const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t patch, void* out,
+                              int64_t out_plane, int32_t planes, void* stream);
 
 /* last Linear + log_softmax + argmax (pl_torch_modules.py:122-123,:294); in: hi/lo planes [2][M][ld]; C <= 32 */
 int dinoseg_op_head_final(const void* in, int64_t in_plane, int32_t ld, int32_t M, int32_t K, const float* W,
