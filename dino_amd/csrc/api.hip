@@ -44,6 +44,8 @@ int device_cu_count() {
 
 
 
+static std::string block_prefix(int i) { return "dino.blocks." + std::to_string(i) + "."; }
+
 static void add_expected(dinoseg_handle* h) {
     const dinoseg_config& c = h->cfg;
     const int64_t D = c.embed_dim, F = (int64_t)c.embed_dim * c.mlp_ratio, C = c.n_classes, p = c.patch;
@@ -53,7 +55,7 @@ static void add_expected(dinoseg_handle* h) {
     e["dino.patch_embed.proj.weight"] = {D, 3, p, p};
     e["dino.patch_embed.proj.bias"] = {D};
     for (int i = 0; i < c.n_blocks; ++i) {
-        const std::string b = "dino.blocks." + std::to_string(i) + ".";
+        const std::string b = block_prefix(i);
         e[b + "norm1.weight"] = {D};
         e[b + "norm1.bias"] = {D};
         e[b + "attn.qkv.weight"] = {3 * D, D};
@@ -143,17 +145,7 @@ extern "C" int dinoseg_destroy(dinoseg_handle* h) {
 }
 
 // forget every packed copy (they point into wbuf): a refresh lays out only the copies its options ask for
-static void clear_packs(dinoseg_handle* h) {
-    h->packed.clear();
-    h->packed_slab.clear();
-    h->packed_mlp.clear();
-    h->packed_proj.clear();
-    h->packed_qkvf.clear();
-    h->packed_mlp3.clear();
-    h->packed_mlp4.clear();
-    h->packed_rs.clear();
-    h->packed_rs_bias.clear();
-}
+static void clear_packs(dinoseg_handle* h) { h->model = ModelRec(); }
 
 extern "C" int dinoseg_bind_weight(dinoseg_handle* h, const char* name, const void* dev_ptr, const int64_t* shape,
                                    int32_t ndim) {
@@ -224,43 +216,40 @@ extern "C" int dinoseg_bind_weight(dinoseg_handle* h, const char* name, const vo
 
 
 
-// names of every nn.Linear-shaped weight that feeds gemm.hip, with its logical [N, K] and padded [n_pad, k_pad]
+// names of every nn.Linear-shaped weight that feeds gemm.hip, with its logical [N, K] and padded [n_pad, k_pad], its record in m
+// and, for a block linear, its block and gemm_rs option bit (LinearRec::rs_bit)
 struct LinSpec {
     std::string wname, bname;
     int N, K, n_pad, k_pad, planes, fmt;
+    LinearRec* rec;
+    int block, rs_bit;
 };
 
-static std::vector<LinSpec> linear_specs(const dinoseg_handle* h) {
+static std::vector<LinSpec> linear_specs(const dinoseg_handle* h, ModelRec& m) {
     const dinoseg_config& c = h->cfg;
     const int D = c.embed_dim, F = c.embed_dim * c.mlp_ratio, P = h->planes, FM = h->fmt;
     std::vector<LinSpec> v;
     // (fp16 mode: the patch embedding runs split like the head -- 0.13 % of the FLOPs, and its operands are raw pixels)
-    v.push_back({"dino.patch_embed.proj.weight", "dino.patch_embed.proj.bias", D, 3 * c.patch * c.patch, D, 3 * c.patch * c.patch, patch_planes(h), patch_fmt(h)});
+    v.push_back({"dino.patch_embed.proj.weight", "dino.patch_embed.proj.bias", D, 3 * c.patch * c.patch, D, 3 * c.patch * c.patch, patch_planes(h), patch_fmt(h), &m.patch, -1, 0});
     for (int i = 0; i < c.n_blocks; ++i) {
-        const std::string b = "dino.blocks." + std::to_string(i) + ".";
-        v.push_back({b + "attn.qkv.weight", b + "attn.qkv.bias", 3 * D, D, 3 * D, D, P, FM});
-        v.push_back({b + "attn.proj.weight", b + "attn.proj.bias", D, D, D, D, P, FM});
-        v.push_back({b + "mlp.fc1.weight", b + "mlp.fc1.bias", F, D, F, D, P, FM});
-        v.push_back({b + "mlp.fc2.weight", b + "mlp.fc2.bias", D, F, D, F, P, FM});
+        const std::string b = block_prefix(i);
+        BlockRec& k = m.blocks[i];
+        v.push_back({b + "attn.qkv.weight", b + "attn.qkv.bias", 3 * D, D, 3 * D, D, P, FM, &k.qkv, i, 2});
+        v.push_back({b + "attn.proj.weight", b + "attn.proj.bias", D, D, D, D, P, FM, &k.proj, i, 4});
+        v.push_back({b + "mlp.fc1.weight", b + "mlp.fc1.bias", F, D, F, D, P, FM, &k.fc1, i, 1});
+        v.push_back({b + "mlp.fc2.weight", b + "mlp.fc2.bias", D, F, D, F, P, FM, &k.fc2, i, 4});
     }
     if (c.head_kind == DINOSEG_HEAD_MLP) {
-        v.push_back({"clf.layer_1.weight", "clf.layer_1.bias", 200, D, 256, D, head_planes(), split_fmt(h)});
-        v.push_back({"clf.layer_2.weight", "clf.layer_2.bias", 100, 200, 128, 256, head_planes(), split_fmt(h)});
+        v.push_back({"clf.layer_1.weight", "clf.layer_1.bias", 200, D, 256, D, head_planes(), split_fmt(h), &m.head[0], -1, 0});
+        v.push_back({"clf.layer_2.weight", "clf.layer_2.bias", 100, 200, 128, 256, head_planes(), split_fmt(h), &m.head[1], -1, 0});
     }
     // more than 32 classes: the classifier as hi+lo planes [round_up(C, 32)][ld] for the wide kernel (head_wide.hip)
     if (c.n_classes > HEAD_FINAL_MAX_C) {
         const bool mlp = c.head_kind == DINOSEG_HEAD_MLP;
         v.push_back({mlp ? "clf.layer_3.weight" : "clf.layer_1.weight", mlp ? "clf.layer_3.bias" : "clf.layer_1.bias", c.n_classes,
-                     mlp ? 100 : D, (c.n_classes + 31) / 32 * 32, mlp ? 128 : D, head_planes(), split_fmt(h)});
+                     mlp ? 100 : D, (c.n_classes + 31) / 32 * 32, mlp ? 128 : D, head_planes(), split_fmt(h), &m.clf, -1, 0});
     }
     return v;
-}
-
-static int ensure_mlp_packs(dinoseg_handle* h, hipStream_t s);
-
-// the gemm_rs option bit of a block linear: 1 mlp.fc1, 2 attn.qkv, 4 attn.proj and mlp.fc2
-static int rs_bit(const std::string& wname) {
-    return wname.find("mlp.fc1.weight") != std::string::npos ? 1 : wname.find("attn.qkv.weight") != std::string::npos ? 2 : 4;
 }
 
 // does gemm_rs.hip take this block linear (with the LayerNorm inside: ln)?  gemm_rs_supported on the shape and strides the forward
@@ -269,16 +258,71 @@ static bool rs_shape_supported(const dinoseg_handle* h, const LinSpec& sp, bool 
     static float placeholder[1];
     float* f = placeholder;
     bf16_t* b = reinterpret_cast<bf16_t*>(placeholder);
-    const int bit = rs_bit(sp.wname);
     GemmParams g = {};
     g.A = b; g.lda = sp.K; g.W = b;
-    g.M = 1; g.N = sp.N; g.K = sp.K; g.planes = 1; g.fmt = sp.fmt; g.epi = bit == 1 ? EPI_GELU : bit == 2 ? EPI_QKV : EPI_RESID;
+    g.M = 1; g.N = sp.N; g.K = sp.K; g.planes = 1; g.fmt = sp.fmt; g.epi = sp.rs_bit == 1 ? EPI_GELU : sp.rs_bit == 2 ? EPI_QKV : EPI_RESID;
     g.bias = f;
     g.out_f32 = f; g.ldo_f32 = sp.N;        // attn.proj / mlp.fc2: the fp32 residual rows, N = embed_dim wide
     g.out_bf16 = b; g.ldo = sp.N;           // mlp.fc1: the hidden rows
     g.q = g.k = g.v = b; g.heads = h->cfg.num_heads; g.dmodel = h->cfg.embed_dim;
     if (ln) { g.ln_x = f; g.ln_eps = h->cfg.ln_eps; }
     return gemm_rs_supported(g);
+}
+
+// the fp32 parameters a fused launch of block b folds into its slot stream (mlp_fused3.hip / mlp_fused4.hip); next = the block
+// whose LayerNorm1 + qkv are the tail of that launch (null behind the last block)
+static MlpFused3Weights fused_block_weights(const BlockRec& b, const BlockRec* next) {
+    MlpFused3Weights w = {};
+    w.Wproj = b.proj.w; w.W1 = b.fc1.w; w.b1 = b.fc1.b; w.W2 = b.fc2.w;
+    w.gamma2 = b.norm2_w; w.beta2 = b.norm2_b;
+    if (next) {
+        w.Wqkv_next = next->qkv.w; w.bqkv_next = next->qkv.b;
+        w.gamma1_next = next->norm1_w; w.beta1_next = next->norm1_b;
+    }
+    return w;
+}
+
+// Packs every copy the records name (their pointers are set), in stream order: padded biases and slabs, the operand planes of all
+// linears as one launch, the row-stationary copies, then the fused launches' streams.  Always here, with the refresh: a forward
+// captured in a graph contains no pack kernels, so a deferred pack would let a replay after a fine-tune step read stale fused-kernel
+// weights next to fresh ones.
+static int pack_copies(dinoseg_handle* h, const std::vector<LinSpec>& specs, hipStream_t s) {
+    const int Dm = h->cfg.embed_dim, Fh = h->cfg.embed_dim * h->cfg.mlp_ratio;
+    std::vector<BlockRec>& blocks = h->model.blocks;
+    std::vector<PackJob> jobs;
+    for (const LinSpec& sp : specs) {
+        const LinearRec& r = *sp.rec;
+        jobs.push_back({r.w, r.pk.w, r.pk.plane, sp.N, sp.K, sp.n_pad, sp.k_pad, sp.planes, 0, sp.fmt});
+        if (r.pk.bias_pad) {
+            DSEG_CHECK_HIP(hipMemsetAsync(r.pk.bias_pad, 0, (size_t)sp.n_pad * sizeof(float), s));
+            DSEG_CHECK_HIP(hipMemcpyAsync(r.pk.bias_pad, r.b, (size_t)sp.N * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+        if (r.slab) DSEG_TRY(launch_pack_slabs(r.w, sp.N, sp.K, sp.planes, r.slab, s, sp.fmt));
+    }
+    DSEG_TRY(launch_multi_pack(jobs.data(), (int)jobs.size(), s));
+    for (const LinSpec& sp : specs) {
+        const LinearRec& r = *sp.rec;
+        if (!r.rs) continue;
+        if (r.rs_bias) {      // the copy carries the LayerNorm in front of the linear: norm1 for qkv, norm2 for fc1
+            const BlockRec& k = blocks[sp.block];
+            const bool qkv = sp.rs_bit == 2;
+            DSEG_TRY(launch_pack_rs_ln(r.w, qkv ? k.norm1_w : k.norm2_w, qkv ? k.norm1_b : k.norm2_b, r.b, sp.N, sp.K, r.rs, r.rs_bias, s, sp.fmt));
+        } else {
+            DSEG_TRY(launch_pack_rs(r.w, sp.N, sp.K, sp.rs_bit == 4 ? 1 : 0, r.rs, s, sp.fmt));
+        }
+    }
+    for (const BlockRec& k : blocks) {
+        if (k.mlp) DSEG_TRY(launch_pack_mlp(k.fc1.w, k.fc2.w, Dm, Fh, k.mlp, s, h->fmt));
+        if (k.projf) DSEG_TRY(launch_pack_proj(k.proj.w, Dm, k.projf, s, h->fmt));
+        if (k.qkvf) DSEG_TRY(launch_pack_qkv(k.qkv.w, Dm, k.qkvf, s, h->fmt));
+    }
+    // (block i's stream ends with the qkv weight of block i + 1: the tail of its fused launch)
+    for (size_t i = 0; i < blocks.size(); ++i) {
+        const MlpFused3Weights w = fused_block_weights(blocks[i], i + 1 < blocks.size() ? &blocks[i + 1] : nullptr);
+        if (blocks[i].mlp4) DSEG_TRY(launch_pack_mlp4(w, Dm, Fh, blocks[i].mlp4, s, h->fmt));
+        if (blocks[i].mlp3) DSEG_TRY(launch_pack_mlp3(w, Dm, Fh, blocks[i].mlp3, s, h->fmt));
+    }
+    return 0;
 }
 
 extern "C" int dinoseg_refresh_weights(dinoseg_handle* h, void* stream) {
@@ -300,42 +344,73 @@ extern "C" int dinoseg_refresh_weights(dinoseg_handle* h, void* stream) {
     h->gemm_rs_ln_snap = options().gemm_rs_ln;
     // every copy of the previous refresh is dropped: only those these options ask for are laid out again (a copy left over from
     // another layout would be re-packed over, or read from, whatever lives at its old offset now)
-    clear_packs(h);
     h->weights_ready = false;
-    const std::vector<LinSpec> specs = linear_specs(h);
-    auto ln_fed = [&](const LinSpec& sp) {        // qkv / fc1: also kept slab-major for the LayerNorm-fused kernel
-        const bool qkv = sp.wname.find("attn.qkv.weight") != std::string::npos;
-        const bool fc1 = sp.wname.find("mlp.fc1.weight") != std::string::npos;
-        if (sp.planes == 2 && sp.fmt != FMT_BF16) return false;      // (the hi+lo LayerNorm-fused kernel is bf16 only: gemm_ln.hip)
-        return (qkv || fc1) && gemm_ln_supported(sp.K, sp.N, sp.planes, qkv ? EPI_QKV : EPI_GELU, h->cfg.embed_dim);
-    };
-    size_t total = 0;
-    for (const LinSpec& sp : specs) {
-        total += align_up((size_t)sp.planes * sp.n_pad * sp.k_pad * sizeof(bf16_t), 256);
-        if (sp.n_pad != sp.N) total += align_up((size_t)sp.n_pad * sizeof(float), 256);
-        if (ln_fed(sp)) total += align_up((size_t)gemm_ln_slab_elems(sp.N, sp.K, sp.planes) * sizeof(bf16_t), 256);
+    ModelRec& m = h->model;
+    m = ModelRec();
+    m.blocks.resize(h->cfg.n_blocks);
+    m.cls_token = W(h, "dino.cls_token");
+    m.pos_embed = W(h, "dino.pos_embed");
+    m.norm_w = W(h, "dino.norm.weight");
+    m.norm_b = W(h, "dino.norm.bias");
+    for (int i = 0; i < h->cfg.n_blocks; ++i) {
+        const std::string b = block_prefix(i);
+        m.blocks[i].norm1_w = W(h, b + "norm1.weight"); m.blocks[i].norm1_b = W(h, b + "norm1.bias");
+        m.blocks[i].norm2_w = W(h, b + "norm2.weight"); m.blocks[i].norm2_b = W(h, b + "norm2.bias");
     }
+    {   // (launch_head_final reads the classifier in fp32; the specs below add its planes for the wide kernel)
+        const std::string clf = h->cfg.head_kind == DINOSEG_HEAD_MLP ? "clf.layer_3" : "clf.layer_1";
+        m.clf.w = W(h, clf + ".weight"); m.clf.b = W(h, clf + ".bias");
+    }
+    // ---- the plan: every copy of this refresh, in wbuf order -- what it is, how long it is, which record pointer it becomes.  Each
+    // size and each "does this copy exist" is written here and nowhere else: the buffer's size and every offset follow from this list.
+    struct Copy { std::string what; size_t bytes; void** slot; };
+    std::vector<Copy> plan;
+    auto copy16 = [&](const std::string& what, size_t elems, bf16_t*& slot) { plan.push_back({what, elems * sizeof(bf16_t), reinterpret_cast<void**>(&slot)}); };
+    auto copy32 = [&](const std::string& what, size_t elems, float*& slot) { plan.push_back({what, elems * sizeof(float), reinterpret_cast<void**>(&slot)}); };
+    const std::vector<LinSpec> specs = linear_specs(h, m);
     const int Dm = h->cfg.embed_dim, Fh = h->cfg.embed_dim * h->cfg.mlp_ratio;
-    const bool mlp_fusable = mlp_fused_supported(Dm, Fh, h->planes);
-    const bool mlp3_fusable = mlp_fused3_supported(Dm, Fh, h->planes);
-    const bool mlp4_fusable = h->mlp_fused4_snap && mlp_fused4_supported(Dm, Fh, h->planes);      // (a fine-tune step re-packs what exists)
+    for (const LinSpec& sp : specs) {
+        LinearRec& r = *sp.rec;
+        r.w = W(h, sp.wname); r.b = W(h, sp.bname);
+        r.N = sp.N; r.K = sp.K; r.planes = sp.planes; r.fmt = sp.fmt; r.rs_bit = sp.rs_bit;
+        r.pk.plane = (long)sp.n_pad * sp.k_pad; r.pk.n_pad = sp.n_pad; r.pk.k_pad = sp.k_pad;
+        copy16(sp.wname, (size_t)sp.planes * sp.n_pad * sp.k_pad, r.pk.w);
+        if (sp.n_pad != sp.N) copy32("bias_pad " + sp.bname, sp.n_pad, r.pk.bias_pad);
+        // qkv / fc1: also kept slab-major for the LayerNorm-fused kernel (the hi+lo one is bf16 only: gemm_ln.hip)
+        if ((sp.rs_bit == 2 || sp.rs_bit == 1) && !(sp.planes == 2 && sp.fmt != FMT_BF16) &&
+            gemm_ln_supported(sp.K, sp.N, sp.planes, sp.rs_bit == 2 ? EPI_QKV : EPI_GELU, Dm))
+            copy16("slab " + sp.wname, (size_t)gemm_ln_slab_elems(sp.N, sp.K, sp.planes), r.slab);
+    }
     // one-plane modes of the wide model: fragment-order copies of the four block linears for the row-stationary GEMMs (gemm_rs.hip),
-    // for the linears whose gemm_rs bit is set and whose shape gemm_rs.hip takes (kind 0: qkv / fc1, kind 1: proj / fc2)
-    auto rs_kind = [&](const LinSpec& sp) -> int {
-        if (h->planes != 1 || Dm != 768 || sp.wname.rfind("dino.blocks.", 0) != 0 || !(h->gemm_rs_snap & rs_bit(sp.wname))) return -1;
-        const int kind = rs_bit(sp.wname) == 4 ? 1 : 0;
-        return rs_shape_supported(h, sp, kind == 0 && h->gemm_rs_ln_snap) ? kind : -1;
-    };
-    // (kind 0 with option gemm_rs_ln: the copy carries the LayerNorm in front of the linear -- norm1 for qkv, norm2 for fc1 -- and a folded bias)
-    auto rs_ln = [&](const LinSpec& sp) -> bool { return rs_kind(sp) == 0 && h->gemm_rs_ln_snap; };
-    for (const LinSpec& sp : specs)
-        if (rs_kind(sp) >= 0) total += align_up((size_t)sp.N * sp.K * sizeof(bf16_t), 256) + (rs_ln(sp) ? align_up((size_t)sp.N * sizeof(float), 256) : 0);
-    if (mlp3_fusable) total += (size_t)h->cfg.n_blocks * align_up((size_t)mlp_fused3_pack_elems(Dm, Fh) * sizeof(bf16_t), 256);
-    if (mlp4_fusable) total += (size_t)h->cfg.n_blocks * align_up((size_t)mlp_fused4_pack_elems(Dm, Fh) * sizeof(bf16_t), 256);
-    if (mlp_fusable)
-        total += (size_t)h->cfg.n_blocks * (align_up((size_t)mlp_fused_pack_elems(Dm, Fh) * sizeof(bf16_t), 256) +
-                                            align_up((size_t)mlp_fused_proj_pack_elems(Dm) * sizeof(bf16_t), 256) +
-                                            align_up((size_t)mlp_fused_qkv_pack_elems(Dm) * sizeof(bf16_t), 256));
+    // for the linears whose gemm_rs bit is set and whose shape gemm_rs.hip takes.  qkv / fc1 with option gemm_rs_ln: the copy carries
+    // the LayerNorm in front of the linear -- norm1 for qkv, norm2 for fc1 -- and a folded bias
+    for (const LinSpec& sp : specs) {
+        if (h->planes != 1 || Dm != 768 || !(h->gemm_rs_snap & sp.rs_bit)) continue;
+        const bool ln = sp.rs_bit != 4 && h->gemm_rs_ln_snap;
+        if (!rs_shape_supported(h, sp, ln)) continue;
+        copy16("rs " + sp.wname, (size_t)sp.N * sp.K, sp.rec->rs);
+        if (ln) copy32("rs_bias " + sp.wname, sp.N, sp.rec->rs_bias);
+    }
+    if (mlp_fused3_supported(Dm, Fh, h->planes))
+        for (int i = 0; i < h->cfg.n_blocks; ++i) copy16("mlp3 " + block_prefix(i), (size_t)mlp_fused3_pack_elems(Dm, Fh), m.blocks[i].mlp3);
+    if (h->mlp_fused4_snap && mlp_fused4_supported(Dm, Fh, h->planes))      // (a fine-tune step re-packs what exists)
+        for (int i = 0; i < h->cfg.n_blocks; ++i) copy16("mlp4 " + block_prefix(i), (size_t)mlp_fused4_pack_elems(Dm, Fh), m.blocks[i].mlp4);
+    if (mlp_fused_supported(Dm, Fh, h->planes)) {
+        const long mlp_elems = mlp_fused_pack_elems(Dm, Fh), proj_elems = mlp_fused_proj_pack_elems(Dm), qkv_elems = mlp_fused_qkv_pack_elems(Dm);
+        for (int i = 0; i < h->cfg.n_blocks; ++i) {
+            const std::string b = block_prefix(i);
+            copy16("mlp " + b, mlp_elems, m.blocks[i].mlp);
+            if (proj_elems > 0) copy16("proj " + b, proj_elems, m.blocks[i].projf);
+            if (i > 0 && qkv_elems > 0) copy16("qkvf " + b, qkv_elems, m.blocks[i].qkvf);      // (block 0's qkv has no fused kernel in front of it)
+        }
+    }
+    // ---- the buffer: each copy 256-byte aligned, in plan order
+    std::vector<dinoseg_handle::WbufEntry> layout;
+    size_t total = 0;
+    for (const Copy& cp : plan) {
+        layout.push_back({cp.what, total, cp.bytes});
+        total += align_up(cp.bytes, 256);
+    }
     if (total > h->wbuf_bytes) {
         ++h->generation;
         if (h->wbuf) DSEG_CHECK_HIP(hipFree(h->wbuf));
@@ -343,86 +418,20 @@ extern "C" int dinoseg_refresh_weights(dinoseg_handle* h, void* stream) {
         DSEG_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&h->wbuf), total));
         h->wbuf_bytes = total;
     }
-    size_t off = 0;
-    std::vector<dinoseg_handle::WbufEntry> layout;
-    auto carve = [&](const std::string& what, size_t bytes) -> char* {      // the next copy, 256-byte aligned, recorded in the layout
-        char* p = h->wbuf + off;
-        layout.push_back({what, off, bytes});
-        off += align_up(bytes, 256);
-        return p;
-    };
-    std::vector<PackJob> jobs;
-    for (const LinSpec& sp : specs) {
-        PackedLinear pk;
-        pk.w = reinterpret_cast<bf16_t*>(carve(sp.wname, (size_t)sp.planes * sp.n_pad * sp.k_pad * sizeof(bf16_t)));
-        pk.plane = (long)sp.n_pad * sp.k_pad;
-        pk.n_pad = sp.n_pad;
-        pk.k_pad = sp.k_pad;
-        jobs.push_back({W(h, sp.wname), pk.w, pk.plane, sp.N, sp.K, sp.n_pad, sp.k_pad, sp.planes, 0, sp.fmt});
-        if (sp.n_pad != sp.N) {
-            pk.bias_pad = reinterpret_cast<float*>(carve("bias_pad " + sp.bname, (size_t)sp.n_pad * sizeof(float)));
-            DSEG_CHECK_HIP(hipMemsetAsync(pk.bias_pad, 0, (size_t)sp.n_pad * sizeof(float), s));
-            DSEG_CHECK_HIP(hipMemcpyAsync(pk.bias_pad, W(h, sp.bname), (size_t)sp.N * sizeof(float),
-                                          hipMemcpyDeviceToDevice, s));
-        }
-        h->packed[sp.wname] = pk;
-        if (ln_fed(sp)) {
-            bf16_t* slab = reinterpret_cast<bf16_t*>(carve("slab " + sp.wname, (size_t)gemm_ln_slab_elems(sp.N, sp.K, sp.planes) * sizeof(bf16_t)));
-            DSEG_TRY(launch_pack_slabs(W(h, sp.wname), sp.N, sp.K, sp.planes, slab, s, sp.fmt));
-            h->packed_slab[sp.wname] = slab;
-        }
-    }
-    DSEG_TRY(launch_multi_pack(jobs.data(), (int)jobs.size(), s));
-    for (const LinSpec& sp : specs)
-        if (rs_kind(sp) >= 0) {
-            bf16_t* dst = reinterpret_cast<bf16_t*>(carve("rs " + sp.wname, (size_t)sp.N * sp.K * sizeof(bf16_t)));
-            if (rs_ln(sp)) {
-                float* fb = reinterpret_cast<float*>(carve("rs_bias " + sp.wname, (size_t)sp.N * sizeof(float)));
-                const std::string blk = sp.wname.substr(0, sp.wname.find(sp.wname.find("attn.qkv") != std::string::npos ? "attn.qkv" : "mlp.fc1"));
-                const std::string nrm = blk + (sp.wname.find("attn.qkv") != std::string::npos ? "norm1" : "norm2");
-                DSEG_TRY(launch_pack_rs_ln(W(h, sp.wname), W(h, nrm + ".weight"), W(h, nrm + ".bias"), W(h, sp.bname), sp.N, sp.K, dst, fb, s, sp.fmt));
-                h->packed_rs_bias[sp.wname] = fb;
-            } else {
-                DSEG_TRY(launch_pack_rs(W(h, sp.wname), sp.N, sp.K, rs_kind(sp), dst, s, sp.fmt));
-            }
-            h->packed_rs[sp.wname] = dst;
-        }
-    if (mlp3_fusable)
-        for (int i = 0; i < h->cfg.n_blocks; ++i) {
-            const std::string b = "dino.blocks." + std::to_string(i) + ".";
-            h->packed_mlp3[b] = reinterpret_cast<bf16_t*>(carve("mlp3 " + b, (size_t)mlp_fused3_pack_elems(Dm, Fh) * sizeof(bf16_t)));
-        }
-    if (mlp4_fusable)
-        for (int i = 0; i < h->cfg.n_blocks; ++i) {
-            const std::string b = "dino.blocks." + std::to_string(i) + ".";
-            h->packed_mlp4[b] = reinterpret_cast<bf16_t*>(carve("mlp4 " + b, (size_t)mlp_fused4_pack_elems(Dm, Fh) * sizeof(bf16_t)));
-        }
-    if (mlp_fusable)
-        for (int i = 0; i < h->cfg.n_blocks; ++i) {
-            const std::string b = "dino.blocks." + std::to_string(i) + ".";
-            h->packed_mlp[b] = reinterpret_cast<bf16_t*>(carve("mlp " + b, (size_t)mlp_fused_pack_elems(Dm, Fh) * sizeof(bf16_t)));
-            if (mlp_fused_proj_pack_elems(Dm) > 0)
-                h->packed_proj[b] = reinterpret_cast<bf16_t*>(carve("proj " + b, (size_t)mlp_fused_proj_pack_elems(Dm) * sizeof(bf16_t)));
-            if (i > 0 && mlp_fused_qkv_pack_elems(Dm) > 0)      // (block 0's qkv has no fused kernel in front of it)
-                h->packed_qkvf[b] = reinterpret_cast<bf16_t*>(carve("qkvf " + b, (size_t)mlp_fused_qkv_pack_elems(Dm) * sizeof(bf16_t)));
-        }
+    for (size_t i = 0; i < plan.size(); ++i) *plan[i].slot = h->wbuf + layout[i].off;
     // a captured forward bakes in the address and the format of every copy it reads: another layout in the same buffer (a copy
     // that changed size, appeared or left) is a new state generation, like a new buffer; the same layout is not (an in-place weight
     // update replays the captured forward, which reads the re-packed copies)
     if (layout != h->wbuf_layout) ++h->generation;
     h->wbuf_layout = std::move(layout);
-    // Always packed here, in stream order with the other packs: a forward captured in a graph contains no pack kernels, so a
-    // deferred pack (round 3 skipped these while gradient buffers were bound) would let a replay after a fine-tune step read stale
-    // fused-kernel weights next to fresh ones.  Three small launches per block.
-    h->packed_mlp_stale = true;
-    DSEG_TRY(ensure_mlp_packs(h, s));
+    DSEG_TRY(pack_copies(h, specs, s));
     h->weights_ready = true;
     // pos_embed may have changed in place (load_state_dict into the same storage, an optimizer step on an unfrozen backbone).  A
     // captured forward contains no resample launch and never calls dinoseg_prepare_resolution, so "resample on the next forward"
     // (pos_hp = -1 alone) would let a replay read the OLD rows next to freshly packed linears: resample here, in stream order with
     // the packs, into the SAME buffer: like the re-packed linears, the captured pointers stay valid and the replay reads new rows.
-    if (h->pos_hp > 0 && h->pos_cache != nullptr && h->bound.count("dino.pos_embed")) {
-        DSEG_TRY(launch_pos_resample(W(h, "dino.pos_embed"), h->cfg.pos_grid, h->cfg.embed_dim, h->pos_hp, h->pos_wp, h->pos_cache, s));
+    if (h->pos_hp > 0 && h->pos_cache != nullptr) {
+        DSEG_TRY(launch_pos_resample(m.pos_embed, h->cfg.pos_grid, h->cfg.embed_dim, h->pos_hp, h->pos_wp, h->pos_cache, s));
     } else {
         h->pos_hp = h->pos_wp = -1;      // (nothing cached: the next forward resamples, and dinoseg_prepare_resolution counts a new generation)
     }
@@ -571,44 +580,8 @@ struct MaskRequest {            // forward_mask / get_last_selfattention(x, cls_
 };
 
 // the fused MLP kernel runs for this many token rows (options mlp_fused / mlp_fused_min_rows)
-static bool mlp_fuse_wanted(const dinoseg_handle* h, long rows) {
-    return (!h->packed_mlp.empty() || !h->packed_mlp3.empty()) &&
-           (options().mlp_fused == 2 || (options().mlp_fused == 1 && rows >= options().mlp_fused_min_rows));
-}
-// fragment-order MLP weights (mlp_fused2.hip), packed on first use after a weight refresh
-static int ensure_mlp_packs(dinoseg_handle* h, hipStream_t s) {
-    if (!h->packed_mlp_stale) return 0;
-    const int Dm = h->cfg.embed_dim, Fh = h->cfg.embed_dim * h->cfg.mlp_ratio;
-    for (auto& kv : h->packed_mlp)
-        DSEG_TRY(launch_pack_mlp(W(h, kv.first + "mlp.fc1.weight"), W(h, kv.first + "mlp.fc2.weight"), Dm, Fh, kv.second, s, h->fmt));
-    for (auto& kv : h->packed_proj) DSEG_TRY(launch_pack_proj(W(h, kv.first + "attn.proj.weight"), Dm, kv.second, s, h->fmt));
-    for (auto& kv : h->packed_qkvf) DSEG_TRY(launch_pack_qkv(W(h, kv.first + "attn.qkv.weight"), Dm, kv.second, s, h->fmt));
-    for (int i = 0; i < h->cfg.n_blocks; ++i) {      // (one-plane copies of the same streams: mlp_fused4.hip)
-        const std::string b = "dino.blocks." + std::to_string(i) + ".", nb = "dino.blocks." + std::to_string(i + 1) + ".";
-        if (!h->packed_mlp4.count(b)) continue;
-        MlpFused3Weights w = {};
-        w.Wproj = W(h, b + "attn.proj.weight"); w.W1 = W(h, b + "mlp.fc1.weight"); w.b1 = W(h, b + "mlp.fc1.bias"); w.W2 = W(h, b + "mlp.fc2.weight");
-        w.gamma2 = W(h, b + "norm2.weight"); w.beta2 = W(h, b + "norm2.bias");
-        if (i + 1 < h->cfg.n_blocks) {
-            w.Wqkv_next = W(h, nb + "attn.qkv.weight"); w.bqkv_next = W(h, nb + "attn.qkv.bias");
-            w.gamma1_next = W(h, nb + "norm1.weight"); w.beta1_next = W(h, nb + "norm1.bias");
-        }
-        DSEG_TRY(launch_pack_mlp4(w, Dm, Fh, h->packed_mlp4.at(b), s, h->fmt));
-    }
-    for (int i = 0; i < h->cfg.n_blocks; ++i) {      // (block i's stream ends with the qkv weight of block i + 1: the tail of its fused launch)
-        const std::string b = "dino.blocks." + std::to_string(i) + ".", nb = "dino.blocks." + std::to_string(i + 1) + ".";
-        if (!h->packed_mlp3.count(b)) continue;
-        MlpFused3Weights w = {};
-        w.Wproj = W(h, b + "attn.proj.weight"); w.W1 = W(h, b + "mlp.fc1.weight"); w.b1 = W(h, b + "mlp.fc1.bias"); w.W2 = W(h, b + "mlp.fc2.weight");
-        w.gamma2 = W(h, b + "norm2.weight"); w.beta2 = W(h, b + "norm2.bias");
-        if (i + 1 < h->cfg.n_blocks) {
-            w.Wqkv_next = W(h, nb + "attn.qkv.weight"); w.bqkv_next = W(h, nb + "attn.qkv.bias");
-            w.gamma1_next = W(h, nb + "norm1.weight"); w.beta1_next = W(h, nb + "norm1.bias");
-        }
-        DSEG_TRY(launch_pack_mlp3(w, Dm, Fh, h->packed_mlp3.at(b), s, h->fmt));
-    }
-    h->packed_mlp_stale = false;
-    return 0;
+static bool mlp_fuse_wanted(long rows) {
+    return options().mlp_fused == 2 || (options().mlp_fused == 1 && rows >= options().mlp_fused_min_rows);
 }
 
 static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t Hf, int32_t Wf, float* logp_out,
@@ -658,22 +631,21 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
     // the last refresh), the bit is still set, the batch fills the chip and the kernel takes the parameters.  A copy that carries the
     // LayerNorm in front of qkv / fc1 (gemm_rs_ln at that refresh) runs with the LayerNorm inside -- no LayerNorm launch, no 16-bit A
     // round trip -- and only so.  The one predicate for both the LayerNorm launch and the GEMM; *r = the kernel's parameters.
-    auto rs_route = [&](const GemmParams& g, const std::string& wname, GemmParams* r) -> bool {
-        const auto w = h->packed_rs.find(wname);
-        if (w == h->packed_rs.end() || !(options().gemm_rs & h->gemm_rs_snap & rs_bit(wname)) || disp_M < options().gemm_rs_min_rows) return false;
+    auto rs_route = [&](const GemmParams& g, const LinearRec& lin, GemmParams* r) -> bool {
+        if (!lin.rs || !(options().gemm_rs & h->gemm_rs_snap & lin.rs_bit) || disp_M < options().gemm_rs_min_rows) return false;
         *r = g;
-        r->W = w->second;
-        const auto fb = h->packed_rs_bias.find(wname);
-        if (fb != h->packed_rs_bias.end()) {
+        r->W = lin.rs;
+        if (lin.rs_bias) {
             if (mreq && mreq->cls_mask) return false;
-            r->ln_x = X; r->ln_eps = c.ln_eps; r->bias = fb->second;
+            r->ln_x = X; r->ln_eps = c.ln_eps; r->bias = lin.rs_bias;
         }
         return gemm_rs_supported(*r);
     };
-    auto gemm_any = [&](const GemmParams& g, const std::string& wname) -> int {
+    auto gemm_any = [&](const GemmParams& g, const LinearRec& lin) -> int {
         GemmParams r;
-        return rs_route(g, wname, &r) ? launch_gemm_rs(r, s) : launch_gemm(g, s);
+        return rs_route(g, lin, &r) ? launch_gemm_rs(r, s) : launch_gemm(g, s);
     };
+    const ModelRec& m = h->model;
 
     // ---- prepare_tokens (vision_transformer.py:224-235) ----
     float mean255[3], inv255[3];
@@ -683,17 +655,14 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
     const int PP = patch_planes(h);
     DSEG_PROF(DINOSEG_PROF_PATCH, DSEG_TRY(launch_patch_gather(x, x_kind, B, Hf, Wf, mean255, inv255, A, pg_plane, PP, s, patch_fmt(h), c.patch)));
     {
-        const PackedLinear& pk = h->packed.at("dino.patch_embed.proj.weight");
-        GemmParams g = {};
+        GemmParams g = linear_gemm(m.patch);
         g.A = A; g.a_plane = pg_plane; g.lda = KP;
-        g.W = pk.w; g.w_plane = pk.plane;
-        g.M = L.Mp; g.N = D; g.K = KP; g.planes = PP; g.fmt = patch_fmt(h); g.epi = EPI_PATCH; g.dispatch_rows = disp_Mp;
-        g.bias = W(h, "dino.patch_embed.proj.bias");
+        g.M = L.Mp; g.epi = EPI_PATCH; g.dispatch_rows = disp_Mp;
         g.out_f32 = X; g.ldo_f32 = D;
         g.pos = h->pos_cache; g.n_patches = L.n;
         DSEG_PROF(DINOSEG_PROF_PATCH, DSEG_TRY(launch_gemm(g, s)));
     }
-    DSEG_PROF(DINOSEG_PROF_PATCH, DSEG_TRY(launch_cls_rows(X, W(h, "dino.cls_token"), h->pos_cache, B, L.ntok, D, s)));
+    DSEG_PROF(DINOSEG_PROF_PATCH, DSEG_TRY(launch_cls_rows(X, m.cls_token, h->pos_cache, B, L.ntok, D, s)));
     const size_t xbytes = (size_t)L.M * D * sizeof(float);
     if (tap_block == 0 && tap_out) DSEG_CHECK_HIP(hipMemcpyAsync(tap_out, X, xbytes, hipMemcpyDeviceToDevice, s));
 
@@ -706,7 +675,7 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
     // ---- transformer blocks (vision_transformer.py:122-140) ----
     bool qkv_ready = false;      // Q / K / V of block i were written by block i-1's fused launch (mlp_fused2.hip, QKV tail)
     for (int i = 0; i < c.n_blocks; ++i) {
-        const std::string b = "dino.blocks." + std::to_string(i) + ".";
+        const BlockRec& blk = m.blocks[i];
         // gemm_ln: 0 never fused, 2 always, 1 (default) by measurement (round 4, tools/r4_smallbatch.sh, 1..6 frames @480):
         //  * single plane (bf16 / fp16): fused from 80 row panels of 128 on -- below that its persistent 128 x 384 panels leave most
         //    CUs idle (one frame = 29 panels: qkv 31 against 21 us with LayerNorm + the 128x128 kernel, fc1 40 against 23; the
@@ -721,29 +690,26 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
         // (the fused kernel keeps 32-bit output row offsets)
         if (qkv_ready) {
             qkv_ready = false;
-        } else if (fuse_ln && h->packed_slab.count(b + "attn.qkv.weight") && L.qkv_plane < (1L << 31)) {
+        } else if (fuse_ln && blk.qkv.slab && L.qkv_plane < (1L << 31)) {
             // LN1 + qkv in one launch: X rows are normalised in the GEMM's prologue, no bf16 A round trip (gemm_ln.hip)
             LnGemmParams g = {};
-            g.X = X; g.ldx = D; g.gamma = W(h, b + "norm1.weight"); g.beta = W(h, b + "norm1.bias"); g.eps = c.ln_eps;
-            g.W = h->packed_slab.at(b + "attn.qkv.weight"); g.bias = W(h, b + "attn.qkv.bias");
+            g.X = X; g.ldx = D; g.gamma = blk.norm1_w; g.beta = blk.norm1_b; g.eps = c.ln_eps;
+            g.W = blk.qkv.slab; g.bias = blk.qkv.b;
             g.M = L.M; g.N = 3 * D; g.epi = EPI_QKV;
             g.q = Q; g.k = Kb; g.v = V; g.qkv_plane = L.qkv_plane;
             g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.dmodel = D; g.qscale = qscale; g.fmt = FM;
             DSEG_PROF(DINOSEG_PROF_QKV, DSEG_TRY(launch_gemm_ln(g, D, P, s)));
         } else {
-            const PackedLinear& pk = h->packed.at(b + "attn.qkv.weight");
-            GemmParams g = {};
+            GemmParams g = linear_gemm(blk.qkv);
             g.A = A; g.a_plane = L.a_plane; g.lda = D;
-            g.W = pk.w; g.w_plane = pk.plane;
-            g.M = L.M; g.N = 3 * D; g.K = D; g.planes = P; g.fmt = FM; g.epi = EPI_QKV; g.dispatch_rows = disp_M;
+            g.M = L.M; g.epi = EPI_QKV; g.dispatch_rows = disp_M;
             g.v_bf16 = v_bf16;
-            g.bias = W(h, b + "attn.qkv.bias");
             g.q = Q; g.k = Kb; g.v = V; g.qkv_plane = L.qkv_plane;
             g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.dmodel = D; g.qscale = qscale;
             GemmParams r;
-            const bool rs = rs_route(g, b + "attn.qkv.weight", &r);
+            const bool rs = rs_route(g, blk.qkv, &r);
             if (!rs || !r.ln_x)
-                DSEG_PROF(DINOSEG_PROF_LN, DSEG_TRY(launch_layernorm(X, W(h, b + "norm1.weight"), W(h, b + "norm1.bias"), c.ln_eps, L.M, D, A, L.a_plane,
+                DSEG_PROF(DINOSEG_PROF_LN, DSEG_TRY(launch_layernorm(X, blk.norm1_w, blk.norm1_b, c.ln_eps, L.M, D, A, L.a_plane,
                                                                      P, nullptr, 0, L.ntok, s, FM)));
             DSEG_PROF(DINOSEG_PROF_QKV, DSEG_TRY(rs ? launch_gemm_rs(r, s) : launch_gemm(g, s)));
         }
@@ -759,24 +725,20 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
             if (!mreq->emb_out) return 0;
             float* Xm = X + D;                        // rows 1 .. Nm
             DSEG_TRY(launch_broadcast_row0(X, D, Nm, s));
-            auto lin = [&](const std::string& name, const bf16_t* Ain, long a_plane, int lda, int N, int K, int epi, bf16_t* ob,
-                           long o_plane) -> int {
-                const PackedLinear& pk = h->packed.at(name + ".weight");
-                GemmParams g = {};
-                g.A = Ain; g.a_plane = a_plane; g.lda = lda;
-                g.W = pk.w; g.w_plane = pk.plane;
-                g.M = Nm; g.N = N; g.K = K; g.planes = P; g.fmt = FM; g.epi = epi;
-                g.bias = W(h, name + ".bias");
+            auto lin = [&](const LinearRec& l, const bf16_t* Ain, long a_plane, int epi, bf16_t* ob, long o_plane) -> int {
+                GemmParams g = linear_gemm(l);
+                g.A = Ain; g.a_plane = a_plane; g.lda = l.K;
+                g.M = Nm; g.epi = epi;
                 g.out_f32 = Xm; g.ldo_f32 = D;
-                g.out_bf16 = ob; g.out_plane = o_plane; g.ldo = N;
+                g.out_bf16 = ob; g.out_plane = o_plane; g.ldo = l.N;
                 return launch_gemm_small(g, s);
             };
-            DSEG_TRY(lin(b + "attn.proj", CTX, L.ctx_plane, D, D, D, EPI_RESID, nullptr, 0));
-            DSEG_TRY(launch_layernorm(Xm, W(h, b + "norm2.weight"), W(h, b + "norm2.bias"), c.ln_eps, Nm, D, A, L.a_plane, P, nullptr, 0,
+            DSEG_TRY(lin(blk.proj, CTX, L.ctx_plane, EPI_RESID, nullptr, 0));
+            DSEG_TRY(launch_layernorm(Xm, blk.norm2_w, blk.norm2_b, c.ln_eps, Nm, D, A, L.a_plane, P, nullptr, 0,
                                       L.ntok, s, FM));
-            DSEG_TRY(lin(b + "mlp.fc1", A, L.a_plane, D, F, D, EPI_GELU, HB, L.hb_plane));
-            DSEG_TRY(lin(b + "mlp.fc2", HB, L.hb_plane, F, D, F, EPI_RESID, nullptr, 0));
-            return launch_layernorm(Xm, W(h, "dino.norm.weight"), W(h, "dino.norm.bias"), c.ln_eps, Nm, D, A, L.a_plane, P,
+            DSEG_TRY(lin(blk.fc1, A, L.a_plane, EPI_GELU, HB, L.hb_plane));
+            DSEG_TRY(lin(blk.fc2, HB, L.hb_plane, EPI_RESID, nullptr, 0));
+            return launch_layernorm(Xm, m.norm_w, m.norm_b, c.ln_eps, Nm, D, A, L.a_plane, P,
                                     mreq->emb_out, 0, L.ntok, s, FM);
         }
         {
@@ -789,30 +751,26 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
             a.v_bf16 = v_bf16;
             DSEG_PROF(DINOSEG_PROF_ATTN, DSEG_TRY(launch_attention(a, s)));
         }
-        const bool fuse_mlp3 = P == 2 && h->packed_mlp3.count(b) &&      // hi + lo planes: mlp_fused3.hip
+        const bool fuse_mlp3 = P == 2 && blk.mlp3 &&      // hi + lo planes: mlp_fused3.hip
                                (options().mlp_fused == 2 || (options().mlp_fused == 1 && disp_M >= options().mlp_fused3_min_rows));
-        const bool fuse_mlp = fuse_mlp3 || (h->packed_mlp.count(b) && mlp_fuse_wanted(h, disp_M));
+        const bool fuse_mlp = fuse_mlp3 || (blk.mlp && mlp_fuse_wanted(disp_M));
         // (the fused MLP kernels take the attention output projection along: x += proj(ctx) + b, then the MLP, one launch)
-        const bool fuse_proj = fuse_mlp && options().proj_fused && (fuse_mlp3 || (P == 1 && h->packed_proj.count(b)));
+        const bool fuse_proj = fuse_mlp && options().proj_fused && (fuse_mlp3 || (P == 1 && blk.projf));
         if (!fuse_proj) {
-            const PackedLinear& pk = h->packed.at(b + "attn.proj.weight");
-            GemmParams g = {};
+            GemmParams g = linear_gemm(blk.proj);
             g.A = CTX; g.a_plane = L.ctx_plane; g.lda = D;
-            g.W = pk.w; g.w_plane = pk.plane;
-            g.M = L.M; g.N = D; g.K = D; g.planes = P; g.fmt = FM; g.epi = EPI_RESID; g.dispatch_rows = disp_M;
-            g.bias = W(h, b + "attn.proj.bias");
+            g.M = L.M; g.epi = EPI_RESID; g.dispatch_rows = disp_M;
             g.out_f32 = X; g.ldo_f32 = D;
-            DSEG_PROF(DINOSEG_PROF_PROJ, DSEG_TRY(gemm_any(g, b + "attn.proj.weight")));
+            DSEG_PROF(DINOSEG_PROF_PROJ, DSEG_TRY(gemm_any(g, blk.proj)));
         }
         if (fuse_mlp3) {
-            DSEG_TRY(ensure_mlp_packs(h, s));
             // projection + LN2 + fc1 + GELU + fc2 + residual on hi + lo planes in one launch (mlp_fused3.hip)
             MlpFused3Params g = {};
             g.X = X; g.eps = c.ln_eps;
-            g.Wp = h->packed_mlp3.at(b); g.b2 = W(h, b + "mlp.fc2.bias");
+            g.Wp = blk.mlp3; g.b2 = blk.fc2.b;
             g.M = L.M; g.fmt = FM;
             if (fuse_proj) {
-                g.ctx = CTX; g.ctx_plane = L.ctx_plane; g.bproj = W(h, b + "attn.proj.bias");
+                g.ctx = CTX; g.ctx_plane = L.ctx_plane; g.bproj = blk.proj.b;
                 // ... and LayerNorm1 + qkv of the next block (a tap of this block's output still reads X, which is complete)
                 if (options().qkv_fused3 && i + 1 < c.n_blocks && L.qkv_plane < (1L << 31)) {
                     g.q = Q; g.k = Kb; g.v = V; g.qkv_plane = L.qkv_plane;
@@ -821,14 +779,13 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
                 }
             }
             DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(launch_mlp_fused3(g, s)));
-        } else if (fuse_mlp && fuse_proj && options().mlp_fused4 && h->mlp_fused4_snap && !options().qkv_fused && h->packed_mlp4.count(b)) {
-            DSEG_TRY(ensure_mlp_packs(h, s));
+        } else if (fuse_mlp && fuse_proj && options().mlp_fused4 && h->mlp_fused4_snap && !options().qkv_fused && blk.mlp4) {
             // the same launch with one wave per SIMD (mlp_fused4.hip)
             MlpFused3Params g = {};
             g.X = X; g.eps = c.ln_eps;
-            g.Wp = h->packed_mlp4.at(b); g.b2 = W(h, b + "mlp.fc2.bias");
+            g.Wp = blk.mlp4; g.b2 = blk.fc2.b;
             g.M = L.M; g.fmt = FM;
-            g.ctx = CTX; g.bproj = W(h, b + "attn.proj.bias");
+            g.ctx = CTX; g.bproj = blk.proj.b;
             // ... and LayerNorm1 + qkv of the next block (a tap of this block's output still reads X, which is complete)
             if (options().qkv_fused4 && i + 1 < c.n_blocks) {
                 g.q = Q; g.k = Kb; g.v = V; g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.qscale = qscale;
@@ -836,100 +793,87 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
             }
             DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(launch_mlp_fused4(g, s)));
         } else if (fuse_mlp) {
-            DSEG_TRY(ensure_mlp_packs(h, s));      // (a split forward has done this before its fork)
             // LN2 + fc1 + GELU + fc2 + residual in one launch: the hidden activation never reaches HBM (mlp_fused2.hip)
             MlpFusedParams g = {};
-            g.X = X; g.ldx = D; g.gamma = W(h, b + "norm2.weight"); g.beta = W(h, b + "norm2.bias"); g.eps = c.ln_eps;
-            g.Wp = h->packed_mlp.at(b); g.b1 = W(h, b + "mlp.fc1.bias"); g.b2 = W(h, b + "mlp.fc2.bias");
+            g.X = X; g.ldx = D; g.gamma = blk.norm2_w; g.beta = blk.norm2_b; g.eps = c.ln_eps;
+            g.Wp = blk.mlp; g.b1 = blk.fc1.b; g.b2 = blk.fc2.b;
             g.M = L.M; g.fmt = FM;
             if (fuse_proj) {
-                g.ctx = CTX; g.Wproj = h->packed_proj.at(b); g.bproj = W(h, b + "attn.proj.bias");
-                const std::string nb = "dino.blocks." + std::to_string(i + 1) + ".";
+                g.ctx = CTX; g.Wproj = blk.projf; g.bproj = blk.proj.b;
                 // ... and LayerNorm1 + qkv of the next block (a tap of this block's output still reads X, which is complete)
-                if (options().qkv_fused && i + 1 < c.n_blocks && h->packed_qkvf.count(nb)) {
-                    g.Wqkv = h->packed_qkvf.at(nb); g.bqkv = W(h, nb + "attn.qkv.bias");
-                    g.gamma1 = W(h, nb + "norm1.weight"); g.beta1 = W(h, nb + "norm1.bias");
+                if (options().qkv_fused && i + 1 < c.n_blocks && m.blocks[i + 1].qkvf) {
+                    const BlockRec& nb = m.blocks[i + 1];
+                    g.Wqkv = nb.qkvf; g.bqkv = nb.qkv.b;
+                    g.gamma1 = nb.norm1_w; g.beta1 = nb.norm1_b;
                     g.q = Q; g.k = Kb; g.v = V; g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.qscale = qscale;
                     qkv_ready = true;
                 }
             }
             DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(launch_mlp_fused2(g, s)));
         } else {
-        if (fuse_ln && h->packed_slab.count(b + "mlp.fc1.weight") && L.hb_plane < (1L << 31)) {
+        if (fuse_ln && blk.fc1.slab && L.hb_plane < (1L << 31)) {
             LnGemmParams g = {};
-            g.X = X; g.ldx = D; g.gamma = W(h, b + "norm2.weight"); g.beta = W(h, b + "norm2.bias"); g.eps = c.ln_eps;
-            g.W = h->packed_slab.at(b + "mlp.fc1.weight"); g.bias = W(h, b + "mlp.fc1.bias");
+            g.X = X; g.ldx = D; g.gamma = blk.norm2_w; g.beta = blk.norm2_b; g.eps = c.ln_eps;
+            g.W = blk.fc1.slab; g.bias = blk.fc1.b;
             g.M = L.M; g.N = F; g.epi = EPI_GELU; g.fmt = FM;
             g.out_bf16 = HB; g.out_plane = L.hb_plane; g.ldo = F;
             DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(launch_gemm_ln(g, D, P, s)));
         } else {
-            const PackedLinear& pk = h->packed.at(b + "mlp.fc1.weight");
-            GemmParams g = {};
+            GemmParams g = linear_gemm(blk.fc1);
             g.A = A; g.a_plane = L.a_plane; g.lda = D;
-            g.W = pk.w; g.w_plane = pk.plane;
-            g.M = L.M; g.N = F; g.K = D; g.planes = P; g.fmt = FM; g.epi = EPI_GELU; g.dispatch_rows = disp_M;
-            g.bias = W(h, b + "mlp.fc1.bias");
+            g.M = L.M; g.epi = EPI_GELU; g.dispatch_rows = disp_M;
             g.out_bf16 = HB; g.out_plane = L.hb_plane; g.ldo = F;
             GemmParams r;
-            const bool rs = rs_route(g, b + "mlp.fc1.weight", &r);
+            const bool rs = rs_route(g, blk.fc1, &r);
             if (!rs || !r.ln_x)
-                DSEG_PROF(DINOSEG_PROF_LN, DSEG_TRY(launch_layernorm(X, W(h, b + "norm2.weight"), W(h, b + "norm2.bias"), c.ln_eps, L.M, D, A, L.a_plane,
+                DSEG_PROF(DINOSEG_PROF_LN, DSEG_TRY(launch_layernorm(X, blk.norm2_w, blk.norm2_b, c.ln_eps, L.M, D, A, L.a_plane,
                                                                      P, nullptr, 0, L.ntok, s, FM)));
             DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(rs ? launch_gemm_rs(r, s) : launch_gemm(g, s)));
         }
         {
-            const PackedLinear& pk = h->packed.at(b + "mlp.fc2.weight");
-            GemmParams g = {};
+            GemmParams g = linear_gemm(blk.fc2);
             g.A = HB; g.a_plane = L.hb_plane; g.lda = F;
-            g.W = pk.w; g.w_plane = pk.plane;
-            g.M = L.M; g.N = D; g.K = F; g.planes = P; g.fmt = FM; g.epi = EPI_RESID; g.dispatch_rows = disp_M;
-            g.bias = W(h, b + "mlp.fc2.bias");
+            g.M = L.M; g.epi = EPI_RESID; g.dispatch_rows = disp_M;
             g.out_f32 = X; g.ldo_f32 = D;
-            DSEG_PROF(DINOSEG_PROF_FC2, DSEG_TRY(gemm_any(g, b + "mlp.fc2.weight")));
+            DSEG_PROF(DINOSEG_PROF_FC2, DSEG_TRY(gemm_any(g, blk.fc2)));
         }
         }
         if (tap_block == i + 1 && tap_out) DSEG_CHECK_HIP(hipMemcpyAsync(tap_out, X, xbytes, hipMemcpyDeviceToDevice, s));
         if (mreq && mreq->feat_out && mreq->feat_blocks == i + 1 && i + 1 < c.n_blocks)      // forward(x, intermediate=k)
-            return launch_layernorm(X, W(h, "dino.norm.weight"), W(h, "dino.norm.bias"), c.ln_eps, L.M, D, nullptr, 0, 1, mreq->feat_out, 0,
+            return launch_layernorm(X, m.norm_w, m.norm_b, c.ln_eps, L.M, D, nullptr, 0, 1, mreq->feat_out, 0,
                                     L.ntok, s);
     }
     if (mreq && mreq->feat_out)     // VisionTransformer.forward(x, all=True): every token through the final norm, fp32
-        return launch_layernorm(X, W(h, "dino.norm.weight"), W(h, "dino.norm.bias"), c.ln_eps, L.M, D, nullptr, 0, 1, mreq->feat_out, 0,
+        return launch_layernorm(X, m.norm_w, m.norm_b, c.ln_eps, L.M, D, nullptr, 0, 1, mreq->feat_out, 0,
                                 L.ntok, s);
 
     // ---- final norm, drop CLS (vision_transformer.py:243; pl_torch_modules.py:243,253) ----
-    DSEG_PROF(DINOSEG_PROF_LN, DSEG_TRY(launch_layernorm(X, W(h, "dino.norm.weight"), W(h, "dino.norm.bias"), c.ln_eps, L.M, D, FEAT, L.feat_plane,
+    DSEG_PROF(DINOSEG_PROF_LN, DSEG_TRY(launch_layernorm(X, m.norm_w, m.norm_b, c.ln_eps, L.M, D, FEAT, L.feat_plane,
                               HP, nullptr, 1, L.ntok, s, SF)));
 
     // ---- segmentation head (pl_torch_modules.py:108-138), always in split precision ----
     if (c.head_kind == DINOSEG_HEAD_MLP) {
         {
-            const PackedLinear& pk = h->packed.at("clf.layer_1.weight");
-            GemmParams g = {};
+            GemmParams g = linear_gemm(m.head[0]);
             g.A = FEAT; g.a_plane = L.feat_plane; g.lda = D;
-            g.W = pk.w; g.w_plane = pk.plane;
-            g.M = L.Mp; g.N = 256; g.K = D; g.planes = HP; g.fmt = SF; g.epi = EPI_RELU;
-            g.bias = pk.bias_pad;
+            g.M = L.Mp; g.epi = EPI_RELU;
             g.out_bf16 = H1; g.out_plane = L.h1_plane; g.ldo = 256;
             DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_gemm(g, s)));
         }
         {
-            const PackedLinear& pk = h->packed.at("clf.layer_2.weight");
-            GemmParams g = {};
+            GemmParams g = linear_gemm(m.head[1]);
             g.A = H1; g.a_plane = L.h1_plane; g.lda = 256;
-            g.W = pk.w; g.w_plane = pk.plane;
-            g.M = L.Mp; g.N = 128; g.K = 256; g.planes = HP; g.fmt = SF; g.epi = EPI_RELU;
-            g.bias = pk.bias_pad;
+            g.M = L.Mp; g.epi = EPI_RELU;
             g.out_bf16 = H2; g.out_plane = L.h2_plane; g.ldo = 128;
             DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_gemm(g, s)));
         }
-        DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_head_final(H2, L.h2_plane, 128, L.Mp, 100, W(h, "clf.layer_3.weight"), W(h, "clf.layer_3.bias"),
+        DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_head_final(H2, L.h2_plane, 128, L.Mp, 100, m.clf.w, m.clf.b,
                                    c.n_classes, logp_out ? logp_out : reinterpret_cast<float*>(ws + L.HB), argmax_out, s, SF,
-                                   wide_clf(h).w, wide_clf(h).plane)));
+                                   m.clf.pk.w, m.clf.pk.plane)));
     } else {
-        DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_head_final(FEAT, L.feat_plane, D, L.Mp, D, W(h, "clf.layer_1.weight"), W(h, "clf.layer_1.bias"),
+        DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_head_final(FEAT, L.feat_plane, D, L.Mp, D, m.clf.w, m.clf.b,
                                    c.n_classes, logp_out ? logp_out : reinterpret_cast<float*>(ws + L.HB), argmax_out, s, SF,
-                                   wide_clf(h).w, wide_clf(h).plane)));
+                                   m.clf.pk.w, m.clf.pk.plane)));
     }
     return 0;
 }
@@ -962,8 +906,6 @@ extern "C" int dinoseg_forward_hw(dinoseg_handle* h, const void* x, int32_t x_ki
     const long n = (long)(H / h->cfg.patch) * (W / h->cfg.patch);
     const size_t frame_bytes = x_kind == DINOSEG_INPUT_U8_HWC ? (size_t)H * W * 3 : (size_t)H * W * 3 * sizeof(float);
     const void* x1 = reinterpret_cast<const char*>(x) + (size_t)B0 * frame_bytes;
-    const long ntok_ = n + 1;
-    if (mlp_fuse_wanted(h, B * ntok_)) DSEG_TRY(ensure_mlp_packs(h, s));   // before the fork: both halves read them
     DSEG_CHECK_HIP(hipEventRecord(h->ev_fork, s));
     DSEG_CHECK_HIP(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
     h->in_split = true;

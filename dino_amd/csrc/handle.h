@@ -29,6 +29,37 @@ struct PackedLinear {       // W[N,K] operand planes of one nn.Linear, padded to
     float* bias_pad = nullptr;   // only when N was padded (head layers); else the bound bias is used
 };
 
+// The weights as dinoseg_refresh_weights resolved them: the bound fp32 tensors and the library-owned copies (pointers into wbuf;
+// null = that copy does not exist under the options of the last refresh).  Filled by the refresh and by nothing else; every
+// reader checks weights_ready first, which dinoseg_bind_weight clears, so a record is never read stale.
+struct LinearRec {          // one nn.Linear
+    const float* w = nullptr;    // bound weight [N, K] and bias [N]
+    const float* b = nullptr;
+    int N = 0, K = 0, planes = 0, fmt = 0;
+    int rs_bit = 0;              // its bit of option gemm_rs (block linears: 1 mlp.fc1, 2 attn.qkv, 4 attn.proj and mlp.fc2; else 0)
+    PackedLinear pk;             // operand planes (every linear that feeds gemm.hip)
+    bf16_t* slab = nullptr;      // qkv / fc1: slab-major copy for the LayerNorm-fused kernel (gemm_ln.hip), where supported
+    bf16_t* rs = nullptr;        // one-plane modes at embed_dim 768: the fragment-order copy gemm_rs.hip streams ...
+    float* rs_bias = nullptr;    // ... and, when that copy carries the LayerNorm in front of the linear (gemm_rs_ln_snap), the folded bias
+};
+struct BlockRec {           // one transformer block
+    const float *norm1_w = nullptr, *norm1_b = nullptr, *norm2_w = nullptr, *norm2_b = nullptr;
+    LinearRec qkv, proj, fc1, fc2;
+    bf16_t* mlp = nullptr;       // fc1 + fc2 in MFMA fragment order (mlp_fused2.hip)
+    bf16_t* projf = nullptr;     // attn.proj.weight in the same fragment order (mlp_fused2.hip, PROJ)
+    bf16_t* qkvf = nullptr;      // attn.qkv.weight in fragment order (mlp_fused2.hip, QKV tail of the block before; never block 0)
+    bf16_t* mlp3 = nullptr;      // hi + lo modes: attn.proj + fc1 + fc2 (+ the next block's qkv) as the slot stream of mlp_fused3.hip
+    bf16_t* mlp4 = nullptr;      // one-plane modes, option mlp_fused4: the same as the slot stream of mlp_fused4.hip
+};
+struct ModelRec {
+    LinearRec patch;             // dino.patch_embed.proj
+    const float *cls_token = nullptr, *pos_embed = nullptr, *norm_w = nullptr, *norm_b = nullptr;
+    std::vector<BlockRec> blocks;
+    LinearRec head[2];           // clf.layer_1 / layer_2 of the MLP head
+    LinearRec clf;               // the classifier (layer_3 of the MLP head, layer_1 of the linear head): fp32 for launch_head_final;
+                                 // pk = its hi+lo planes for the wide head kernel (n_classes > 32), empty below that
+};
+
 struct dinoseg_handle {
     dinoseg_config cfg;
     int planes;
@@ -39,17 +70,7 @@ struct dinoseg_handle {
     // packed weights (library-owned)
     char* wbuf = nullptr;
     size_t wbuf_bytes = 0;
-    std::map<std::string, PackedLinear> packed;
-    std::map<std::string, bf16_t*> packed_slab;     // slab-major copies of the LN-fed weights (gemm_ln.hip), when supported
-    std::map<std::string, bf16_t*> packed_mlp;      // per block ("dino.blocks.i."): fc1 + fc2 in MFMA fragment order (mlp_fused2.hip)
-    std::map<std::string, bf16_t*> packed_proj;     // per block: attn.proj.weight in the same fragment order (mlp_fused2.hip, PROJ)
-    std::map<std::string, bf16_t*> packed_rs;       // per Linear weight name, one-plane modes at embed_dim 768: the fragment-order copy gemm_rs.hip streams
-    std::map<std::string, float*> packed_rs_bias;   // ... those of them that carry the LayerNorm in front of the linear (qkv / fc1, gemm_rs_ln_snap): the folded bias
-    std::map<std::string, bf16_t*> packed_mlp4;     // per block, one-plane modes: attn.proj + fc1 + fc2 as the slot stream of mlp_fused4.hip
-    std::map<std::string, bf16_t*> packed_mlp3;     // per block, hi + lo modes: attn.proj + fc1 + fc2 as the slot stream of mlp_fused3.hip
-    std::map<std::string, bf16_t*> packed_qkvf;     // per block: attn.qkv.weight in fragment order (mlp_fused2.hip, QKV tail of the block before)
-    bool packed_mlp_stale = false;         // the fragment-order packs are made on the first forward that uses them (the fine-tune
-                                           // step refreshes the weights every step and never runs the fused MLP kernel)
+    ModelRec model;             // what the last dinoseg_refresh_weights resolved and packed (valid while weights_ready)
     bool weights_ready = false;
     int fp16_patch_planes_snap = 1;        // option fp16_patch_planes as of the last dinoseg_refresh_weights (what the packs were made for)
     int mlp_fused4_snap = 0;               // ... mlp_fused4, gemm_rs and gemm_rs_ln likewise (kernels.h Options: which of them a forward reads)
@@ -78,7 +99,6 @@ struct dinoseg_handle {
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool in_split = false;                 // a split forward is being queued (both halves' launches share the chip)
-    // optional per-kernel-class timing with HIP events on the caller's stream (bench.py roofline leg)
     // fine-tune step state (train_api.hip)
     std::map<std::string, float*> grads;   // bound gradient buffers (absent / null = frozen tensor)
     char* tws = nullptr;                   // training workspace: saved activations + backward scratch
@@ -96,6 +116,7 @@ struct dinoseg_handle {
     std::vector<hipEvent_t> bw_ev;
     char* twbuf = nullptr;                 // transposed packed weights for the input-gradient GEMMs
     size_t twbuf_bytes = 0;
+    // optional per-kernel-class timing with HIP events on the caller's stream (bench.py roofline leg)
     int prof_level = 0;                    // 0 off, 1 attention only, 2 every class
     struct ProfRec { int cat; hipEvent_t a, b; };
     std::vector<ProfRec> prof_recs;
@@ -167,14 +188,17 @@ static inline int patch_planes(const dinoseg_handle* h) { return (h->fmt == FMT_
 static inline int split_fmt(const dinoseg_handle* h) { return h->planes == 2 ? h->fmt : (int)FMT_BF16; }
 // format of the patch-embedding operands: the mode's own when it runs on the mode's planes, the split format otherwise
 static inline int patch_fmt(const dinoseg_handle* h) { return patch_planes(h) == h->planes ? h->fmt : split_fmt(h); }   // the classifier head always runs in split precision (it is tiny)
-// the classifier packed for the wide head kernel (n_classes > 32, dinoseg_refresh_weights); empty below that
-static inline PackedLinear wide_clf(const dinoseg_handle* h) {
-    if (h->cfg.n_classes <= HEAD_FINAL_MAX_C) return PackedLinear();
-    auto it = h->packed.find(h->cfg.head_kind == DINOSEG_HEAD_MLP ? "clf.layer_3.weight" : "clf.layer_1.weight");
-    return it == h->packed.end() ? PackedLinear() : it->second;
-}
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline const float* W(const dinoseg_handle* h, const std::string& k) { return h->bound.at(k).ptr; }
+// the GemmParams fields that follow from which linear it is (a padded head layer multiplies its padded shape, with the padded bias);
+// the call site adds what is its own: A, the outputs, the epilogue
+static inline GemmParams linear_gemm(const LinearRec& l) {
+    GemmParams g = {};
+    g.W = l.pk.w; g.w_plane = l.pk.plane;
+    g.N = l.pk.n_pad; g.K = l.pk.k_pad; g.planes = l.planes; g.fmt = l.fmt;
+    g.bias = l.pk.bias_pad ? l.pk.bias_pad : l.b;
+    return g;
+}
 static inline void norm_consts(float mean255[3], float inv255[3]) {
     const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};
     for (int c = 0; c < 3; ++c) {

@@ -389,6 +389,7 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
     const int NB = c.n_blocks;
     const bool mlp_head = c.head_kind == DINOSEG_HEAD_MLP;
     const TrainLayout L = make_train_layout(h, B, Hf, Wf);
+    const ModelRec& m = h->model;
 
     // ---- workspace
     if (!h->bad_label_flag) {       // (its own allocation: a change of batch shape re-lays the workspace, the latched flag must survive it)
@@ -425,21 +426,18 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
     DSEG_TRY(launch_patch_gather(x, x_kind, B, Hf, Wf, mean255, inv255, PATCH, L.patch_plane, P, s, FMT_BF16, c.patch));
     float* X0 = NB > 0 ? F32(L.Xin) : F32(L.Xfin);
     {
-        const PackedLinear& pk = h->packed.at("dino.patch_embed.proj.weight");
-        GemmParams g = {};
+        GemmParams g = linear_gemm(m.patch);
         g.A = PATCH; g.a_plane = L.patch_plane; g.lda = 3 * c.patch * c.patch;
-        g.W = pk.w; g.w_plane = pk.plane;
-        g.M = L.Mp; g.N = D; g.K = 3 * c.patch * c.patch; g.planes = P; g.epi = EPI_PATCH;
-        g.bias = W(h, "dino.patch_embed.proj.bias");
+        g.M = L.Mp; g.epi = EPI_PATCH;
         g.out_f32 = X0; g.ldo_f32 = D;
         g.pos = h->pos_cache; g.n_patches = L.n;
         DSEG_TRY(launch_gemm(g, s));
     }
-    DSEG_TRY(launch_cls_rows(X0, W(h, "dino.cls_token"), h->pos_cache, B, L.ntok, D, s));
+    DSEG_TRY(launch_cls_rows(X0, m.cls_token, h->pos_cache, B, L.ntok, D, s));
     const float qscale = 0.125f * 1.44269504088896340736f;
 
     for (int l = 0; l < NB; ++l) {
-        const std::string b = "dino.blocks." + std::to_string(l) + ".";
+        const BlockRec& blk = m.blocks[l];
         const size_t o = l * L.blk_stride;
         float* Xin = F32(L.Xin + o);
         float* Xmid = F32(L.Xmid + o);
@@ -447,24 +445,23 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
         bf16_t *A1 = B16(L.A1 + o), *Q = B16(L.Q + o), *Kb = B16(L.K + o), *V = B16(L.V + o), *CTX = B16(L.CTX + o);
         bf16_t *A2 = B16(L.A2 + o), *HPRE = B16(L.HPRE + o), *HB = B16(L.HB + o);
         const bool fuse_ln = options().gemm_ln != 0 && L.qkv_plane < (1L << 31) && L.f_plane < (1L << 31);
-        if (fuse_ln && h->packed_slab.count(b + "attn.qkv.weight")) {
+        if (fuse_ln && blk.qkv.slab) {
             // LN1 + qkv in one launch; the normalised planes the weight gradient needs are a by-product (a_out)
             LnGemmParams g = {};
-            g.X = Xin; g.ldx = D; g.gamma = W(h, b + "norm1.weight"); g.beta = W(h, b + "norm1.bias"); g.eps = c.ln_eps;
-            g.W = h->packed_slab.at(b + "attn.qkv.weight"); g.bias = W(h, b + "attn.qkv.bias");
+            g.X = Xin; g.ldx = D; g.gamma = blk.norm1_w; g.beta = blk.norm1_b; g.eps = c.ln_eps;
+            g.W = blk.qkv.slab; g.bias = blk.qkv.b;
             g.M = L.M; g.N = 3 * D; g.epi = EPI_QKV;
             g.q = Q; g.k = Kb; g.v = V; g.qkv_plane = L.qkv_plane;
             g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.dmodel = D; g.qscale = qscale;
             g.a_out = A1; g.a_plane = L.a_plane;
             DSEG_TRY(launch_gemm_ln(g, D, P, s));
         } else {
-        DSEG_TRY(launch_layernorm(Xin, W(h, b + "norm1.weight"), W(h, b + "norm1.bias"), c.ln_eps, L.M, D, A1, L.a_plane, P,
+        DSEG_TRY(launch_layernorm(Xin, blk.norm1_w, blk.norm1_b, c.ln_eps, L.M, D, A1, L.a_plane, P,
                                   nullptr, 0, L.ntok, s));
         {
-            const PackedLinear& pk = h->packed.at(b + "attn.qkv.weight");
-            GemmParams g = {};
-            g.A = A1; g.a_plane = L.a_plane; g.lda = D; g.W = pk.w; g.w_plane = pk.plane;
-            g.M = L.M; g.N = 3 * D; g.K = D; g.planes = P; g.epi = EPI_QKV; g.bias = W(h, b + "attn.qkv.bias");
+            GemmParams g = linear_gemm(blk.qkv);
+            g.A = A1; g.a_plane = L.a_plane; g.lda = D;
+            g.M = L.M; g.epi = EPI_QKV;
             g.q = Q; g.k = Kb; g.v = V; g.qkv_plane = L.qkv_plane;
             g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.dmodel = D; g.qscale = qscale;
             DSEG_TRY(launch_gemm(g, s));
@@ -478,39 +475,36 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
             DSEG_TRY(launch_attention(a, s));
         }
         {
-            const PackedLinear& pk = h->packed.at(b + "attn.proj.weight");
-            GemmParams g = {};
-            g.A = CTX; g.a_plane = L.a_plane; g.lda = D; g.W = pk.w; g.w_plane = pk.plane;
-            g.M = L.M; g.N = D; g.K = D; g.planes = P; g.epi = EPI_RESID; g.bias = W(h, b + "attn.proj.bias");
+            GemmParams g = linear_gemm(blk.proj);
+            g.A = CTX; g.a_plane = L.a_plane; g.lda = D;
+            g.M = L.M; g.epi = EPI_RESID;
             g.resid = Xin; g.out_f32 = Xmid; g.ldo_f32 = D;
             DSEG_TRY(launch_gemm(g, s));
         }
-        if (fuse_ln && h->packed_slab.count(b + "mlp.fc1.weight")) {
+        if (fuse_ln && blk.fc1.slab) {
             LnGemmParams g = {};
-            g.X = Xmid; g.ldx = D; g.gamma = W(h, b + "norm2.weight"); g.beta = W(h, b + "norm2.bias"); g.eps = c.ln_eps;
-            g.W = h->packed_slab.at(b + "mlp.fc1.weight"); g.bias = W(h, b + "mlp.fc1.bias");
+            g.X = Xmid; g.ldx = D; g.gamma = blk.norm2_w; g.beta = blk.norm2_b; g.eps = c.ln_eps;
+            g.W = blk.fc1.slab; g.bias = blk.fc1.b;
             g.M = L.M; g.N = F; g.epi = EPI_GELU;
             g.out_bf16 = HB; g.out_plane = L.f_plane; g.ldo = F;
             g.a_out = A2; g.a_plane = L.a_plane;
             g.aux_out = HPRE; g.aux_plane = L.f_plane;
             DSEG_TRY(launch_gemm_ln(g, D, P, s));
         } else {
-        DSEG_TRY(launch_layernorm(Xmid, W(h, b + "norm2.weight"), W(h, b + "norm2.bias"), c.ln_eps, L.M, D, A2, L.a_plane, P,
+        DSEG_TRY(launch_layernorm(Xmid, blk.norm2_w, blk.norm2_b, c.ln_eps, L.M, D, A2, L.a_plane, P,
                                   nullptr, 0, L.ntok, s));
         {
-            const PackedLinear& pk = h->packed.at(b + "mlp.fc1.weight");
-            GemmParams g = {};
-            g.A = A2; g.a_plane = L.a_plane; g.lda = D; g.W = pk.w; g.w_plane = pk.plane;
-            g.M = L.M; g.N = F; g.K = D; g.planes = P; g.epi = EPI_GELU; g.bias = W(h, b + "mlp.fc1.bias");
+            GemmParams g = linear_gemm(blk.fc1);
+            g.A = A2; g.a_plane = L.a_plane; g.lda = D;
+            g.M = L.M; g.epi = EPI_GELU;
             g.out_bf16 = HB; g.out_plane = L.f_plane; g.ldo = F; g.aux_out = HPRE; g.aux_plane = L.f_plane;
             DSEG_TRY(launch_gemm(g, s));
         }
         }
         {
-            const PackedLinear& pk = h->packed.at(b + "mlp.fc2.weight");
-            GemmParams g = {};
-            g.A = HB; g.a_plane = L.f_plane; g.lda = F; g.W = pk.w; g.w_plane = pk.plane;
-            g.M = L.M; g.N = D; g.K = F; g.planes = P; g.epi = EPI_RESID; g.bias = W(h, b + "mlp.fc2.bias");
+            GemmParams g = linear_gemm(blk.fc2);
+            g.A = HB; g.a_plane = L.f_plane; g.lda = F;
+            g.M = L.M; g.epi = EPI_RESID;
             g.resid = Xmid; g.out_f32 = Xout; g.ldo_f32 = D;
             DSEG_TRY(launch_gemm(g, s));
         }
@@ -518,30 +512,28 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
     float* Xfin = F32(L.Xfin);
     bf16_t *FEAT = B16(L.FEAT), *H1 = B16(L.H1), *H2 = B16(L.H2);
     float* LOGP = F32(L.LOGP);
-    DSEG_TRY(launch_layernorm(Xfin, W(h, "dino.norm.weight"), W(h, "dino.norm.bias"), c.ln_eps, L.M, D, FEAT, L.feat_plane, HP,
+    DSEG_TRY(launch_layernorm(Xfin, m.norm_w, m.norm_b, c.ln_eps, L.M, D, FEAT, L.feat_plane, HP,
                               nullptr, 1, L.ntok, s));
     if (mlp_head) {
         {
-            const PackedLinear& pk = h->packed.at("clf.layer_1.weight");
-            GemmParams g = {};
-            g.A = FEAT; g.a_plane = L.feat_plane; g.lda = D; g.W = pk.w; g.w_plane = pk.plane;
-            g.M = L.Mp; g.N = 256; g.K = D; g.planes = HP; g.epi = EPI_RELU; g.bias = pk.bias_pad;
+            GemmParams g = linear_gemm(m.head[0]);
+            g.A = FEAT; g.a_plane = L.feat_plane; g.lda = D;
+            g.M = L.Mp; g.epi = EPI_RELU;
             g.out_bf16 = H1; g.out_plane = L.h1_plane; g.ldo = 256;
             DSEG_TRY(launch_gemm(g, s));
         }
         {
-            const PackedLinear& pk = h->packed.at("clf.layer_2.weight");
-            GemmParams g = {};
-            g.A = H1; g.a_plane = L.h1_plane; g.lda = 256; g.W = pk.w; g.w_plane = pk.plane;
-            g.M = L.Mp; g.N = 128; g.K = 256; g.planes = HP; g.epi = EPI_RELU; g.bias = pk.bias_pad;
+            GemmParams g = linear_gemm(m.head[1]);
+            g.A = H1; g.a_plane = L.h1_plane; g.lda = 256;
+            g.M = L.Mp; g.epi = EPI_RELU;
             g.out_bf16 = H2; g.out_plane = L.h2_plane; g.ldo = 128;
             DSEG_TRY(launch_gemm(g, s));
         }
-        DSEG_TRY(launch_head_final(H2, L.h2_plane, 128, L.Mp, 100, W(h, "clf.layer_3.weight"), W(h, "clf.layer_3.bias"), C, LOGP,
-                                   nullptr, s, FMT_BF16, wide_clf(h).w, wide_clf(h).plane));
+        DSEG_TRY(launch_head_final(H2, L.h2_plane, 128, L.Mp, 100, m.clf.w, m.clf.b, C, LOGP,
+                                   nullptr, s, FMT_BF16, m.clf.pk.w, m.clf.pk.plane));
     } else {
-        DSEG_TRY(launch_head_final(FEAT, L.feat_plane, D, L.Mp, D, W(h, "clf.layer_1.weight"), W(h, "clf.layer_1.bias"), C, LOGP,
-                                   nullptr, s, FMT_BF16, wide_clf(h).w, wide_clf(h).plane));
+        DSEG_TRY(launch_head_final(FEAT, L.feat_plane, D, L.Mp, D, m.clf.w, m.clf.b, C, LOGP,
+                                   nullptr, s, FMT_BF16, m.clf.pk.w, m.clf.pk.plane));
     }
     if (logp_out) DSEG_CHECK_HIP(hipMemcpyAsync(logp_out, LOGP, (size_t)L.Mp * C * 4, hipMemcpyDeviceToDevice, s));
     h->tr_B = B;
