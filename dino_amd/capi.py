@@ -130,6 +130,14 @@ SIGNATURES = {
     "dinoseg_op_patch_gather_hw": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
     # the gather at either patch size (8 or 16): H, W, patch
     "dinoseg_op_patch_gather_p": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
+    # the helper kernels on their own (tests/test_helper_ops_gpu.py)
+    "dinoseg_op_attn_probs": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _fp, _vp]),
+    "dinoseg_op_cls_mask_attn": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _fp, _i32, _vp, _i64, _fp, _vp]),
+    "dinoseg_op_cls_rows": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _vp]),
+    "dinoseg_op_broadcast_row0": (C.c_int, [_fp, _i32, _i32, _vp]),
+    "dinoseg_op_batch_sum_rows": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _vp]),
+    "dinoseg_op_multi_pack": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dinoseg_op_multi_zero": (C.c_int, [_i32, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

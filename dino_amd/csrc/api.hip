@@ -1501,3 +1501,119 @@ extern "C" int dinoseg_op_head_wide(const void* in, int64_t in_plane, int32_t ld
     return launch_head_wide(reinterpret_cast<const bf16_t*>(in), in_plane, ld, M, K, reinterpret_cast<const bf16_t*>(Wp), w_plane, b, C,
                             logp, argmax, reinterpret_cast<hipStream_t>(stream), options().op_fmt);
 }
+
+// ---- the helper kernels on their own (tests/test_helper_ops_gpu.py): every entry checks its arguments on the host first ----
+extern "C" int dinoseg_op_attn_probs(const void* q, const void* k, int64_t qkv_plane, int32_t planes, int32_t B, int32_t heads, int32_t ntok,
+                                     int32_t npad, float* out, void* stream) {
+    if (!q || !k || !out) {
+        dinoseg_set_error("dinoseg_op_attn_probs: null pointer");
+        return -1;
+    }
+    if ((planes != 1 && planes != 2) || B < 1 || heads < 1 || ntok < 1 || npad < ntok || (int64_t)B * heads > 65535 ||
+        (planes == 2 && qkv_plane < (int64_t)B * heads * npad * 64)) {
+        dinoseg_set_error("dinoseg_op_attn_probs: bad argument (planes=%d B=%d heads=%d ntok=%d npad=%d qkv_plane=%lld)", planes, B, heads, ntok,
+                          npad, (long long)qkv_plane);
+        return -1;
+    }
+    return launch_attn_probs(reinterpret_cast<const bf16_t*>(q), reinterpret_cast<const bf16_t*>(k), qkv_plane, planes, B, heads, ntok, npad, out,
+                             reinterpret_cast<hipStream_t>(stream), options().op_fmt);
+}
+
+extern "C" int dinoseg_op_cls_mask_attn(const void* q, const void* k, const void* v, int64_t qkv_plane, int32_t planes, int32_t heads,
+                                        int32_t ntok, int32_t npad, const float* mask, int32_t n_masks, void* ctx, int64_t ctx_plane,
+                                        float* probs, void* stream) {
+    if (!q || !k || !v || !mask || !ctx) {
+        dinoseg_set_error("dinoseg_op_cls_mask_attn: null pointer");
+        return -1;
+    }
+    if ((planes != 1 && planes != 2) || heads < 1 || heads > 65535 || ntok < 1 || npad < ntok || n_masks < 1 ||
+        (planes == 2 && (qkv_plane < (int64_t)heads * npad * 64 || ctx_plane < (int64_t)n_masks * heads * 64))) {
+        dinoseg_set_error("dinoseg_op_cls_mask_attn: bad argument (planes=%d heads=%d ntok=%d npad=%d n_masks=%d qkv_plane=%lld ctx_plane=%lld)",
+                          planes, heads, ntok, npad, n_masks, (long long)qkv_plane, (long long)ctx_plane);
+        return -1;
+    }
+    return launch_cls_mask_attn(reinterpret_cast<const bf16_t*>(q), reinterpret_cast<const bf16_t*>(k), reinterpret_cast<const bf16_t*>(v),
+                                qkv_plane, planes, heads, ntok, npad, mask, n_masks, reinterpret_cast<bf16_t*>(ctx), ctx_plane, probs,
+                                reinterpret_cast<hipStream_t>(stream), options().op_fmt);
+}
+
+extern "C" int dinoseg_op_cls_rows(float* X, const float* cls, const float* pos, int32_t B, int32_t ntok, int32_t D, void* stream) {
+    if (!X || !cls || !pos) {
+        dinoseg_set_error("dinoseg_op_cls_rows: null pointer");
+        return -1;
+    }
+    if (B < 1 || ntok < 1 || D < 1 || (int64_t)B * D > INT32_MAX) {
+        dinoseg_set_error("dinoseg_op_cls_rows: bad shape B=%d ntok=%d D=%d", B, ntok, D);
+        return -1;
+    }
+    return launch_cls_rows(X, cls, pos, B, ntok, D, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_broadcast_row0(float* X, int32_t D, int32_t n, void* stream) {
+    if (!X) {
+        dinoseg_set_error("dinoseg_op_broadcast_row0: null pointer");
+        return -1;
+    }
+    if (D < 1 || n < 0) {
+        dinoseg_set_error("dinoseg_op_broadcast_row0: bad shape D=%d n=%d", D, n);
+        return -1;
+    }
+    if (n == 0) return 0;
+    return launch_broadcast_row0(X, D, n, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_batch_sum_rows(const float* X, int32_t B, int32_t ntok, int32_t D, float* out, void* stream) {
+    if (!X || !out) {
+        dinoseg_set_error("dinoseg_op_batch_sum_rows: null pointer");
+        return -1;
+    }
+    if (B < 1 || ntok < 1 || D < 1) {
+        dinoseg_set_error("dinoseg_op_batch_sum_rows: bad shape B=%d ntok=%d D=%d", B, ntok, D);
+        return -1;
+    }
+    return launch_batch_sum_rows(X, B, ntok, D, out, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_multi_pack(int32_t count, const float* const* src, void* const* dst, const int64_t* plane, const int32_t* rows,
+                                     const int32_t* cols, const int32_t* rows_pad, const int32_t* cols_pad, const int32_t* planes,
+                                     const int32_t* transposed, const int32_t* fmt, void* stream) {
+    if (count < 0 || (count > 0 && (!src || !dst || !plane || !rows || !cols || !rows_pad || !cols_pad || !planes || !transposed || !fmt))) {
+        dinoseg_set_error("dinoseg_op_multi_pack: bad argument");
+        return -1;
+    }
+    std::vector<PackJob> jobs(count);
+    for (int i = 0; i < count; ++i) {
+        const int64_t elems = (int64_t)rows_pad[i] * cols_pad[i];
+        if (rows[i] < 0 || cols[i] < 0 || rows_pad[i] < rows[i] || cols_pad[i] < cols[i] || (planes[i] != 1 && planes[i] != 2) ||
+            (transposed[i] != 0 && transposed[i] != 1) || (fmt[i] != FMT_BF16 && fmt[i] != FMT_FP16) || (planes[i] == 2 && plane[i] < elems)) {
+            dinoseg_set_error("dinoseg_op_multi_pack: bad job %d (rows=%d cols=%d rows_pad=%d cols_pad=%d planes=%d transposed=%d fmt=%d plane=%lld)",
+                              i, rows[i], cols[i], rows_pad[i], cols_pad[i], planes[i], transposed[i], fmt[i], (long long)plane[i]);
+            return -1;
+        }
+        if (elems > 0 && (!dst[i] || (!src[i] && (int64_t)rows[i] * cols[i] > 0))) {      // (an empty job may carry null pointers)
+            dinoseg_set_error("dinoseg_op_multi_pack: null pointer at job %d", i);
+            return -1;
+        }
+        PackJob& j = jobs[i];
+        j.src = src[i]; j.dst = reinterpret_cast<bf16_t*>(dst[i]); j.plane = plane[i];
+        j.rows = rows[i]; j.cols = cols[i]; j.rows_pad = rows_pad[i]; j.cols_pad = cols_pad[i];
+        j.planes = planes[i]; j.transposed = transposed[i]; j.fmt = fmt[i];
+    }
+    return launch_multi_pack(jobs.data(), count, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_multi_zero(int32_t count, float* const* p, const int64_t* n, void* stream) {
+    if (count < 0 || (count > 0 && (!p || !n))) {
+        dinoseg_set_error("dinoseg_op_multi_zero: bad argument");
+        return -1;
+    }
+    std::vector<long> nn(count);
+    for (int i = 0; i < count; ++i) {
+        if (!p[i] || n[i] < 0) {
+            dinoseg_set_error("dinoseg_op_multi_zero: null pointer or negative size at tensor %d", i);
+            return -1;
+        }
+        nn[i] = (long)n[i];
+    }
+    return launch_multi_zero(count, p, nn.data(), reinterpret_cast<hipStream_t>(stream));
+}

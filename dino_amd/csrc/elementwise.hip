@@ -32,29 +32,6 @@ int launch_pack_planes(const float* src, int rows, int cols, bf16_t* dst, long p
     return 0;
 }
 
-// transposed variant: dst[pl][c][r] = src[r][c]   (W^T operand planes for the input-gradient GEMMs)
-__global__ void pack_planes_t_kernel(const float* __restrict__ src, int rows, int cols, bf16_t* __restrict__ dst,
-                                     long plane, int rows_pad, int cols_pad, int planes) {
-    const long total = (long)rows_pad * cols_pad;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int c = (int)(i / rows_pad), r = (int)(i - (long)c * rows_pad);
-        const float v = (r < rows && c < cols) ? src[(long)r * cols + c] : 0.f;
-        const uint32_t hi = pack_bf16x2(v, 0.f);
-        dst[i] = (bf16_t)(hi & 0xFFFF);
-        if (planes == 2) dst[plane + i] = (bf16_t)(pack_bf16x2(v - bf16_lo_to_f32(hi), 0.f) & 0xFFFF);
-    }
-}
-
-int launch_pack_planes_t(const float* src, int rows, int cols, bf16_t* dst, long plane, int rows_pad, int cols_pad,
-                         int planes, hipStream_t s) {
-    const long total = (long)rows_pad * cols_pad;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(pack_planes_t_kernel, dim3(grid), dim3(256), 0, s, src, rows, cols, dst, plane, rows_pad, cols_pad, planes);
-    DSEG_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
 // Many packs in one launch: block b serves job t with boff[t] <= b < boff[t+1] (a wave-uniform scan of kernel arguments).
 constexpr int PACK_MAX = 40;
 struct MultiPackTable {
@@ -744,8 +721,9 @@ __global__ __launch_bounds__(256) void confusion_kernel(const int32_t* __restric
     for (int i = threadIdx.x; i < C * C; i += 256) h[i] = 0;
     __syncthreads();
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int g = (int)gt[i], pr = pred[i];
-        if (g >= 0 && g < C && pr >= 0 && pr < C) atomicAdd(&h[g * C + pr], 1u);
+        const long g = gt[i];          // (checked as int64: a label of 2^32 + 3 is out of range, not class 3)
+        const int pr = pred[i];
+        if (g >= 0 && g < C && pr >= 0 && pr < C) atomicAdd(&h[(int)g * C + pr], 1u);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < C * C; i += 256)

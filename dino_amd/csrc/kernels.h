@@ -330,16 +330,14 @@ int launch_multi_adam(int count, float* const* p, const float* const* g, float* 
 int launch_multi_zero(int count, float* const* p, const long* n, hipStream_t s);
 int launch_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float wd,
                 int decoupled, int step, float gscale, hipStream_t s);
-// several pack_planes / pack_planes_t jobs in ONE launch (a weight refresh is ~30 of them, each a few microseconds of work
-// behind a launch: the fine-tune step repacks every weight after every optimiser step)
+// several pack_planes jobs in ONE launch, plain or transposed (dst[pl][c][r] = src[r][c], planes [planes][cols_pad][rows_pad]: the W^T
+// operands of dgrad).  A weight refresh is ~30 of them, each a few microseconds of work behind a launch: the fine-tune step repacks
+// every weight after every optimiser step
 struct PackJob {
     const float* src; bf16_t* dst; long plane;
     int rows, cols, rows_pad, cols_pad, planes, transposed;
     int fmt = 0;                    // FMT_BF16 / FMT_FP16
 };
 int launch_multi_pack(const PackJob* jobs, int count, hipStream_t s);
-// fp32 [rows, cols] -> TRANSPOSED bf16 planes [planes][cols_pad][rows_pad] (zero padded): W^T operands for dgrad
-int launch_pack_planes_t(const float* src, int rows, int cols, bf16_t* dst, long plane, int rows_pad, int cols_pad,
-                         int planes, hipStream_t s);
 
 }  // namespace dseg

@@ -484,6 +484,36 @@ int dinoseg_op_nll_loss_grad(const float* logp, const int64_t* labels, const flo
 int dinoseg_op_pos_resample_bwd_hw(const float* dpos, int32_t g, int32_t D, int32_t oh, int32_t ow, float* dpe, float* scratch,
                                    void* stream);
 
+/* ---- the helper kernels on their own (tests).  16-bit operands are in the format of option "op_fmt"; every entry refuses null
+ * pointers and negative sizes on the host (-1 with a message) before anything is launched. ---- */
+
+/* Materialised softmax(q k^T) of one block (get_last_selfattention, vision_transformer.py:273-280 -> :85, :101): q (pre-scaled by
+ * 64^-0.5 * log2(e)) and k as [planes][B, heads, npad, 64] (lo plane at + qkv_plane elements; rows >= ntok are never read),
+ * out fp32 [B, heads, ntok, ntok]. */
+int dinoseg_op_attn_probs(const void* q, const void* k, int64_t qkv_plane, int32_t planes, int32_t B, int32_t heads, int32_t ntok,
+                          int32_t npad, float* out, void* stream);
+/* Attention.forward(x, cls_mask) for the CLS query of ONE frame (vision_transformer.py:80-107): the CLS row's logits times
+ * [0, mask], softmax over all ntok keys, @ V.  q, k, v: [planes][heads, npad, 64] (with one fp16 plane V is bf16, as the fused
+ * attention has it); mask fp32 [n_masks][ntok - 1]; ctx: planes [planes][n_masks][heads * 64] (lo at + ctx_plane elements); probs
+ * (nullable): fp32 [heads][n_masks][ntok].  More than 15 360 tokens exceed the score buffer (-1). */
+int dinoseg_op_cls_mask_attn(const void* q, const void* k, const void* v, int64_t qkv_plane, int32_t planes, int32_t heads, int32_t ntok,
+                             int32_t npad, const float* mask, int32_t n_masks, void* ctx, int64_t ctx_plane, float* probs, void* stream);
+/* X[b * ntok, :] = cls + pos[0, :] for b < B (prepare_tokens, vision_transformer.py:229-233); X fp32 [B * ntok, D]; other rows untouched */
+int dinoseg_op_cls_rows(float* X, const float* cls, const float* pos, int32_t B, int32_t ntok, int32_t D, void* stream);
+/* rows 1 .. n of X fp32 [n + 1, D] = row 0 (the CLS residual once per mask, vision_transformer.py:131-135); n == 0 does nothing */
+int dinoseg_op_broadcast_row0(float* X, int32_t D, int32_t n, void* stream);
+/* out[t, d] = sum over b < B of X[b, t, d] (the pos-embed gradient of a batch); X fp32 [B, ntok, D], out fp32 [ntok, D] */
+int dinoseg_op_batch_sum_rows(const float* X, int32_t B, int32_t ntok, int32_t D, float* out, void* stream);
+/* `count` weight packs in one launch per 40 jobs, what dinoseg_refresh_weights runs: job i turns src[i] fp32 [rows, cols] into planes
+ * [planes][rows_pad][cols_pad] at dst[i] (transposed[i] = 1: [planes][cols_pad][rows_pad], dst[c][r] = src[r][c]), zero padded, the lo
+ * plane at + plane[i] elements, fmt[i] 0 = bf16, 1 = fp16.  Host arrays of `count` entries, as dinoseg_adam_step_multi takes them.  A job
+ * with rows_pad * cols_pad == 0 is skipped. */
+int dinoseg_op_multi_pack(int32_t count, const float* const* src, void* const* dst, const int64_t* plane, const int32_t* rows,
+                          const int32_t* cols, const int32_t* rows_pad, const int32_t* cols_pad, const int32_t* planes,
+                          const int32_t* transposed, const int32_t* fmt, void* stream);
+/* p[i][0 .. n[i]) = 0 for `count` fp32 tensors in one launch per 64 (the gradient reset of a fine-tune step); n[i] == 0 is legal */
+int dinoseg_op_multi_zero(int32_t count, float* const* p, const int64_t* n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,56 @@ def test_backward_op_entries_refuse_bad_shapes_without_gpu():
     assert "bad shape g=28 D=384 oh=0 ow=60" in capi.last_error()
 
 
+def test_helper_op_entries_refuse_bad_arguments_without_gpu():
+    """The stand-alone entries of the helper kernels refuse null pointers and negative sizes on the host, with a message."""
+    lib = capi.lib()
+    fake = 256      # never dereferenced: every call below is refused on the host
+    assert lib.dinoseg_op_attn_probs(fake, None, 0, 1, 1, 2, 16, 64, fake, None) == -1
+    assert "dinoseg_op_attn_probs: null pointer" in capi.last_error()
+    assert lib.dinoseg_op_attn_probs(fake, fake, 0, 1, 1, 2, -16, 64, fake, None) == -1
+    assert "dinoseg_op_attn_probs: bad argument (planes=1 B=1 heads=2 ntok=-16 npad=64" in capi.last_error()
+    assert lib.dinoseg_op_attn_probs(fake, fake, 100, 2, 1, 2, 16, 64, fake, None) == -1      # a lo plane inside the hi plane
+    assert "qkv_plane=100" in capi.last_error()
+    assert lib.dinoseg_op_cls_mask_attn(fake, fake, fake, 0, 1, 2, 65, 128, None, 3, fake, 0, None, None) == -1
+    assert "dinoseg_op_cls_mask_attn: null pointer" in capi.last_error()
+    assert lib.dinoseg_op_cls_mask_attn(fake, fake, fake, 0, 1, 2, 65, 64, fake, 3, fake, 0, None, None) == -1      # npad < ntok
+    assert "dinoseg_op_cls_mask_attn: bad argument (planes=1 heads=2 ntok=65 npad=64 n_masks=3" in capi.last_error()
+    assert lib.dinoseg_op_cls_mask_attn(fake, fake, fake, 0, 1, 2, 15361, 15424, fake, 1, fake, 0, None, None) == -1
+    assert "cls_mask_attn: 15361 tokens exceed the LDS score buffer" in capi.last_error()
+    assert lib.dinoseg_op_cls_rows(fake, fake, None, 1, 2, 128, None) == -1
+    assert "dinoseg_op_cls_rows: null pointer" in capi.last_error()
+    assert lib.dinoseg_op_cls_rows(fake, fake, fake, -1, 2, 128, None) == -1
+    assert "dinoseg_op_cls_rows: bad shape B=-1 ntok=2 D=128" in capi.last_error()
+    assert lib.dinoseg_op_broadcast_row0(None, 128, 3, None) == -1
+    assert "dinoseg_op_broadcast_row0: null pointer" in capi.last_error()
+    assert lib.dinoseg_op_broadcast_row0(fake, 128, -3, None) == -1
+    assert "dinoseg_op_broadcast_row0: bad shape D=128 n=-3" in capi.last_error()
+    assert lib.dinoseg_op_broadcast_row0(fake, 128, 0, None) == 0            # no rows to fill: legal, nothing is launched
+    assert lib.dinoseg_op_batch_sum_rows(fake, 2, 3, 128, None, None) == -1
+    assert "dinoseg_op_batch_sum_rows: null pointer" in capi.last_error()
+    assert lib.dinoseg_op_batch_sum_rows(fake, 2, -3, 128, fake, None) == -1
+    assert "dinoseg_op_batch_sum_rows: bad shape B=2 ntok=-3 D=128" in capi.last_error()
+    one = lambda v: (ctypes.c_int32 * 1)(v)
+    ptr1, plane1 = (ctypes.c_void_p * 1)(fake), (ctypes.c_int64 * 1)(0)
+    assert lib.dinoseg_op_multi_pack(-1, None, None, None, None, None, None, None, None, None, None, None) == -1
+    assert "dinoseg_op_multi_pack: bad argument" in capi.last_error()
+    assert lib.dinoseg_op_multi_pack(1, ptr1, ptr1, plane1, one(-4), one(4), one(64), one(64), one(1), one(0), one(0), None) == -1
+    assert "dinoseg_op_multi_pack: bad job 0 (rows=-4 cols=4 rows_pad=64 cols_pad=64 planes=1" in capi.last_error()
+    assert lib.dinoseg_op_multi_pack(1, ptr1, (ctypes.c_void_p * 1)(None), plane1, one(4), one(4), one(64), one(64), one(1), one(0), one(0), None) == -1
+    assert "dinoseg_op_multi_pack: null pointer at job 0" in capi.last_error()
+    assert lib.dinoseg_op_multi_pack(0, None, None, None, None, None, None, None, None, None, None, None) == 0
+    assert lib.dinoseg_op_multi_pack(1, (ctypes.c_void_p * 1)(None), (ctypes.c_void_p * 1)(None), plane1, one(0), one(0), one(0), one(0), one(1),
+                                     one(0), one(0), None) == 0              # an empty job: legal, nothing is launched
+    assert lib.dinoseg_op_multi_zero(1, (ctypes.c_void_p * 1)(None), (ctypes.c_int64 * 1)(4), None) == -1
+    assert "dinoseg_op_multi_zero: null pointer or negative size at tensor 0" in capi.last_error()
+    assert lib.dinoseg_op_multi_zero(1, ptr1, (ctypes.c_int64 * 1)(-4), None) == -1
+    assert "dinoseg_op_multi_zero: null pointer or negative size at tensor 0" in capi.last_error()
+    assert lib.dinoseg_op_multi_zero(-1, None, None, None) == -1
+    assert "dinoseg_op_multi_zero: bad argument" in capi.last_error()
+    assert lib.dinoseg_op_multi_zero(1, ptr1, (ctypes.c_int64 * 1)(0), None) == 0           # an empty tensor: legal
+    assert lib.dinoseg_op_multi_zero(0, None, None, None) == 0
+
+
 def test_handle_lifecycle_and_errors_without_gpu():
     lib = capi.lib()
     h = ctypes.c_void_p()
