@@ -138,6 +138,9 @@ SIGNATURES = {
     "dinoseg_op_batch_sum_rows": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _vp]),
     "dinoseg_op_multi_pack": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dinoseg_op_multi_zero": (C.c_int, [_i32, _vp, _vp, _vp]),
+    # pixel-resolution output: bilinear upsample + argmax of the log-probs, alone and behind the forward
+    "dinoseg_op_upsample_argmax": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _vp]),
+    "dinoseg_forward_dense_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

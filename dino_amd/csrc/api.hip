@@ -584,9 +584,16 @@ static bool mlp_fuse_wanted(long rows) {
     return options().mlp_fused == 2 || (options().mlp_fused == 1 && rows >= options().mlp_fused_min_rows);
 }
 
+// dinoseg_forward_dense_hw: after the head, the log-probs of this (half-)batch upsampled to OH x OW on the same stream
+struct DenseRequest {
+    int OH, OW;
+    int32_t* labels;            // int32 [B, OH, OW] (nullable)
+    float* dense;               // fp32 [B, n_classes, OH, OW] (nullable)
+};
+
 static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t Hf, int32_t Wf, float* logp_out,
                         int32_t* argmax_out, int32_t tap_block, float* tap_out, float* attn_out, void* stream,
-                        const MaskRequest* mreq = nullptr, int slot = 0, int disp_B = 0) {
+                        const MaskRequest* mreq = nullptr, int slot = 0, int disp_B = 0, const DenseRequest* dreq = nullptr) {
     if (!h || !x || B <= 0) {
         dinoseg_set_error("dinoseg_forward: bad argument");
         return -1;
@@ -875,6 +882,9 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
                                    c.n_classes, logp_out ? logp_out : reinterpret_cast<float*>(ws + L.HB), argmax_out, s, SF,
                                    m.clf.pk.w, m.clf.pk.plane)));
     }
+    if (dreq)       // (timed with the head: its output side)
+        DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_upsample_argmax(logp_out ? logp_out : reinterpret_cast<float*>(ws + L.HB), B, Hf / c.patch,
+                                   Wf / c.patch, c.n_classes, dreq->OH, dreq->OW, dreq->labels, dreq->dense, s)));
     return 0;
 }
 
@@ -892,11 +902,11 @@ int ensure_aux_stream(dinoseg_handle* h) {
 // semantics and stays capturable).  Frames are independent (pl_torch_modules.py:253 flattens them); kernels of different
 // layers of the two halves overlap: one half's attention fills the CUs the other half's GEMM tail rounds and memory phases
 // leave idle (measured: +4.5 % frames/s at B = 32; four quarter-batches: -5 %).  The two workspaces together are the size of one.
-extern "C" int dinoseg_forward_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, float* logp_out,
-                                  int32_t* argmax_out, int32_t tap_block, float* tap_out, void* stream) {
+static int forward_split(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, float* logp_out,
+                         int32_t* argmax_out, int32_t tap_block, float* tap_out, void* stream, const DenseRequest* dreq) {
     const bool split = h && x && options().streams >= 2 && B >= options().split_min && B >= 2 && tap_block < 0 && !tap_out &&
                        frame_ok(H, W, patch_of(h)) && (x_kind == DINOSEG_INPUT_U8_HWC || x_kind == DINOSEG_INPUT_F32_CHW) && h->weights_ready;
-    if (!split) return forward_impl(h, x, x_kind, B, H, W, logp_out, argmax_out, tap_block, tap_out, nullptr, stream);
+    if (!split) return forward_impl(h, x, x_kind, B, H, W, logp_out, argmax_out, tap_block, tap_out, nullptr, stream, nullptr, 0, 0, dreq);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     DeviceGuard guard(h);
     DSEG_TRY(check_stream_device(h, s));
@@ -909,14 +919,48 @@ extern "C" int dinoseg_forward_hw(dinoseg_handle* h, const void* x, int32_t x_ki
     DSEG_CHECK_HIP(hipEventRecord(h->ev_fork, s));
     DSEG_CHECK_HIP(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
     h->in_split = true;
-    const int rc0 = forward_impl(h, x, x_kind, B0, H, W, logp_out, argmax_out, -1, nullptr, nullptr, stream, nullptr, 0, B);
+    DenseRequest d1 = {0, 0, nullptr, nullptr};          // the second half's slice of the pixel-resolution outputs
+    if (dreq) {
+        const size_t px = (size_t)B0 * dreq->OH * dreq->OW;
+        d1 = {dreq->OH, dreq->OW, dreq->labels ? dreq->labels + px : nullptr, dreq->dense ? dreq->dense + px * h->cfg.n_classes : nullptr};
+    }
+    const int rc0 = forward_impl(h, x, x_kind, B0, H, W, logp_out, argmax_out, -1, nullptr, nullptr, stream, nullptr, 0, B, dreq);
     const int rc1 = forward_impl(h, x1, x_kind, B1, H, W, logp_out ? logp_out + (size_t)B0 * n * h->cfg.n_classes : nullptr,
-                                 argmax_out ? argmax_out + (size_t)B0 * n : nullptr, -1, nullptr, nullptr, h->aux_stream, nullptr, 1, B);
+                                 argmax_out ? argmax_out + (size_t)B0 * n : nullptr, -1, nullptr, nullptr, h->aux_stream, nullptr, 1, B,
+                                 dreq ? &d1 : nullptr);
     h->in_split = false;
     // join even after an error: the caller's stream must not run ahead of work already queued on the internal one
     DSEG_CHECK_HIP(hipEventRecord(h->ev_join, h->aux_stream));
     DSEG_CHECK_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
     return rc0 ? rc0 : rc1;
+}
+
+extern "C" int dinoseg_forward_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, float* logp_out,
+                                  int32_t* argmax_out, int32_t tap_block, float* tap_out, void* stream) {
+    return forward_split(h, x, x_kind, B, H, W, logp_out, argmax_out, tap_block, tap_out, stream, nullptr);
+}
+
+// The forward, then the bilinear upsample + argmax of its log-probs (upsample.hip) behind the head on the same stream(s).  Everything the
+// upsample would refuse is refused here, before the forward enqueues anything.
+extern "C" int dinoseg_forward_dense_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t OH,
+                                        int32_t OW, float* logp_out, int32_t* argmax_out, int32_t* labels_out, float* dense_out,
+                                        void* stream) {
+    if (!h || !x || B <= 0) {
+        dinoseg_set_error("dinoseg_forward_dense_hw: bad argument (null handle or frames, or B=%d)", B);
+        return -1;
+    }
+    if (!labels_out && !dense_out) {
+        dinoseg_set_error("dinoseg_forward_dense_hw: null pointer (at least one of labels_out / dense_out is required)");
+        return -1;
+    }
+    if (!frame_ok(H, W, h->cfg.patch)) {
+        set_resolution_error(h->cfg.patch);
+        return -1;
+    }
+    const int hp = H / h->cfg.patch, wp = W / h->cfg.patch;
+    if (upsample_check_shape("dinoseg_forward_dense_hw", B, hp, wp, h->cfg.n_classes, OH, OW)) return -1;
+    const DenseRequest dreq = {OH, OW, labels_out, dense_out};
+    return forward_split(h, x, x_kind, B, H, W, logp_out, argmax_out, -1, nullptr, stream, &dreq);
 }
 
 extern "C" int dinoseg_forward(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* logp_out,
@@ -979,6 +1023,11 @@ extern "C" int dinoseg_op_resize_u8(const uint8_t* src, int32_t sh, int32_t sw, 
         return -1;
     }
     return launch_resize_u8(src, sh, sw, dst, dh, dw, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_upsample_argmax(const float* logp, int32_t B, int32_t hp, int32_t wp, int32_t C, int32_t OH, int32_t OW,
+                                          int32_t* labels_out, float* dense_out, void* stream) {
+    return launch_upsample_argmax(logp, B, hp, wp, C, OH, OW, labels_out, dense_out, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int dinoseg_op_confusion(const int32_t* pred, const int64_t* gt, int64_t n, int32_t n_classes, int64_t* cm, void* stream) {

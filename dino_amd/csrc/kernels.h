@@ -281,6 +281,11 @@ int launch_cls_mask_attn(const bf16_t* q, const bf16_t* k, const bf16_t* v, long
 int launch_broadcast_row0(float* X, int D, int n, hipStream_t s);
 int launch_resize_u8(const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw, hipStream_t s);
 int launch_confusion(const int32_t* pred, const int64_t* gt, long n, int C, int64_t* cm, hipStream_t s);
+// Bilinear upsample (F.interpolate, align_corners=False, exact integer coordinates) of the head's log-probs logp [B, hp*wp, C] to
+// OH x OW (>= hp x wp) fused with the first-maximum argmax (upsample.hip): labels int32 [B, OH, OW] and / or dense fp32 [B, C, OH, OW]
+// its shape check alone (-1 and a message starting with `who`): sizes positive, 1 <= C <= 256, OH >= hp, OW >= wp, the integer ranges
+int upsample_check_shape(const char* who, int B, int hp, int wp, int C, int OH, int OW);
+int launch_upsample_argmax(const float* logp, int B, int hp, int wp, int C, int OH, int OW, int32_t* labels, float* dense, hipStream_t s);
 
 // ---- fine-tune step (train.hip, attention_bwd.hip) ----
 struct AttnBwdParams {

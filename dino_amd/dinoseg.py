@@ -516,6 +516,62 @@ class DINOSeg(nn.Module):
                                   want_logp=want_logp, want_argmax=True)
         return logp, amax
 
+    # ---- pixel-resolution output (bilinear upsample + argmax of the log-probs, fused: csrc/upsample.hip) ----
+    def _out_size(self, size, default):
+        OH, OW = (int(v) for v in (default if size is None else size))
+        return OH, OW
+
+    def _run_dense(self, x: torch.Tensor, kind: int, B: int, H: int, W: int, OH: int, OW: int, want_dense: bool = False,
+                   want_logp: bool = False):
+        """The forward and the upsample of its log-probs to OH x OW in one library call: (labels int32 [B,OH,OW], dense fp32
+        [B,C,OH,OW] or None, low-res log-probs [B*n, C] or None).  Without ``want_logp`` the low-res log-probs stay in the
+        library's workspace; the [B,C,OH,OW] tensor exists only when asked for."""
+        self._sync_weights()
+        C_, dev = self.cfg.n_classes, x.device
+        n = (H // self.cfg.patch) * (W // self.cfg.patch)
+        labels = torch.empty((B, OH, OW), dtype=torch.int32, device=dev)
+        dense = torch.empty((B, C_, OH, OW), dtype=torch.float32, device=dev) if want_dense else None
+        logp = torch.empty((B * n, C_), dtype=torch.float32, device=dev) if want_logp else None
+        capi.check(capi.lib().dinoseg_forward_dense_hw(self._handle, x.data_ptr(), kind, B, H, W, OH, OW, capi.ptr(logp), None,
+                                                       labels.data_ptr(), capi.ptr(dense), self._stream()))
+        return labels, dense, logp
+
+    @torch.no_grad()
+    def segment(self, x: torch.Tensor, size=None, want_logp: bool = False):
+        """Pixel-resolution labels: uint8 [B,H,W,3] or fp32 [B,3,H,W] frames -> (labels int32 [B,OH,OW], dense or None).
+        The log-probabilities of the patch grid are interpolated bilinearly to ``size = (OH, OW)`` (default: the frames' own
+        (H, W); any OH >= H/patch, OW >= W/patch) and the argmax is taken per pixel -- ``F.interpolate(logp.view(B, hp, wp,
+        C).permute(0, 3, 1, 2), size=size, mode="bilinear", align_corners=False).argmax(1)`` with exact coordinates and the first
+        maximum -- in one launch behind the head, without the [B,C,OH,OW] transient.  ``want_logp=True`` also returns those
+        interpolated log-probabilities (``dense``, fp32 [B,C,OH,OW]: CRFs, multi-scale averaging).  Inference only."""
+        self._require_gpu()
+        x, kind, B, H, W = self._prep_batch(x)
+        OH, OW = self._out_size(size, (H, W))
+        labels, dense, _ = self._run_dense(x, kind, B, H, W, OH, OW, want_dense=want_logp)
+        return labels, dense
+
+    def predict_dense(self, img, size=None) -> np.ndarray:
+        """The pixel-resolution sibling of ``predict()``: the image (PIL.Image or HxWx3 uint8 array) is resized to r x r on the
+        device exactly as ``predict()`` does, the log-probabilities are upsampled to ``size`` (default: the IMAGE's own (rows,
+        cols)) and the per-pixel argmax comes back as an int64 map.  Eager launches (``predict()`` keeps its captured graph)."""
+        with torch.no_grad():
+            raw = np.asarray(img)
+            if raw.dtype != np.uint8 or not raw.flags.c_contiguous:
+                raw = np.ascontiguousarray(raw, dtype=np.uint8)
+            if raw.ndim != 3 or raw.shape[2] != 3:
+                raise ValueError(f"expected an HxWx3 image, got {raw.shape}")
+            r = self.resolution
+            self._require_gpu()
+            OH, OW = self._out_size(size, raw.shape[:2])
+            frames = torch.from_numpy(raw).unsqueeze(0).to(self.device)
+            if raw.shape[0] != r or raw.shape[1] != r:                           # Resize(r, r) of get_transforms, on the GPU
+                resized = torch.empty((1, r, r, 3), dtype=torch.uint8, device=self.device)
+                capi.check(capi.lib().dinoseg_op_resize_u8(frames.data_ptr(), raw.shape[0], raw.shape[1], resized.data_ptr(), r, r,
+                                                          self._stream()))
+                frames = resized
+            labels, _, _ = self._run_dense(frames, capi.INPUT_U8_HWC, 1, r, r, OH, OW)
+            return labels[0].cpu().numpy().astype(np.int64)
+
     def _predict_graph(self, r: int):
         """The single-frame forward of ``predict()`` as a captured HIP graph (one replay instead of ~150 launches: a 12-block
         forward is 1.33 ms of kernels that the eager launch path stretches to 1.50).  Static input / output buffers; captured once
@@ -643,6 +699,24 @@ class DINOSeg(nn.Module):
             capi.check(capi.lib().dinoseg_op_confusion(amax.data_ptr(), y.data_ptr(), y.numel(), self.cfg.n_classes,
                                                        cm.data_ptr(), self._stream()))
         return {"pred": amax, "gt": y, "probs": logp, "confusion": cm}
+
+    def validation_step_dense(self, batch, batch_idx=0):
+        """``validation_step`` scored per pixel: ``y`` is [B, OH, OW] pixel labels, the prediction is ``segment`` at y's size and
+        the confusion matrix counts pixels.  Labels outside [0, n_classes) -- 255 or -100 "void" -- are skipped by the confusion
+        kernel.  Same keys as ``validation_step`` ("pred": the pixel labels, "probs": the low-res log-probs), so
+        ``validation_epoch_end`` takes its outputs unchanged."""
+        x, y = batch
+        self._require_gpu()
+        with torch.no_grad():
+            xx, kind, B, H, W = self._prep_batch(x)
+            if y.dim() != 3 or y.shape[0] != B:
+                raise ValueError(f"expected pixel labels [B={B}, OH, OW], got {tuple(y.shape)}")
+            labels, _, logp = self._run_dense(xx, kind, B, H, W, int(y.shape[1]), int(y.shape[2]), want_logp=True)
+            y = y.to(self.device).reshape(-1).long().contiguous()
+            cm = torch.zeros((self.cfg.n_classes, self.cfg.n_classes), dtype=torch.int64, device=self.device)
+            capi.check(capi.lib().dinoseg_op_confusion(labels.data_ptr(), y.data_ptr(), y.numel(), self.cfg.n_classes,
+                                                       cm.data_ptr(), self._stream()))
+        return {"pred": labels, "gt": y, "probs": logp, "confusion": cm}
 
     def validation_epoch_end(self, outputs, prefix="val"):
         """Balanced accuracy, macro F1 and macro IoU over all patches of the split, from the summed confusion matrices

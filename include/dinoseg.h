@@ -154,6 +154,28 @@ int dinoseg_op_resize_u8(const uint8_t* src, int32_t sh, int32_t sw, uint8_t* ds
  * cm[gt][pred] += 1 over n patches; cm int64 [n_classes, n_classes] on device (zero it first); 1 <= n_classes <= 256. */
 int dinoseg_op_confusion(const int32_t* pred, const int64_t* gt, int64_t n, int32_t n_classes, int64_t* cm, void* stream);
 
+/* ---- pixel-resolution output (no reference counterpart: the reference stops at the patch grid and np.kron's the labels,
+ * pl_torch_modules.py:294-298).  What ViT segmenters do instead: interpolate the class scores to the pixel grid, then argmax. ----
+ *
+ * dinoseg_op_upsample_argmax: F.interpolate(logp.view(B, hp, wp, C).permute(0, 3, 1, 2), size=(OH, OW), mode="bilinear",
+ * align_corners=False) and its argmax over classes in one launch, without the [B, C, OH, OW] transient.
+ *   logp       : fp32 [B, hp*wp, C], the layout the head writes; 1 <= C <= 256
+ *   labels_out : int32 [B, OH, OW], the FIRST maximum over classes (nullable); dinoseg_op_confusion takes it as `pred`
+ *   dense_out  : fp32 [B, C, OH, OW], the interpolated log-probs in torch's layout (nullable); at least one output is required
+ * Coordinates are exact.  Per axis, with input size i, output size o, output index d:  num = max((2d+1) i - o, 0), den = 2 o in
+ * integers;  i0 = min(num / den, i-1), i1 = min(i0+1, i-1);  lambda = float(num % den) / float(den), 0 when num / den >= i-1;  the
+ * value is a + (b - a) lambda, along x and then along y, in fp32.  Any OH >= hp and OW >= wp (upsampling and identity); a smaller
+ * output, a null input, C outside 1..256 and non-positive sizes are refused on the host (-1) before anything is launched. */
+int dinoseg_op_upsample_argmax(const float* logp, int32_t B, int32_t hp, int32_t wp, int32_t C, int32_t OH, int32_t OW,
+                               int32_t* labels_out, float* dense_out, void* stream);
+/* dinoseg_forward_hw (without the debug tap) followed by dinoseg_op_upsample_argmax of its log-probs to OH x OW on the same stream.
+ * logp_out [B*n, n_classes] and argmax_out [B*n] are the optional low-res outputs of dinoseg_forward_hw; with logp_out == NULL the
+ * log-probs stay in the workspace (no new memory).  labels_out int32 [B, OH, OW], dense_out fp32 [B, n_classes, OH, OW]: at least
+ * one.  OH >= H/patch, OW >= W/patch.  Under the two-stream split each half-batch upsamples on its own stream into its slice of the
+ * outputs before the join: stream-ordered, capturable, no host synchronisation. */
+int dinoseg_forward_dense_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t OH, int32_t OW,
+                             float* logp_out, int32_t* argmax_out, int32_t* labels_out, float* dense_out, void* stream);
+
 /* ---- fine-tune step (replaces DINOSeg.training_step + autograd + optimizer.step, pl_torch_modules.py:258-268) ---- */
 
 /* Bind (or, with NULL, unbind) the fp32 gradient buffer of a parameter, same shape as the bound weight.  A parameter
