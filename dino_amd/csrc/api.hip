@@ -557,7 +557,9 @@ static int ensure_workspace(dinoseg_handle* h, int slot, const WsLayout& L, int 
         wB = -1;
     }
     if (wB != B || wH != Hf || wW != Wf) {
-        // key/value pad rows beyond ntok must be finite: zero Q/K/V once per layout (never written afterwards).  A layout change is a
+        // pad rows (include/dinoseg.h, dinoseg_op_attention): rows ntok..npad of q, k and v are read with the 64-row tiles they share with
+        // real rows and must hold FINITE values -- any finite values, zero is not required (a pad key gets probability 0, 0 x finite = 0;
+        // 0 x Inf is not).  Fresh memory may hold anything: zero Q/K/V once per layout (never written afterwards).  A layout change is a
         // new state generation: a forward captured under the OLD layout holds no memset node, and another layout's launches have since
         // written other things (fp32 residual rows ...) where its pad rows live -- the owner of the graph must capture again.
         DSEG_CHECK_HIP(hipMemsetAsync(ws + L.Q, 0, L.CTX - L.Q, s));

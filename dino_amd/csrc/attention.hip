@@ -264,6 +264,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p) {
 
         // ---- P fragments (B operand: k = key, col = query): registers 8*s2..8*s2+7 of sacc[kb] ----
         bf16x8 pf[PLANES][4];
+        float psr = 0.f;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -275,11 +276,16 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p) {
                 split2<FMT>(sacc[kb][s2 * 8 + 6], sacc[kb][s2 * 8 + 7], hi.w, lo.w);
                 pf[0][kb * 2 + s2] = __builtin_bit_cast(bf16x8, hi);
                 if (PLANES == 2) pf[PLANES - 1][kb * 2 + s2] = __builtin_bit_cast(bf16x8, lo);
+                if (PLANES == 1) psr += (bf16_lo_to_f32(hi.x) + bf16_hi_to_f32(hi.x)) + (bf16_lo_to_f32(hi.y) + bf16_hi_to_f32(hi.y)) +
+                                        (bf16_lo_to_f32(hi.z) + bf16_hi_to_f32(hi.z)) + (bf16_lo_to_f32(hi.w) + bf16_hi_to_f32(hi.w));
             }
 
-        // ---- row sums on the VALU: in-lane partial sums of the fp32 probabilities, the two lane halves are joined at the end
-        // (a ones-vector MFMA for the sums measured 5-7 % slower: the matrix pipe is the scarce unit)
-        l_run += ps;
+        // ---- row sums on the VALU: in-lane partial sums, the two lane halves are joined at the end
+        // (a ones-vector MFMA for the sums measured 5-7 % slower: the matrix pipe is the scarce unit).
+        // One plane: the sum of the probabilities AS ROUNDED to bf16 for P.V, so that their rounding (2^-9 each) cancels in O / l
+        // as it does in the zero-reference kernels; the fp32 sum there put 2^-9 sum(p |v|) on top of ctx's own rounding.
+        // Hi + lo planes carry the fp32 probabilities to 2^-16: the fp32 sum.
+        l_run += PLANES == 1 ? psr : ps;
 
         // ---- O^T[d][q] += V^T . P^T  (V^T fragments by transposing LDS reads) ----
         if (!(dbg & 4))

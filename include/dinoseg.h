@@ -419,8 +419,10 @@ int dinoseg_op_block_tail_fused(float* X, const void* ctx, const void* Wproj, co
                                 int32_t ntok, int32_t npad, int32_t heads, float qscale, int32_t D, int32_t F, void* stream);
 
 /* fused softmax(q k^T) v (vision_transformer.py:85,101,104); q must be pre-scaled by 64^-0.5 * log2(e).
- * q, k, v: [planes][B,heads,npad,64] (rows >= ntok zero); ctx: bf16 planes [planes][B*ntok][heads*64];
- * lse (optional): fp32 [B,heads,ntok], log2 domain. */
+ * q, k, v: [planes][B,heads,npad,64]; ctx: bf16 planes [planes][B*ntok][heads*64]; lse (optional): fp32 [B,heads,ntok], log2 domain.
+ * Pad rows: rows ntok..npad of q, k and v are read with the 64-row tiles they share with real rows and must hold FINITE values -- any
+ * finite values, zero is not required.  Every kernel masks them: a pad key gets probability 0 and 0 x finite = 0, so they never
+ * reach ctx or lse (bit for bit: tests/test_forward_containment_gpu.py); a NaN or Inf there may (0 x Inf). */
 int dinoseg_op_attention(const void* q, const void* k, const void* v, int64_t qkv_plane, void* ctx, int64_t ctx_plane,
                          float* lse, int32_t B, int32_t heads, int32_t ntok, int32_t npad, int32_t planes, void* stream);
 

@@ -19,7 +19,7 @@ import torch
 from dino_amd import DINOSeg, ViTConfig, capi, procedural_state_dict
 from dino_amd.weights import synthetic_frames
 from oracle import dinoseg_oracle as O
-from tests.gpu_util import pack
+from tests.gpu_util import NAN16, nan16, pack, untouched
 
 pytestmark = pytest.mark.gpu
 S = capi.stream_ptr
@@ -29,7 +29,6 @@ ULP32 = 2.0 ** -23
 DT = {"bf16": torch.bfloat16, "fp16": torch.float16}
 FMT = {"bf16": 0, "fp16": 1}
 ULP16 = {("bf16", 1): 2.0 ** -8, ("bf16", 2): 2.0 ** -15, ("fp16", 1): 2.0 ** -11, ("fp16", 2): 2.0 ** -22}
-NAN16 = 0x7FC1                          # a NaN in both 16-bit formats: guard pattern of the int16 buffers
 
 
 @contextlib.contextmanager
@@ -63,15 +62,6 @@ def report(kernel, case, what, err, e32, ulp):
     ratio = err / e32 if e32 > 0 else float("nan")
     print(f"helper_ops {kernel} [{case}] {what}: kernel {err:.3e} fp32 {e32:.3e} ratio {ratio:.2f} bar {bar:.3e}")
     return bar
-
-
-def nan16(shape):
-    return torch.full(shape, NAN16, dtype=torch.int16, device="cuda")
-
-
-def untouched(t):
-    """every element still carries the guard pattern (NaN for floats, NAN16 for int16 planes)"""
-    return bool(torch.isnan(t).all()) if t.is_floating_point() else bool((t == NAN16).all())
 
 
 # ------------------------------------------------------------------------------------------------ layernorm
