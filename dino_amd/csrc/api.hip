@@ -46,41 +46,80 @@ int device_cu_count() {
 
 static std::string block_prefix(int i) { return "dino.blocks." + std::to_string(i) + "."; }
 
-static void add_expected(dinoseg_handle* h) {
+// every nn.Linear-shaped parameter pair: its names, its logical [N, K] and the padded [n_pad, k_pad] of its operand planes, its record
+// in m and its gradient slots in g and, for a block linear, its block and gemm_rs option bit (LinearRec::rs_bit).  The ONE shape
+// table of the linears: the bind API's index, the refresh and the transposed copies of the fine-tune step all follow it
+struct LinSpec {
+    std::string wname, bname;
+    int N, K, n_pad, k_pad, planes, fmt;
+    LinearRec* rec;
+    int block, rs_bit;
+    LinearGrad* grad;
+    int t_n_pad;        // columns of the transposed copy W^T [k_pad][t_n_pad] (0: none)
+    bool pack;          // operand planes in wbuf (the classifier has them only for the wide head kernel)
+};
+
+static std::vector<LinSpec> linear_specs(dinoseg_handle* h, ModelRec& m) {
     const dinoseg_config& c = h->cfg;
-    const int64_t D = c.embed_dim, F = (int64_t)c.embed_dim * c.mlp_ratio, C = c.n_classes, p = c.patch;
-    auto& e = h->expected;
-    e["dino.cls_token"] = {1, 1, D};
-    e["dino.pos_embed"] = {1, (int64_t)c.pos_grid * c.pos_grid + 1, D};
-    e["dino.patch_embed.proj.weight"] = {D, 3, p, p};
-    e["dino.patch_embed.proj.bias"] = {D};
+    const int D = c.embed_dim, F = c.embed_dim * c.mlp_ratio, P = h->planes, FM = h->fmt, HP = head_planes(), SF = split_fmt(h), C = c.n_classes;
+    GradRec& g = h->grad;
+    std::vector<LinSpec> v;
+    // (fp16 mode: the patch embedding runs split like the head -- 0.13 % of the FLOPs, and its operands are raw pixels)
+    v.push_back({"dino.patch_embed.proj.weight", "dino.patch_embed.proj.bias", D, 3 * c.patch * c.patch, D, 3 * c.patch * c.patch, patch_planes(h), patch_fmt(h), &m.patch, -1, 0, &g.patch, 0, true});
     for (int i = 0; i < c.n_blocks; ++i) {
         const std::string b = block_prefix(i);
-        e[b + "norm1.weight"] = {D};
-        e[b + "norm1.bias"] = {D};
-        e[b + "attn.qkv.weight"] = {3 * D, D};
-        e[b + "attn.qkv.bias"] = {3 * D};
-        e[b + "attn.proj.weight"] = {D, D};
-        e[b + "attn.proj.bias"] = {D};
-        e[b + "norm2.weight"] = {D};
-        e[b + "norm2.bias"] = {D};
-        e[b + "mlp.fc1.weight"] = {F, D};
-        e[b + "mlp.fc1.bias"] = {F};
-        e[b + "mlp.fc2.weight"] = {D, F};
-        e[b + "mlp.fc2.bias"] = {D};
+        BlockRec& k = m.blocks[i];
+        BlockGrad& kg = g.blocks[i];
+        v.push_back({b + "attn.qkv.weight", b + "attn.qkv.bias", 3 * D, D, 3 * D, D, P, FM, &k.qkv, i, 2, &kg.qkv, 3 * D, true});
+        v.push_back({b + "attn.proj.weight", b + "attn.proj.bias", D, D, D, D, P, FM, &k.proj, i, 4, &kg.proj, D, true});
+        v.push_back({b + "mlp.fc1.weight", b + "mlp.fc1.bias", F, D, F, D, P, FM, &k.fc1, i, 1, &kg.fc1, F, true});
+        v.push_back({b + "mlp.fc2.weight", b + "mlp.fc2.bias", D, F, D, F, P, FM, &k.fc2, i, 4, &kg.fc2, D, true});
     }
-    e["dino.norm.weight"] = {D};
-    e["dino.norm.bias"] = {D};
-    if (c.head_kind == DINOSEG_HEAD_MLP) {
-        e["clf.layer_1.weight"] = {200, D};
-        e["clf.layer_1.bias"] = {200};
-        e["clf.layer_2.weight"] = {100, 200};
-        e["clf.layer_2.bias"] = {100};
-        e["clf.layer_3.weight"] = {C, 100};
-        e["clf.layer_3.bias"] = {C};
-    } else {
-        e["clf.layer_1.weight"] = {C, D};
-        e["clf.layer_1.bias"] = {C};
+    const bool mlp = c.head_kind == DINOSEG_HEAD_MLP;
+    if (mlp) {
+        v.push_back({"clf.layer_1.weight", "clf.layer_1.bias", HEAD_H1, D, HEAD_H1_PAD, D, HP, SF, &m.head[0], -1, 0, &g.head[0], HEAD_H1_PAD, true});
+        v.push_back({"clf.layer_2.weight", "clf.layer_2.bias", HEAD_H2, HEAD_H1, HEAD_H2_PAD, HEAD_H1_PAD, HP, SF, &m.head[1], -1, 0, &g.head[1], HEAD_H2_PAD, true});
+    }
+    // the classifier: launch_head_final reads it in fp32; more than 32 classes: also as hi+lo planes [round_up(C, 32)][ld] for the wide
+    // kernel (head_wide.hip).  Its transposed copy pads the classes to the width of the d logits planes instead
+    v.push_back({mlp ? "clf.layer_3.weight" : "clf.layer_1.weight", mlp ? "clf.layer_3.bias" : "clf.layer_1.bias", C, mlp ? HEAD_H2 : D,
+                 (C + 31) / 32 * 32, mlp ? HEAD_H2_PAD : D, HP, SF, &m.clf, -1, 0, &g.clf, dz_ld(C), C > HEAD_FINAL_MAX_C});
+    return v;
+}
+
+// the bind API's name index, built once: the expected shape of every key and the gradient slot it names
+static void index_params(dinoseg_handle* h) {
+    const dinoseg_config& c = h->cfg;
+    const int64_t D = c.embed_dim, p = c.patch;
+    GradRec& g = h->grad;
+    g.blocks.resize(c.n_blocks);
+    ModelRec unused;        // (the table also names each linear's record: no use for that here)
+    unused.blocks.resize(c.n_blocks);
+    auto add = [&](const std::string& name, std::vector<int64_t> shape, GradSlot& slot) {
+        slot.numel = 1;
+        for (int64_t d : shape) slot.numel *= (long)d;
+        slot.backbone = name.rfind("dino.", 0) == 0;
+        h->expected[name] = std::move(shape);
+        h->grad_index[name] = &slot;
+    };
+    add("dino.cls_token", {1, 1, D}, g.cls_token);
+    add("dino.pos_embed", {1, (int64_t)c.pos_grid * c.pos_grid + 1, D}, g.pos_embed);
+    add("dino.norm.weight", {D}, g.norm_w);
+    add("dino.norm.bias", {D}, g.norm_b);
+    for (int i = 0; i < c.n_blocks; ++i) {
+        const std::string b = block_prefix(i);
+        add(b + "norm1.weight", {D}, g.blocks[i].norm1_w);
+        add(b + "norm1.bias", {D}, g.blocks[i].norm1_b);
+        add(b + "norm2.weight", {D}, g.blocks[i].norm2_w);
+        add(b + "norm2.bias", {D}, g.blocks[i].norm2_b);
+    }
+    for (const LinSpec& sp : linear_specs(h, unused)) {
+        if (sp.grad == &g.patch) add(sp.wname, {D, 3, p, p}, sp.grad->dw);      // (the one weight that is bound as a convolution's)
+        else add(sp.wname, {sp.N, sp.K}, sp.grad->dw);
+        add(sp.bname, {sp.N}, sp.grad->db);
+        sp.grad->n_pad = sp.t_n_pad;
+        sp.grad->k_pad = sp.t_n_pad ? sp.k_pad : 0;
+        sp.grad->t_plane = (long)sp.grad->n_pad * sp.grad->k_pad;
     }
 }
 
@@ -103,7 +142,7 @@ extern "C" int dinoseg_create(const dinoseg_config* cfg, dinoseg_handle** out) {
     h->cfg = *cfg;
     h->planes = (cfg->precision == DINOSEG_BF16X3 || cfg->precision == DINOSEG_FP16X3) ? 2 : 1;
     h->fmt = (cfg->precision == DINOSEG_FP16 || cfg->precision == DINOSEG_FP16X3) ? FMT_FP16 : FMT_BF16;
-    add_expected(h);
+    index_params(h);
     *out = h;
     return 0;
 }
@@ -200,7 +239,7 @@ extern "C" int dinoseg_bind_weight(dinoseg_handle* h, const char* name, const vo
                 h->tws_B = h->tws_H = h->tws_W = h->tr_B = -1;
                 clear_packs(h);
                 h->bound.clear();
-                h->grads.clear();
+                for (auto& kv : h->grad_index) kv.second->ptr = nullptr;
             }
             h->device = attr.device;
         }
@@ -215,42 +254,6 @@ extern "C" int dinoseg_bind_weight(dinoseg_handle* h, const char* name, const vo
 }
 
 
-
-// names of every nn.Linear-shaped weight that feeds gemm.hip, with its logical [N, K] and padded [n_pad, k_pad], its record in m
-// and, for a block linear, its block and gemm_rs option bit (LinearRec::rs_bit)
-struct LinSpec {
-    std::string wname, bname;
-    int N, K, n_pad, k_pad, planes, fmt;
-    LinearRec* rec;
-    int block, rs_bit;
-};
-
-static std::vector<LinSpec> linear_specs(const dinoseg_handle* h, ModelRec& m) {
-    const dinoseg_config& c = h->cfg;
-    const int D = c.embed_dim, F = c.embed_dim * c.mlp_ratio, P = h->planes, FM = h->fmt;
-    std::vector<LinSpec> v;
-    // (fp16 mode: the patch embedding runs split like the head -- 0.13 % of the FLOPs, and its operands are raw pixels)
-    v.push_back({"dino.patch_embed.proj.weight", "dino.patch_embed.proj.bias", D, 3 * c.patch * c.patch, D, 3 * c.patch * c.patch, patch_planes(h), patch_fmt(h), &m.patch, -1, 0});
-    for (int i = 0; i < c.n_blocks; ++i) {
-        const std::string b = block_prefix(i);
-        BlockRec& k = m.blocks[i];
-        v.push_back({b + "attn.qkv.weight", b + "attn.qkv.bias", 3 * D, D, 3 * D, D, P, FM, &k.qkv, i, 2});
-        v.push_back({b + "attn.proj.weight", b + "attn.proj.bias", D, D, D, D, P, FM, &k.proj, i, 4});
-        v.push_back({b + "mlp.fc1.weight", b + "mlp.fc1.bias", F, D, F, D, P, FM, &k.fc1, i, 1});
-        v.push_back({b + "mlp.fc2.weight", b + "mlp.fc2.bias", D, F, D, F, P, FM, &k.fc2, i, 4});
-    }
-    if (c.head_kind == DINOSEG_HEAD_MLP) {
-        v.push_back({"clf.layer_1.weight", "clf.layer_1.bias", 200, D, 256, D, head_planes(), split_fmt(h), &m.head[0], -1, 0});
-        v.push_back({"clf.layer_2.weight", "clf.layer_2.bias", 100, 200, 128, 256, head_planes(), split_fmt(h), &m.head[1], -1, 0});
-    }
-    // more than 32 classes: the classifier as hi+lo planes [round_up(C, 32)][ld] for the wide kernel (head_wide.hip)
-    if (c.n_classes > HEAD_FINAL_MAX_C) {
-        const bool mlp = c.head_kind == DINOSEG_HEAD_MLP;
-        v.push_back({mlp ? "clf.layer_3.weight" : "clf.layer_1.weight", mlp ? "clf.layer_3.bias" : "clf.layer_1.bias", c.n_classes,
-                     mlp ? 100 : D, (c.n_classes + 31) / 32 * 32, mlp ? 128 : D, head_planes(), split_fmt(h), &m.clf, -1, 0});
-    }
-    return v;
-}
 
 // does gemm_rs.hip take this block linear (with the LayerNorm inside: ln)?  gemm_rs_supported on the shape and strides the forward
 // fills in; the addresses are placeholders it never reads
@@ -292,6 +295,7 @@ static int pack_copies(dinoseg_handle* h, const std::vector<LinSpec>& specs, hip
     std::vector<PackJob> jobs;
     for (const LinSpec& sp : specs) {
         const LinearRec& r = *sp.rec;
+        if (!sp.pack) continue;
         jobs.push_back({r.w, r.pk.w, r.pk.plane, sp.N, sp.K, sp.n_pad, sp.k_pad, sp.planes, 0, sp.fmt});
         if (r.pk.bias_pad) {
             DSEG_CHECK_HIP(hipMemsetAsync(r.pk.bias_pad, 0, (size_t)sp.n_pad * sizeof(float), s));
@@ -357,10 +361,6 @@ extern "C" int dinoseg_refresh_weights(dinoseg_handle* h, void* stream) {
         m.blocks[i].norm1_w = W(h, b + "norm1.weight"); m.blocks[i].norm1_b = W(h, b + "norm1.bias");
         m.blocks[i].norm2_w = W(h, b + "norm2.weight"); m.blocks[i].norm2_b = W(h, b + "norm2.bias");
     }
-    {   // (launch_head_final reads the classifier in fp32; the specs below add its planes for the wide kernel)
-        const std::string clf = h->cfg.head_kind == DINOSEG_HEAD_MLP ? "clf.layer_3" : "clf.layer_1";
-        m.clf.w = W(h, clf + ".weight"); m.clf.b = W(h, clf + ".bias");
-    }
     // ---- the plan: every copy of this refresh, in wbuf order -- what it is, how long it is, which record pointer it becomes.  Each
     // size and each "does this copy exist" is written here and nowhere else: the buffer's size and every offset follow from this list.
     struct Copy { std::string what; size_t bytes; void** slot; };
@@ -373,6 +373,7 @@ extern "C" int dinoseg_refresh_weights(dinoseg_handle* h, void* stream) {
         LinearRec& r = *sp.rec;
         r.w = W(h, sp.wname); r.b = W(h, sp.bname);
         r.N = sp.N; r.K = sp.K; r.planes = sp.planes; r.fmt = sp.fmt; r.rs_bit = sp.rs_bit;
+        if (!sp.pack) continue;
         r.pk.plane = (long)sp.n_pad * sp.k_pad; r.pk.n_pad = sp.n_pad; r.pk.k_pad = sp.k_pad;
         copy16(sp.wname, (size_t)sp.planes * sp.n_pad * sp.k_pad, r.pk.w);
         if (sp.n_pad != sp.N) copy32("bias_pad " + sp.bname, sp.n_pad, r.pk.bias_pad);
@@ -514,9 +515,9 @@ static WsLayout make_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
     }
     L.feat_plane = (long)L.Mp * D;
     L.FEAT = take((size_t)HP * L.feat_plane * 2);
-    L.h1_plane = (long)L.Mp * 256;
+    L.h1_plane = (long)L.Mp * HEAD_H1_PAD;
     L.H1 = take((size_t)HP * L.h1_plane * 2);
-    L.h2_plane = (long)L.Mp * 128;
+    L.h2_plane = (long)L.Mp * HEAD_H2_PAD;
     L.H2 = take((size_t)HP * L.h2_plane * 2);
     L.total = off;
     return L;
@@ -866,17 +867,17 @@ static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_
             GemmParams g = linear_gemm(m.head[0]);
             g.A = FEAT; g.a_plane = L.feat_plane; g.lda = D;
             g.M = L.Mp; g.epi = EPI_RELU;
-            g.out_bf16 = H1; g.out_plane = L.h1_plane; g.ldo = 256;
+            g.out_bf16 = H1; g.out_plane = L.h1_plane; g.ldo = HEAD_H1_PAD;
             DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_gemm(g, s)));
         }
         {
             GemmParams g = linear_gemm(m.head[1]);
-            g.A = H1; g.a_plane = L.h1_plane; g.lda = 256;
+            g.A = H1; g.a_plane = L.h1_plane; g.lda = HEAD_H1_PAD;
             g.M = L.Mp; g.epi = EPI_RELU;
-            g.out_bf16 = H2; g.out_plane = L.h2_plane; g.ldo = 128;
+            g.out_bf16 = H2; g.out_plane = L.h2_plane; g.ldo = HEAD_H2_PAD;
             DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_gemm(g, s)));
         }
-        DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_head_final(H2, L.h2_plane, 128, L.Mp, 100, m.clf.w, m.clf.b,
+        DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_head_final(H2, L.h2_plane, HEAD_H2_PAD, L.Mp, HEAD_H2, m.clf.w, m.clf.b,
                                    c.n_classes, logp_out ? logp_out : reinterpret_cast<float*>(ws + L.HB), argmax_out, s, SF,
                                    m.clf.pk.w, m.clf.pk.plane)));
     } else {

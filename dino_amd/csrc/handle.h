@@ -60,13 +60,41 @@ struct ModelRec {
                                  // pk = its hi+lo planes for the wide head kernel (n_classes > 32), empty below that
 };
 
+// The training half, in ModelRec's shape: where dinoseg_bind_grad put each parameter's gradient buffer (null = frozen), and the
+// transposed copies of the linears' weights the input-gradient GEMMs multiply by.  Not part of ModelRec: a refresh resets that
+// record, the gradient bindings outlive it.  Sized by dinoseg_create and never resized (grad_index points into it).
+struct GradSlot {
+    float* ptr = nullptr;        // the caller's fp32 buffer
+    long numel = 0;
+    bool backbone = false;       // a dino.* parameter (as opposed to the head's)
+};
+struct LinearGrad {
+    GradSlot dw, db;
+    bf16_t* tw = nullptr;        // W^T planes [k_pad][n_pad] in twbuf, packed at the top of every backward
+    long t_plane = 0;
+    int n_pad = 0, k_pad = 0;    // (0: no transposed copy -- the patch embedding has no input gradient)
+};
+struct BlockGrad {
+    GradSlot norm1_w, norm1_b, norm2_w, norm2_b;
+    LinearGrad qkv, proj, fc1, fc2;
+};
+struct GradRec {
+    LinearGrad patch;
+    GradSlot cls_token, pos_embed, norm_w, norm_b;
+    std::vector<BlockGrad> blocks;
+    LinearGrad head[2], clf;
+};
+
 struct dinoseg_handle {
     dinoseg_config cfg;
     int planes;
     int fmt = 0;                // operand format: FMT_BF16 / FMT_FP16 (DINOSEG_FP16: planes = 1, DINOSEG_FP16X3: planes = 2, both fmt = FMT_FP16)
     int device = -1;            // ordinal of the GPU that owns the bound tensors (set by the first dinoseg_bind_weight)
+    // the bind API's name index: what each key must look like, what was bound to it, which gradient slot it names.  Readers of the
+    // parameters work from the typed records (model, grad), never from these
     std::map<std::string, BoundTensor> bound;
     std::map<std::string, std::vector<int64_t>> expected;
+    std::map<std::string, GradSlot*> grad_index;
     // packed weights (library-owned)
     char* wbuf = nullptr;
     size_t wbuf_bytes = 0;
@@ -100,8 +128,8 @@ struct dinoseg_handle {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool in_split = false;                 // a split forward is being queued (both halves' launches share the chip)
     // fine-tune step state (train_api.hip)
-    std::map<std::string, float*> grads;   // bound gradient buffers (absent / null = frozen tensor)
-    char* tws = nullptr;                   // training workspace: saved activations + backward scratch
+    GradRec grad;                          // bound gradient buffers and the transposed weights
+    char* tws = nullptr;                  // training workspace: saved activations + backward scratch
     size_t tws_bytes = 0;
     int tws_B = -1, tws_H = -1, tws_W = -1;
     int tr_B = -1, tr_H = -1, tr_W = -1;   // batch / frame size of the saved forward dinoseg_backward will differentiate
@@ -180,6 +208,10 @@ static inline void prof_end(dinoseg_handle* h, int idx, hipStream_t s) {
 
 
 static inline int head_planes() { return 2; }
+// the MLP head: embed_dim -> 200 -> 100 -> classes; the hidden activations are stored 256 / 128 wide, zero beyond their columns
+constexpr int HEAD_H1 = 200, HEAD_H1_PAD = 256, HEAD_H2 = 100, HEAD_H2_PAD = 128;
+// width of the d logits planes DZ: the classes rounded up to the 64-column k-step of the head's dgrad GEMM (launch_gemm_small: K % 64)
+static inline int dz_ld(int C) { return (C + 63) / 64 * 64; }
 // planes of the patch-embedding GEMM: the mode's own, except that the fp16 mode runs it split like the head (raw pixel operands,
 // 0.13 % of the FLOPs)
 static inline int patch_planes(const dinoseg_handle* h) { return (h->fmt == FMT_FP16 && h->fp16_patch_planes_snap == 2) ? 2 : h->planes; }

@@ -24,9 +24,6 @@ inline int splitk_budget() {
     return v < 1 ? 1 : v > SPLITK_TILES ? SPLITK_TILES : v;
 }
 
-// width of the d logits planes DZ: the classes rounded up to the 64-column k-step of the head's dgrad GEMM (launch_gemm_small: K % 64)
-static int dz_ld(int C) { return (C + 63) / 64 * 64; }
-
 struct TrainLayout {
     int n, ntok, npad, M, Mp, Mpad, Mppad, Cmax;
     // per block (offsets are for block 0; block l adds l * blk_stride)
@@ -81,9 +78,9 @@ TrainLayout make_train_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
     L.PATCH = take((size_t)P * L.patch_plane * 2);
     L.feat_plane = (long)L.Mp * D;
     L.FEAT = take((size_t)HP * L.feat_plane * 2);
-    L.h1_plane = (long)L.Mp * 256;
+    L.h1_plane = (long)L.Mp * HEAD_H1_PAD;
     L.H1 = take((size_t)HP * L.h1_plane * 2);
-    L.h2_plane = (long)L.Mp * 128;
+    L.h2_plane = (long)L.Mp * HEAD_H2_PAD;
     L.H2 = take((size_t)HP * L.h2_plane * 2);
     L.LOGP = take((size_t)L.Mp * c.n_classes * 4);
     L.dz_plane = (long)L.Mp * dz_ld(c.n_classes);
@@ -95,7 +92,7 @@ TrainLayout make_train_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
     L.g_plane = (long)L.M * L.Cmax;
     L.G = take((size_t)2 * L.g_plane * 2);
     {   // d ctx planes [M, D]; also hosts the head's d h1 planes [Mp, 256]
-        const size_t e = (size_t)L.a_plane > (size_t)L.Mp * 256 ? (size_t)L.a_plane : (size_t)L.Mp * 256;
+        const size_t e = (size_t)L.a_plane > (size_t)L.h1_plane ? (size_t)L.a_plane : (size_t)L.h1_plane;
         L.dCTX = take(2 * e * 2);
     }
     {   // a transposed plane holds the widest operand of a weight gradient: a block linear (Cmax rows), or the patch matrix, whose
@@ -121,35 +118,26 @@ TrainLayout make_train_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
     return L;
 }
 
-struct TLin {
-    std::string wname;
-    int N, K, n_pad, k_pad, planes;     // W is [N][K]; W^T planes are [k_pad][n_pad]
+// typed pointers into the training workspace: the saved activations the forward writes and the backward reads
+struct BlockWs {
+    float *Xin, *Xmid, *LSE;
+    bf16_t *A1, *Q, *K, *V, *CTX, *A2, *HPRE, *HB;
 };
-
-std::vector<TLin> transposed_specs(const dinoseg_handle* h) {
-    const dinoseg_config& c = h->cfg;
-    const int D = c.embed_dim, F = D * c.mlp_ratio, P = h->planes, HP = head_planes(), C = c.n_classes;
-    std::vector<TLin> v;
-    for (int i = 0; i < c.n_blocks; ++i) {
-        const std::string b = "dino.blocks." + std::to_string(i) + ".";
-        v.push_back({b + "attn.qkv.weight", 3 * D, D, 3 * D, D, P});
-        v.push_back({b + "attn.proj.weight", D, D, D, D, P});
-        v.push_back({b + "mlp.fc1.weight", F, D, F, D, P});
-        v.push_back({b + "mlp.fc2.weight", D, F, D, F, P});
+struct HeadWs {
+    float *Xfin, *LOGP;
+    bf16_t *FEAT, *H1, *H2;
+};
+struct TrainWs {
+    char* base;
+    const TrainLayout& L;
+    float* f32(size_t o) const { return reinterpret_cast<float*>(base + o); }
+    bf16_t* b16(size_t o) const { return reinterpret_cast<bf16_t*>(base + o); }
+    BlockWs block(int l) const {
+        const size_t o = l * L.blk_stride;
+        return {f32(L.Xin + o), f32(L.Xmid + o), f32(L.LSE + o), b16(L.A1 + o), b16(L.Q + o), b16(L.K + o), b16(L.V + o),
+                b16(L.CTX + o), b16(L.A2 + o), b16(L.HPRE + o), b16(L.HB + o)};
     }
-    if (c.head_kind == DINOSEG_HEAD_MLP) {
-        v.push_back({"clf.layer_1.weight", 200, D, 256, D, HP});
-        v.push_back({"clf.layer_2.weight", 100, 200, 128, 256, HP});
-        v.push_back({"clf.layer_3.weight", C, 100, dz_ld(C), 128, HP});
-    } else {
-        v.push_back({"clf.layer_1.weight", C, D, dz_ld(C), D, HP});
-    }
-    return v;
-}
-
-struct TW {
-    bf16_t* w;
-    long plane;
+    HeadWs head() const { return {f32(L.Xfin), f32(L.LOGP), b16(L.FEAT), b16(L.H1), b16(L.H2)}; }
 };
 
 // batch slices of the narrow-layer weight gradient below: as many as the split-K budget allows, at least two k-steps each
@@ -201,12 +189,12 @@ extern "C" int dinoseg_bind_grad(dinoseg_handle* h, const char* name, float* dev
         dinoseg_set_error("dinoseg_bind_grad: null argument");
         return -1;
     }
-    if (!h->expected.count(name)) {
+    auto it = h->grad_index.find(name);
+    if (it == h->grad_index.end()) {
         dinoseg_set_error("dinoseg_bind_grad: unexpected key '%s'", name);
         return -1;
     }
-    if (dev_ptr) h->grads[name] = dev_ptr;
-    else h->grads.erase(name);
+    it->second->ptr = dev_ptr;
     return 0;
 }
 
@@ -408,6 +396,7 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
         h->tws_B = -1;
     }
     char* ws = h->tws;
+    const TrainWs w = {ws, L};
     if (h->tws_B != B || h->tws_H != Hf || h->tws_W != Wf) {
         for (int l = 0; l < NB; ++l)   // Q/K/V pad rows must be zero (never written afterwards)
             DSEG_CHECK_HIP(hipMemsetAsync(ws + L.Q + l * L.blk_stride, 0, L.LSE - L.Q, s));
@@ -416,15 +405,13 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
         h->tws_H = Hf;
         h->tws_W = Wf;
     }
-    auto F32 = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
-    auto B16 = [&](size_t o) { return reinterpret_cast<bf16_t*>(ws + o); };
 
     // =============================================================== forward (activations kept)
     float mean255[3], inv255[3];
     norm_consts(mean255, inv255);
-    bf16_t* PATCH = B16(L.PATCH);
+    bf16_t* PATCH = w.b16(L.PATCH);
     DSEG_TRY(launch_patch_gather(x, x_kind, B, Hf, Wf, mean255, inv255, PATCH, L.patch_plane, P, s, FMT_BF16, c.patch));
-    float* X0 = NB > 0 ? F32(L.Xin) : F32(L.Xfin);
+    float* X0 = NB > 0 ? w.f32(L.Xin) : w.f32(L.Xfin);
     {
         GemmParams g = linear_gemm(m.patch);
         g.A = PATCH; g.a_plane = L.patch_plane; g.lda = 3 * c.patch * c.patch;
@@ -438,12 +425,8 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
 
     for (int l = 0; l < NB; ++l) {
         const BlockRec& blk = m.blocks[l];
-        const size_t o = l * L.blk_stride;
-        float* Xin = F32(L.Xin + o);
-        float* Xmid = F32(L.Xmid + o);
-        float* Xout = l + 1 < NB ? F32(L.Xin + o + L.blk_stride) : F32(L.Xfin);
-        bf16_t *A1 = B16(L.A1 + o), *Q = B16(L.Q + o), *Kb = B16(L.K + o), *V = B16(L.V + o), *CTX = B16(L.CTX + o);
-        bf16_t *A2 = B16(L.A2 + o), *HPRE = B16(L.HPRE + o), *HB = B16(L.HB + o);
+        const auto [Xin, Xmid, LSE, A1, Q, Kb, V, CTX, A2, HPRE, HB] = w.block(l);
+        float* Xout = l + 1 < NB ? w.block(l + 1).Xin : w.f32(L.Xfin);
         const bool fuse_ln = options().gemm_ln != 0 && L.qkv_plane < (1L << 31) && L.f_plane < (1L << 31);
         if (fuse_ln && blk.qkv.slab) {
             // LN1 + qkv in one launch; the normalised planes the weight gradient needs are a by-product (a_out)
@@ -470,7 +453,7 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
         {
             AttnParams a = {};
             a.q = Q; a.k = Kb; a.v = V; a.qkv_plane = L.qkv_plane; a.ctx = CTX; a.ctx_plane = L.a_plane;
-            a.lse = F32(L.LSE + o);
+            a.lse = LSE;
             a.B = B; a.heads = H; a.ntok = L.ntok; a.npad = L.npad; a.planes = P;
             DSEG_TRY(launch_attention(a, s));
         }
@@ -509,9 +492,7 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
             DSEG_TRY(launch_gemm(g, s));
         }
     }
-    float* Xfin = F32(L.Xfin);
-    bf16_t *FEAT = B16(L.FEAT), *H1 = B16(L.H1), *H2 = B16(L.H2);
-    float* LOGP = F32(L.LOGP);
+    const auto [Xfin, LOGP, FEAT, H1, H2] = w.head();
     DSEG_TRY(launch_layernorm(Xfin, m.norm_w, m.norm_b, c.ln_eps, L.M, D, FEAT, L.feat_plane, HP,
                               nullptr, 1, L.ntok, s));
     if (mlp_head) {
@@ -519,17 +500,17 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
             GemmParams g = linear_gemm(m.head[0]);
             g.A = FEAT; g.a_plane = L.feat_plane; g.lda = D;
             g.M = L.Mp; g.epi = EPI_RELU;
-            g.out_bf16 = H1; g.out_plane = L.h1_plane; g.ldo = 256;
+            g.out_bf16 = H1; g.out_plane = L.h1_plane; g.ldo = HEAD_H1_PAD;
             DSEG_TRY(launch_gemm(g, s));
         }
         {
             GemmParams g = linear_gemm(m.head[1]);
-            g.A = H1; g.a_plane = L.h1_plane; g.lda = 256;
+            g.A = H1; g.a_plane = L.h1_plane; g.lda = HEAD_H1_PAD;
             g.M = L.Mp; g.epi = EPI_RELU;
-            g.out_bf16 = H2; g.out_plane = L.h2_plane; g.ldo = 128;
+            g.out_bf16 = H2; g.out_plane = L.h2_plane; g.ldo = HEAD_H2_PAD;
             DSEG_TRY(launch_gemm(g, s));
         }
-        DSEG_TRY(launch_head_final(H2, L.h2_plane, 128, L.Mp, 100, m.clf.w, m.clf.b, C, LOGP,
+        DSEG_TRY(launch_head_final(H2, L.h2_plane, HEAD_H2_PAD, L.Mp, HEAD_H2, m.clf.w, m.clf.b, C, LOGP,
                                    nullptr, s, FMT_BF16, m.clf.pk.w, m.clf.pk.plane));
     } else {
         DSEG_TRY(launch_head_final(FEAT, L.feat_plane, D, L.Mp, D, m.clf.w, m.clf.b, C, LOGP,
@@ -565,16 +546,23 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
     const int NB = c.n_blocks;
     const bool mlp_head = c.head_kind == DINOSEG_HEAD_MLP;
     const TrainLayout L = make_train_layout(h, B, h->tr_H, h->tr_W);
-    char* ws = h->tws;
-    auto F32 = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
-    auto B16 = [&](size_t o) { return reinterpret_cast<bf16_t*>(ws + o); };
+    const TrainWs w = {h->tws, L};
+    const ModelRec& m = h->model;
+    GradRec& gr = h->grad;
 
     // ---- transposed packed weights for dX = dY . W  (weights change every optimiser step: repack)
-    const std::vector<TLin> tspecs = transposed_specs(h);
-    std::map<std::string, TW> tw;
     {
+        std::vector<std::pair<const LinearRec*, LinearGrad*>> lins;      // every linear with an input gradient, in twbuf order
+        for (int l = 0; l < NB; ++l) {
+            const BlockRec& blk = m.blocks[l];
+            BlockGrad& bg = gr.blocks[l];
+            lins.insert(lins.end(), {{&blk.qkv, &bg.qkv}, {&blk.proj, &bg.proj}, {&blk.fc1, &bg.fc1}, {&blk.fc2, &bg.fc2}});
+        }
+        if (mlp_head) lins.insert(lins.end(), {{&m.head[0], &gr.head[0]}, {&m.head[1], &gr.head[1]}});
+        lins.push_back({&m.clf, &gr.clf});
+        auto bytes = [](const LinearRec& r, const LinearGrad& g) { return align_up((size_t)r.planes * g.t_plane * 2, 256); };
         size_t total = 0;
-        for (const TLin& t : tspecs) total += align_up((size_t)t.planes * t.k_pad * t.n_pad * 2, 256);
+        for (auto& rg : lins) total += bytes(*rg.first, *rg.second);
         if (total > h->twbuf_bytes) {
             if (h->twbuf) {
                 DSEG_CHECK_HIP(hipStreamSynchronize(s));
@@ -586,35 +574,27 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
         }
         size_t off = 0;
         std::vector<dseg::PackJob> jobs;
-        for (const TLin& t : tspecs) {
-            TW e;
-            e.w = reinterpret_cast<bf16_t*>(h->twbuf + off);
-            e.plane = (long)t.k_pad * t.n_pad;
-            off += align_up((size_t)t.planes * t.k_pad * t.n_pad * 2, 256);
+        for (auto& rg : lins) {
+            const LinearRec& r = *rg.first;
+            LinearGrad& g = *rg.second;
+            g.tw = reinterpret_cast<bf16_t*>(h->twbuf + off);
+            off += bytes(r, g);
             // W [N][K] fp32 -> W^T planes [k_pad][n_pad]: "rows" of the source are N, transposed destination rows are K
-            jobs.push_back({W(h, t.wname), e.w, e.plane, t.N, t.K, t.n_pad, t.k_pad, t.planes, 1});
-            tw[t.wname] = e;
+            jobs.push_back({r.w, g.tw, g.t_plane, r.N, r.K, g.n_pad, g.k_pad, r.planes, 1});
         }
         DSEG_TRY(launch_multi_pack(jobs.data(), (int)jobs.size(), s));
     }
 
-    auto grad = [&](const std::string& name) -> float* {
-        auto it = h->grads.find(name);
-        return it == h->grads.end() ? nullptr : it->second;
-    };
-    auto numel = [&](const std::string& name) {
-        size_t n = 1;
-        for (int64_t d : h->expected.at(name)) n *= (size_t)d;
-        return n;
-    };
     bool backbone = false;
     {
         std::vector<float*> zp;
         std::vector<long> zn;
-        for (auto& kv : h->grads) {
-            zp.push_back(kv.second);
-            zn.push_back((long)numel(kv.first));
-            if (kv.first.rfind("dino.", 0) == 0) backbone = true;
+        for (auto& kv : h->grad_index) {
+            const GradSlot& g = *kv.second;
+            if (!g.ptr) continue;
+            zp.push_back(g.ptr);
+            zn.push_back(g.numel);
+            backbone |= g.backbone;
         }
         if (!zp.empty()) DSEG_TRY(launch_multi_zero((int)zp.size(), zp.data(), zn.data(), s));      // one launch instead of ~50 memset nodes
     }
@@ -631,14 +611,13 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
             dinoseg_set_error("dinoseg_backward: option deterministic allows one backward at a time per process (another one is being queued)");
             return -1;
         }
-        det_scratch() = DetScratch{F32(L.DET), DET_FLOATS, {F32(L.DET) + DET_FLOATS, F32(L.DET) + DET_FLOATS + DET_TN_FLOATS}, DET_TN_FLOATS};
+        float* det = w.f32(L.DET);
+        det_scratch() = DetScratch{det, DET_FLOATS, {det + DET_FLOATS, det + DET_FLOATS + DET_TN_FLOATS}, DET_TN_FLOATS};
         det_guard.mine = true;
     }
     const hipStream_t main_stream = s;
-    float* Xfin = F32(L.Xfin);
-    bf16_t *FEAT = B16(L.FEAT), *H1 = B16(L.H1), *H2 = B16(L.H2), *DZ = B16(L.DZ);
-    float* LOGP = F32(L.LOGP);
-    bf16_t* PATCH = B16(L.PATCH);
+    const auto [Xfin, LOGP, FEAT, H1, H2] = w.head();
+    bf16_t *DZ = w.b16(L.DZ), *PATCH = w.b16(L.PATCH);
 
     // =============================================================== backward
     // stage events: a side stream can start reducing a gradient bucket while the rest of backward still runs
@@ -661,7 +640,7 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
     // event the caller's stream waits on (side_wait) before it overwrites an operand the side kernels read, and before every
     // gradient-stage event.  Fork and join are events only: the call stays stream-ordered for the caller and capturable.
     // (deterministic mode: the side stream's only partial sums are gemm_tn's bias sums: they have their own part of the scratch area)
-    const bool side = options().train_streams >= 2 && D % 128 == 0 && F % 128 == 0;   // (narrow layers go through T1 / T2: one stream)
+    const bool side = options().train_streams >= 2;
     hipStream_t ws_ = s;
     size_t bw_i = 0;
     auto bw_event = [&](hipEvent_t* out) -> int {
@@ -697,14 +676,14 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
         done = nullptr;
         return 0;
     };
-    float* sink = F32(L.SINK);
-    bf16_t *T1 = B16(L.T1), *T2 = B16(L.T2);
+    float* sink = w.f32(L.SINK);
+    bf16_t *T1 = w.b16(L.T1), *T2 = w.b16(L.T2);
 
     // dX[M_, Kin] = dY[M_, Ncols] . W   with optional activation-derivative epilogue
-    auto dgrad = [&](const bf16_t* dY, long dy_plane, int ld, int M_, int n_contract, const TW& wt, int k_out, int planes, int epi,
+    auto dgrad = [&](const bf16_t* dY, long dy_plane, int ld, int M_, int n_contract, const LinearGrad& wt, int k_out, int planes, int epi,
                      float* out_f32, bf16_t* out_bf16, long out_plane, const bf16_t* aux, long aux_plane) -> int {
         GemmParams g = {};
-        g.A = dY; g.a_plane = dy_plane; g.lda = ld; g.W = wt.w; g.w_plane = wt.plane;
+        g.A = dY; g.a_plane = dy_plane; g.lda = ld; g.W = wt.tw; g.w_plane = wt.t_plane;
         g.M = M_; g.N = k_out; g.K = n_contract; g.planes = planes; g.epi = epi;
         g.out_f32 = out_f32; g.ldo_f32 = k_out;
         g.out_bf16 = out_bf16; g.out_plane = out_plane; g.ldo = k_out; g.aux_in = aux; g.aux_plane = aux_plane;
@@ -715,171 +694,131 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
                      float* dW) -> int {
         if (!dW) return 0;
         return wgrad_nt(Tdy, Tx, tplane, m_pad, n_rows, k_pad128, k_cols, planes, wgrad_nt_slices(n_rows, k_pad128, m_pad),
-                        F32(L.SPLITK), dW, s);
+                        w.f32(L.SPLITK), dW, s);
     };
     auto pad128 = [](int v) { return (v + 127) / 128 * 128; };
     // weight gradient straight from the row-major dY and layer-input planes (gemm_tn.hip): no operand transposes
-    // dbias (optional): the layer's bias gradient = column sums of Y, taken inside the weight-gradient kernel; when that kernel
-    // does not run (frozen weight, narrow layer) a pack pass over Y produces them
+    // dbias (optional): the layer's bias gradient = column sums of Y, taken inside the weight-gradient kernel.  When the weight is
+    // frozen that kernel still runs for the column sums alone if colsum_alone (the head layers); otherwise (the block linears) a
+    // pack pass over Y produces them
     // k_pad (optional): the stored width of X when that is a multiple of 128 and k_cols is not (the classifier's zero-padded hidden
     // activations): the kernel multiplies all k_pad columns, the reduce writes the first k_cols
     auto wgrad_tn = [&](const bf16_t* Y, long y_plane, int ldy, const bf16_t* X, long x_plane, int ldx, int m_rows, int n_rows,
-                        int k_cols, int planes, float* dW, float* dbias, hipStream_t s, int k_pad = 0) -> int {
-        if (k_pad > 0 && k_pad % 128 == 0 && k_pad <= ldx) {
-            if (!dW && !dbias) return 0;
-            TnParams g = {};
-            g.Y = Y; g.y_plane = y_plane; g.ldy = ldy; g.X = X; g.x_plane = x_plane; g.ldx = ldx;
-            g.M = m_rows; g.N = n_rows; g.Kc = k_pad; g.planes = planes;
-            const int row_tiles = (n_rows + 127) / 128, tiles = row_tiles * (k_pad / 128), nchunks = (m_rows + 31) / 32;
-            int ks = splitk_budget() / tiles;
-            if (ks > nchunks / 4) ks = nchunks / 4;
-            if (ks >= 8 && !(dseg::options().route_ab & 4)) ks &= ~7;      // a multiple of 8: the kernel's XCD-aware form (gemm_tn.hip)
-            if (ks < 1) ks = 1;
-            const int per = (nchunks + ks - 1) / ks, used = (nchunks + per - 1) / per;
-            g.part = F32(L.SPLITK); g.ld_part = k_pad; g.split_stride = (long)row_tiles * 128 * k_pad; g.ksplit = ks;
-            g.colsum = dbias;
-            g.det_region = s != main_stream;
-            DSEG_TRY(launch_gemm_tn(g, s));
-            if (!dW) return 0;
-            return launch_splitk_reduce(g.part, used, g.split_stride, n_rows, k_pad, dW, k_cols, k_cols, s);
-        }
-        if (dbias && (!dW || k_cols % 128 != 0))
-            DSEG_TRY(launch_transpose_planes(nullptr, Y, y_plane, ldy, m_rows, n_rows, nullptr, 0, pad128(n_rows), L.Mpad, nullptr, 0, 0,
-                                             dbias, planes, 0, 0, s, s != main_stream));
-        if (!dW) return 0;
-        if (k_cols % 128 != 0) {        // narrow layers (embed_dim not a multiple of 128): transposed operands + the NT kernel
-            bf16_t* T1f = B16(L.T1);
-            bf16_t* T2f = B16(L.T2);
-            DSEG_TRY(launch_transpose_planes(nullptr, Y, y_plane, ldy, m_rows, n_rows, T1f, L.t_plane, pad128(n_rows), L.Mpad, nullptr, 0, 0,
-                                             nullptr, planes, 0, 0, s));
-            DSEG_TRY(launch_transpose_planes(nullptr, X, x_plane, ldx, m_rows, k_cols, T2f, L.t_plane, pad128(k_cols), L.Mpad, nullptr, 0, 0,
-                                             nullptr, planes, 0, 0, s));
-            return wgrad(T1f, T2f, L.t_plane, L.Mpad, n_rows, pad128(k_cols), k_cols, planes, dW);
-        }
+                        int k_cols, int planes, float* dW, float* dbias, hipStream_t s, int k_pad, bool colsum_alone) -> int {
+        if (!dW && !dbias) return 0;
+        if (!dW && !colsum_alone)
+            return launch_transpose_planes(nullptr, Y, y_plane, ldy, m_rows, n_rows, nullptr, 0, pad128(n_rows), L.Mpad, nullptr, 0, 0,
+                                           dbias, planes, 0, 0, s, s != main_stream);
+        const int Kc = k_pad ? k_pad : k_cols;
         TnParams g = {};
         g.Y = Y; g.y_plane = y_plane; g.ldy = ldy; g.X = X; g.x_plane = x_plane; g.ldx = ldx;
-        g.M = m_rows; g.N = n_rows; g.Kc = k_cols; g.planes = planes;
-        const int row_tiles = (n_rows + 127) / 128, tiles = row_tiles * (k_cols / 128), nchunks = (m_rows + 31) / 32;
+        g.M = m_rows; g.N = n_rows; g.Kc = Kc; g.planes = planes;
+        const int row_tiles = (n_rows + 127) / 128, tiles = row_tiles * (Kc / 128), nchunks = (m_rows + 31) / 32;
         int ks = splitk_budget() / tiles;
         if (ks > nchunks / 4) ks = nchunks / 4;
         if (ks >= 8 && !(dseg::options().route_ab & 4)) ks &= ~7;      // a multiple of 8: the kernel's XCD-aware form (gemm_tn.hip)
         if (ks < 1) ks = 1;
         const int per = (nchunks + ks - 1) / ks, used = (nchunks + per - 1) / per;
-        g.part = F32(L.SPLITK); g.ld_part = k_cols; g.split_stride = (long)row_tiles * 128 * k_cols; g.ksplit = ks;
+        g.part = w.f32(L.SPLITK); g.ld_part = Kc; g.split_stride = (long)row_tiles * 128 * Kc; g.ksplit = ks;
         g.colsum = dbias;
         g.det_region = s != main_stream;
         DSEG_TRY(launch_gemm_tn(g, s));
-        return launch_splitk_reduce(g.part, used, g.split_stride, n_rows, k_cols, dW, k_cols, k_cols, s);
+        if (!dW) return 0;
+        return launch_splitk_reduce(g.part, used, g.split_stride, n_rows, Kc, dW, k_cols, k_cols, s);
     };
 
     // ---- loss and d logits (pl_torch_modules.py:264-265)
     const int ldz = dz_ld(C);
-    DSEG_TRY(launch_nll_loss_grad(LOGP, labels, dlogp, L.Mp, C, F32(L.ACC), h->bad_label_flag, loss_out, DZ,
+    DSEG_TRY(launch_nll_loss_grad(LOGP, labels, dlogp, L.Mp, C, w.f32(L.ACC), h->bad_label_flag, loss_out, DZ,
                                   L.dz_plane, ldz, s));
     const long tpl = L.t_plane;
-    float* dX = F32(L.dX);
-    float* dA = F32(L.dA);
-    bf16_t* G = B16(L.G);
+    float* dX = w.f32(L.dX);
+    float* dA = w.f32(L.dA);
+    bf16_t* G = w.b16(L.G);
     if (mlp_head) {
         // layer_3: z = h2 W3^T + b3      (weight and bias gradients straight from the row-major planes: gemm_tn.hip; h2 / h1 are stored
         // 128 / 256 wide, zero beyond their 100 / 200 columns)
-        DSEG_TRY(wgrad_tn(DZ, L.dz_plane, ldz, H2, L.h2_plane, 128, L.Mp, C, 100, HP, grad("clf.layer_3.weight"), grad("clf.layer_3.bias"), s, 128));
+        const LinearGrad &g1 = gr.head[0], &g2 = gr.head[1], &g3 = gr.clf;
+        DSEG_TRY(wgrad_tn(DZ, L.dz_plane, ldz, H2, L.h2_plane, HEAD_H2_PAD, L.Mp, C, HEAD_H2, HP, g3.dw.ptr, g3.db.ptr, s, HEAD_H2_PAD, true));
         bf16_t* dH2 = G;                         // [HP][Mp][128]
-        const long dh2_plane = (long)L.Mp * 128;
-        DSEG_TRY(dgrad(DZ, L.dz_plane, ldz, L.Mp, ldz, tw.at("clf.layer_3.weight"), 128, HP, EPI_DRELU, nullptr, dH2, dh2_plane, H2, L.h2_plane));
+        const long dh2_plane = (long)L.Mp * HEAD_H2_PAD;
+        DSEG_TRY(dgrad(DZ, L.dz_plane, ldz, L.Mp, ldz, g3, HEAD_H2_PAD, HP, EPI_DRELU, nullptr, dH2, dh2_plane, H2, L.h2_plane));
         // layer_2
-        DSEG_TRY(wgrad_tn(dH2, dh2_plane, 128, H1, L.h1_plane, 256, L.Mp, 100, 200, HP, grad("clf.layer_2.weight"), grad("clf.layer_2.bias"), s, 256));
-        bf16_t* dH1 = B16(L.dCTX);               // [HP][Mp][256] fits: Mp*256 <= M*D
-        const long dh1_plane = (long)L.Mp * 256;
-        DSEG_TRY(dgrad(dH2, dh2_plane, 128, L.Mp, 128, tw.at("clf.layer_2.weight"), 256, HP, EPI_DRELU, nullptr, dH1, dh1_plane, H1, L.h1_plane));
+        DSEG_TRY(wgrad_tn(dH2, dh2_plane, HEAD_H2_PAD, H1, L.h1_plane, HEAD_H1_PAD, L.Mp, HEAD_H2, HEAD_H1, HP, g2.dw.ptr, g2.db.ptr, s, HEAD_H1_PAD, true));
+        bf16_t* dH1 = w.b16(L.dCTX);             // [HP][Mp][256] fits: Mp*256 <= M*D
+        const long dh1_plane = (long)L.Mp * HEAD_H1_PAD;
+        DSEG_TRY(dgrad(dH2, dh2_plane, HEAD_H2_PAD, L.Mp, HEAD_H2_PAD, g2, HEAD_H1_PAD, HP, EPI_DRELU, nullptr, dH1, dh1_plane, H1, L.h1_plane));
         // layer_1
-        if (D % 128 == 0) {
-            DSEG_TRY(wgrad_tn(dH1, dh1_plane, 256, FEAT, L.feat_plane, D, L.Mp, 200, D, HP, grad("clf.layer_1.weight"), grad("clf.layer_1.bias"), s, D));
-        } else {
-            DSEG_TRY(launch_transpose_planes(nullptr, dH1, dh1_plane, 256, L.Mp, 200, T1, tpl, 256, L.Mppad, nullptr, 0, 0,
-                                             grad("clf.layer_1.bias"), HP, 0, 0, s));
-            DSEG_TRY(launch_transpose_planes(nullptr, FEAT, L.feat_plane, D, L.Mp, D, T2, tpl, pad128(D), L.Mppad, nullptr, 0, 0, nullptr, HP, 0, 0, s));
-            DSEG_TRY(wgrad(T1, T2, tpl, L.Mppad, 200, pad128(D), D, HP, grad("clf.layer_1.weight")));
-        }
+        DSEG_TRY(wgrad_tn(dH1, dh1_plane, HEAD_H1_PAD, FEAT, L.feat_plane, D, L.Mp, HEAD_H1, D, HP, g1.dw.ptr, g1.db.ptr, s, D, true));
         if (backbone)
-            DSEG_TRY(dgrad(dH1, dh1_plane, 256, L.Mp, 256, tw.at("clf.layer_1.weight"), D, HP, EPI_PLAIN, dA, nullptr, 0, nullptr, 0));
+            DSEG_TRY(dgrad(dH1, dh1_plane, HEAD_H1_PAD, L.Mp, HEAD_H1_PAD, g1, D, HP, EPI_PLAIN, dA, nullptr, 0, nullptr, 0));
     } else {
-        if (D % 128 == 0) {
-            DSEG_TRY(wgrad_tn(DZ, L.dz_plane, ldz, FEAT, L.feat_plane, D, L.Mp, C, D, HP, grad("clf.layer_1.weight"), grad("clf.layer_1.bias"), s, D));
-        } else {
-            DSEG_TRY(launch_transpose_planes(nullptr, DZ, L.dz_plane, ldz, L.Mp, C, T1, tpl, pad128(C), L.Mppad, nullptr, 0, 0,
-                                             grad("clf.layer_1.bias"), HP, 0, 0, s));
-            DSEG_TRY(launch_transpose_planes(nullptr, FEAT, L.feat_plane, D, L.Mp, D, T2, tpl, pad128(D), L.Mppad, nullptr, 0, 0, nullptr, HP, 0, 0, s));
-            DSEG_TRY(wgrad(T1, T2, tpl, L.Mppad, C, pad128(D), D, HP, grad("clf.layer_1.weight")));
-        }
+        DSEG_TRY(wgrad_tn(DZ, L.dz_plane, ldz, FEAT, L.feat_plane, D, L.Mp, C, D, HP, gr.clf.dw.ptr, gr.clf.db.ptr, s, D, true));
         if (backbone)
-            DSEG_TRY(dgrad(DZ, L.dz_plane, ldz, L.Mp, ldz, tw.at("clf.layer_1.weight"), D, HP, EPI_PLAIN, dA, nullptr, 0, nullptr, 0));
+            DSEG_TRY(dgrad(DZ, L.dz_plane, ldz, L.Mp, ldz, gr.clf, D, HP, EPI_PLAIN, dA, nullptr, 0, nullptr, 0));
     }
     DSEG_TRY(stage_mark(0));
     if (!backbone) return 0;      // frozen backbone (freeze_bb, pl_torch_modules.py:434-436): only the head trains
 
     // ---- final norm (CLS rows get no gradient from the head)
-    auto gsink = [&](const std::string& name) { float* g = grad(name); return g ? g : sink; };
+    auto gsink = [&](const GradSlot& g) { return g.ptr ? g.ptr : sink; };      // (LayerNorm backward always writes its gain / shift sums)
     // (every LayerNorm backward also leaves its dX rows as bf16 planes dXp and their column sums = the bias gradient of the
     //  layer the walk reaches next: mlp.fc2 of the last block here)
-    bf16_t* dXp = B16(L.dXp);
-    DSEG_TRY(launch_layernorm_bwd(dA, Xfin, W(h, "dino.norm.weight"), c.ln_eps, L.M, D, dX, 0, gsink("dino.norm.weight"),
-                                  gsink("dino.norm.bias"), 1, L.ntok, s, dXp, L.a_plane, P,
-                                  NB > 0 ? grad("dino.blocks." + std::to_string(NB - 1) + ".mlp.fc2.bias") : nullptr));
+    bf16_t* dXp = w.b16(L.dXp);
+    DSEG_TRY(launch_layernorm_bwd(dA, Xfin, m.norm_w, c.ln_eps, L.M, D, dX, 0, gsink(gr.norm_w), gsink(gr.norm_b), 1, L.ntok, s, dXp,
+                                  L.a_plane, P, NB > 0 ? gr.blocks[NB - 1].fc2.db.ptr : nullptr));
 
-    bf16_t* dCTX = B16(L.dCTX);
+    bf16_t* dCTX = w.b16(L.dCTX);
     hipEvent_t w_fc2 = nullptr, w_fc1 = nullptr, w_proj = nullptr, w_qkv = nullptr;
     for (int l = NB - 1; l >= 0; --l) {
-        const std::string b = "dino.blocks." + std::to_string(l) + ".";
-        const size_t o = l * L.blk_stride;
-        bf16_t *A1 = B16(L.A1 + o), *Q = B16(L.Q + o), *Kb = B16(L.K + o), *V = B16(L.V + o), *CTX = B16(L.CTX + o);
-        bf16_t *A2 = B16(L.A2 + o), *HPRE = B16(L.HPRE + o), *HB = B16(L.HB + o);
+        const BlockRec& blk = m.blocks[l];
+        const BlockGrad& bg = gr.blocks[l];
+        const auto [Xin, Xmid, LSE, A1, Q, Kb, V, CTX, A2, HPRE, HB] = w.block(l);
         // ---- mlp.fc2 : X_out = X_mid + H W2^T + b
         // (dXp = bf16 planes of dX and the fc2 bias gradient were left by the LayerNorm backward that produced dX; the weight
         //  gradient reads dXp and HB row-major)
         DSEG_TRY(side_begin());
-        DSEG_TRY(wgrad_tn(dXp, L.a_plane, D, HB, L.f_plane, F, L.M, D, F, P, grad(b + "mlp.fc2.weight"), nullptr, ws_));
+        DSEG_TRY(wgrad_tn(dXp, L.a_plane, D, HB, L.f_plane, F, L.M, D, F, P, bg.fc2.dw.ptr, nullptr, ws_, 0, false));
         DSEG_TRY(side_end(&w_fc2));
         // dHpre = (dX . W2) * gelu'(Hpre)      (writes G: the previous block's qkv weight gradient reads it)
         DSEG_TRY(side_wait(w_qkv));
-        DSEG_TRY(dgrad(dXp, L.a_plane, D, L.M, D, tw.at(b + "mlp.fc2.weight"), F, P, EPI_DGELU, nullptr, G, (long)L.M * F, HPRE, L.f_plane));
+        DSEG_TRY(dgrad(dXp, L.a_plane, D, L.M, D, bg.fc2, F, P, EPI_DGELU, nullptr, G, (long)L.M * F, HPRE, L.f_plane));
         // ---- mlp.fc1 : Hpre = A2 W1^T + b
         DSEG_TRY(side_begin());
-        DSEG_TRY(wgrad_tn(G, (long)L.M * F, F, A2, L.a_plane, D, L.M, F, D, P, grad(b + "mlp.fc1.weight"), grad(b + "mlp.fc1.bias"), ws_));
+        DSEG_TRY(wgrad_tn(G, (long)L.M * F, F, A2, L.a_plane, D, L.M, F, D, P, bg.fc1.dw.ptr, bg.fc1.db.ptr, ws_, 0, false));
         DSEG_TRY(side_end(&w_fc1));
-        DSEG_TRY(dgrad(G, (long)L.M * F, F, L.M, F, tw.at(b + "mlp.fc1.weight"), D, P, EPI_PLAIN, dA, nullptr, 0, nullptr, 0));
+        DSEG_TRY(dgrad(G, (long)L.M * F, F, L.M, F, bg.fc1, D, P, EPI_PLAIN, dA, nullptr, 0, nullptr, 0));
         // ---- norm2 (input X_mid); the residual branch keeps dX      (rewrites dXp: the fc2 weight gradient reads it)
         DSEG_TRY(side_wait(w_fc2));
-        DSEG_TRY(launch_layernorm_bwd(dA, F32(L.Xmid + o), W(h, b + "norm2.weight"), c.ln_eps, L.M, D, dX, 1, gsink(b + "norm2.weight"),
-                                      gsink(b + "norm2.bias"), 0, L.ntok, s, dXp, L.a_plane, P, grad(b + "attn.proj.bias")));
+        DSEG_TRY(launch_layernorm_bwd(dA, Xmid, blk.norm2_w, c.ln_eps, L.M, D, dX, 1, gsink(bg.norm2_w), gsink(bg.norm2_b), 0, L.ntok, s,
+                                      dXp, L.a_plane, P, bg.proj.db.ptr));
         // ---- attn.proj : X_mid = X_in + ctx Wp^T + b
         DSEG_TRY(side_begin());
-        DSEG_TRY(wgrad_tn(dXp, L.a_plane, D, CTX, L.a_plane, D, L.M, D, D, P, grad(b + "attn.proj.weight"), nullptr, ws_));
+        DSEG_TRY(wgrad_tn(dXp, L.a_plane, D, CTX, L.a_plane, D, L.M, D, D, P, bg.proj.dw.ptr, nullptr, ws_, 0, false));
         DSEG_TRY(side_end(&w_proj));
-        DSEG_TRY(dgrad(dXp, L.a_plane, D, L.M, D, tw.at(b + "attn.proj.weight"), D, P, EPI_BF16, nullptr, dCTX, L.a_plane, nullptr, 0));
+        DSEG_TRY(dgrad(dXp, L.a_plane, D, L.M, D, bg.proj, D, P, EPI_BF16, nullptr, dCTX, L.a_plane, nullptr, 0));
         // ---- attention      (writes G: the fc1 weight gradient reads it)
         DSEG_TRY(side_wait(w_fc1));
         {
             AttnBwdParams a = {};
             a.q = Q; a.k = Kb; a.v = V; a.qkv_plane = L.qkv_plane;
-            a.dO = dCTX; a.O = CTX; a.dO_plane = L.a_plane; a.lse = F32(L.LSE + o);
-            a.neg_lse = F32(L.NLSE); a.neg_delta = F32(L.NDEL);
+            a.dO = dCTX; a.O = CTX; a.dO_plane = L.a_plane; a.lse = LSE;
+            a.neg_lse = w.f32(L.NLSE); a.neg_delta = w.f32(L.NDEL);
             a.dqkv = G; a.dqkv_plane = (long)L.M * 3 * D;
             a.B = B; a.heads = H; a.ntok = L.ntok; a.npad = L.npad; a.planes = P;
             DSEG_PROF(DINOSEG_PROF_ATTN_BWD, DSEG_TRY(launch_attention_bwd(a, s)));
         }
         // ---- attn.qkv : qkv = A1 Wqkv^T + b
         DSEG_TRY(side_begin());
-        DSEG_TRY(wgrad_tn(G, (long)L.M * 3 * D, 3 * D, A1, L.a_plane, D, L.M, 3 * D, D, P, grad(b + "attn.qkv.weight"),
-                          grad(b + "attn.qkv.bias"), ws_));
+        DSEG_TRY(wgrad_tn(G, (long)L.M * 3 * D, 3 * D, A1, L.a_plane, D, L.M, 3 * D, D, P, bg.qkv.dw.ptr,
+                          bg.qkv.db.ptr, ws_, 0, false));
         DSEG_TRY(side_end(&w_qkv));
-        DSEG_TRY(dgrad(G, (long)L.M * 3 * D, 3 * D, L.M, 3 * D, tw.at(b + "attn.qkv.weight"), D, P, EPI_PLAIN, dA, nullptr, 0, nullptr, 0));
+        DSEG_TRY(dgrad(G, (long)L.M * 3 * D, 3 * D, L.M, 3 * D, bg.qkv, D, P, EPI_PLAIN, dA, nullptr, 0, nullptr, 0));
         // ---- norm1 (input X_in)      (rewrites dXp: the proj weight gradient reads it)
         // (by-products for mlp.fc2 of block l-1; the embedding step after block 0 packs dX itself: it drops the CLS rows)
         DSEG_TRY(side_wait(w_proj));
-        DSEG_TRY(launch_layernorm_bwd(dA, F32(L.Xin + o), W(h, b + "norm1.weight"), c.ln_eps, L.M, D, dX, 1, gsink(b + "norm1.weight"),
-                                      gsink(b + "norm1.bias"), 0, L.ntok, s, l > 0 ? dXp : nullptr, L.a_plane, P,
-                                      l > 0 ? grad("dino.blocks." + std::to_string(l - 1) + ".mlp.fc2.bias") : nullptr));
+        DSEG_TRY(launch_layernorm_bwd(dA, Xin, blk.norm1_w, c.ln_eps, L.M, D, dX, 1, gsink(bg.norm1_w), gsink(bg.norm1_b), 0, L.ntok, s,
+                                      l > 0 ? dXp : nullptr, L.a_plane, P, l > 0 ? gr.blocks[l - 1].fc2.db.ptr : nullptr));
         // this block's gradients are complete once the side stream has finished its qkv weight gradient; the stage event is
         // recorded on the side stream (it has waited for everything the block queued on s up to the qkv weight gradient -- the
         // LayerNorm backward above is covered by the extra fork), so the caller's stream does not stall here
@@ -895,28 +834,28 @@ static int train_backward_impl(dinoseg_handle* h, const int64_t* labels, const f
     // below reuses the split-K workspace
     DSEG_TRY(side_wait(w_qkv));
     // ---- embeddings: tokens = [cls ; conv(patches)] + pos   (vision_transformer.py:224-235)
-    float* dpos = F32(L.DPOS);
+    float* dpos = w.f32(L.DPOS);
     DSEG_TRY(launch_batch_sum_rows(dX, B, L.ntok, D, dpos, s));
-    if (grad("dino.cls_token"))
-        DSEG_CHECK_HIP(hipMemcpyAsync(grad("dino.cls_token"), dpos, (size_t)D * 4, hipMemcpyDeviceToDevice, s));
+    if (gr.cls_token.ptr)
+        DSEG_CHECK_HIP(hipMemcpyAsync(gr.cls_token.ptr, dpos, (size_t)D * 4, hipMemcpyDeviceToDevice, s));
     // (scratch: the T2 transpose buffer, idle until the patch-embed gradient below; make_train_layout sizes it for [pos_grid][W/patch][D] floats)
-    if (grad("dino.pos_embed")) {
+    if (gr.pos_embed.ptr) {
         if ((size_t)c.pos_grid * ow * D * sizeof(float) > L.t2_bytes) {
             dinoseg_set_error("dinoseg_backward: pos-embed scratch does not fit (pos_grid %d, grid %d x %d)", c.pos_grid, oh, ow);
             return -1;
         }
-        DSEG_TRY(launch_pos_resample_bwd(dpos, c.pos_grid, D, oh, ow, grad("dino.pos_embed"), reinterpret_cast<float*>(T2), s));
+        DSEG_TRY(launch_pos_resample_bwd(dpos, c.pos_grid, D, oh, ow, gr.pos_embed.ptr, reinterpret_cast<float*>(T2), s));
     }
     DSEG_TRY(launch_transpose_planes(dX, nullptr, 0, D, L.Mp, D, T1, tpl, pad128(D), L.Mppad, nullptr, 0, 0,
-                                     grad("dino.patch_embed.proj.bias"), P, 1, L.ntok, s));
-    if (grad("dino.patch_embed.proj.weight")) {
+                                     gr.patch.db.ptr, P, 1, L.ntok, s));
+    if (gr.patch.dw.ptr) {
         const int kp = 3 * c.patch * c.patch;       // 192 columns in 256 transposed rows at patch 8; 768 in 768 at patch 16
         if ((long)pad128(kp) * L.Mppad > tpl) {
             dinoseg_set_error("dinoseg_backward: the transposed patch matrix (%d x %d) does not fit its plane (%ld)", pad128(kp), L.Mppad, tpl);
             return -1;
         }
         DSEG_TRY(launch_transpose_planes(nullptr, PATCH, L.patch_plane, kp, L.Mp, kp, T2, tpl, pad128(kp), L.Mppad, nullptr, 0, 0, nullptr, P, 0, 0, s));
-        DSEG_TRY(wgrad(T1, T2, tpl, L.Mppad, D, pad128(kp), kp, P, grad("dino.patch_embed.proj.weight")));
+        DSEG_TRY(wgrad(T1, T2, tpl, L.Mppad, D, pad128(kp), kp, P, gr.patch.dw.ptr));
     }
     return stage_mark(NB + 1);
 }

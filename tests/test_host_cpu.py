@@ -143,6 +143,42 @@ def test_handle_lifecycle_and_errors_without_gpu():
         DINOSeg(precision="fp32")
 
 
+def test_native_name_and_shape_table_matches_tensor_shapes():
+    """The library's own name / shape table (what dinoseg_bind_weight and dinoseg_bind_grad accept) against
+    dino_amd.weights.tensor_shapes, key by key, without a GPU: a host pointer gets as far as "is not a device pointer" only when the
+    name and the shape were accepted; the last dimension + 1 is a shape mismatch; every key names a gradient slot, NULL unbinds it;
+    an unknown key is refused by both."""
+    lib = capi.lib()
+    configs = [ViTConfig(n_blocks=2),                                                                # ViT-S/8, MLP head, C = 7
+               ViTConfig(embed_dim=768, num_heads=12, mlp_ratio=6, n_blocks=2, head="linear", n_classes=150),
+               ViTConfig(embed_dim=128, num_heads=2, n_blocks=2),                                    # the suite's TINY
+               ViTConfig(patch=16, pos_grid=14, n_blocks=1, n_classes=40)]
+    buf = (ctypes.c_float * 4)()
+    for cfg in configs:
+        h = ctypes.c_void_p()
+        native = capi.Config(cfg.embed_dim, cfg.num_heads, cfg.n_blocks, cfg.patch, cfg.mlp_ratio, cfg.n_classes,
+                             capi.HEAD_MLP if cfg.head == "mlp" else capi.HEAD_LINEAR, cfg.pos_grid, cfg.ln_eps, capi.BF16X3)
+        assert lib.dinoseg_create(ctypes.byref(native), ctypes.byref(h)) == 0
+        try:
+            shapes = tensor_shapes(cfg)
+            assert len(shapes) == 6 + 12 * cfg.n_blocks + (6 if cfg.head == "mlp" else 2)
+            for name, shape in shapes.items():
+                key = name.encode()
+                good = (ctypes.c_int64 * len(shape))(*shape)
+                assert lib.dinoseg_bind_weight(h, key, ctypes.addressof(buf), good, len(shape)) == -1, name
+                assert "is not a device pointer" in capi.last_error(), (name, capi.last_error())
+                bad = (ctypes.c_int64 * len(shape))(*shape[:-1], shape[-1] + 1)
+                assert lib.dinoseg_bind_weight(h, key, ctypes.addressof(buf), bad, len(shape)) == -1, name
+                assert "shape mismatch" in capi.last_error(), (name, capi.last_error())
+                assert lib.dinoseg_bind_grad(h, key, None) == 0, name
+            assert lib.dinoseg_bind_grad(h, b"dino.nope", None) == -1
+            assert "unexpected key" in capi.last_error()
+            assert lib.dinoseg_bind_weight(h, b"dino.nope", ctypes.addressof(buf), (ctypes.c_int64 * 1)(4), 1) == -1
+            assert "unexpected key" in capi.last_error()
+        finally:
+            assert lib.dinoseg_destroy(h) == 0
+
+
 def test_state_dict_keys_match_reference_schema():
     for head, L in (("mlp", 3), ("linear", 1)):
         m = DINOSeg(head=head, n_blocks=L)

@@ -597,3 +597,96 @@ def test_deterministic_bias_only_layers_on_the_side_stream(cuda):
     for n in g1:
         den = float(g1[n].abs().max()) + 1e-12
         assert float((ga[n] - g1[n]).abs().max()) <= 2e-5 * den + 1e-9, n
+
+
+# ------------------------------------------------------------------------------------------------ partial freezes and unbinding
+# ViT-S/8, 2 blocks, MLP head, 2 frames @64: 130 token rows, one over a 128-row tile -- the smallest shape that crosses a tile in every
+# GEMM of the backward walk.  Option deterministic: every sum has a fixed order, so "the same kernel on the same operands" means
+# the same bits.
+def _is_block_weight(n, p):
+    return n.startswith("dino.blocks.") and n.endswith(".weight") and p.dim() == 2
+
+
+def _freeze_case():
+    cfg = ViTConfig(n_blocks=2)
+    m, _ = build(cfg, "bf16x3")
+    fr = torch.from_numpy(synthetic_frames(2, 64, seed=171)).cuda()
+    lb = torch.from_numpy(synthetic_labels(2, 64, cfg.n_classes, seed=172)).cuda()
+    return m, (fr, lb)
+
+
+def _step_with(m, batch, trainable):
+    """One fused step with exactly the parameters trainable(name, p) trainable: {name: gradient} of those."""
+    for n, p in m.named_parameters():
+        p.requires_grad_(bool(trainable(n, p)))
+    m.fused_training_step(batch, 0)
+    torch.cuda.synchronize()
+    return {n: p.grad.clone() for n, p in m.named_parameters() if p.requires_grad}
+
+
+def _assert_same_gradients(got, base, frozen_weight_of, tag):
+    """Bit-identical wherever the kernel route is the same.  The bias of attn.qkv, mlp.fc1 or a head layer comes out of the
+    weight-gradient kernel while its weight trains and out of a column-sum pass once that weight is frozen: equal up to the
+    summation order (the bound of test_deterministic_option_makes_the_fine_tune_step_bit_reproducible)."""
+    assert got, tag
+    for n, g in got.items():
+        rerouted = n.endswith(".bias") and (".attn.qkv." in n or ".mlp.fc1." in n or n.startswith("clf.")) and frozen_weight_of(n)
+        if rerouted:
+            den = float(base[n].abs().max())
+            err = float((g - base[n]).abs().max())
+            print(f"{tag}: {n} through the column-sum pass: |d| {err:.3e}, bound {2e-5 * den + 1e-9:.3e}")
+            assert err <= 2e-5 * den + 1e-9, (tag, n, err)
+        else:
+            assert torch.equal(g, base[n]), (tag, n, float((g - base[n]).abs().max()))
+
+
+@pytest.mark.parametrize("streams", [1, 2])
+def test_partial_freezes_leave_the_other_gradients_unchanged(cuda, streams):
+    """Freezing a subset of the parameters unbinds their gradient buffers and changes nothing else: every gradient a partly frozen
+    step produces equals the fully unfrozen step's bit for bit, except the biases whose kernel route changes with their weight (see
+    _assert_same_gradients)."""
+    import dino_amd
+    subsets = {
+        "block weights": _is_block_weight,
+        "block biases and norms": lambda n, p: n.startswith("dino.blocks.") and not _is_block_weight(n, p),
+        "block 1 and the head": lambda n, p: n.startswith("dino.blocks.1.") or n.startswith("clf."),
+        "cls, pos and patch embedding": lambda n, p: n in ("dino.cls_token", "dino.pos_embed") or n.startswith("dino.patch_embed."),
+    }
+    dino_amd.set_option("deterministic", 1)
+    dino_amd.set_option("train_streams", streams)
+    try:
+        m, batch = _freeze_case()
+        base = _step_with(m, batch, lambda n, p: True)
+        assert len(base) == len(list(m.named_parameters()))
+        for tag, trainable in subsets.items():
+            got = _step_with(m, batch, trainable)
+            assert set(got) == {n for n, p in m.named_parameters() if trainable(n, p)}
+            _assert_same_gradients(got, base, lambda n: n[:-len("bias")] + "weight" not in got, f"{tag} [streams {streams}]")
+    finally:
+        dino_amd.set_option("deterministic", 0)
+        dino_amd.set_option("train_streams", 2)
+
+
+@pytest.mark.parametrize("streams", [1, 2])
+def test_unbinding_a_gradient_really_unbinds_it(cuda, streams):
+    """requires_grad_(False) after a step: the next step neither writes nor zeroes the buffers that were bound for those
+    parameters (a sentinel left in them survives), and the gradients still bound equal the first step's."""
+    import dino_amd
+    dino_amd.set_option("deterministic", 1)
+    dino_amd.set_option("train_streams", streams)
+    try:
+        m, batch = _freeze_case()
+        base = _step_with(m, batch, lambda n, p: True)
+        old = {n: p.grad for n, p in m.named_parameters() if _is_block_weight(n, p)}      # the buffers the library holds
+        assert len(old) == 8
+        for g in old.values():
+            g.fill_(12345.0)
+        torch.cuda.synchronize()
+        got = _step_with(m, batch, lambda n, p: not _is_block_weight(n, p))
+        for n, g in old.items():
+            assert bool((g == 12345.0).all()), f"{n}: the unbound gradient buffer was written"
+        assert set(got) == set(base) - set(old)
+        _assert_same_gradients(got, base, lambda n: n[:-len("bias")] + "weight" not in got, f"block weights unbound [streams {streams}]")
+    finally:
+        dino_amd.set_option("deterministic", 0)
+        dino_amd.set_option("train_streams", 2)
