@@ -141,6 +141,10 @@ SIGNATURES = {
     # pixel-resolution output: bilinear upsample + argmax of the log-probs, alone and behind the forward
     "dinoseg_op_upsample_argmax": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _vp]),
     "dinoseg_forward_dense_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _vp]),
+    # pixel-resolution training loss: upsample + cross-entropy + its gradient, alone and as the fine-tune step on pixel labels
+    "dinoseg_op_upsample_nll_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "dinoseg_op_upsample_nll": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _i32, _fp, _fp, _fp, _fp, _vp, _vp]),
+    "dinoseg_train_step_dense_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _i32, _fp, _fp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -144,6 +144,8 @@ struct dinoseg_handle {
     std::vector<hipEvent_t> bw_ev;
     char* twbuf = nullptr;                 // transposed packed weights for the input-gradient GEMMs
     size_t twbuf_bytes = 0;
+    char* dws = nullptr;                   // pixel-label step (dinoseg_train_step_dense_hw): d loss / d logp [B*n, C], then the loss scratch
+    size_t dws_bytes = 0;
     // optional per-kernel-class timing with HIP events on the caller's stream (bench.py roofline leg)
     int prof_level = 0;                    // 0 off, 1 attention only, 2 every class
     struct ProfRec { int cat; hipEvent_t a, b; };

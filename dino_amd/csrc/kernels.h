@@ -286,6 +286,15 @@ int launch_confusion(const int32_t* pred, const int64_t* gt, long n, int C, int6
 // its shape check alone (-1 and a message starting with `who`): sizes positive, 1 <= C <= 256, OH >= hp, OW >= wp, the integer ranges
 int upsample_check_shape(const char* who, int B, int hp, int wp, int C, int OH, int OW);
 int launch_upsample_argmax(const float* logp, int B, int hp, int wp, int C, int OH, int OW, int32_t* labels, float* dense, hipStream_t s);
+// Pixel-resolution training loss (upsample_loss.hip): loss = F.cross_entropy(that upsample of logp, labels int64 [B, OH, OW]) with the
+// mean over the valid pixels (0 <= label < C; ignore_index and -100 skipped, anything else skipped and flags[0] |= 1), and dlogp
+// [B, hp*wp, C] = d loss / d logp (nullable: loss only), without a [B, C, OH, OW] tensor.  dlogp is a gather in a fixed order (no
+// floating-point atomics); the loss sum uses atomics, or under option deterministic per-tile partials + launch_det_finalize.
+// scratch: upsample_nll_scratch_bytes (<= 8 bytes per pixel + 64 KiB).  upsample_nll_check: the host-side refusals alone.
+long long upsample_nll_scratch_bytes(int B, int hp, int wp, int C, int OH, int OW);
+int upsample_nll_check(const char* who, int B, int hp, int wp, int C, int OH, int OW, int ignore_index);
+int launch_upsample_nll(const float* logp, int B, int hp, int wp, int C, int OH, int OW, const int64_t* labels, int ignore_index,
+                        float* loss, float* dlogp, float* n_valid, int* flags, void* scratch, hipStream_t s);
 
 // ---- fine-tune step (train.hip, attention_bwd.hip) ----
 struct AttnBwdParams {

@@ -176,6 +176,9 @@ int wgrad_nt(const bf16_t* Tdy, const bf16_t* Tx, long tplane, int m_pad, int n_
 int dinoseg_train_release(dinoseg_handle* h) {
     if (h->tws) (void)hipFree(h->tws);
     if (h->twbuf) (void)hipFree(h->twbuf);
+    if (h->dws) (void)hipFree(h->dws);
+    h->dws = nullptr;
+    h->dws_bytes = 0;
     if (h->bad_label_flag) (void)hipFree(h->bad_label_flag);
     h->bad_label_flag = nullptr;
     h->tws = nullptr;
@@ -898,6 +901,55 @@ extern "C" int dinoseg_train_step_hw(dinoseg_handle* h, const void* x, int32_t x
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     DSEG_TRY(train_forward_impl(h, x, x_kind, B, H, W, logp_out, s));
     return backward_joined(h, labels, nullptr, loss_out, s);
+}
+
+extern "C" int64_t dinoseg_op_upsample_nll_scratch_bytes(int32_t B, int32_t hp, int32_t wp, int32_t C, int32_t OH, int32_t OW) {
+    return upsample_nll_scratch_bytes(B, hp, wp, C, OH, OW);
+}
+
+extern "C" int dinoseg_op_upsample_nll(const float* logp, int32_t B, int32_t hp, int32_t wp, int32_t C, int32_t OH, int32_t OW,
+                                       const int64_t* labels, int32_t ignore_index, float* loss_out, float* dlogp_out, float* n_valid_out,
+                                       int32_t* flags, void* scratch, void* stream) {
+    return launch_upsample_nll(logp, B, hp, wp, C, OH, OW, labels, ignore_index, loss_out, dlogp_out, n_valid_out, flags, scratch,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+
+// The fine-tune step on pixel labels: the forward with saved activations, the cross-entropy of its log-probs upsampled to OH x OW
+// (upsample_loss.hip: loss and d loss / d logp, no [B, C, OH, OW] tensor), then the backward from that d logp.  Everything the loss
+// would refuse is refused here, before the forward enqueues anything.
+extern "C" int dinoseg_train_step_dense_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t OH,
+                                           int32_t OW, const int64_t* labels, int32_t ignore_index, float* loss_out, float* logp_out,
+                                           void* stream) {
+    if (!h || !x || !labels || !loss_out || B <= 0) {
+        dinoseg_set_error("dinoseg_train_step_dense_hw: bad argument (null handle, frames, labels or loss_out, or B=%d)", B);
+        return -1;
+    }
+    if (!frame_ok(H, W, h->cfg.patch)) {
+        set_resolution_error(h->cfg.patch);
+        return -1;
+    }
+    const int hp = H / h->cfg.patch, wp = W / h->cfg.patch, C = h->cfg.n_classes;
+    if (upsample_nll_check("dinoseg_train_step_dense_hw", B, hp, wp, C, OH, OW, ignore_index)) return -1;
+    DeviceGuard guard(h);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    DSEG_TRY(train_forward_impl(h, x, x_kind, B, H, W, logp_out, s));
+    const size_t dl_bytes = align_up((size_t)B * hp * wp * C * sizeof(float), 256);
+    const size_t need = dl_bytes + (size_t)upsample_nll_scratch_bytes(B, hp, wp, C, OH, OW);
+    if (need > h->dws_bytes) {
+        if (h->dws) {
+            DSEG_CHECK_HIP(hipStreamSynchronize(s));
+            DSEG_CHECK_HIP(hipFree(h->dws));
+        }
+        h->dws = nullptr;
+        h->dws_bytes = 0;
+        DSEG_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&h->dws), need));
+        h->dws_bytes = need;
+    }
+    const TrainLayout L = make_train_layout(h, B, H, W);
+    float* dlogp = reinterpret_cast<float*>(h->dws);
+    DSEG_TRY(launch_upsample_nll(reinterpret_cast<const float*>(h->tws + L.LOGP), B, hp, wp, C, OH, OW, labels, ignore_index, loss_out, dlogp,
+                                 nullptr, h->bad_label_flag, h->dws + dl_bytes, s));
+    return backward_joined(h, nullptr, dlogp, nullptr, s);
 }
 
 extern "C" int dinoseg_train_step(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r,

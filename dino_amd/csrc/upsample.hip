@@ -19,37 +19,9 @@
 // value moves up and one new one is formed -- 6 LDS reads per class for 8 pixels at an 8x ratio instead of 32.
 #include "common.h"
 #include "kernels.h"
+#include "upsample_common.h"
 
 namespace dseg {
-
-constexpr int UP_TW = 64, UP_ROWS = 8, UP_WAVES = 4, UP_TH = UP_ROWS * UP_WAVES;
-constexpr int UP_LDS_WORDS = 16384;         // 64 KiB: the footprint of a 64 x 32 tile at an 8x ratio holds 256 classes in one pass
-
-struct UpCoord {
-    int i0, i1;
-    float lam;
-};
-// (the host guarantees (2 o + 1) i < 2^31 and o <= 2^22: every integer below is exact in its type)
-__host__ __device__ inline void up_index(int d, int i, int o, int* i0, int* i1, unsigned* rem) {
-    int num = (2 * d + 1) * i - o;
-    if (num < 0) num = 0;
-    const unsigned den = 2u * (unsigned)o;
-    unsigned q = (unsigned)num / den;
-    *rem = (unsigned)num - q * den;
-    if ((int)q >= i - 1) {
-        q = (unsigned)(i - 1);
-        *rem = 0;
-    }
-    *i0 = (int)q;
-    *i1 = (int)q + 1 < i ? (int)q + 1 : i - 1;
-}
-__device__ inline UpCoord up_coord(int d, int i, int o) {
-    UpCoord c;
-    unsigned rem;
-    up_index(d, i, o, &c.i0, &c.i1, &rem);
-    c.lam = __fdiv_rn((float)rem, (float)(2u * (unsigned)o));
-    return c;
-}
 
 template <bool DENSE>
 __global__ __launch_bounds__(256) void upsample_argmax_kernel(const float* __restrict__ logp, int hp, int wp, int C, int OH, int OW,
@@ -167,13 +139,8 @@ int upsample_check_shape(const char* who, int B, int hp, int wp, int C, int OH, 
     return 0;
 }
 
-int launch_upsample_argmax(const float* logp, int B, int hp, int wp, int C, int OH, int OW, int32_t* labels, float* dense,
-                           hipStream_t s) {
-    if (!logp || (!labels && !dense)) {
-        dinoseg_set_error("upsample_argmax: null pointer (logp, and at least one of labels / dense, are required)");
-        return -1;
-    }
-    if (upsample_check_shape("upsample_argmax", B, hp, wp, C, OH, OW)) return -1;
+// the tile grid and the LDS staging of a tile's source footprint (upsample_common.h); the shape has passed upsample_check_shape
+int upsample_tile_plan(const char* who, int hp, int wp, int C, int OH, int OW, UpTilePlan* plan) {
     const int tiles_x = (OW + UP_TW - 1) / UP_TW, tiles_y = (OH + UP_TH - 1) / UP_TH;
     // the largest source footprint of a tile, with the kernel's own index rule
     int max_cols = 1, max_rows = 1;
@@ -200,7 +167,21 @@ int launch_upsample_argmax(const float* logp, int B, int hp, int wp, int C, int 
     const int stride = CC | 1;
     int kw_log2 = 0;
     while (kw_log2 < 6 && (1 << kw_log2) < CC) ++kw_log2;
-    const size_t lds = (size_t)cells * stride * sizeof(float);
+    *plan = {tiles_x, tiles_y, CC, stride, kw_log2, (size_t)cells * stride * sizeof(float)};
+    return 0;
+}
+
+int launch_upsample_argmax(const float* logp, int B, int hp, int wp, int C, int OH, int OW, int32_t* labels, float* dense,
+                           hipStream_t s) {
+    if (!logp || (!labels && !dense)) {
+        dinoseg_set_error("upsample_argmax: null pointer (logp, and at least one of labels / dense, are required)");
+        return -1;
+    }
+    if (upsample_check_shape("upsample_argmax", B, hp, wp, C, OH, OW)) return -1;
+    UpTilePlan pl;
+    if (upsample_tile_plan("upsample_argmax", hp, wp, C, OH, OW, &pl)) return -1;
+    const int tiles_x = pl.tiles_x, tiles_y = pl.tiles_y, CC = pl.CC, stride = pl.stride, kw_log2 = pl.kw_log2;
+    const size_t lds = pl.lds_bytes;
     const unsigned grid = (unsigned)((long long)tiles_x * tiles_y * B);
     if (dense)
         hipLaunchKernelGGL(upsample_argmax_kernel<true>, dim3(grid), dim3(256), lds, s, logp, hp, wp, C, OH, OW, tiles_x, tiles_y, CC, stride,

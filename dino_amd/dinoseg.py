@@ -213,6 +213,53 @@ class _DinoSegFunction(torch.autograd.Function):
         return (None, None, None, None, None, None) + grads
 
 
+class _DenseNLLFunction(torch.autograd.Function):
+    """Cross-entropy of the bilinearly upsampled log-probs against pixel labels (csrc/upsample_loss.hip).  The forward runs
+    ``dinoseg_op_upsample_nll`` and keeps d loss / d logp; the backward scales it by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, logp, y, hp, wp, ignore_index, flags):
+        if not logp.is_cuda:
+            raise capi.DinosegError("dense_nll_loss runs only on a ROCm device; there is no CPU path")
+        if y.dim() != 3:
+            raise ValueError(f"expected pixel labels [B, OH, OW], got {tuple(y.shape)}")
+        B, OH, OW = (int(v) for v in y.shape)
+        C_ = int(logp.shape[-1])
+        if logp.numel() != B * hp * wp * C_:
+            raise ValueError(f"logp {tuple(logp.shape)} does not hold B*hp*wp = {B * hp * wp} rows of {C_} classes")
+        lp = logp.detach().to(torch.float32).contiguous()
+        y = y.to(device=lp.device, dtype=torch.int64).contiguous()
+        lib = capi.lib()
+        with torch.cuda.device(lp.device):
+            nbytes = lib.dinoseg_op_upsample_nll_scratch_bytes(B, hp, wp, C_, OH, OW)
+            if nbytes < 0:
+                raise capi.DinosegError(f"dinoseg error -1: {capi.last_error()}")
+            scratch = torch.empty((nbytes,), dtype=torch.uint8, device=lp.device)
+            loss = torch.zeros((), dtype=torch.float32, device=lp.device)
+            dlogp = torch.empty_like(lp)
+            capi.check(lib.dinoseg_op_upsample_nll(lp.data_ptr(), B, hp, wp, C_, OH, OW, y.data_ptr(), int(ignore_index), loss.data_ptr(),
+                                                   dlogp.data_ptr(), None, capi.ptr(flags), scratch.data_ptr(),
+                                                   capi.stream_ptr(lp.device)))
+        ctx.save_for_backward(dlogp)
+        ctx.shape = logp.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (dlogp,) = ctx.saved_tensors
+        return (grad_out * dlogp).view(ctx.shape), None, None, None, None, None
+
+
+def dense_nll_loss(logp: torch.Tensor, y: torch.Tensor, grid, ignore_index: int = 255, flags: Optional[torch.Tensor] = None):
+    """``F.cross_entropy(F.interpolate(logp.view(B, hp, wp, C).permute(0, 3, 1, 2), size=y.shape[1:], mode="bilinear",
+    align_corners=False), y, ignore_index=ignore_index)`` in two launches without the [B, C, OH, OW] tensor, differentiable with
+    respect to ``logp`` (fp32 [B*hp*wp, C] or [B, hp*wp, C] on the GPU; ``grid = (hp, wp)``; y any integer dtype, [B, OH, OW] with
+    OH >= hp, OW >= wp).  Labels equal to ``ignore_index`` or -100 are skipped; any other label outside [0, C) is skipped as well and
+    sets ``flags[0]`` (an int32 device tensor, optional).  The gradient is summed in a fixed order: bit-identical run to run."""
+    hp, wp = (int(v) for v in grid)
+    return _DenseNLLFunction.apply(logp, y, hp, wp, ignore_index, flags)
+
+
 # --------------------------------------------------------------------------- the model
 class DINOSeg(nn.Module):
     """DINO ViT + per-patch segmentation head on MI355X.
@@ -828,6 +875,10 @@ class DINOSeg(nn.Module):
             return
         bad = C.c_int32(0)
         capi.check(capi.lib().dinoseg_train_status(self._handle, C.byref(bad), self._stream()))
+        flags = self.__dict__.get("_dense_flags")       # (training_step_dense: the loss runs outside the handle)
+        if flags is not None and int(flags.item()):
+            flags.zero_()
+            bad.value = 1
         if bad.value:
             raise IndexError(f"Target out of bounds: labels must be in [0, {self.cfg.n_classes}) or -100 (ignore_index)")
 
@@ -862,6 +913,58 @@ class DINOSeg(nn.Module):
                                                     logp.data_ptr(), self._stream()))
         self._fwd_epoch = getattr(self, "_fwd_epoch", 0) + 1
         return {"loss": loss, "pred": logp.argmax(dim=-1).detach(), "gt": y, "probs": logp}
+
+    # ---- the step on pixel labels (upsample + cross-entropy + its gradient, fused: csrc/upsample_loss.hip) ----
+    def _dense_pred(self, logp: torch.Tensor, B: int, hp: int, wp: int, OH: int, OW: int) -> torch.Tensor:
+        pred = torch.empty((B, OH, OW), dtype=torch.int32, device=logp.device)
+        capi.check(capi.lib().dinoseg_op_upsample_argmax(logp.data_ptr(), B, hp, wp, self.cfg.n_classes, OH, OW, pred.data_ptr(), None,
+                                                         self._stream()))
+        return pred
+
+    def training_step_dense(self, batch, batch_idx=0, ignore_index=255):
+        """``training_step`` on pixel labels: ``probs = self(x); loss = dense_nll_loss(probs, y)`` with y int [B, OH, OW] (255 /
+        -100 = ignored) -- the cross-entropy of the bilinearly upsampled log-probs, what ``validation_step_dense`` scores.
+        ``loss.backward()`` reaches the native backward through ``DINOSeg.forward``'s autograd node and ACCUMULATES into ``.grad``.
+        ``fused_training_step_dense`` is the same arithmetic in one native call."""
+        x, y = batch
+        self._require_gpu()
+        if y.dim() != 3 or y.shape[0] != x.shape[0]:
+            raise ValueError(f"expected pixel labels [B={x.shape[0]}, OH, OW], got {tuple(y.shape)}")
+        probs = self(x)
+        H, W = (x.shape[1], x.shape[2]) if x.dtype == torch.uint8 else (x.shape[2], x.shape[3])
+        hp, wp = H // self.cfg.patch, W // self.cfg.patch
+        y = y.to(self.device).long().contiguous()
+        flags = self.__dict__.get("_dense_flags")
+        if flags is None or flags.device != self.device:
+            flags = self.__dict__["_dense_flags"] = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        loss = dense_nll_loss(probs, y, (hp, wp), ignore_index, flags)
+        with torch.no_grad():
+            pred = self._dense_pred(probs.detach(), y.shape[0], hp, wp, int(y.shape[1]), int(y.shape[2]))
+        return {"loss": loss, "pred": pred, "gt": y.reshape(-1), "probs": probs.detach()}
+
+    def fused_training_step_dense(self, batch, batch_idx=0, ignore_index=255):
+        """``fused_training_step`` on pixel labels, one native call (``dinoseg_train_step_dense_hw``): zero_grad + forward +
+        cross-entropy of the log-probs upsampled to the labels' size + backward; every trainable parameter's ``.grad`` is
+        OVERWRITTEN.  x: fp32 [B,3,H,W] (normalised) or uint8 [B,H,W,3]; y: any integer dtype [B, OH, OW] with OH >= H/patch,
+        OW >= W/patch; ``ignore_index`` (outside the classes) and -100 are skipped.  Returns {"loss", "pred": int32 [B, OH, OW]
+        (the pixel argmax of the step's own log-probs), "gt": the flat int64 labels, "probs": the low-res log-probs}."""
+        x, y = batch
+        self._require_gpu()
+        self._sync_weights(train=True)
+        self._sync_grads("grad")
+        x, kind, B, H, W = self._prep_batch(x)
+        dev = self.device
+        if y.dim() != 3 or y.shape[0] != B:
+            raise ValueError(f"expected pixel labels [B={B}, OH, OW], got {tuple(y.shape)}")
+        OH, OW = int(y.shape[1]), int(y.shape[2])
+        hp, wp = H // self.cfg.patch, W // self.cfg.patch
+        y = y.to(dev).reshape(-1).long().contiguous()
+        loss = torch.zeros((), dtype=torch.float32, device=dev)
+        logp = torch.empty((B * hp * wp, self.cfg.n_classes), dtype=torch.float32, device=dev)
+        capi.check(capi.lib().dinoseg_train_step_dense_hw(self._handle, x.data_ptr(), kind, B, H, W, OH, OW, y.data_ptr(), int(ignore_index),
+                                                          loss.data_ptr(), logp.data_ptr(), self._stream()))
+        self._fwd_epoch = getattr(self, "_fwd_epoch", 0) + 1
+        return {"loss": loss, "pred": self._dense_pred(logp, B, hp, wp, OH, OW), "gt": y, "probs": logp}
 
     def _autograd_forward(self, x: torch.Tensor, kind: int, B: int, H: int, W: int) -> torch.Tensor:
         self._sync_weights(train=True)
@@ -947,6 +1050,12 @@ class DINOSeg(nn.Module):
     def test_dataloader(self):
         self._no_dataset("test_dataloader")
 
+    def _eval_step(self, batch, batch_idx, test=False):
+        """fit()'s validation / test step: pixel labels ([B, OH, OW]) are scored per pixel, patch labels as before."""
+        if batch[1].dim() == 3:
+            return self.validation_step_dense(batch, batch_idx)
+        return self.test_step(batch, batch_idx) if test else self.validation_step(batch, batch_idx)
+
     def _fit_phase(self, train_dataloader, val_dataloader, ck_path, max_epochs, step):
         """One ``Trainer.fit`` of the reference: ``max_epochs`` epochs, validation after each, best ``val_acc`` checkpointed.
         Every phase starts from a FRESH optimizer (moments and per-parameter step counts dropped): the reference builds a new
@@ -957,7 +1066,7 @@ class DINOSeg(nn.Module):
         for epoch in range(max_epochs):
             cms, losses = [], []
             for bi, (x, y) in enumerate(train_dataloader):
-                out = self.fused_training_step((x, y), bi)
+                out = self.fused_training_step_dense((x, y), bi) if y.dim() == 3 else self.fused_training_step((x, y), bi)
                 self.fused_adam_step()
                 losses.append(out["loss"])
                 cm = torch.zeros((self.cfg.n_classes, self.cfg.n_classes), dtype=torch.int64, device=self.device)
@@ -968,7 +1077,7 @@ class DINOSeg(nn.Module):
             self.check_labels()
             metrics = self.validation_epoch_end(cms, prefix="train") if cms else {}
             metrics["train_loss"] = float(torch.stack(losses).mean()) if losses else float("nan")
-            metrics.update(self.validation_epoch_end([self.validation_step(b, i) for i, b in enumerate(val_dataloader)]))
+            metrics.update(self.validation_epoch_end([self._eval_step(b, i) for i, b in enumerate(val_dataloader)]))
             metrics["epoch"] = epoch
             history.append(metrics)
             if metrics["val_acc"] > best:
@@ -988,6 +1097,8 @@ class DINOSeg(nn.Module):
         main phase's best is what ``best_ck`` names.  The dataset / augmentation pipeline is out of scope,
         so the dataloaders are arguments (or the ``train_dataloader() / val_dataloader() / test_dataloader()`` hooks of a
         subclass): any iterables of ``(x, y)`` batches with x uint8 [B,H,W,3] or fp32 [B,3,H,W] and y int [B,(H/8)*(W/8)].
+        A batch whose y is [B, OH, OW] PIXEL labels (255 / -100 = void) trains through ``fused_training_step_dense`` and is
+        validated / tested through ``validation_step_dense``.
         Returns {'history': [per-epoch metrics of the main phase], 'sim_history': [...] or None, 'test': test metrics or None}."""
         import os
 
@@ -1024,7 +1135,7 @@ class DINOSeg(nn.Module):
         self.best_ck = ck_path if history else None
         test = None
         if test_dataloader is not None:
-            test = self.test_epoch_end([self.test_step(b, i) for i, b in enumerate(test_dataloader)])
+            test = self.test_epoch_end([self._eval_step(b, i, test=True) for i, b in enumerate(test_dataloader)])
         if self.comet_logger is not None and self.best_ck is not None:
             self.comet_logger.experiment.log_asset(self.best_ck)
         return {"history": history, "sim_history": sim_history, "test": test}

@@ -176,6 +176,26 @@ int dinoseg_op_upsample_argmax(const float* logp, int32_t B, int32_t hp, int32_t
 int dinoseg_forward_dense_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t OH, int32_t OW,
                              float* logp_out, int32_t* argmax_out, int32_t* labels_out, float* dense_out, void* stream);
 
+/* ---- pixel-resolution training loss (what ViT segmenters train on: F.cross_entropy(F.interpolate(scores, size=mask.shape,
+ * mode="bilinear", align_corners=False), mask, ignore_index=255)), without the [B, C, OH, OW] transient ----
+ *
+ * dinoseg_op_upsample_nll: with U = the bilinear upsample of logp (the coordinates and arithmetic of dinoseg_op_upsample_argmax) and
+ * n = the number of valid pixels of the batch,
+ *   loss  = (1/n) sum over valid pixels of logsumexp_c U[b,c,y,x] - U[b,t,y,x]                  -> *loss_out (device float)
+ *   dlogp = d loss / d logp, fp32 [B, hp*wp, C]: what dinoseg_backward takes (nullable: loss only)
+ *   logp   : fp32 [B, hp*wp, C];  labels: int64 [B, OH, OW];  1 <= C <= 256;  OH >= hp, OW >= wp
+ * A pixel is valid when 0 <= label < C.  ignore_index (outside [0, C), e.g. 255) and -100 are skipped; any other label is skipped
+ * too and sets flags[0] |= 1 (device int32, nullable).  n == 0: loss is NaN, dlogp all zeros.  n_valid_out (device float, nullable)
+ * receives n.  dlogp is summed in a fixed order without floating-point atomics: bit-identical from run to run; the loss sum uses
+ * atomics unless option "deterministic" is 1.  scratch: dinoseg_op_upsample_nll_scratch_bytes(...) bytes of device memory (one fp32
+ * per pixel plus reduction partials: at most 8 bytes per pixel + 64 KiB; -1 for a shape the op refuses).  Stream-ordered, no host
+ * synchronisation, capturable.  Null logp / labels / loss_out / scratch, a bad shape and an ignore_index inside [0, C) are refused
+ * on the host (-1) before anything is launched. */
+int64_t dinoseg_op_upsample_nll_scratch_bytes(int32_t B, int32_t hp, int32_t wp, int32_t C, int32_t OH, int32_t OW);
+int dinoseg_op_upsample_nll(const float* logp, int32_t B, int32_t hp, int32_t wp, int32_t C, int32_t OH, int32_t OW,
+                            const int64_t* labels, int32_t ignore_index, float* loss_out, float* dlogp_out, float* n_valid_out,
+                            int32_t* flags, void* scratch, void* stream);
+
 /* ---- fine-tune step (replaces DINOSeg.training_step + autograd + optimizer.step, pl_torch_modules.py:258-268) ---- */
 
 /* Bind (or, with NULL, unbind) the fp32 gradient buffer of a parameter, same shape as the bound weight.  A parameter
@@ -204,6 +224,13 @@ int dinoseg_train_step_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int3
 int dinoseg_train_forward_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, float* logp_out,
                              void* stream);
 int dinoseg_backward(dinoseg_handle* h, const float* dlogp, void* stream);
+/* The step on PIXEL labels: dinoseg_train_forward_hw, then dinoseg_op_upsample_nll of its log-probs against labels int64 [B, OH, OW]
+ * (OH >= H/patch, OW >= W/patch; ignore_index outside [0, n_classes)), then dinoseg_backward of that d logp -- the same three
+ * launches sequences, so the same loss and gradients bit for bit under option "deterministic".  The d logp buffer and the loss
+ * scratch live in the handle (sized on first use: warm the handle before capturing); an out-of-range label latches the flag
+ * dinoseg_train_status reads.  *loss_out (device float) receives the loss, logp_out (optional) the low-res log-probabilities. */
+int dinoseg_train_step_dense_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t OH, int32_t OW,
+                                const int64_t* labels, int32_t ignore_index, float* loss_out, float* logp_out, void* stream);
 
 /* Gradient stages of the backward, for overlapping the data-parallel all-reduce with it (no reference
  * counterpart: the reference trains on one GPU).  dinoseg_backward / dinoseg_train_step record an event on their stream when the
