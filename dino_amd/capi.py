@@ -145,6 +145,9 @@ SIGNATURES = {
     "dinoseg_op_upsample_nll_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "dinoseg_op_upsample_nll": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _i32, _fp, _fp, _fp, _fp, _vp, _vp]),
     "dinoseg_train_step_dense_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _i32, _fp, _fp, _vp]),
+    # multi-scale + flip ensemble at pixel resolution: K low-res log-prob grids -> mean softmax, its argmax and confidence
+    "dinoseg_op_upsample_ensemble_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "dinoseg_op_upsample_ensemble": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

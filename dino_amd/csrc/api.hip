@@ -1033,6 +1033,26 @@ extern "C" int dinoseg_op_upsample_argmax(const float* logp, int32_t B, int32_t 
     return launch_upsample_argmax(logp, B, hp, wp, C, OH, OW, labels_out, dense_out, reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int64_t dinoseg_op_upsample_ensemble_scratch_bytes(int32_t K, int32_t B, int32_t OH, int32_t OW) {
+    return upsample_ensemble_scratch_bytes(K, B, OH, OW);
+}
+
+extern "C" int dinoseg_op_upsample_ensemble(const float* const* logp, const int32_t* hp, const int32_t* wp, const int32_t* flip, int32_t K,
+                                            int32_t B, int32_t C, int32_t OH, int32_t OW, int32_t* labels_out, float* conf_out,
+                                            float* probs_out, void* scratch, void* stream) {
+    if (K < 1 || K > UPE_MAX_VIEWS) {
+        dinoseg_set_error("dinoseg_op_upsample_ensemble: %d views (1 <= K <= %d)", K, UPE_MAX_VIEWS);
+        return -1;
+    }
+    if (!logp || !hp || !wp || !flip) {
+        dinoseg_set_error("dinoseg_op_upsample_ensemble: null view table (logp, hp, wp and flip are host arrays of K entries)");
+        return -1;
+    }
+    UpEnsViews views = {};
+    for (int k = 0; k < K; ++k) views.v[k] = {logp[k], hp[k], wp[k], flip[k], 0};
+    return launch_upsample_ensemble(views, K, B, C, OH, OW, labels_out, conf_out, probs_out, scratch, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int dinoseg_op_confusion(const int32_t* pred, const int64_t* gt, int64_t n, int32_t n_classes, int64_t* cm, void* stream) {
     return launch_confusion(pred, gt, n, n_classes, cm, reinterpret_cast<hipStream_t>(stream));
 }

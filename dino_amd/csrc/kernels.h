@@ -295,6 +295,24 @@ long long upsample_nll_scratch_bytes(int B, int hp, int wp, int C, int OH, int O
 int upsample_nll_check(const char* who, int B, int hp, int wp, int C, int OH, int OW, int ignore_index);
 int launch_upsample_nll(const float* logp, int B, int hp, int wp, int C, int OH, int OW, const int64_t* labels, int ignore_index,
                         float* loss, float* dlogp, float* n_valid, int* flags, void* scratch, hipStream_t s);
+// Multi-scale + flip ensemble at pixel resolution (upsample_ensemble.hip): per pixel the mean over K views of softmax_c(that upsample
+// of view k's log-probs logp_k [B, hp_k*wp_k, C], the grid mirrored horizontally first when flip_k), in view order in fp32; labels int32
+// [B, OH, OW] = its first maximum, conf fp32 [B, OH, OW] = that maximum, probs fp32 [B, C, OH, OW] = the mean itself (each nullable, at
+// least one).  One launch, no atomics, no [B, C, OH, OW] transient; scratch: upsample_ensemble_scratch_bytes (4 K bytes per pixel).
+// The view table travels to the kernel by value.  upsample_ensemble_check: the host-side refusals alone (1 <= K <= 12, non-null views,
+// flip 0 / 1, upsample_check_shape per view, the summed footprints of a tile within the LDS).
+constexpr int UPE_MAX_VIEWS = 12;
+struct UpEnsView {
+    const float* logp;
+    int hp, wp, flip, pad_;
+};
+struct UpEnsViews {
+    UpEnsView v[UPE_MAX_VIEWS];
+};
+long long upsample_ensemble_scratch_bytes(int K, int B, int OH, int OW);
+int upsample_ensemble_check(const char* who, const UpEnsViews& views, int K, int B, int C, int OH, int OW);
+int launch_upsample_ensemble(const UpEnsViews& views, int K, int B, int C, int OH, int OW, int32_t* labels, float* conf, float* probs,
+                             void* scratch, hipStream_t s);
 
 // ---- fine-tune step (train.hip, attention_bwd.hip) ----
 struct AttnBwdParams {

@@ -1,5 +1,6 @@
-// The bilinear upsample's coordinate rule and tile plan, shared by upsample.hip (argmax / dense values) and upsample_loss.hip
-// (cross-entropy and its gradient): ONE copy of the integer arithmetic, so both sides interpolate the same values bit for bit.
+// The bilinear upsample's coordinate rule and tile plan, shared by upsample.hip (argmax / dense values), upsample_loss.hip
+// (cross-entropy and its gradient) and upsample_ensemble.hip (multi-scale + flip ensemble): ONE copy of the integer arithmetic, so
+// all of them interpolate the same values bit for bit.
 #pragma once
 #include "common.h"
 

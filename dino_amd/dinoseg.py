@@ -9,11 +9,13 @@ the model without a ROCm device raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import weakref
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 from . import capi
@@ -261,6 +263,17 @@ def dense_nll_loss(logp: torch.Tensor, y: torch.Tensor, grid, ignore_index: int 
 
 
 # --------------------------------------------------------------------------- the model
+ENSEMBLE_MAX_VIEWS = 12        # include/dinoseg.h: dinoseg_op_upsample_ensemble takes 1 .. 12 views
+
+
+def view_sizes(H: int, W: int, scales, patch: int) -> List[Tuple[int, int]]:
+    """The frame sizes of a multi-scale protocol: per scale s the H x W frame scaled by s and rounded to the nearest multiple of
+    the patch (halves up, at least one patch): ``H_k = patch * max(1, floor(H * s / patch + 0.5))``, the same for W."""
+    def one(v, s):
+        return patch * max(1, int(math.floor(v * s / patch + 0.5)))
+    return [(one(H, float(s)), one(W, float(s))) for s in scales]
+
+
 class DINOSeg(nn.Module):
     """DINO ViT + per-patch segmentation head on MI355X.
 
@@ -597,10 +610,87 @@ class DINOSeg(nn.Module):
         labels, dense, _ = self._run_dense(x, kind, B, H, W, OH, OW, want_dense=want_logp)
         return labels, dense
 
-    def predict_dense(self, img, size=None) -> np.ndarray:
+    # ---- multi-scale + flip ensemble at pixel resolution (csrc/upsample_ensemble.hip) ----
+    def _resize_view(self, x: torch.Tensor, kind: int, Hk: int, Wk: int) -> torch.Tensor:
+        """The batch resized to Hk x Wk: F.interpolate for fp32 [B,3,H,W], dinoseg_op_resize_u8 frame by frame for uint8 [B,H,W,3]."""
+        if kind != capi.INPUT_U8_HWC:
+            return F.interpolate(x, size=(Hk, Wk), mode="bilinear", align_corners=False).contiguous()
+        B, H, W = x.shape[0], x.shape[1], x.shape[2]
+        out = torch.empty((B, Hk, Wk, 3), dtype=torch.uint8, device=x.device)
+        for i in range(B):
+            capi.check(capi.lib().dinoseg_op_resize_u8(x.data_ptr() + i * H * W * 3, H, W, out.data_ptr() + i * Hk * Wk * 3, Hk, Wk,
+                                                      self._stream()))
+        return out
+
+    def _multiscale(self, x: torch.Tensor, scales, flip: bool, size, want_conf: bool, want_probs: bool):
+        """segment_multiscale, also returning the views' low-res log-probs and their (H_k, W_k, flip_k)."""
+        x, kind, B, H, W = self._prep_batch(x)
+        scales = tuple(float(s) for s in scales)
+        K = len(scales) * (2 if flip else 1)
+        if not 1 <= K <= ENSEMBLE_MAX_VIEWS:
+            raise ValueError(f"{len(scales)} scales{' with flip' if flip else ''} are {K} views; the ensemble takes 1 to {ENSEMBLE_MAX_VIEWS}")
+        if any(not (s > 0.0 and math.isfinite(s)) for s in scales):
+            raise ValueError(f"scales must be positive, got {scales}")
+        p = self.cfg.patch
+        OH, OW = self._out_size(size, (H, W))
+        views = [(Hk, Wk, f) for Hk, Wk in view_sizes(H, W, scales, p) for f in ((0, 1) if flip else (0,))]
+        for Hk, Wk, _ in views:
+            if Hk // p > OH or Wk // p > OW:
+                raise ValueError(f"the {Hk}x{Wk} view's grid {Hk // p}x{Wk // p} exceeds the output size {OH}x{OW} "
+                                 "(upsampling and identity only)")
+        self._require_gpu()
+        w_axis = 2 if kind == capi.INPUT_U8_HWC else 3
+        logps, xv, cur = [], None, None
+        for Hk, Wk, f in views:                         # scale-major, the unflipped view first: one resize per scale
+            if cur != (Hk, Wk):
+                xv, cur = (x if (Hk, Wk) == (H, W) else self._resize_view(x, kind, Hk, Wk)), (Hk, Wk)
+            xin = torch.flip(xv, dims=[w_axis]).contiguous() if f else xv
+            logps.append(self._run(xin, kind, B, Hk, Wk, want_logp=True)[0])
+        del xv, xin
+        dev = x.device
+        labels = torch.empty((B, OH, OW), dtype=torch.int32, device=dev)
+        conf = torch.empty((B, OH, OW), dtype=torch.float32, device=dev) if want_conf else None
+        probs = torch.empty((B, self.cfg.n_classes, OH, OW), dtype=torch.float32, device=dev) if want_probs else None
+        lib = capi.lib()
+        need = int(lib.dinoseg_op_upsample_ensemble_scratch_bytes(K, B, OH, OW))
+        if need < 0:
+            raise ValueError(f"bad ensemble shape: K={K} B={B} output {OH}x{OW}")
+        scratch = torch.empty((need,), dtype=torch.uint8, device=dev)
+        i32 = lambda xs: (C.c_int32 * K)(*xs)
+        capi.check(lib.dinoseg_op_upsample_ensemble((C.c_void_p * K)(*[t.data_ptr() for t in logps]), i32([v[0] // p for v in views]),
+                                                    i32([v[1] // p for v in views]), i32([v[2] for v in views]), K, B,
+                                                    self.cfg.n_classes, OH, OW, labels.data_ptr(), capi.ptr(conf), capi.ptr(probs),
+                                                    scratch.data_ptr(), self._stream()))
+        return labels, conf, probs, logps, views
+
+    @torch.no_grad()
+    def segment_multiscale(self, x: torch.Tensor, scales=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), flip: bool = True, size=None,
+                           want_conf: bool = False, want_probs: bool = False):
+        """The multi-scale + horizontal-flip ensemble (the evaluation protocol of ADE20K / COCO-Stuff / Pascal-Context segmenters):
+        uint8 [B,H,W,3] or fp32 [B,3,H,W] frames -> (labels int32 [B,OH,OW], conf fp32 [B,OH,OW] or None, probs fp32 [B,C,OH,OW] or
+        None).  The model runs on the frame at every scale (``view_sizes``: sizes rounded to the patch; a view at the frame's own
+        size is the frame itself, fp32 frames are resized by ``F.interpolate(..., mode="bilinear", align_corners=False)``, uint8
+        frames by ``dinoseg_op_resize_u8``) and, with ``flip``, on its mirror image (``torch.flip`` on the width axis); views are
+        ordered scale-major, the unflipped one first; at most 12.  One fused launch then interpolates every view's log-probs to
+        ``size`` (default (H, W)) -- a mirrored view's grid is flipped back first --, softmaxes each view, adds the probabilities
+        in view order and takes the first maximum per pixel: ``labels``, ``conf`` = the mean probability of that label, ``probs``
+        = the mean probabilities.  No [B,C,OH,OW] tensor exists unless ``want_probs``; the transient is one fp32 per view and pixel
+        plus the views' low-res log-probs.  A view whose grid exceeds ``size`` raises ``ValueError`` before any forward runs.
+        Inference only.
+
+        The library keeps one resampled position embedding and one workspace size, so every change of resolution between views
+        re-derives them: the views run in a fixed order with each size visited once (the flipped view right after the
+        unflipped one).  Measured (``tools/ensemble_cost.py``, ViT-S/8 x12 @480, batch 8, fp16): the K forwards in this order
+        against the same forwards each repeated at its own resolution differ by -1.0 .. +0.4 ms of 17 (3 views) to 90 ms (12
+        views) -- below what the medians resolve; the fused launch itself is 1.1 / 4.8 ms at 150 classes."""
+        labels, conf, probs, _, _ = self._multiscale(x, scales, flip, size, want_conf, want_probs)
+        return labels, conf, probs
+
+    def predict_dense(self, img, size=None, scales=None, flip: bool = False) -> np.ndarray:
         """The pixel-resolution sibling of ``predict()``: the image (PIL.Image or HxWx3 uint8 array) is resized to r x r on the
         device exactly as ``predict()`` does, the log-probabilities are upsampled to ``size`` (default: the IMAGE's own (rows,
-        cols)) and the per-pixel argmax comes back as an int64 map.  Eager launches (``predict()`` keeps its captured graph)."""
+        cols)) and the per-pixel argmax comes back as an int64 map.  Eager launches (``predict()`` keeps its captured graph).
+        With ``scales`` the labels are those of ``segment_multiscale(resized frame, scales, flip, size)`` instead."""
         with torch.no_grad():
             raw = np.asarray(img)
             if raw.dtype != np.uint8 or not raw.flags.c_contiguous:
@@ -616,7 +706,10 @@ class DINOSeg(nn.Module):
                 capi.check(capi.lib().dinoseg_op_resize_u8(frames.data_ptr(), raw.shape[0], raw.shape[1], resized.data_ptr(), r, r,
                                                           self._stream()))
                 frames = resized
-            labels, _, _ = self._run_dense(frames, capi.INPUT_U8_HWC, 1, r, r, OH, OW)
+            if scales is not None:
+                labels = self._multiscale(frames, scales, flip, (OH, OW), False, False)[0]
+            else:
+                labels, _, _ = self._run_dense(frames, capi.INPUT_U8_HWC, 1, r, r, OH, OW)
             return labels[0].cpu().numpy().astype(np.int64)
 
     def _predict_graph(self, r: int):
@@ -747,18 +840,25 @@ class DINOSeg(nn.Module):
                                                        cm.data_ptr(), self._stream()))
         return {"pred": amax, "gt": y, "probs": logp, "confusion": cm}
 
-    def validation_step_dense(self, batch, batch_idx=0):
+    def validation_step_dense(self, batch, batch_idx=0, scales=None, flip: bool = False):
         """``validation_step`` scored per pixel: ``y`` is [B, OH, OW] pixel labels, the prediction is ``segment`` at y's size and
         the confusion matrix counts pixels.  Labels outside [0, n_classes) -- 255 or -100 "void" -- are skipped by the confusion
         kernel.  Same keys as ``validation_step`` ("pred": the pixel labels, "probs": the low-res log-probs), so
-        ``validation_epoch_end`` takes its outputs unchanged."""
+        ``validation_epoch_end`` takes its outputs unchanged.  With ``scales`` the prediction is ``segment_multiscale(x, scales,
+        flip, size=y's)`` and "probs" the low-res log-probs of the unflipped scale-1.0 view (the first view's without one)."""
         x, y = batch
         self._require_gpu()
         with torch.no_grad():
             xx, kind, B, H, W = self._prep_batch(x)
             if y.dim() != 3 or y.shape[0] != B:
                 raise ValueError(f"expected pixel labels [B={B}, OH, OW], got {tuple(y.shape)}")
-            labels, _, logp = self._run_dense(xx, kind, B, H, W, int(y.shape[1]), int(y.shape[2]), want_logp=True)
+            if scales is not None:
+                labels, _, _, logps, views = self._multiscale(xx, scales, flip, (int(y.shape[1]), int(y.shape[2])), False, False)
+                own = [i for i, (s, v) in enumerate(zip([s for s in scales for _ in range(2 if flip else 1)], views))
+                       if float(s) == 1.0 and v[2] == 0]
+                logp = logps[own[0] if own else 0]
+            else:
+                labels, _, logp = self._run_dense(xx, kind, B, H, W, int(y.shape[1]), int(y.shape[2]), want_logp=True)
             y = y.to(self.device).reshape(-1).long().contiguous()
             cm = torch.zeros((self.cfg.n_classes, self.cfg.n_classes), dtype=torch.int64, device=self.device)
             capi.check(capi.lib().dinoseg_op_confusion(labels.data_ptr(), y.data_ptr(), y.numel(), self.cfg.n_classes,

@@ -196,6 +196,34 @@ int dinoseg_op_upsample_nll(const float* logp, int32_t B, int32_t hp, int32_t wp
                             const int64_t* labels, int32_t ignore_index, float* loss_out, float* dlogp_out, float* n_valid_out,
                             int32_t* flags, void* scratch, void* stream);
 
+/* ---- multi-scale + flip ensemble at pixel resolution (the standard evaluation protocol of ADE20K / COCO-Stuff / Pascal-Context
+ * segmenters: run the frame at several scales, each also mirrored, bring every view's scores to the output size, softmax each view,
+ * average, argmax), without any [B, C, OH, OW] transient ----
+ *
+ * dinoseg_op_upsample_ensemble: sum_k softmax_c(F.interpolate(grid_k, size=(OH, OW), mode="bilinear", align_corners=False)) / K with
+ * grid_k = logp[k].view(B, hp[k], wp[k], C).permute(0, 3, 1, 2), flipped along its width first when flip[k] == 1; one launch.
+ *   logp, hp, wp, flip : HOST arrays of K entries (as dinoseg_adam_step_multi takes its arrays); logp[k] a device pointer to fp32
+ *                        [B, hp[k]*wp[k], C], the layout the head writes; flip[k] 0 or 1; 1 <= K <= 12; 1 <= C <= 256
+ *   labels_out : int32 [B, OH, OW], the FIRST maximum over classes of the summed probabilities (nullable)
+ *   conf_out   : fp32 [B, OH, OW], that maximum / K: the ensemble's probability of the label (nullable)
+ *   probs_out  : fp32 [B, C, OH, OW], the mean probabilities in torch's layout (nullable); at least one output is required
+ *   scratch    : dinoseg_op_upsample_ensemble_scratch_bytes(K, B, OH, OW) bytes of device memory = one fp32 per view and pixel
+ *                (-1 for K or a size out of range)
+ * Per pixel, view k and class c: v_k[c] is the bilinear value with the coordinates and arithmetic of dinoseg_op_upsample_argmax
+ * (exact integer coordinates, a + (b - a) lambda along x and then along y); when flip[k] == 1 the two column taps are wp-1-i0 and
+ * wp-1-i1, in that order, with the same lambda, so a flipped view fed a mirrored grid is bit-identical to an unflipped view fed the
+ * original.  lse_k = m_k + logf(sum_c expf(v_k[c] - m_k)) with m_k the (running) maximum over classes, p_k[c] = expf(v_k[c] - lse_k)
+ * (expf of these arguments <= 0 is the hardware's 2^(x log2 e): within 3e-8 absolute of the libm value);
+ * s[c] = p_0[c] + p_1[c] + ... in view order in fp32; probs = s / K, conf = max_c s[c] / K.  No atomics: bit-identical from run to
+ * run.  Every view needs OH >= hp[k] and OW >= wp[k].  K outside 1..12, a null table or view pointer, a flip other than 0 / 1, all
+ * outputs null, a null scratch, a shape dinoseg_op_upsample_argmax refuses, and views whose footprints under one 64 x 32 output tile
+ * add up to more cells than the LDS holds (the message names the count) are refused on the host (-1) before anything is launched.
+ * Stream-ordered, no host synchronisation. */
+int64_t dinoseg_op_upsample_ensemble_scratch_bytes(int32_t K, int32_t B, int32_t OH, int32_t OW);
+int dinoseg_op_upsample_ensemble(const float* const* logp, const int32_t* hp, const int32_t* wp, const int32_t* flip, int32_t K, int32_t B,
+                                 int32_t C, int32_t OH, int32_t OW, int32_t* labels_out, float* conf_out, float* probs_out, void* scratch,
+                                 void* stream);
+
 /* ---- fine-tune step (replaces DINOSeg.training_step + autograd + optimizer.step, pl_torch_modules.py:258-268) ---- */
 
 /* Bind (or, with NULL, unbind) the fp32 gradient buffer of a parameter, same shape as the bound weight.  A parameter
