@@ -148,6 +148,10 @@ SIGNATURES = {
     # multi-scale + flip ensemble at pixel resolution: K low-res log-prob grids -> mean softmax, its argmax and confidence
     "dinoseg_op_upsample_ensemble_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "dinoseg_op_upsample_ensemble": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _vp, _vp]),
+    # sliding-window inference at pixel resolution: the window rule, the crop of a run of windows, the merge of their log-probs
+    "dinoseg_window_origins": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), _i32]),
+    "dinoseg_op_crop_windows": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "dinoseg_op_window_merge": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

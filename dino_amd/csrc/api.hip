@@ -1053,6 +1053,21 @@ extern "C" int dinoseg_op_upsample_ensemble(const float* const* logp, const int3
     return launch_upsample_ensemble(views, K, B, C, OH, OW, labels_out, conf_out, probs_out, scratch, reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int dinoseg_window_origins(int32_t L, int32_t win, int32_t stride, int32_t* out, int32_t cap) {
+    return window_origins(L, win, stride, out, cap);
+}
+
+extern "C" int dinoseg_op_crop_windows(const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t win_h, int32_t win_w,
+                                       int32_t stride_h, int32_t stride_w, int32_t first, int32_t count, void* out, void* stream) {
+    return launch_crop_windows(x, x_kind, B, H, W, win_h, win_w, stride_h, stride_w, first, count, out, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_window_merge(const float* logp, int32_t B, int32_t H, int32_t W, int32_t patch, int32_t win_h, int32_t win_w,
+                                       int32_t stride_h, int32_t stride_w, int32_t C, int32_t* labels_out, float* dense_out, void* stream) {
+    return launch_window_merge(logp, B, H, W, patch, win_h, win_w, stride_h, stride_w, C, labels_out, dense_out,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int dinoseg_op_confusion(const int32_t* pred, const int64_t* gt, int64_t n, int32_t n_classes, int64_t* cm, void* stream) {
     return launch_confusion(pred, gt, n, n_classes, cm, reinterpret_cast<hipStream_t>(stream));
 }

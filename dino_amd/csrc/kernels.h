@@ -314,6 +314,23 @@ int upsample_ensemble_check(const char* who, const UpEnsViews& views, int K, int
 int launch_upsample_ensemble(const UpEnsViews& views, int K, int B, int C, int OH, int OW, int32_t* labels, float* conf, float* probs,
                              void* scratch, hipStream_t s);
 
+// Sliding-window inference at pixel resolution (windows.hip).  The window rule per axis: g = max(L - w + s - 1, 0) / s + 1 windows at
+// o[i] = max(min(i s + w, L) - w, 0); windows of a frame row-major over (gy, gx), of a batch frame-major.
+// window_origins: the rule on the host (out == null with cap == 0 asks for g alone); -1 for w > L, s < 1 or too little room.
+// launch_crop_windows: windows [first, first + count) of x (kind 0: uint8 [B,H,W,3], 1: fp32 [B,3,H,W]) -> a contiguous batch of the
+// same kind ([count, wh, ww, 3] / [count, 3, wh, ww]; ww % 8 == 0, out 16-byte aligned), one launch.
+// launch_window_merge: logp fp32 [B gh gw, (wh/patch)(ww/patch), C] -> per pixel the mean over the windows that contain it of the
+// bilinear upsample of each window's grid to (wh, ww) (upsample.hip's coordinates and arithmetic), fp32 adds in window order, IEEE
+// division by the count: labels int32 [B,H,W] = its first maximum, dense fp32 [B,C,H,W] = the mean (each nullable, at least one).
+// One launch, no atomics, no scratch.  window_merge_check: the host-side refusals of the shape alone (C, patch, window / stride
+// values, more than 4 windows over a pixel row or column, integer ranges, the LDS plan).
+int window_origins(int L, int win, int stride, int32_t* out, int cap);
+int launch_crop_windows(const void* x, int kind, int B, int H, int W, int win_h, int win_w, int stride_h, int stride_w, int first,
+                        int count, void* out, hipStream_t s);
+int window_merge_check(const char* who, int B, int H, int W, int patch, int win_h, int win_w, int stride_h, int stride_w, int C);
+int launch_window_merge(const float* logp, int B, int H, int W, int patch, int win_h, int win_w, int stride_h, int stride_w, int C,
+                        int32_t* labels, float* dense, hipStream_t s);
+
 // ---- fine-tune step (train.hip, attention_bwd.hip) ----
 struct AttnBwdParams {
     const bf16_t* q; const bf16_t* k; const bf16_t* v; long qkv_plane;   // forward operands [planes][B,H,npad,64]

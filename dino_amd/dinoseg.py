@@ -274,6 +274,43 @@ def view_sizes(H: int, W: int, scales, patch: int) -> List[Tuple[int, int]]:
     return [(one(H, float(s)), one(W, float(s))) for s in scales]
 
 
+WINDOW_MAX_COVERAGE = 4        # include/dinoseg.h: dinoseg_op_window_merge takes at most 4 windows over a pixel row / column
+
+
+def window_origins(L: int, window: int, stride: int) -> List[int]:
+    """The origins of the sliding windows along one axis (mmsegmentation's ``slide_inference``): frame side ``L``, window
+    ``1 <= window <= L``, stride ``>= 1``; ``g = max(L - window + stride - 1, 0) // stride + 1`` windows at ``max(min(i * stride +
+    window, L) - window, 0)`` -- the last one is shifted back to end at ``L``.  The rule lives in the library
+    (``dinoseg_window_origins``, host only: no device needed)."""
+    L, window, stride = int(L), int(window), int(stride)
+    lib = capi.lib()
+    g = lib.dinoseg_window_origins(L, window, stride, None, 0)
+    if g < 1:
+        raise ValueError(f"bad window rule: frame side {L}, window {window}, stride {stride} (1 <= window <= frame side, stride >= 1)")
+    out = (C.c_int32 * g)()
+    if lib.dinoseg_window_origins(L, window, stride, out, g) != g:
+        raise capi.DinosegError(capi.last_error())
+    return list(out)
+
+
+def _pair(v, what: str) -> Tuple[int, int]:
+    try:
+        a, b = (v, v) if isinstance(v, (int, np.integer)) else v
+        return int(a), int(b)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be an integer or a pair of integers, got {v!r}") from None
+
+
+def _axis_coverage(origins: List[int], window: int) -> int:
+    """The most windows over one pixel of the axis (attained at a window's first pixel)."""
+    most, i = 1, 0
+    for j, oj in enumerate(origins):
+        while origins[i] + window <= oj:
+            i += 1
+        most = max(most, j - i + 1)
+    return most
+
+
 class DINOSeg(nn.Module):
     """DINO ViT + per-patch segmentation head on MI355X.
 
@@ -686,17 +723,115 @@ class DINOSeg(nn.Module):
         labels, conf, probs, _, _ = self._multiscale(x, scales, flip, size, want_conf, want_probs)
         return labels, conf, probs
 
-    def predict_dense(self, img, size=None, scales=None, flip: bool = False) -> np.ndarray:
+    # ---- sliding-window inference at pixel resolution (csrc/windows.hip) ----
+    def _window_plan(self, H: int, W: int, window, stride):
+        """The window and stride of a sliding-window call on H x W frames, per axis: ((wh, ww), (sh, sw), (gh, gw)).  Every
+        ``ValueError`` of the protocol is raised here, before any device use."""
+        p = self.cfg.patch
+        if H < p or W < p:
+            raise ValueError(f"frames of {H}x{W} are smaller than one {p}x{p} patch")
+        win, out_s, grid = _pair(window, "window"), [], []
+        st = (None, None) if stride is None else _pair(stride, "stride")
+        win = list(win)
+        for axis, L in enumerate((H, W)):
+            w, name = win[axis], ("vertical", "horizontal")[axis]
+            if w < 1:
+                raise ValueError(f"window must be positive, got {tuple(_pair(window, 'window'))}")
+            if w % p != 0:
+                raise ValueError(f"{name} window {w} is not a multiple of the patch ({p})")
+            w = min(w, (L // p) * p)                    # clamped to the largest patch multiple inside the frame
+            s = (2 * w) // 3 if st[axis] is None else st[axis]
+            if s < 1:
+                raise ValueError(f"stride must be positive, got {tuple(st)}")
+            origins = window_origins(L, w, s)
+            cov = _axis_coverage(origins, w)
+            if cov > WINDOW_MAX_COVERAGE:
+                raise ValueError(f"{name} coverage {cov}: window {w} at stride {s} puts {cov} windows over one pixel "
+                                 f"{'row' if axis == 0 else 'column'} (at most {WINDOW_MAX_COVERAGE} per axis)")
+            win[axis] = w
+            out_s.append(s)
+            grid.append(len(origins))
+        return tuple(win), tuple(out_s), tuple(grid)
+
+    def _prep_frames(self, x: torch.Tensor):
+        """The shape check of ``_prep_batch`` for frames of ANY size: (input kind, B, H, W)."""
+        if x.dtype == torch.uint8:
+            if x.dim() != 4 or x.shape[3] != 3:
+                raise ValueError(f"expected uint8 [B,H,W,3], got {tuple(x.shape)}")
+            return capi.INPUT_U8_HWC, x.shape[0], x.shape[1], x.shape[2]
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"expected [B,3,H,W], got {tuple(x.shape)}")
+        return capi.INPUT_F32_CHW, x.shape[0], x.shape[2], x.shape[3]
+
+    def _windows(self, x: torch.Tensor, window, stride, want_dense: bool, max_windows: int):
+        """segment_windows, also returning the windows' low-res log-probs [B*G, n, C]."""
+        kind, B, H, W = self._prep_frames(x)
+        (wh, ww), (sh, sw), (gh, gw) = self._window_plan(H, W, window, stride)
+        max_windows = int(max_windows)
+        if max_windows < 1:
+            raise ValueError(f"max_windows must be positive, got {max_windows}")
+        if B < 1:
+            raise ValueError("empty batch")
+        self._require_gpu()
+        dev, p, C_ = self.device, self.cfg.patch, self.cfg.n_classes
+        x = x.to(dev).contiguous() if kind == capi.INPUT_U8_HWC else x.to(device=dev, dtype=torch.float32).contiguous()
+        self._sync_weights()
+        lib, total, n = capi.lib(), B * gh * gw, (wh // p) * (ww // p)
+        logp = torch.empty((total, n, C_), dtype=torch.float32, device=dev)
+        for first in range(0, total, max_windows):      # the flattened window list in chunks, each chunk one crop + one forward
+            count = min(max_windows, total - first)
+            if kind == capi.INPUT_U8_HWC:
+                crop = torch.empty((count, wh, ww, 3), dtype=torch.uint8, device=dev)
+            else:
+                crop = torch.empty((count, 3, wh, ww), dtype=torch.float32, device=dev)
+            capi.check(lib.dinoseg_op_crop_windows(x.data_ptr(), kind, B, H, W, wh, ww, sh, sw, first, count, crop.data_ptr(),
+                                                   self._stream()))
+            capi.check(lib.dinoseg_forward_hw(self._handle, crop.data_ptr(), kind, count, wh, ww,
+                                              logp.data_ptr() + 4 * first * n * C_, None, -1, None, self._stream()))
+        del crop
+        labels = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+        dense = torch.empty((B, C_, H, W), dtype=torch.float32, device=dev) if want_dense else None
+        capi.check(lib.dinoseg_op_window_merge(logp.data_ptr(), B, H, W, p, wh, ww, sh, sw, C_, labels.data_ptr(), capi.ptr(dense),
+                                               self._stream()))
+        return labels, dense, logp
+
+    @torch.no_grad()
+    def segment_windows(self, x: torch.Tensor, window=(480, 480), stride=None, want_logp: bool = False, max_windows: int = 32):
+        """Sliding-window inference (mmsegmentation's ``mode='slide'``): uint8 [B,H,W,3] or fp32 [B,3,H,W] frames of ANY
+        ``H, W >= patch`` -> (labels int32 [B,H,W], dense fp32 [B,C,H,W] or None).  The frame is cut into windows of ``window``
+        pixels (an integer or (rows, cols), multiples of the patch; clamped per axis to the largest patch multiple inside the
+        frame) at ``stride`` (default ``(2 * window) // 3`` per axis: 480 -> 320) by the rule of ``window_origins`` -- the last
+        row and column of windows are shifted back to end at the frame's edge, so the frame itself is never resized.  The
+        flattened window list (frame-major, then row-major) is cropped and run through the forward in chunks of at most
+        ``max_windows`` windows; one fused launch then interpolates every window's log-probs to pixel resolution, averages them
+        where windows overlap (fp32 adds in window order, divided by the count) and takes the first maximum per pixel.
+        ``want_logp=True`` also returns those mean log-probabilities.  No [B,C,H,W] tensor exists otherwise: the transient is the
+        windows' low-res log-probs and one chunk of cropped windows.  A window or stride that is not positive, a window that is
+        not a patch multiple, and more than 4 windows over one pixel row or column (any stride >= window / 3 is fine) raise
+        ``ValueError`` before any forward runs.  Inference only."""
+        labels, dense, _ = self._windows(x, window, stride, want_logp, max_windows)
+        return labels, dense
+
+    def predict_dense(self, img, size=None, scales=None, flip: bool = False, window=None, stride=None) -> np.ndarray:
         """The pixel-resolution sibling of ``predict()``: the image (PIL.Image or HxWx3 uint8 array) is resized to r x r on the
         device exactly as ``predict()`` does, the log-probabilities are upsampled to ``size`` (default: the IMAGE's own (rows,
         cols)) and the per-pixel argmax comes back as an int64 map.  Eager launches (``predict()`` keeps its captured graph).
-        With ``scales`` the labels are those of ``segment_multiscale(resized frame, scales, flip, size)`` instead."""
+        With ``scales`` the labels are those of ``segment_multiscale(resized frame, scales, flip, size)`` instead.
+        With ``window`` the image is NOT resized: it is segmented at its own size by ``segment_windows(image, window, stride)``
+        (``size`` other than the image's own, and ``scales``, raise ``ValueError``)."""
         with torch.no_grad():
             raw = np.asarray(img)
             if raw.dtype != np.uint8 or not raw.flags.c_contiguous:
                 raw = np.ascontiguousarray(raw, dtype=np.uint8)
             if raw.ndim != 3 or raw.shape[2] != 3:
                 raise ValueError(f"expected an HxWx3 image, got {raw.shape}")
+            if window is not None:
+                if scales is not None:
+                    raise ValueError("window and scales cannot be combined")
+                if size is not None and tuple(int(v) for v in size) != tuple(raw.shape[:2]):
+                    raise ValueError(f"with window the image is segmented at its own size {tuple(raw.shape[:2])}, got size={tuple(size)}")
+                labels = self._windows(torch.from_numpy(raw).unsqueeze(0), window, stride, False, 32)[0]
+                return labels[0].cpu().numpy().astype(np.int64)
             r = self.resolution
             self._require_gpu()
             OH, OW = self._out_size(size, raw.shape[:2])
@@ -840,13 +975,17 @@ class DINOSeg(nn.Module):
                                                        cm.data_ptr(), self._stream()))
         return {"pred": amax, "gt": y, "probs": logp, "confusion": cm}
 
-    def validation_step_dense(self, batch, batch_idx=0, scales=None, flip: bool = False):
+    def validation_step_dense(self, batch, batch_idx=0, scales=None, flip: bool = False, window=None, stride=None):
         """``validation_step`` scored per pixel: ``y`` is [B, OH, OW] pixel labels, the prediction is ``segment`` at y's size and
         the confusion matrix counts pixels.  Labels outside [0, n_classes) -- 255 or -100 "void" -- are skipped by the confusion
         kernel.  Same keys as ``validation_step`` ("pred": the pixel labels, "probs": the low-res log-probs), so
         ``validation_epoch_end`` takes its outputs unchanged.  With ``scales`` the prediction is ``segment_multiscale(x, scales,
-        flip, size=y's)`` and "probs" the low-res log-probs of the unflipped scale-1.0 view (the first view's without one)."""
+        flip, size=y's)`` and "probs" the low-res log-probs of the unflipped scale-1.0 view (the first view's without one).
+        With ``window`` the prediction is ``segment_windows(x, window, stride)`` on frames of any size, ``y`` has the frames' own
+        H x W, and "probs" is the windows' low-res log-probs [B*G, n, C]; ``window`` with ``scales`` raises ``ValueError``."""
         x, y = batch
+        if window is not None:
+            return self._validation_step_windows(x, y, scales, window, stride)
         self._require_gpu()
         with torch.no_grad():
             xx, kind, B, H, W = self._prep_batch(x)
@@ -859,6 +998,20 @@ class DINOSeg(nn.Module):
                 logp = logps[own[0] if own else 0]
             else:
                 labels, _, logp = self._run_dense(xx, kind, B, H, W, int(y.shape[1]), int(y.shape[2]), want_logp=True)
+            y = y.to(self.device).reshape(-1).long().contiguous()
+            cm = torch.zeros((self.cfg.n_classes, self.cfg.n_classes), dtype=torch.int64, device=self.device)
+            capi.check(capi.lib().dinoseg_op_confusion(labels.data_ptr(), y.data_ptr(), y.numel(), self.cfg.n_classes,
+                                                       cm.data_ptr(), self._stream()))
+        return {"pred": labels, "gt": y, "probs": logp, "confusion": cm}
+
+    def _validation_step_windows(self, x, y, scales, window, stride):
+        if scales is not None:
+            raise ValueError("window and scales cannot be combined")
+        with torch.no_grad():
+            _, B, H, W = self._prep_frames(x)
+            if y.dim() != 3 or tuple(y.shape) != (B, H, W):
+                raise ValueError(f"expected pixel labels [B={B}, {H}, {W}] (the frames' own size), got {tuple(y.shape)}")
+            labels, _, logp = self._windows(x, window, stride, False, 32)
             y = y.to(self.device).reshape(-1).long().contiguous()
             cm = torch.zeros((self.cfg.n_classes, self.cfg.n_classes), dtype=torch.int64, device=self.device)
             capi.check(capi.lib().dinoseg_op_confusion(labels.data_ptr(), y.data_ptr(), y.numel(), self.cfg.n_classes,

@@ -224,6 +224,48 @@ int dinoseg_op_upsample_ensemble(const float* const* logp, const int32_t* hp, co
                                  int32_t C, int32_t OH, int32_t OW, int32_t* labels_out, float* conf_out, float* probs_out, void* scratch,
                                  void* stream);
 
+/* ---- sliding-window inference at pixel resolution (mmsegmentation's mode='slide'; the evaluation protocol of Segmenter, SETR and
+ * the DINO-based ADE20K / Pascal-Context segmenters for frames larger than the training size): cut the frame into overlapping
+ * windows of the training size, run the model on every window, bring each window's scores to pixel resolution, average them where
+ * windows overlap, argmax -- without a [B, C, H, W] accumulator ----
+ *
+ * The window rule, per axis, with frame side L, window w (1 <= w <= L) and stride s (>= 1), in integers:
+ *   g    = max(L - w + s - 1, 0) / s + 1                   windows
+ *   o[i] = max(min(i s + w, L) - w, 0),  i = 0 .. g-1      their origins: the last window is shifted back so that it ends at L
+ * Windows of a frame are ordered row-major over (gy, gx), windows of a batch frame-major: window (b, gy, gx) has the index
+ * (b gh + gy) gw + gx in the flattened list of B gh gw windows.  Origins need not be multiples of the patch, and H, W need not be.
+ *
+ * dinoseg_window_origins (host only, no device): writes o[0 .. g-1] to out (room for cap entries) and returns g; with out == NULL and
+ * cap == 0 it returns g alone.  -1 for w > L, w < 1, s < 1 or cap < g. */
+int dinoseg_window_origins(int32_t L, int32_t win, int32_t stride, int32_t* out, int32_t cap);
+/* dinoseg_op_crop_windows: windows [first, first + count) of the flattened list, gathered into one contiguous batch that
+ * dinoseg_forward_hw takes, in one launch.
+ *   x   : the frames, x_kind 0 = uint8 [B, H, W, 3], 1 = fp32 [B, 3, H, W]
+ *   out : uint8 [count, win_h, win_w, 3] or fp32 [count, 3, win_h, win_w]; 16-byte aligned (the start of an allocation)
+ * win_w is a multiple of 8 (the destination is written with vector stores; the source is read element by element, a window starts
+ * at any pixel).  Null pointers, an x_kind other than 0 / 1, non-positive sizes or strides, a window larger than the frame, and
+ * first < 0, count < 1 or first + count > B gh gw are refused on the host (-1) before anything is launched. */
+int dinoseg_op_crop_windows(const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t win_h, int32_t win_w,
+                            int32_t stride_h, int32_t stride_w, int32_t first, int32_t count, void* out, void* stream);
+/* dinoseg_op_window_merge: the log-probs of all windows -> pixel-resolution mean and labels, in ONE launch.
+ *   logp       : fp32 [B gh gw, (win_h/patch) (win_w/patch), C], the layout the head writes for the window batch in the order above
+ *   labels_out : int32 [B, H, W], the FIRST maximum over classes of the mean (nullable)
+ *   dense_out  : fp32 [B, C, H, W], the mean log-probs in torch's layout (nullable); at least one output is required
+ *   1 <= C <= 256; patch 8 or 16; win_h, win_w multiples of the patch, win_h <= H, win_w <= W; strides >= 1; any H, W
+ * Per pixel (y, x) and class c: for every window that contains the pixel, in window order, u_w[c] is the bilinear value of that
+ * window's grid at the window's local pixel (y - oy, x - ox), upsampled from (win_h/patch, win_w/patch) to (win_h, win_w) with the
+ * coordinates and arithmetic of dinoseg_op_upsample_argmax (exact integer coordinates, a + (b - a) lambda along x and then along
+ * y);  m[c] = (u_w0[c] + u_w1[c] + ...) / (float)n with fp32 adds in window order, n the number of windows that contain the pixel,
+ * and an IEEE division;  dense = m, label = the first maximum of m.  No atomics and no scratch: bit-identical from run to run; one
+ * window equal to the frame gives exactly dinoseg_op_upsample_argmax.
+ * Accepted: every frame in which no pixel row lies in more than 4 window rows and no pixel column in more than 4 window columns
+ * (at most 16 windows over a pixel); any stride >= ceil(window / 3) qualifies.  Denser coverage is refused with a message that
+ * names it.  Also refused on the host (-1) before anything is launched: a null logp, both outputs null, C outside 1..256, a patch
+ * other than 8 or 16, window sides that are not patch multiples, a window larger than the frame, non-positive strides or sizes,
+ * and sizes beyond the integer ranges of dinoseg_op_upsample_argmax.  Stream-ordered, no host synchronisation. */
+int dinoseg_op_window_merge(const float* logp, int32_t B, int32_t H, int32_t W, int32_t patch, int32_t win_h, int32_t win_w,
+                            int32_t stride_h, int32_t stride_w, int32_t C, int32_t* labels_out, float* dense_out, void* stream);
+
 /* ---- fine-tune step (replaces DINOSeg.training_step + autograd + optimizer.step, pl_torch_modules.py:258-268) ---- */
 
 /* Bind (or, with NULL, unbind) the fp32 gradient buffer of a parameter, same shape as the bound weight.  A parameter
