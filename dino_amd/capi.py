@@ -152,6 +152,8 @@ SIGNATURES = {
     "dinoseg_window_origins": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), _i32]),
     "dinoseg_op_crop_windows": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dinoseg_op_window_merge": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _vp]),
+    # augmentation of fine-tuning frames and masks from a per-frame table (int32 [B, 36] on the device): warp + colour + labels, blur
+    "dinoseg_op_augment": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _fp, _fp, _i32, _fp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1068,6 +1068,13 @@ extern "C" int dinoseg_op_window_merge(const float* logp, int32_t B, int32_t H, 
                                reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int dinoseg_op_augment(const uint8_t* frames, const void* masks, int32_t mask_kind, int32_t B, int32_t H, int32_t W,
+                                  const dinoseg_augment_frame* table, int32_t max_radius, int32_t OH, int32_t OW, int32_t out_kind, void* out,
+                                  int64_t* pixel_labels, int64_t* patch_labels, int32_t patch, float* scratch, void* stream) {
+    return launch_augment(frames, masks, mask_kind, B, H, W, table, max_radius, OH, OW, out_kind, out, pixel_labels, patch_labels, patch,
+                          scratch, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int dinoseg_op_confusion(const int32_t* pred, const int64_t* gt, int64_t n, int32_t n_classes, int64_t* cm, void* stream) {
     return launch_confusion(pred, gt, n, n_classes, cm, reinterpret_cast<hipStream_t>(stream));
 }

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct dinoseg_augment_frame;       // include/dinoseg.h: one frame's augmentation parameters (36 words)
+
 namespace dseg {
 
 typedef uint16_t bf16_t;
@@ -330,6 +332,15 @@ int launch_crop_windows(const void* x, int kind, int B, int H, int W, int win_h,
 int window_merge_check(const char* who, int B, int H, int W, int patch, int win_h, int win_w, int stride_h, int stride_w, int C);
 int launch_window_merge(const float* logp, int B, int H, int W, int patch, int win_h, int win_w, int stride_h, int stride_w, int C,
                         int32_t* labels, float* dense, hipStream_t s);
+
+// Augmentation of fine-tuning frames and masks (augment.hip; the rule: include/dinoseg.h, dinoseg_op_augment).  frames uint8 [B,H,W,3],
+// masks uint8 / int64 [B,H,W] (nullable, with both label outputs), table a DEVICE array of B records -> out in out_kind (uint8
+// [B,OH,OW,3] / normalised fp32 [B,3,OH,OW]), int64 pixel labels [B,OH,OW] and patch labels [B,(OH/patch)(OW/patch)] (each nullable).
+// max_radius == 0: one launch (warp + colour + labels + conversion); otherwise the warp launch writes the fp32 planar scratch
+// [B,3,OH,OW] and the blur launch (tile + halo in LDS, both passes without HBM in between) writes out.  Every refusal is on the host.
+int launch_augment(const uint8_t* frames, const void* masks, int mask_kind, int B, int H, int W, const dinoseg_augment_frame* table,
+                   int max_radius, int OH, int OW, int out_kind, void* out, int64_t* pixel_labels, int64_t* patch_labels, int patch,
+                   float* scratch, hipStream_t s);
 
 // ---- fine-tune step (train.hip, attention_bwd.hip) ----
 struct AttnBwdParams {

@@ -1167,6 +1167,69 @@ class DINOSeg(nn.Module):
         self._fwd_epoch = getattr(self, "_fwd_epoch", 0) + 1
         return {"loss": loss, "pred": logp.argmax(dim=-1).detach(), "gt": y, "probs": logp}
 
+    # ---- augmentation of a training batch on the device (csrc/augment.hip; the table: dino_amd/augment.py) ----
+    @torch.no_grad()
+    def augment(self, x: torch.Tensor, y: Optional[torch.Tensor], table: torch.Tensor, out=None, out_kind: str = "f32",
+                labels: str = "pixel"):
+        """Warp, colour-jitter and blur a batch of frames, and warp their label masks, by a per-frame parameter table
+        (``dino_amd.augment.augment_table`` / ``draw_reference_augment``; the rule is stated at ``dinoseg_op_augment`` in
+        ``include/dinoseg.h``): one launch, or two when a frame is blurred.  ``x``: uint8 [B,H,W,3]; ``y``: None or an integer
+        [B,H,W] mask (uint8 and int64 are read as they are, other integer dtypes are widened); ``table``: int32 [B,36], checked on
+        the host before it is uploaded; ``out`` = (OH, OW), default the frames' own size.  Returns ``(image, labels)``: the image
+        is normalised fp32 [B,3,OH,OW] (``out_kind="f32"``) or uint8 [B,OH,OW,3] (``"u8"``) -- what ``forward`` /
+        ``forward_frames`` and the training steps take; the labels are int64 [B,OH,OW] (``labels="pixel"``) or int64
+        [B,(OH/p)*(OW/p)] (``"patch"``: the pixel label at every patch's first pixel, the reference's nearest resize to the patch
+        grid; OH and OW must then be patch multiples), or None without ``y``.  Needs the device, not the weights.  The fp32
+        scratch of the blur ([B,3,OH,OW]) is allocated only when a radius is non-zero."""
+        from .augment import validate_table
+
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+            raise ValueError(f"expected uint8 [B,H,W,3] frames, got {getattr(x, 'dtype', type(x).__name__)} "
+                             f"{tuple(getattr(x, 'shape', ()))}")
+        B, H, W = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+        if B < 1 or H < 1 or W < 1:
+            raise ValueError("empty batch")
+        if out_kind not in ("f32", "u8"):
+            raise ValueError(f"out_kind must be 'f32' or 'u8', got {out_kind!r}")
+        if labels not in ("pixel", "patch"):
+            raise ValueError(f"labels must be 'pixel' or 'patch', got {labels!r}")
+        OH, OW = (H, W) if out is None else _pair(out, "out")
+        if min(OH, OW) < 1 or max(H, W, OH, OW) > 16384:
+            raise ValueError(f"frame sides must be in 1..16384 (source {H} x {W}, output {OH} x {OW})")
+        if y is not None:
+            if not isinstance(y, torch.Tensor) or y.is_floating_point() or y.dtype == torch.bool or tuple(y.shape) != (B, H, W):
+                raise ValueError(f"expected an integer mask [B={B}, {H}, {W}], got {getattr(y, 'dtype', type(y).__name__)} "
+                                 f"{tuple(getattr(y, 'shape', ()))}")
+            p = self.cfg.patch
+            if labels == "patch" and (OH % p != 0 or OW % p != 0):
+                raise ValueError(f"labels='patch' needs an output that is a multiple of the patch ({p}), got {OH} x {OW}")
+        rmax = validate_table(table, B, OH, OW)
+        self._require_gpu()
+        dev = self.device
+        x = x.to(dev).contiguous()
+        table = table.to(dev).contiguous()
+        mask_kind = 0
+        if y is not None:
+            y = y.to(dev)
+            if y.dtype != torch.uint8:
+                y, mask_kind = y.long(), 1
+            y = y.contiguous()
+        if out_kind == "u8":
+            img = torch.empty((B, OH, OW, 3), dtype=torch.uint8, device=dev)
+        else:
+            img = torch.empty((B, 3, OH, OW), dtype=torch.float32, device=dev)
+        lab = None
+        if y is not None:
+            shape = (B, OH, OW) if labels == "pixel" else (B, (OH // self.cfg.patch) * (OW // self.cfg.patch))
+            lab = torch.empty(shape, dtype=torch.int64, device=dev)
+        scratch = torch.empty((B, 3, OH, OW), dtype=torch.float32, device=dev) if rmax > 0 else None
+        capi.check(capi.lib().dinoseg_op_augment(
+            x.data_ptr(), capi.ptr(y), mask_kind, B, H, W, table.data_ptr(), rmax, OH, OW,
+            capi.INPUT_U8_HWC if out_kind == "u8" else capi.INPUT_F32_CHW, img.data_ptr(),
+            capi.ptr(lab) if labels == "pixel" else None, capi.ptr(lab) if labels == "patch" else None, self.cfg.patch,
+            capi.ptr(scratch), self._stream()))
+        return img, lab
+
     # ---- the step on pixel labels (upsample + cross-entropy + its gradient, fused: csrc/upsample_loss.hip) ----
     def _dense_pred(self, logp: torch.Tensor, B: int, hp: int, wp: int, OH: int, OW: int) -> torch.Tensor:
         pred = torch.empty((B, OH, OW), dtype=torch.int32, device=logp.device)
@@ -1291,8 +1354,9 @@ class DINOSeg(nn.Module):
 
     def _no_dataset(self, what):
         raise NotImplementedError(
-            f"DINOSeg.{what}(): the DuckieSegDataset / albumentations pipeline (pl_torch_modules.py:347-365) is not part of "
-            "dino_amd (DESIGN.md section 6); pass dataloaders to fit(), or override this hook in a subclass")
+            f"DINOSeg.{what}(): the DuckieSegDataset file reader (pl_torch_modules.py:347-365) is not part of dino_amd (DESIGN.md "
+            "section 6); pass dataloaders of raw uint8 frames and masks to fit(), or override this hook in a subclass.  The "
+            "augmentations of get_augmented_transforms() run on the device: fit(augment=dino_amd.Augmenter(...))")
 
     def train_dataloader(self, sim=False):
         self._no_dataset("train_dataloader")
@@ -1309,7 +1373,7 @@ class DINOSeg(nn.Module):
             return self.validation_step_dense(batch, batch_idx)
         return self.test_step(batch, batch_idx) if test else self.validation_step(batch, batch_idx)
 
-    def _fit_phase(self, train_dataloader, val_dataloader, ck_path, max_epochs, step):
+    def _fit_phase(self, train_dataloader, val_dataloader, ck_path, max_epochs, step, augment=None):
         """One ``Trainer.fit`` of the reference: ``max_epochs`` epochs, validation after each, best ``val_acc`` checkpointed.
         Every phase starts from a FRESH optimizer (moments and per-parameter step counts dropped): the reference builds a new
         ``Trainer`` per phase and per ``fit()`` call, so ``configure_optimizers()`` runs again (pl_torch_modules.py:391-421)."""
@@ -1319,6 +1383,8 @@ class DINOSeg(nn.Module):
         for epoch in range(max_epochs):
             cms, losses = [], []
             for bi, (x, y) in enumerate(train_dataloader):
+                if augment is not None:
+                    x, y = augment(self, x, y)
                 out = self.fused_training_step_dense((x, y), bi) if y.dim() == 3 else self.fused_training_step((x, y), bi)
                 self.fused_adam_step()
                 losses.append(out["loss"])
@@ -1339,7 +1405,7 @@ class DINOSeg(nn.Module):
         return history, step
 
     def fit(self, ck_file_name=None, train_dataloader=None, val_dataloader=None, test_dataloader=None, max_epochs=None,
-            sim_dataloader=None):
+            sim_dataloader=None, augment=None):
         """The reference's ``fit`` (pl_torch_modules.py:367-431) without Lightning: freeze / unfreeze the backbone, train
         ``max_epochs`` epochs with ``fused_training_step`` + the fused optimizer step, validate after every epoch
         (``check_val_every_n_epoch=1``), keep the checkpoint with the best ``val_acc`` (``ModelCheckpoint(monitor='val_acc',
@@ -1347,11 +1413,15 @@ class DINOSeg(nn.Module):
         ``self.best_ck``.  With ``pretrain_on_sim=True`` (ctor kwarg, :391-401) a first phase of ``max_epochs`` epochs runs on
         ``sim_dataloader`` (validated on the REAL validation split, like the reference's ``val_dataloader(sim=False)``) before the
         main phase; each phase tracks its own best ``val_acc`` (the reference builds a fresh ``ModelCheckpoint`` per phase), the
-        main phase's best is what ``best_ck`` names.  The dataset / augmentation pipeline is out of scope,
+        main phase's best is what ``best_ck`` names.  The dataset reader is out of scope,
         so the dataloaders are arguments (or the ``train_dataloader() / val_dataloader() / test_dataloader()`` hooks of a
         subclass): any iterables of ``(x, y)`` batches with x uint8 [B,H,W,3] or fp32 [B,3,H,W] and y int [B,(H/8)*(W/8)].
         A batch whose y is [B, OH, OW] PIXEL labels (255 / -100 = void) trains through ``fused_training_step_dense`` and is
         validated / tested through ``validation_step_dense``.
+        ``augment``: None, or a callable ``(model, x, y) -> (x, y)`` -- a ``dino_amd.Augmenter``, the reference's
+        ``get_augmented_transforms()`` recipe on the device (uint8 [B,H,W,3] frames and integer [B,H,W] masks in; its ``labels``
+        choose patch or pixel labels out) -- that every TRAIN batch of both phases passes through before the step; validation
+        and test batches are untouched.  With None, fit runs exactly the calls it ran without the argument.
         Returns {'history': [per-epoch metrics of the main phase], 'sim_history': [...] or None, 'test': test metrics or None}."""
         import os
 
@@ -1383,8 +1453,8 @@ class DINOSeg(nn.Module):
         epochs = self.max_epochs if max_epochs is None else max_epochs
         sim_history, step = None, 0
         if self.pretrain_on_sim:
-            sim_history, step = self._fit_phase(sim_dataloader, val_dataloader, ck_path, epochs, 0)
-        history, step = self._fit_phase(train_dataloader, val_dataloader, ck_path, epochs, 0)
+            sim_history, step = self._fit_phase(sim_dataloader, val_dataloader, ck_path, epochs, 0, augment)
+        history, step = self._fit_phase(train_dataloader, val_dataloader, ck_path, epochs, 0, augment)
         self.best_ck = ck_path if history else None
         test = None
         if test_dataloader is not None:

@@ -266,6 +266,60 @@ int dinoseg_op_crop_windows(const void* x, int32_t x_kind, int32_t B, int32_t H,
 int dinoseg_op_window_merge(const float* logp, int32_t B, int32_t H, int32_t W, int32_t patch, int32_t win_h, int32_t win_w,
                             int32_t stride_h, int32_t stride_w, int32_t C, int32_t* labels_out, float* dense_out, void* stream);
 
+/* ---- augmentation of fine-tuning frames and label masks on the device (the reference's get_augmented_transforms(),
+ * pl_torch_modules.py:44-57: RandomResizedCrop, ShiftScaleRotate, HorizontalFlip, ColorJitter(brightness), GaussianBlur, Normalize,
+ * the mask nearest-resized to the patch grid) as one or two launches.  The device code is a pure function of an explicit per-frame
+ * table: no device random numbers, integer (Q16) coordinates, no atomics -- bit-identical from run to run.  The randomness lives in
+ * the host function that fills the table (dino_amd.augment.draw_reference_augment). ----
+ *
+ * One frame's parameters, 36 32-bit words (Python: a row of an int32 [B, 36] tensor, the floats bit-cast). */
+typedef struct dinoseg_augment_frame {
+    int32_t a[6];        /* inverse affine, OUTPUT pixel (ox, oy) -> source, in Q16 (units of 2^-16 source pixel), evaluated in int64:
+                            Ux = a0 ox + a1 oy + a2,  Uy = a3 ox + a4 oy + a5.  U is the continuous source coordinate in edge
+                            convention (source pixel i covers [i, i+1)); a2 and a5 already contain the output half-pixel term
+                            (a0 + a1) / 2 resp. (a3 + a4) / 2 */
+    int32_t border;      /* 0 = reflect-101 (OpenCV's default, what the reference's ShiftScaleRotate uses), 1 = constant; read as
+                            border & 1 */
+    int32_t void_label;  /* the label written where the nearest source pixel is outside the frame, under border = 1 */
+    float fill[3];       /* RGB in 0..255: the value of every bilinear TAP outside the frame under border = 1 (per tap, as
+                            cv2.BORDER_CONSTANT and grid_sample(padding_mode="zeros") do) */
+    float gain, bias, sat; /* colour: v = fmaf(gain, v, bias) per channel; g = 0.299 r + 0.587 g + 0.114 b of those;
+                            v = fmaf(sat, v - g, g); clamp to [0, 255] */
+    int32_t radius;      /* Gaussian radius r, 0..20 (kernel size 2r + 1 <= 41); 0 = no blur; clamped to [0, max_radius] on the device */
+    float w[21];         /* taps w[|d|], d = -r..r, normalised by the host in fp64; entries past r are ignored */
+} dinoseg_augment_frame;
+/* The rule, per output pixel (ox, oy) of frame b:
+ *   image : Vx = Ux - 32768, x0 = Vx >> 16 (arithmetic), lx = (float)(Vx & 0xFFFF) / 65536.f; the same for y.  The four taps
+ *           (y0, x0), (y0, x0+1), (y0+1, x0), (y0+1, x0+1), every index folded by the border rule: reflect-101 with side n has the
+ *           period 2 (n - 1) (.. 2 1 0 1 2 .. n-2 n-1 n-2 ..; a side of 1 always folds to 0); under border = 1 a tap with an index
+ *           outside the frame has the value fill[c].  Lerp along x, then y, each fmaf(b - a, l, a) (as dinoseg_op_upsample_argmax).
+ *   label : the source mask at (Uy >> 16, Ux >> 16) after folding, or void_label when that is outside under border = 1.
+ *   colour: as the struct states (gray = fmaf(0.114, b, fmaf(0.587, g, 0.299 r)) in fp32).
+ *   blur  : separable, horizontal then vertical, on the OUTPUT frame after colour: sum over d = -r .. r in that order,
+ *           acc = fmaf(w[|d|], v[fold(x + d)], acc) from acc = 0, output coordinates folded by reflect-101 (OH, OW > r); the
+ *           intermediate is fp32 and is not rounded or clamped.  A frame with radius 0 skips the blur altogether.
+ *   out   : out_kind DINOSEG_INPUT_F32_CHW: fp32 [B, 3, OH, OW] = (v / 255 - mean) / std with the ImageNet constants;
+ *           DINOSEG_INPUT_U8_HWC: uint8 [B, OH, OW, 3] = rintf of v clamped to [0, 255].  Both are what dinoseg_forward_hw and the
+ *           train-step entries take.
+ * dinoseg_op_augment:
+ *   frames       : uint8 [B, H, W, 3];  masks: uint8 (mask_kind 0) or int64 (mask_kind 1) [B, H, W], nullable
+ *   table        : DEVICE array of B dinoseg_augment_frame;  max_radius: an upper bound (0..20) of the table's radii, known to the host
+ *   out          : the image in out_kind, 16-byte aligned
+ *   pixel_labels : int64 [B, OH, OW], nullable;  patch_labels: int64 [B, (OH/patch) (OW/patch)], nullable: the pixel label at
+ *                  (patch i, patch j), what the reference's Resize(NEAREST) to res // 8 picks
+ *   scratch      : fp32 [B, 3, OH, OW] of the caller, required when max_radius > 0 (never touched otherwise)
+ * Launch 1 (augment_warp_kernel) does warp, colour and labels per output pixel; with max_radius == 0 it writes the final image and
+ * is the only launch.  Launch 2 (augment_blur_kernel, max_radius > 0) stages each 64 x 32 output tile of the scratch with its
+ * r-wide folded halo in LDS one channel at a time, keeps the horizontal pass's result in LDS, and writes the final image; frames
+ * with radius 0 are converted straight through (bit-identical to the one-launch result).
+ * Refused on the host (-1) before anything is launched: null frames, table or out; a mask_kind or out_kind other than 0 / 1;
+ * non-positive sizes or sides above 16384; max_radius outside 0..20; OH <= max_radius or OW <= max_radius; a label output
+ * without masks; patch_labels with a patch other than 8 or 16 or with OH or OW not a multiple of it; a null scratch when
+ * max_radius > 0; out not 16-byte aligned.  Stream-ordered, no host synchronisation. */
+int dinoseg_op_augment(const uint8_t* frames, const void* masks, int32_t mask_kind, int32_t B, int32_t H, int32_t W,
+                       const dinoseg_augment_frame* table, int32_t max_radius, int32_t OH, int32_t OW, int32_t out_kind, void* out,
+                       int64_t* pixel_labels, int64_t* patch_labels, int32_t patch, float* scratch, void* stream);
+
 /* ---- fine-tune step (replaces DINOSeg.training_step + autograd + optimizer.step, pl_torch_modules.py:258-268) ---- */
 
 /* Bind (or, with NULL, unbind) the fp32 gradient buffer of a parameter, same shape as the bound weight.  A parameter
