@@ -79,15 +79,15 @@ def load_checkpoint(cls, path, map_location=None, **overrides):
     if "patch_size" in allowed and "patch_size" not in kwargs and not hasattr(kwargs.get("arch"), "patch") and pw is not None:
         p = int(pw.shape[-1])
         g = int(round((pe.shape[-2] - 1) ** 0.5)) if pe is not None else 224 // p
-        if p != 8 or g != 224 // p:
-            if g == 224 // p:
+        D = int(pw.shape[0])
+        fc1 = sd.get("dino.blocks.0.mlp.fc1.weight")
+        ratio = int(fc1.shape[0]) // D if fc1 is not None else 4
+        if D in (384, 768) and ratio == 4 and g == 224 // p:       # a named arch (vit_small / vit_base) at one of the published patch sizes
+            if p != 8:
                 kwargs["patch_size"] = p
-            else:       # a position grid other than 224 / patch: only a ViTConfig says it (width and MLP ratio from the tensors too)
-                from .weights import ViTConfig
-                D = int(pw.shape[0])
-                fc1 = sd.get("dino.blocks.0.mlp.fc1.weight")
-                kwargs["arch"] = ViTConfig(embed_dim=D, num_heads=D // 64, mlp_ratio=int(fc1.shape[0]) // D if fc1 is not None else 4,
-                                           patch=p, pos_grid=g)
+        else:       # another width, MLP ratio or position grid: only a ViTConfig says it, all of it from the tensors
+            from .weights import ViTConfig
+            kwargs["arch"] = ViTConfig(embed_dim=D, num_heads=D // 64, mlp_ratio=ratio, patch=p, pos_grid=g)
     model = cls(**kwargs)
     model.load_state_dict(OrderedDict((k, v.to(torch.float32)) for k, v in sd.items()), strict=True)
     return model

@@ -134,8 +134,9 @@ extern "C" int dinoseg_create(const dinoseg_config* cfg, dinoseg_handle** out) {
         (cfg->precision != DINOSEG_BF16 && cfg->precision != DINOSEG_BF16X3 && cfg->precision != DINOSEG_FP16 &&
          cfg->precision != DINOSEG_FP16X3) ||
         (cfg->head_kind != DINOSEG_HEAD_MLP && cfg->head_kind != DINOSEG_HEAD_LINEAR)) {
-        dinoseg_set_error("dinoseg_create: unsupported config (embed_dim=%d heads=%d patch=%d blocks=%d classes=%d; patch must be 8 or 16)",
-                          cfg->embed_dim, cfg->num_heads, cfg->patch, cfg->n_blocks, cfg->n_classes);
+        dinoseg_set_error("dinoseg_create: unsupported config (embed_dim=%d heads=%d mlp_ratio=%d patch=%d blocks=%d classes=%d; embed_dim must be "
+                          "a multiple of 128 up to 1024 with heads = embed_dim / 64, mlp_ratio >= 1, patch 8 or 16, 1..%d classes)",
+                          cfg->embed_dim, cfg->num_heads, cfg->mlp_ratio, cfg->patch, cfg->n_blocks, cfg->n_classes, HEAD_WIDE_MAX_C);
         return -1;
     }
     dinoseg_handle* h = new dinoseg_handle();

@@ -112,7 +112,12 @@ TrainLayout make_train_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
     L.DPOS = take((size_t)L.ntok * D * 4);
     L.SINK = take((size_t)4 * 1024 * 4);
     L.ACC = take(256);        // nll_loss accumulators {sum of -logp[y], valid rows} (the sticky bad-label flag lives in the handle)
-    L.SPLITK = take((size_t)SPLITK_TILES * 128 * 128 * 4);     // split-K partial tiles of the weight gradients
+    {   // split-K partial tiles of the weight gradients.  gemm_tn writes one partial tile per 128 x 128 tile of dW even unsplit, and the
+        // largest block linear has (Cmax / 128) x (D / 128) of them: more than the budget from embed_dim x hidden > 768 x 128 x 128 on
+        // (embed_dim 1024 at mlp_ratio 13), where the partials would run into the deterministic scratch behind them
+        const size_t lin_tiles = (size_t)(L.Cmax / 128) * (D / 128);
+        L.SPLITK = take((lin_tiles > (size_t)SPLITK_TILES ? lin_tiles : (size_t)SPLITK_TILES) * 128 * 128 * 4);
+    }
     L.DET = take((size_t)(DET_FLOATS + 2 * DET_TN_FLOATS) * 4);       // option deterministic: per-block partial sums (the largest user: LayerNorm backward, 1024 blocks x 3 x D)
     L.total = off;
     return L;
