@@ -1,6 +1,6 @@
-// C-ABI of libdinoseg_hip.so (see include/dinoseg.h): handle, weight binding/packing, workspace, and the
-// forward orchestration of the DINOSeg hot path on one MI355X.  Host code only; kernels live in
-// gemm.hip / attention.hip / elementwise.hip.
+// C-ABI of libdinoseg_hip.so (see include/dinoseg.h): handle, weight binding / packing, workspaces, options, profiling and the
+// stand-alone ops.  The forward of the DINOSeg hot path is forward.hip, the fine-tune step train_api.hip.  Host code only; kernels
+// live in gemm.hip / attention.hip / elementwise.hip.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -476,13 +476,7 @@ extern "C" int dinoseg_prepare_resolution(dinoseg_handle* h, int32_t r, void* st
 }
 
 // ------------------------------------------------------------------------------------------------ workspace
-struct WsLayout {
-    size_t X, A, Q, K, V, CTX, HB, FEAT, H1, H2, total;
-    long a_plane, qkv_plane, ctx_plane, hb_plane, feat_plane, h1_plane, h2_plane;
-    int n, ntok, npad, M, Mp;
-};
-
-static WsLayout make_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
+WsLayout make_layout(const dinoseg_handle* h, int B, int Hf, int Wf) {
     const dinoseg_config& c = h->cfg;
     const int D = c.embed_dim, F = D * c.mlp_ratio, P = h->planes, HP = head_planes();
     WsLayout L;
@@ -539,8 +533,7 @@ extern "C" int64_t dinoseg_workspace_bytes(const dinoseg_handle* h, int32_t B, i
     return dinoseg_workspace_bytes_hw(h, B, r, r);
 }
 
-// slot 0: the caller's stream; slot 1: the second half-batch of a split forward (its own buffer, the handle's internal stream)
-static int ensure_workspace(dinoseg_handle* h, int slot, const WsLayout& L, int B, int Hf, int Wf, hipStream_t s) {
+int ensure_workspace(dinoseg_handle* h, int slot, const WsLayout& L, int B, int Hf, int Wf, hipStream_t s) {
     char*& ws = slot ? h->ws2 : h->ws;
     size_t& bytes = slot ? h->ws2_bytes : h->ws_bytes;
     int& wB = slot ? h->ws2_B : h->ws_B;
@@ -573,325 +566,6 @@ static int ensure_workspace(dinoseg_handle* h, int slot, const WsLayout& L, int 
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ forward
-struct MaskRequest {            // forward_mask / get_last_selfattention(x, cls_mask): see dinoseg_forward_mask
-    const float* cls_mask;
-    int n_masks;
-    float* emb_out;
-    float* attn_out;
-    float* feat_out;            // dinoseg_features: final-norm tokens [B, N, D] after feat_blocks blocks (0 = all), then stop
-    int feat_blocks;
-};
-
-// the fused MLP kernel runs for this many token rows (options mlp_fused / mlp_fused_min_rows)
-static bool mlp_fuse_wanted(long rows) {
-    return options().mlp_fused == 2 || (options().mlp_fused == 1 && rows >= options().mlp_fused_min_rows);
-}
-
-// dinoseg_forward_dense_hw: after the head, the log-probs of this (half-)batch upsampled to OH x OW on the same stream
-struct DenseRequest {
-    int OH, OW;
-    int32_t* labels;            // int32 [B, OH, OW] (nullable)
-    float* dense;               // fp32 [B, n_classes, OH, OW] (nullable)
-};
-
-static int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t Hf, int32_t Wf, float* logp_out,
-                        int32_t* argmax_out, int32_t tap_block, float* tap_out, float* attn_out, void* stream,
-                        const MaskRequest* mreq = nullptr, int slot = 0, int disp_B = 0, const DenseRequest* dreq = nullptr) {
-    if (!h || !x || B <= 0) {
-        dinoseg_set_error("dinoseg_forward: bad argument");
-        return -1;
-    }
-    if (!frame_ok(Hf, Wf, h->cfg.patch)) {
-        set_resolution_error(h->cfg.patch);
-        return -1;
-    }
-    if (x_kind != DINOSEG_INPUT_U8_HWC && x_kind != DINOSEG_INPUT_F32_CHW) {
-        dinoseg_set_error("dinoseg_forward: bad x_kind %d", x_kind);
-        return -1;
-    }
-    if (!h->weights_ready) {
-        dinoseg_set_error("dinoseg_forward: weights not packed (call dinoseg_refresh_weights after binding)");
-        return -3;
-    }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    DeviceGuard guard(h);
-    DSEG_TRY(check_stream_device(h, s));
-    DSEG_TRY(dinoseg_prepare_resolution_hw(h, Hf, Wf, stream));
-
-    const dinoseg_config& c = h->cfg;
-    const int D = c.embed_dim, F = D * c.mlp_ratio, P = h->planes, HP = head_planes(), H = c.num_heads, FM = h->fmt, SF = split_fmt(h);
-    const WsLayout L = make_layout(h, B, Hf, Wf);
-    DSEG_TRY(ensure_workspace(h, slot, L, B, Hf, Wf, s));
-    // every size-dependent kernel choice below is made for the rows of the WHOLE call: the half-batches of a split forward (disp_B =
-    // the call's batch) then take the routes -- and the summation order -- the unsplit batch takes, so the split changes no bit
-    const int dB = disp_B > 0 ? disp_B : B;
-    const int disp_M = dB * L.ntok, disp_Mp = dB * L.n;
-    char* ws = slot ? h->ws2 : h->ws;
-    float* X = reinterpret_cast<float*>(ws + L.X);
-    bf16_t* A = reinterpret_cast<bf16_t*>(ws + L.A);
-    bf16_t* Q = reinterpret_cast<bf16_t*>(ws + L.Q);
-    bf16_t* Kb = reinterpret_cast<bf16_t*>(ws + L.K);
-    bf16_t* V = reinterpret_cast<bf16_t*>(ws + L.V);
-    bf16_t* CTX = reinterpret_cast<bf16_t*>(ws + L.CTX);
-    bf16_t* HB = reinterpret_cast<bf16_t*>(ws + L.HB);
-    bf16_t* FEAT = reinterpret_cast<bf16_t*>(ws + L.FEAT);
-    bf16_t* H1 = reinterpret_cast<bf16_t*>(ws + L.H1);
-    bf16_t* H2 = reinterpret_cast<bf16_t*>(ws + L.H2);
-    // a block linear through the row-stationary streaming kernels (gemm_rs.hip): its copy exists (the linear's gemm_rs bit was set at
-    // the last refresh), the bit is still set, the batch fills the chip and the kernel takes the parameters.  A copy that carries the
-    // LayerNorm in front of qkv / fc1 (gemm_rs_ln at that refresh) runs with the LayerNorm inside -- no LayerNorm launch, no 16-bit A
-    // round trip -- and only so.  The one predicate for both the LayerNorm launch and the GEMM; *r = the kernel's parameters.
-    auto rs_route = [&](const GemmParams& g, const LinearRec& lin, GemmParams* r) -> bool {
-        if (!lin.rs || !(options().gemm_rs & h->gemm_rs_snap & lin.rs_bit) || disp_M < options().gemm_rs_min_rows) return false;
-        *r = g;
-        r->W = lin.rs;
-        if (lin.rs_bias) {
-            if (mreq && mreq->cls_mask) return false;
-            r->ln_x = X; r->ln_eps = c.ln_eps; r->bias = lin.rs_bias;
-        }
-        return gemm_rs_supported(*r);
-    };
-    auto gemm_any = [&](const GemmParams& g, const LinearRec& lin) -> int {
-        GemmParams r;
-        return rs_route(g, lin, &r) ? launch_gemm_rs(r, s) : launch_gemm(g, s);
-    };
-    const ModelRec& m = h->model;
-
-    // ---- prepare_tokens (vision_transformer.py:224-235) ----
-    float mean255[3], inv255[3];
-    norm_consts(mean255, inv255);
-    const int KP = 3 * c.patch * c.patch;       // the conv's fan-in: 192 at patch 8, 768 at patch 16
-    const long pg_plane = (long)L.Mp * KP;
-    const int PP = patch_planes(h);
-    DSEG_PROF(DINOSEG_PROF_PATCH, DSEG_TRY(launch_patch_gather(x, x_kind, B, Hf, Wf, mean255, inv255, A, pg_plane, PP, s, patch_fmt(h), c.patch)));
-    {
-        GemmParams g = linear_gemm(m.patch);
-        g.A = A; g.a_plane = pg_plane; g.lda = KP;
-        g.M = L.Mp; g.epi = EPI_PATCH; g.dispatch_rows = disp_Mp;
-        g.out_f32 = X; g.ldo_f32 = D;
-        g.pos = h->pos_cache; g.n_patches = L.n;
-        DSEG_PROF(DINOSEG_PROF_PATCH, DSEG_TRY(launch_gemm(g, s)));
-    }
-    DSEG_PROF(DINOSEG_PROF_PATCH, DSEG_TRY(launch_cls_rows(X, m.cls_token, h->pos_cache, B, L.ntok, D, s)));
-    const size_t xbytes = (size_t)L.M * D * sizeof(float);
-    if (tap_block == 0 && tap_out) DSEG_CHECK_HIP(hipMemcpyAsync(tap_out, X, xbytes, hipMemcpyDeviceToDevice, s));
-
-    const float qscale = 0.125f * 1.44269504088896340736f;   // head_dim^-0.5 (vision_transformer.py:73) * log2(e)
-    // fp16 hi + lo planes: from two rounds of 256-query workgroups on, the attention is the zero-reference assembly kernel, whose
-    // probabilities and V are bf16 hi + lo planes -- the qkv epilogue writes V that way (decided for the batch of the WHOLE call; never
-    // on the visualisation paths, whose small kernels read V in the mode's own format)
-    const int v_bf16 = (P == 2 && FM == FMT_FP16 && !attn_out && !(mreq && mreq->cls_mask) && attention_x3_za(dB, H, L.ntok)) ? 1 : 0;
-
-    // ---- transformer blocks (vision_transformer.py:122-140) ----
-    bool qkv_ready = false;      // Q / K / V of block i were written by block i-1's fused launch (mlp_fused2.hip, QKV tail)
-    for (int i = 0; i < c.n_blocks; ++i) {
-        const BlockRec& blk = m.blocks[i];
-        // gemm_ln: 0 never fused, 2 always, 1 (default) by measurement (round 4, tools/r4_smallbatch.sh, 1..6 frames @480):
-        //  * single plane (bf16 / fp16): fused from 80 row panels of 128 on -- below that its persistent 128 x 384 panels leave most
-        //    CUs idle (one frame = 29 panels: qkv 31 against 21 us with LayerNorm + the 128x128 kernel, fc1 40 against 23; the
-        //    whole single-frame forward 1.72 -> 1.33 ms at 12 blocks; crossover between 2 and 3 frames);
-        //  * hi+lo planes: its 64-row panels run one workgroup per CU, so it wins only while they fill about one round of the chip
-        //    (9 600 .. 16 384 rows = 3-4 frames: fc1 1.15 against 1.24 ms; 1 frame 1.01 against 0.48, 6 frames 2.13 against 1.33);
-        //    from 512 tiles of 128 x 384 on, LayerNorm + the hi+lo configuration of the persistent GEMM (B = 32: fc1 30 + 534 us
-        //    against 670 fused).
-        const bool big_x3 = P == 2 && options().gemm_big && (long)((disp_M + 127) / 128) * 3 >= 512;
-        const bool ln_small = P == 1 ? (disp_M + 127) / 128 < 80 : (disp_M < 9600 || disp_M > 16384);
-        const bool fuse_ln = options().gemm_ln == 2 || (options().gemm_ln == 1 && !big_x3 && !ln_small);
-        // (the fused kernel keeps 32-bit output row offsets)
-        if (qkv_ready) {
-            qkv_ready = false;
-        } else if (fuse_ln && blk.qkv.slab && L.qkv_plane < (1L << 31)) {
-            // LN1 + qkv in one launch: X rows are normalised in the GEMM's prologue, no bf16 A round trip (gemm_ln.hip)
-            LnGemmParams g = {};
-            g.X = X; g.ldx = D; g.gamma = blk.norm1_w; g.beta = blk.norm1_b; g.eps = c.ln_eps;
-            g.W = blk.qkv.slab; g.bias = blk.qkv.b;
-            g.M = L.M; g.N = 3 * D; g.epi = EPI_QKV;
-            g.q = Q; g.k = Kb; g.v = V; g.qkv_plane = L.qkv_plane;
-            g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.dmodel = D; g.qscale = qscale; g.fmt = FM;
-            DSEG_PROF(DINOSEG_PROF_QKV, DSEG_TRY(launch_gemm_ln(g, D, P, s)));
-        } else {
-            GemmParams g = linear_gemm(blk.qkv);
-            g.A = A; g.a_plane = L.a_plane; g.lda = D;
-            g.M = L.M; g.epi = EPI_QKV; g.dispatch_rows = disp_M;
-            g.v_bf16 = v_bf16;
-            g.q = Q; g.k = Kb; g.v = V; g.qkv_plane = L.qkv_plane;
-            g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.dmodel = D; g.qscale = qscale;
-            GemmParams r;
-            const bool rs = rs_route(g, blk.qkv, &r);
-            if (!rs || !r.ln_x)
-                DSEG_PROF(DINOSEG_PROF_LN, DSEG_TRY(launch_layernorm(X, blk.norm1_w, blk.norm1_b, c.ln_eps, L.M, D, A, L.a_plane,
-                                                                     P, nullptr, 0, L.ntok, s, FM)));
-            DSEG_PROF(DINOSEG_PROF_QKV, DSEG_TRY(rs ? launch_gemm_rs(r, s) : launch_gemm(g, s)));
-        }
-        if (attn_out && i == c.n_blocks - 1)      // get_last_selfattention: probabilities of the last block, then stop
-            return launch_attn_probs(Q, Kb, L.qkv_plane, P, B, H, L.ntok, L.npad, attn_out, s, FM);
-        if (mreq && mreq->cls_mask && i == c.n_blocks - 1) {
-            // last block with cls_mask (Block.forward, vision_transformer.py:127-140): the CLS token attends through each mask;
-            // its residual is repeated once per mask; MLP and the final norm run on those n_masks rows only.  The patch-token
-            // rows of X / A / CTX / HB are dead from here on and host the n_masks rows (checked: n_masks < ntok).
-            const int Nm = mreq->n_masks;
-            DSEG_TRY(launch_cls_mask_attn(Q, Kb, V, L.qkv_plane, P, H, L.ntok, L.npad, mreq->cls_mask, Nm, CTX, L.ctx_plane,
-                                          mreq->attn_out, s, FM));
-            if (!mreq->emb_out) return 0;
-            float* Xm = X + D;                        // rows 1 .. Nm
-            DSEG_TRY(launch_broadcast_row0(X, D, Nm, s));
-            auto lin = [&](const LinearRec& l, const bf16_t* Ain, long a_plane, int epi, bf16_t* ob, long o_plane) -> int {
-                GemmParams g = linear_gemm(l);
-                g.A = Ain; g.a_plane = a_plane; g.lda = l.K;
-                g.M = Nm; g.epi = epi;
-                g.out_f32 = Xm; g.ldo_f32 = D;
-                g.out_bf16 = ob; g.out_plane = o_plane; g.ldo = l.N;
-                return launch_gemm_small(g, s);
-            };
-            DSEG_TRY(lin(blk.proj, CTX, L.ctx_plane, EPI_RESID, nullptr, 0));
-            DSEG_TRY(launch_layernorm(Xm, blk.norm2_w, blk.norm2_b, c.ln_eps, Nm, D, A, L.a_plane, P, nullptr, 0,
-                                      L.ntok, s, FM));
-            DSEG_TRY(lin(blk.fc1, A, L.a_plane, EPI_GELU, HB, L.hb_plane));
-            DSEG_TRY(lin(blk.fc2, HB, L.hb_plane, EPI_RESID, nullptr, 0));
-            return launch_layernorm(Xm, m.norm_w, m.norm_b, c.ln_eps, Nm, D, A, L.a_plane, P,
-                                    mreq->emb_out, 0, L.ntok, s, FM);
-        }
-        {
-            AttnParams a = {};
-            a.q = Q; a.k = Kb; a.v = V; a.qkv_plane = L.qkv_plane;
-            a.ctx = CTX; a.ctx_plane = L.ctx_plane; a.lse = nullptr;
-            a.B = B; a.heads = H; a.ntok = L.ntok; a.npad = L.npad; a.planes = P; a.fmt = FM;
-            a.shared_gpu = h->in_split ? 1 : 0;
-            a.dispatch_B = dB;
-            a.v_bf16 = v_bf16;
-            DSEG_PROF(DINOSEG_PROF_ATTN, DSEG_TRY(launch_attention(a, s)));
-        }
-        const bool fuse_mlp3 = P == 2 && blk.mlp3 &&      // hi + lo planes: mlp_fused3.hip
-                               (options().mlp_fused == 2 || (options().mlp_fused == 1 && disp_M >= options().mlp_fused3_min_rows));
-        const bool fuse_mlp = fuse_mlp3 || (blk.mlp && mlp_fuse_wanted(disp_M));
-        // (the fused MLP kernels take the attention output projection along: x += proj(ctx) + b, then the MLP, one launch)
-        const bool fuse_proj = fuse_mlp && options().proj_fused && (fuse_mlp3 || (P == 1 && blk.projf));
-        if (!fuse_proj) {
-            GemmParams g = linear_gemm(blk.proj);
-            g.A = CTX; g.a_plane = L.ctx_plane; g.lda = D;
-            g.M = L.M; g.epi = EPI_RESID; g.dispatch_rows = disp_M;
-            g.out_f32 = X; g.ldo_f32 = D;
-            DSEG_PROF(DINOSEG_PROF_PROJ, DSEG_TRY(gemm_any(g, blk.proj)));
-        }
-        if (fuse_mlp3) {
-            // projection + LN2 + fc1 + GELU + fc2 + residual on hi + lo planes in one launch (mlp_fused3.hip)
-            MlpFused3Params g = {};
-            g.X = X; g.eps = c.ln_eps;
-            g.Wp = blk.mlp3; g.b2 = blk.fc2.b;
-            g.M = L.M; g.fmt = FM;
-            if (fuse_proj) {
-                g.ctx = CTX; g.ctx_plane = L.ctx_plane; g.bproj = blk.proj.b;
-                // ... and LayerNorm1 + qkv of the next block (a tap of this block's output still reads X, which is complete)
-                if (options().qkv_fused3 && i + 1 < c.n_blocks && L.qkv_plane < (1L << 31)) {
-                    g.q = Q; g.k = Kb; g.v = V; g.qkv_plane = L.qkv_plane;
-                    g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.qscale = qscale; g.v_bf16 = v_bf16;
-                    qkv_ready = true;
-                }
-            }
-            DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(launch_mlp_fused3(g, s)));
-        } else if (fuse_mlp && fuse_proj && options().mlp_fused4 && h->mlp_fused4_snap && !options().qkv_fused && blk.mlp4) {
-            // the same launch with one wave per SIMD (mlp_fused4.hip)
-            MlpFused3Params g = {};
-            g.X = X; g.eps = c.ln_eps;
-            g.Wp = blk.mlp4; g.b2 = blk.fc2.b;
-            g.M = L.M; g.fmt = FM;
-            g.ctx = CTX; g.bproj = blk.proj.b;
-            // ... and LayerNorm1 + qkv of the next block (a tap of this block's output still reads X, which is complete)
-            if (options().qkv_fused4 && i + 1 < c.n_blocks) {
-                g.q = Q; g.k = Kb; g.v = V; g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.qscale = qscale;
-                qkv_ready = true;
-            }
-            DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(launch_mlp_fused4(g, s)));
-        } else if (fuse_mlp) {
-            // LN2 + fc1 + GELU + fc2 + residual in one launch: the hidden activation never reaches HBM (mlp_fused2.hip)
-            MlpFusedParams g = {};
-            g.X = X; g.ldx = D; g.gamma = blk.norm2_w; g.beta = blk.norm2_b; g.eps = c.ln_eps;
-            g.Wp = blk.mlp; g.b1 = blk.fc1.b; g.b2 = blk.fc2.b;
-            g.M = L.M; g.fmt = FM;
-            if (fuse_proj) {
-                g.ctx = CTX; g.Wproj = blk.projf; g.bproj = blk.proj.b;
-                // ... and LayerNorm1 + qkv of the next block (a tap of this block's output still reads X, which is complete)
-                if (options().qkv_fused && i + 1 < c.n_blocks && m.blocks[i + 1].qkvf) {
-                    const BlockRec& nb = m.blocks[i + 1];
-                    g.Wqkv = nb.qkvf; g.bqkv = nb.qkv.b;
-                    g.gamma1 = nb.norm1_w; g.beta1 = nb.norm1_b;
-                    g.q = Q; g.k = Kb; g.v = V; g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.qscale = qscale;
-                    qkv_ready = true;
-                }
-            }
-            DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(launch_mlp_fused2(g, s)));
-        } else {
-        if (fuse_ln && blk.fc1.slab && L.hb_plane < (1L << 31)) {
-            LnGemmParams g = {};
-            g.X = X; g.ldx = D; g.gamma = blk.norm2_w; g.beta = blk.norm2_b; g.eps = c.ln_eps;
-            g.W = blk.fc1.slab; g.bias = blk.fc1.b;
-            g.M = L.M; g.N = F; g.epi = EPI_GELU; g.fmt = FM;
-            g.out_bf16 = HB; g.out_plane = L.hb_plane; g.ldo = F;
-            DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(launch_gemm_ln(g, D, P, s)));
-        } else {
-            GemmParams g = linear_gemm(blk.fc1);
-            g.A = A; g.a_plane = L.a_plane; g.lda = D;
-            g.M = L.M; g.epi = EPI_GELU; g.dispatch_rows = disp_M;
-            g.out_bf16 = HB; g.out_plane = L.hb_plane; g.ldo = F;
-            GemmParams r;
-            const bool rs = rs_route(g, blk.fc1, &r);
-            if (!rs || !r.ln_x)
-                DSEG_PROF(DINOSEG_PROF_LN, DSEG_TRY(launch_layernorm(X, blk.norm2_w, blk.norm2_b, c.ln_eps, L.M, D, A, L.a_plane,
-                                                                     P, nullptr, 0, L.ntok, s, FM)));
-            DSEG_PROF(DINOSEG_PROF_FC1, DSEG_TRY(rs ? launch_gemm_rs(r, s) : launch_gemm(g, s)));
-        }
-        {
-            GemmParams g = linear_gemm(blk.fc2);
-            g.A = HB; g.a_plane = L.hb_plane; g.lda = F;
-            g.M = L.M; g.epi = EPI_RESID; g.dispatch_rows = disp_M;
-            g.out_f32 = X; g.ldo_f32 = D;
-            DSEG_PROF(DINOSEG_PROF_FC2, DSEG_TRY(gemm_any(g, blk.fc2)));
-        }
-        }
-        if (tap_block == i + 1 && tap_out) DSEG_CHECK_HIP(hipMemcpyAsync(tap_out, X, xbytes, hipMemcpyDeviceToDevice, s));
-        if (mreq && mreq->feat_out && mreq->feat_blocks == i + 1 && i + 1 < c.n_blocks)      // forward(x, intermediate=k)
-            return launch_layernorm(X, m.norm_w, m.norm_b, c.ln_eps, L.M, D, nullptr, 0, 1, mreq->feat_out, 0,
-                                    L.ntok, s);
-    }
-    if (mreq && mreq->feat_out)     // VisionTransformer.forward(x, all=True): every token through the final norm, fp32
-        return launch_layernorm(X, m.norm_w, m.norm_b, c.ln_eps, L.M, D, nullptr, 0, 1, mreq->feat_out, 0,
-                                L.ntok, s);
-
-    // ---- final norm, drop CLS (vision_transformer.py:243; pl_torch_modules.py:243,253) ----
-    DSEG_PROF(DINOSEG_PROF_LN, DSEG_TRY(launch_layernorm(X, m.norm_w, m.norm_b, c.ln_eps, L.M, D, FEAT, L.feat_plane,
-                              HP, nullptr, 1, L.ntok, s, SF)));
-
-    // ---- segmentation head (pl_torch_modules.py:108-138), always in split precision ----
-    if (c.head_kind == DINOSEG_HEAD_MLP) {
-        {
-            GemmParams g = linear_gemm(m.head[0]);
-            g.A = FEAT; g.a_plane = L.feat_plane; g.lda = D;
-            g.M = L.Mp; g.epi = EPI_RELU;
-            g.out_bf16 = H1; g.out_plane = L.h1_plane; g.ldo = HEAD_H1_PAD;
-            DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_gemm(g, s)));
-        }
-        {
-            GemmParams g = linear_gemm(m.head[1]);
-            g.A = H1; g.a_plane = L.h1_plane; g.lda = HEAD_H1_PAD;
-            g.M = L.Mp; g.epi = EPI_RELU;
-            g.out_bf16 = H2; g.out_plane = L.h2_plane; g.ldo = HEAD_H2_PAD;
-            DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_gemm(g, s)));
-        }
-        DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_head_final(H2, L.h2_plane, HEAD_H2_PAD, L.Mp, HEAD_H2, m.clf.w, m.clf.b,
-                                   c.n_classes, logp_out ? logp_out : reinterpret_cast<float*>(ws + L.HB), argmax_out, s, SF,
-                                   m.clf.pk.w, m.clf.pk.plane)));
-    } else {
-        DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_head_final(FEAT, L.feat_plane, D, L.Mp, D, m.clf.w, m.clf.b,
-                                   c.n_classes, logp_out ? logp_out : reinterpret_cast<float*>(ws + L.HB), argmax_out, s, SF,
-                                   m.clf.pk.w, m.clf.pk.plane)));
-    }
-    if (dreq)       // (timed with the head: its output side)
-        DSEG_PROF(DINOSEG_PROF_HEAD, DSEG_TRY(launch_upsample_argmax(logp_out ? logp_out : reinterpret_cast<float*>(ws + L.HB), B, Hf / c.patch,
-                                   Wf / c.patch, c.n_classes, dreq->OH, dreq->OW, dreq->labels, dreq->dense, s)));
-    return 0;
-}
-
 int ensure_aux_stream(dinoseg_handle* h) {
     if (!h->aux_stream) {
         DSEG_CHECK_HIP(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
@@ -899,126 +573,6 @@ int ensure_aux_stream(dinoseg_handle* h) {
         DSEG_CHECK_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     }
     return 0;
-}
-
-// Option "streams" = 2: a batch of >= split_min frames runs as two half-batches, the first on the caller's stream, the second on
-// the handle's internal stream (forked from and joined to the caller's stream by events, so the call keeps its stream-ordered
-// semantics and stays capturable).  Frames are independent (pl_torch_modules.py:253 flattens them); kernels of different
-// layers of the two halves overlap: one half's attention fills the CUs the other half's GEMM tail rounds and memory phases
-// leave idle (measured: +4.5 % frames/s at B = 32; four quarter-batches: -5 %).  The two workspaces together are the size of one.
-static int forward_split(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, float* logp_out,
-                         int32_t* argmax_out, int32_t tap_block, float* tap_out, void* stream, const DenseRequest* dreq) {
-    const bool split = h && x && options().streams >= 2 && B >= options().split_min && B >= 2 && tap_block < 0 && !tap_out &&
-                       frame_ok(H, W, patch_of(h)) && (x_kind == DINOSEG_INPUT_U8_HWC || x_kind == DINOSEG_INPUT_F32_CHW) && h->weights_ready;
-    if (!split) return forward_impl(h, x, x_kind, B, H, W, logp_out, argmax_out, tap_block, tap_out, nullptr, stream, nullptr, 0, 0, dreq);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    DeviceGuard guard(h);
-    DSEG_TRY(check_stream_device(h, s));
-    DSEG_TRY(ensure_aux_stream(h));
-    DSEG_TRY(dinoseg_prepare_resolution_hw(h, H, W, stream));      // the resampled position embedding: before the fork, both halves read it
-    const int B0 = (B + 1) / 2, B1 = B - B0;
-    const long n = (long)(H / h->cfg.patch) * (W / h->cfg.patch);
-    const size_t frame_bytes = x_kind == DINOSEG_INPUT_U8_HWC ? (size_t)H * W * 3 : (size_t)H * W * 3 * sizeof(float);
-    const void* x1 = reinterpret_cast<const char*>(x) + (size_t)B0 * frame_bytes;
-    DSEG_CHECK_HIP(hipEventRecord(h->ev_fork, s));
-    DSEG_CHECK_HIP(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
-    h->in_split = true;
-    DenseRequest d1 = {0, 0, nullptr, nullptr};          // the second half's slice of the pixel-resolution outputs
-    if (dreq) {
-        const size_t px = (size_t)B0 * dreq->OH * dreq->OW;
-        d1 = {dreq->OH, dreq->OW, dreq->labels ? dreq->labels + px : nullptr, dreq->dense ? dreq->dense + px * h->cfg.n_classes : nullptr};
-    }
-    const int rc0 = forward_impl(h, x, x_kind, B0, H, W, logp_out, argmax_out, -1, nullptr, nullptr, stream, nullptr, 0, B, dreq);
-    const int rc1 = forward_impl(h, x1, x_kind, B1, H, W, logp_out ? logp_out + (size_t)B0 * n * h->cfg.n_classes : nullptr,
-                                 argmax_out ? argmax_out + (size_t)B0 * n : nullptr, -1, nullptr, nullptr, h->aux_stream, nullptr, 1, B,
-                                 dreq ? &d1 : nullptr);
-    h->in_split = false;
-    // join even after an error: the caller's stream must not run ahead of work already queued on the internal one
-    DSEG_CHECK_HIP(hipEventRecord(h->ev_join, h->aux_stream));
-    DSEG_CHECK_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
-    return rc0 ? rc0 : rc1;
-}
-
-extern "C" int dinoseg_forward_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, float* logp_out,
-                                  int32_t* argmax_out, int32_t tap_block, float* tap_out, void* stream) {
-    return forward_split(h, x, x_kind, B, H, W, logp_out, argmax_out, tap_block, tap_out, stream, nullptr);
-}
-
-// The forward, then the bilinear upsample + argmax of its log-probs (upsample.hip) behind the head on the same stream(s).  Everything the
-// upsample would refuse is refused here, before the forward enqueues anything.
-extern "C" int dinoseg_forward_dense_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t OH,
-                                        int32_t OW, float* logp_out, int32_t* argmax_out, int32_t* labels_out, float* dense_out,
-                                        void* stream) {
-    if (!h || !x || B <= 0) {
-        dinoseg_set_error("dinoseg_forward_dense_hw: bad argument (null handle or frames, or B=%d)", B);
-        return -1;
-    }
-    if (!labels_out && !dense_out) {
-        dinoseg_set_error("dinoseg_forward_dense_hw: null pointer (at least one of labels_out / dense_out is required)");
-        return -1;
-    }
-    if (!frame_ok(H, W, h->cfg.patch)) {
-        set_resolution_error(h->cfg.patch);
-        return -1;
-    }
-    const int hp = H / h->cfg.patch, wp = W / h->cfg.patch;
-    if (upsample_check_shape("dinoseg_forward_dense_hw", B, hp, wp, h->cfg.n_classes, OH, OW)) return -1;
-    const DenseRequest dreq = {OH, OW, labels_out, dense_out};
-    return forward_split(h, x, x_kind, B, H, W, logp_out, argmax_out, -1, nullptr, stream, &dreq);
-}
-
-extern "C" int dinoseg_forward(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* logp_out,
-                               int32_t* argmax_out, int32_t tap_block, float* tap_out, void* stream) {
-    return dinoseg_forward_hw(h, x, x_kind, B, r, r, logp_out, argmax_out, tap_block, tap_out, stream);
-}
-
-extern "C" int dinoseg_last_selfattention_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W,
-                                             float* attn_out, void* stream) {
-    if (!attn_out || !h || h->cfg.n_blocks < 1) {
-        dinoseg_set_error("dinoseg_last_selfattention: needs an output buffer and at least one block");
-        return -1;
-    }
-    return forward_impl(h, x, x_kind, B, H, W, nullptr, nullptr, -1, nullptr, attn_out, stream);
-}
-
-extern "C" int dinoseg_last_selfattention(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* attn_out,
-                                          void* stream) {
-    return dinoseg_last_selfattention_hw(h, x, x_kind, B, r, r, attn_out, stream);
-}
-
-extern "C" int dinoseg_forward_mask_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t H, int32_t W, const float* cls_mask,
-                                       int32_t n_masks, float* emb_out, float* attn_out, void* stream) {
-    if (!h || h->cfg.n_blocks < 1 || !cls_mask || n_masks < 1 || (!emb_out && !attn_out)) {
-        dinoseg_set_error("dinoseg_forward_mask: needs at least one block, n_masks >= 1 masks and one output buffer");
-        return -1;
-    }
-    const int32_t pz = h->cfg.patch;
-    if (frame_ok(H, W, pz) && n_masks >= (H / pz) * (W / pz) + 1) {
-        dinoseg_set_error("dinoseg_forward_mask: n_masks=%d must be smaller than the token count %d", n_masks, (H / pz) * (W / pz) + 1);
-        return -1;
-    }
-    const MaskRequest mr = {cls_mask, n_masks, emb_out, attn_out, nullptr, 0};
-    return forward_impl(h, x, x_kind, 1, H, W, nullptr, nullptr, -1, nullptr, nullptr, stream, &mr);
-}
-
-extern "C" int dinoseg_forward_mask(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t r, const float* cls_mask,
-                                    int32_t n_masks, float* emb_out, float* attn_out, void* stream) {
-    return dinoseg_forward_mask_hw(h, x, x_kind, r, r, cls_mask, n_masks, emb_out, attn_out, stream);
-}
-
-extern "C" int dinoseg_features_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t n_blocks,
-                                   float* tokens_out, void* stream) {
-    if (!h || !tokens_out || n_blocks < 0 || n_blocks > h->cfg.n_blocks) {
-        dinoseg_set_error("dinoseg_features: needs an output buffer and 0 <= n_blocks <= %d", h ? h->cfg.n_blocks : 0);
-        return -1;
-    }
-    const MaskRequest mr = {nullptr, 0, nullptr, nullptr, tokens_out, n_blocks};
-    return forward_impl(h, x, x_kind, B, H, W, nullptr, nullptr, -1, nullptr, nullptr, stream, &mr);
-}
-
-extern "C" int dinoseg_features(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, int32_t n_blocks,
-                                float* tokens_out, void* stream) {
-    return dinoseg_features_hw(h, x, x_kind, B, r, r, n_blocks, tokens_out, stream);
 }
 
 extern "C" int dinoseg_op_resize_u8(const uint8_t* src, int32_t sh, int32_t sw, uint8_t* dst, int32_t dh, int32_t dw, void* stream) {
@@ -1088,119 +642,63 @@ Options& options() {
 }
 }  // namespace dseg
 
+// what dinoseg_set_option stores for a value: *out, or -1 with the error set
+static int opt_value(int32_t v, int* out) { *out = v; return 0; }
+static int opt_flag(int32_t v, int* out) { *out = v ? 1 : 0; return 0; }
+static int opt_bits3(int32_t v, int* out) { *out = v & 7; return 0; }
+static int opt_min2(int32_t v, int* out) { *out = v < 2 ? 2 : v; return 0; }
+static int opt_1_or_2(int32_t v, int* out) { *out = v == 1 ? 1 : 2; return 0; }
+static int opt_fmt(int32_t v, int* out) {
+    if (v != FMT_BF16 && v != FMT_FP16) {
+        dinoseg_set_error("dinoseg_set_option: op_fmt must be 0 (bf16) or 1 (fp16)");
+        return -1;
+    }
+    *out = v;
+    return 0;
+}
+// every key of dinoseg_set_option: the member of Options it writes (kernels.h: what each one does) and how the value is normalised
+static const struct OptionRow {
+    const char* name;
+    int Options::*member;       // null: accepted and ignored
+    int (*normalise)(int32_t, int*);
+} OPTION_TABLE[] = {
+    {"gemm_ln", &Options::gemm_ln, opt_value},
+    {"gemm_big", &Options::gemm_big, opt_value},
+    {"route_ab", &Options::route_ab, opt_value},
+    {"fp16_patch_planes", &Options::fp16_patch_planes, opt_1_or_2},
+    {"op_v_bf16", &Options::op_v_bf16, opt_flag},        // dinoseg_op_attention with fp16 hi + lo planes: V is given as bf16 hi + lo planes (AttnParams::v_bf16)
+    {"op_fmt", &Options::op_fmt, opt_fmt},               // operand format of the single-plane stand-alone ops (dinoseg_op_*): 0 bf16, 1 fp16
+    {"streams", &Options::streams, opt_value},
+    {"mlp_fused", &Options::mlp_fused, opt_value},
+    {"qkv_fused", &Options::qkv_fused, opt_value},
+    {"proj_fused", &Options::proj_fused, opt_value},
+    {"mlp_stagger", &Options::mlp_stagger, opt_value},
+    {"mlp_grid", &Options::mlp_grid, opt_value},
+    {"splitk_tiles", &Options::splitk_tiles, opt_value},
+    {"deterministic", &Options::deterministic, opt_flag},    // the fine-tune step's reductions in a fixed order (kernels.h Options::deterministic)
+    {"train_streams", &Options::train_streams, opt_value},
+    {"mlp_variant", nullptr, opt_value},                 // (accepted and ignored: the one-wave-per-SIMD build was removed in round 4)
+    {"gemm_rs", &Options::gemm_rs, opt_bits3},
+    {"gemm_rs_ln", &Options::gemm_rs_ln, opt_flag},
+    {"gemm_rs_min_rows", &Options::gemm_rs_min_rows, opt_value},
+    {"qkv_fused3", &Options::qkv_fused3, opt_flag},
+    {"qkv_fused4", &Options::qkv_fused4, opt_flag},
+    {"mlp_fused4", &Options::mlp_fused4, opt_flag},
+    {"mlp_fused3_min_rows", &Options::mlp_fused3_min_rows, opt_value},
+    {"mlp_fused_min_rows", &Options::mlp_fused_min_rows, opt_value},
+    {"split_min", &Options::split_min, opt_min2},
+    {"gemm_dbg", &Options::gemm_dbg, opt_value},
+    {"attn_variant", &Options::attn_variant, opt_value},
+    {"attn_dbg", &Options::attn_dbg, opt_value},
+};
+
 extern "C" int dinoseg_set_option(const char* key, int32_t value) {
     if (!key) return -1;
-    if (strcmp(key, "gemm_ln") == 0) {
-        dseg::options().gemm_ln = value;
-        return 0;
-    }
-    if (strcmp(key, "gemm_big") == 0) {
-        dseg::options().gemm_big = value;
-        return 0;
-    }
-    if (strcmp(key, "route_ab") == 0) {
-        dseg::options().route_ab = value;
-        return 0;
-    }
-    if (strcmp(key, "fp16_patch_planes") == 0) {
-        dseg::options().fp16_patch_planes = value == 1 ? 1 : 2;
-        return 0;
-    }
-    if (strcmp(key, "op_v_bf16") == 0) {      // dinoseg_op_attention with fp16 hi + lo planes: V is given as bf16 hi + lo planes (AttnParams::v_bf16)
-        dseg::options().op_v_bf16 = value ? 1 : 0;
-        return 0;
-    }
-    if (strcmp(key, "op_fmt") == 0) {      // operand format of the single-plane stand-alone ops (dinoseg_op_*): 0 bf16, 1 fp16
-        if (value != FMT_BF16 && value != FMT_FP16) {
-            dinoseg_set_error("dinoseg_set_option: op_fmt must be 0 (bf16) or 1 (fp16)");
-            return -1;
-        }
-        dseg::options().op_fmt = value;
-        return 0;
-    }
-    if (strcmp(key, "streams") == 0) {
-        dseg::options().streams = value;
-        return 0;
-    }
-    if (strcmp(key, "mlp_fused") == 0) {
-        dseg::options().mlp_fused = value;
-        return 0;
-    }
-    if (strcmp(key, "qkv_fused") == 0) {
-        dseg::options().qkv_fused = value;
-        return 0;
-    }
-    if (strcmp(key, "proj_fused") == 0) {
-        dseg::options().proj_fused = value;
-        return 0;
-    }
-    if (strcmp(key, "mlp_stagger") == 0) {
-        dseg::options().mlp_stagger = value;
-        return 0;
-    }
-    if (strcmp(key, "mlp_grid") == 0) {
-        dseg::options().mlp_grid = value;
-        return 0;
-    }
-    if (strcmp(key, "splitk_tiles") == 0) {
-        dseg::options().splitk_tiles = value;
-        return 0;
-    }
-    if (strcmp(key, "deterministic") == 0) {       // the fine-tune step's reductions in a fixed order (kernels.h Options::deterministic)
-        dseg::options().deterministic = value ? 1 : 0;
-        return 0;
-    }
-    if (strcmp(key, "train_streams") == 0) {
-        dseg::options().train_streams = value;
-        return 0;
-    }
-    if (strcmp(key, "mlp_variant") == 0) return 0;      // (accepted and ignored: the one-wave-per-SIMD build was removed in round 4)
-    if (strcmp(key, "gemm_rs") == 0) {
-        dseg::options().gemm_rs = value & 7;
-        return 0;
-    }
-    if (strcmp(key, "gemm_rs_ln") == 0) {
-        dseg::options().gemm_rs_ln = value ? 1 : 0;
-        return 0;
-    }
-    if (strcmp(key, "gemm_rs_min_rows") == 0) {
-        dseg::options().gemm_rs_min_rows = value;
-        return 0;
-    }
-    if (strcmp(key, "qkv_fused3") == 0) {
-        dseg::options().qkv_fused3 = value ? 1 : 0;
-        return 0;
-    }
-    if (strcmp(key, "qkv_fused4") == 0) {
-        dseg::options().qkv_fused4 = value ? 1 : 0;
-        return 0;
-    }
-    if (strcmp(key, "mlp_fused4") == 0) {
-        dseg::options().mlp_fused4 = value ? 1 : 0;
-        return 0;
-    }
-    if (strcmp(key, "mlp_fused3_min_rows") == 0) {
-        dseg::options().mlp_fused3_min_rows = value;
-        return 0;
-    }
-    if (strcmp(key, "mlp_fused_min_rows") == 0) {
-        dseg::options().mlp_fused_min_rows = value;
-        return 0;
-    }
-    if (strcmp(key, "split_min") == 0) {
-        dseg::options().split_min = value < 2 ? 2 : value;
-        return 0;
-    }
-    if (strcmp(key, "gemm_dbg") == 0) {
-        dseg::options().gemm_dbg = value;
-        return 0;
-    }
-    if (strcmp(key, "attn_variant") == 0) {
-        dseg::options().attn_variant = value;
-        return 0;
-    }
-    if (strcmp(key, "attn_dbg") == 0) {
-        dseg::options().attn_dbg = value;
+    for (const OptionRow& row : OPTION_TABLE) {
+        if (strcmp(key, row.name) != 0) continue;
+        int v = 0;
+        DSEG_TRY(row.normalise(value, &v));
+        if (row.member) dseg::options().*row.member = v;
         return 0;
     }
     dinoseg_set_error("dinoseg_set_option: unknown key '%s'", key);

@@ -1,4 +1,4 @@
-// Internal: the handle behind the C-ABI (shared by api.hip and train_api.hip).
+// Internal: the handle behind the C-ABI (shared by api.hip, forward.hip and train_api.hip).
 #pragma once
 #include <map>
 #include <string>
@@ -8,7 +8,7 @@
 #include "common.h"
 #include "kernels.h"
 
-using namespace dseg;   // internal header: only included by the two API translation units
+using namespace dseg;   // internal header: only included by the API translation units
 
 #define DSEG_TRY(expr)            \
     do {                          \
@@ -183,6 +183,16 @@ static inline int check_stream_device(const dinoseg_handle* h, hipStream_t s) {
 // the handle's side stream + its fork / join events (api.hip): created on first use, destroyed with the workspaces
 int ensure_aux_stream(dinoseg_handle* h);
 
+// the inference workspace of B frames of Hf x Wf (api.hip): byte offsets of its buffers, the plane strides, the row counts
+struct WsLayout {
+    size_t X, A, Q, K, V, CTX, HB, FEAT, H1, H2, total;
+    long a_plane, qkv_plane, ctx_plane, hb_plane, feat_plane, h1_plane, h2_plane;
+    int n, ntok, npad, M, Mp;
+};
+WsLayout make_layout(const dinoseg_handle* h, int B, int Hf, int Wf);
+// slot 0: the caller's stream; slot 1: the second half-batch of a split forward (its own buffer, the handle's internal stream)
+int ensure_workspace(dinoseg_handle* h, int slot, const WsLayout& L, int B, int Hf, int Wf, hipStream_t s);
+
 static inline int prof_begin(dinoseg_handle* h, int cat, hipStream_t s) {
     if (h->prof_level == 0 || (h->prof_level == 1 && cat != DINOSEG_PROF_ATTN)) return -1;
     hipEvent_t ev[2];
@@ -201,13 +211,20 @@ static inline int prof_begin(dinoseg_handle* h, int cat, hipStream_t s) {
 static inline void prof_end(dinoseg_handle* h, int idx, hipStream_t s) {
     if (idx >= 0) (void)hipEventRecord(h->prof_recs[idx].b, s);
 }
-#define DSEG_PROF(cat, stmt)                  \
-    do {                                      \
-        const int _pi = prof_begin(h, cat, s); \
-        stmt;                                 \
-        prof_end(h, _pi, s);                  \
+// who enqueues: the handle, the stream, and whether the profiler counts the launches (the training forward records no events)
+struct StepEnv {
+    dinoseg_handle* h;
+    hipStream_t s;
+    bool profiled;
+};
+#define DSEG_PROF_ENV(env, cat, stmt)                                                         \
+    do {                                                                                   \
+        const int _pi = (env).profiled ? prof_begin((env).h, cat, (env).s) : -1;           \
+        stmt;                                                                              \
+        prof_end((env).h, _pi, (env).s);                                                   \
     } while (0)
-
+// ... with h and s of the enclosing function
+#define DSEG_PROF(cat, stmt) DSEG_PROF_ENV((StepEnv{h, s, true}), cat, stmt)
 
 static inline int head_planes() { return 2; }
 // the MLP head: embed_dim -> 200 -> 100 -> classes; the hidden activations are stored 256 / 128 wide, zero beyond their columns

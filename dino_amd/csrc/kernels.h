@@ -153,7 +153,7 @@ long mlp_fused4_pack_elems(int D, int F);       // 16-bit elements of the packed
 int launch_pack_mlp4(const MlpFused3Weights& w, int D, int F, bf16_t* dst, hipStream_t s, int fmt);
 int launch_mlp_fused4(const MlpFused3Params& p, hipStream_t s);
 
-// tuning knobs (dinoseg_set_option): see api.hip.  A handle's forward reads them as it runs, except four that decide which packed
+// tuning knobs (dinoseg_set_option: the table in api.hip).  A handle's forward reads them as it runs (forward.hip: plan_block), except four that decide which packed
 // copies dinoseg_refresh_weights lays out (every load_state_dict, in-place weight update and fine-tune step refreshes):
 // fp16_patch_planes and gemm_rs_ln are refresh-only, mlp_fused4 and the gemm_rs bits switch-off-only (below).  Every forward
 // equals, bit for bit, the same forward of a fresh handle whose first refresh saw fp16_patch_planes and gemm_rs_ln at their values
@@ -161,7 +161,7 @@ int launch_mlp_fused4(const MlpFused3Params& p, hipStream_t s);
 // current value (tests/test_refresh_routes_gpu.py).  A refresh that
 // changes which copies exist, or their offsets or sizes, bumps dinoseg_state_generation; one that keeps them does not.
 struct Options {
-    int gemm_ln = 1;         // qkv / fc1 through the LayerNorm-fused kernel (gemm_ln.hip): 0 never, 2 wherever it applies, 1 = by measurement (api.hip)
+    int gemm_ln = 1;         // qkv / fc1 through the LayerNorm-fused kernel (gemm_ln.hip): 0 never, 2 wherever it applies, 1 = by measurement (forward.hip: plan_block)
     int gemm_big = 1;        // use gemm_big.hip where it applies
     int gemm_dbg = 0;        // ablation bits copied into GemmParams::dbg (wrong results; timing only)
     int attn_dbg = 0;        // same for AttnParams::dbg (bits 0-2: attention.hip ablations, wrong results); bit 3: attention_za's one-block body for the
@@ -192,7 +192,7 @@ struct Options {
                              // Refresh-only: the copy carries the LayerNorm or not as this was at the last refresh; setting it in between
                              // changes nothing until the next refresh
     int proj_fused = 1;      // 1: the block's attention output projection runs inside the fused MLP launch
-    int streams = 2;         // 2: dinoseg_forward runs a batch of >= split_min frames as two half-batches on two streams (api.hip)
+    int streams = 2;         // 2: dinoseg_forward runs a batch of >= split_min frames as two half-batches on two streams (forward.hip)
     int split_min = 8;       // (8 frames @480: +6 %, 12: +16 %, 16: +12 %; 6 frames and fewer: slower split)
     int route_ab = 0;        // A/B switches of dispatch routes that do not change results: bit 0 = 128-row tiles for the residual GEMMs of a small
                              // batch (gemm.hip HALFM off), bit 1 = one wave per row in the LayerNorm backward (train.hip), bit 2 = the weight-

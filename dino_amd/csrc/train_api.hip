@@ -12,7 +12,7 @@
 
 #include <vector>
 
-#include "handle.h"
+#include "forward_steps.h"
 
 namespace {
 
@@ -357,22 +357,7 @@ extern "C" int dinoseg_op_pos_resample_bwd_hw(const float* dpos, int32_t g, int3
 // until the next call; train_backward_impl consumes it.
 static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t Hf, int32_t Wf, float* logp_out,
                               hipStream_t s) {
-    if (!h || !x || B <= 0) {
-        dinoseg_set_error("dinoseg_train_forward: bad argument");
-        return -1;
-    }
-    if (!frame_ok(Hf, Wf, h->cfg.patch)) {
-        set_resolution_error(h->cfg.patch);
-        return -1;
-    }
-    if (x_kind != DINOSEG_INPUT_U8_HWC && x_kind != DINOSEG_INPUT_F32_CHW) {
-        dinoseg_set_error("dinoseg_train_forward: bad x_kind %d", x_kind);
-        return -1;
-    }
-    if (!h->weights_ready) {
-        dinoseg_set_error("dinoseg_train_forward: weights not packed (call dinoseg_refresh_weights after binding)");
-        return -3;
-    }
+    DSEG_TRY(check_forward_args("dinoseg_train_forward", h, x, x_kind, B, Hf, Wf));
     if (h->fmt != FMT_BF16) {
         dinoseg_set_error("dinoseg_train_forward: precision fp16 is inference-only (fp16 gradients would need loss scaling); use bf16 or bf16x3");
         return -1;
@@ -381,9 +366,8 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
     DSEG_TRY(check_stream_device(h, s));
     DSEG_TRY(dinoseg_prepare_resolution_hw(h, Hf, Wf, reinterpret_cast<void*>(s)));
     const dinoseg_config& c = h->cfg;
-    const int D = c.embed_dim, F = D * c.mlp_ratio, P = h->planes, HP = head_planes(), H = c.num_heads, C = c.n_classes;
+    const int D = c.embed_dim, F = D * c.mlp_ratio, P = h->planes, H = c.num_heads, C = c.n_classes;
     const int NB = c.n_blocks;
-    const bool mlp_head = c.head_kind == DINOSEG_HEAD_MLP;
     const TrainLayout L = make_train_layout(h, B, Hf, Wf);
     const ModelRec& m = h->model;
 
@@ -415,26 +399,15 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
     }
 
     // =============================================================== forward (activations kept)
-    float mean255[3], inv255[3];
-    norm_consts(mean255, inv255);
-    bf16_t* PATCH = w.b16(L.PATCH);
-    DSEG_TRY(launch_patch_gather(x, x_kind, B, Hf, Wf, mean255, inv255, PATCH, L.patch_plane, P, s, FMT_BF16, c.patch));
+    const StepEnv env = {h, s, false};      // (no profile events: the classes count the inference forward's launches)
     float* X0 = NB > 0 ? w.f32(L.Xin) : w.f32(L.Xfin);
-    {
-        GemmParams g = linear_gemm(m.patch);
-        g.A = PATCH; g.a_plane = L.patch_plane; g.lda = 3 * c.patch * c.patch;
-        g.M = L.Mp; g.epi = EPI_PATCH;
-        g.out_f32 = X0; g.ldo_f32 = D;
-        g.pos = h->pos_cache; g.n_patches = L.n;
-        DSEG_TRY(launch_gemm(g, s));
-    }
-    DSEG_TRY(launch_cls_rows(X0, m.cls_token, h->pos_cache, B, L.ntok, D, s));
-    const float qscale = 0.125f * 1.44269504088896340736f;
+    DSEG_TRY(embed_tokens(env, {x, x_kind, B, Hf, Wf, w.b16(L.PATCH), L.patch_plane, P, FMT_BF16, X0, 0}));
 
     for (int l = 0; l < NB; ++l) {
         const BlockRec& blk = m.blocks[l];
         const auto [Xin, Xmid, LSE, A1, Q, Kb, V, CTX, A2, HPRE, HB] = w.block(l);
         float* Xout = l + 1 < NB ? w.block(l + 1).Xin : w.f32(L.Xfin);
+        const QkvOut qkv = {Q, Kb, V, L.qkv_plane, L.ntok, L.npad, H, D, QK_SCALE};
         const bool fuse_ln = options().gemm_ln != 0 && L.qkv_plane < (1L << 31) && L.f_plane < (1L << 31);
         if (fuse_ln && blk.qkv.slab) {
             // LN1 + qkv in one launch; the normalised planes the weight gradient needs are a by-product (a_out)
@@ -442,8 +415,7 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
             g.X = Xin; g.ldx = D; g.gamma = blk.norm1_w; g.beta = blk.norm1_b; g.eps = c.ln_eps;
             g.W = blk.qkv.slab; g.bias = blk.qkv.b;
             g.M = L.M; g.N = 3 * D; g.epi = EPI_QKV;
-            g.q = Q; g.k = Kb; g.v = V; g.qkv_plane = L.qkv_plane;
-            g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.dmodel = D; g.qscale = qscale;
+            set_qkv(g, qkv);
             g.a_out = A1; g.a_plane = L.a_plane;
             DSEG_TRY(launch_gemm_ln(g, D, P, s));
         } else {
@@ -453,8 +425,7 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
             GemmParams g = linear_gemm(blk.qkv);
             g.A = A1; g.a_plane = L.a_plane; g.lda = D;
             g.M = L.M; g.epi = EPI_QKV;
-            g.q = Q; g.k = Kb; g.v = V; g.qkv_plane = L.qkv_plane;
-            g.ntok = L.ntok; g.npad = L.npad; g.heads = H; g.dmodel = D; g.qscale = qscale;
+            set_qkv(g, qkv);
             DSEG_TRY(launch_gemm(g, s));
         }
         }
@@ -466,10 +437,8 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
             DSEG_TRY(launch_attention(a, s));
         }
         {
-            GemmParams g = linear_gemm(blk.proj);
-            g.A = CTX; g.a_plane = L.a_plane; g.lda = D;
-            g.M = L.M; g.epi = EPI_RESID;
-            g.resid = Xin; g.out_f32 = Xmid; g.ldo_f32 = D;
+            GemmParams g = resid_gemm(blk.proj, CTX, L.a_plane, L.M, Xmid);
+            g.resid = Xin;
             DSEG_TRY(launch_gemm(g, s));
         }
         if (fuse_ln && blk.fc1.slab) {
@@ -477,7 +446,7 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
             g.X = Xmid; g.ldx = D; g.gamma = blk.norm2_w; g.beta = blk.norm2_b; g.eps = c.ln_eps;
             g.W = blk.fc1.slab; g.bias = blk.fc1.b;
             g.M = L.M; g.N = F; g.epi = EPI_GELU;
-            g.out_bf16 = HB; g.out_plane = L.f_plane; g.ldo = F;
+            set_hidden_out(g, HB, L.f_plane, F);
             g.a_out = A2; g.a_plane = L.a_plane;
             g.aux_out = HPRE; g.aux_plane = L.f_plane;
             DSEG_TRY(launch_gemm_ln(g, D, P, s));
@@ -488,42 +457,19 @@ static int train_forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, 
             GemmParams g = linear_gemm(blk.fc1);
             g.A = A2; g.a_plane = L.a_plane; g.lda = D;
             g.M = L.M; g.epi = EPI_GELU;
-            g.out_bf16 = HB; g.out_plane = L.f_plane; g.ldo = F; g.aux_out = HPRE; g.aux_plane = L.f_plane;
+            set_hidden_out(g, HB, L.f_plane, F);
+            g.aux_out = HPRE; g.aux_plane = L.f_plane;
             DSEG_TRY(launch_gemm(g, s));
         }
         }
         {
-            GemmParams g = linear_gemm(blk.fc2);
-            g.A = HB; g.a_plane = L.f_plane; g.lda = F;
-            g.M = L.M; g.epi = EPI_RESID;
-            g.resid = Xmid; g.out_f32 = Xout; g.ldo_f32 = D;
+            GemmParams g = resid_gemm(blk.fc2, HB, L.f_plane, L.M, Xout);
+            g.resid = Xmid;
             DSEG_TRY(launch_gemm(g, s));
         }
     }
     const auto [Xfin, LOGP, FEAT, H1, H2] = w.head();
-    DSEG_TRY(launch_layernorm(Xfin, m.norm_w, m.norm_b, c.ln_eps, L.M, D, FEAT, L.feat_plane, HP,
-                              nullptr, 1, L.ntok, s));
-    if (mlp_head) {
-        {
-            GemmParams g = linear_gemm(m.head[0]);
-            g.A = FEAT; g.a_plane = L.feat_plane; g.lda = D;
-            g.M = L.Mp; g.epi = EPI_RELU;
-            g.out_bf16 = H1; g.out_plane = L.h1_plane; g.ldo = HEAD_H1_PAD;
-            DSEG_TRY(launch_gemm(g, s));
-        }
-        {
-            GemmParams g = linear_gemm(m.head[1]);
-            g.A = H1; g.a_plane = L.h1_plane; g.lda = HEAD_H1_PAD;
-            g.M = L.Mp; g.epi = EPI_RELU;
-            g.out_bf16 = H2; g.out_plane = L.h2_plane; g.ldo = HEAD_H2_PAD;
-            DSEG_TRY(launch_gemm(g, s));
-        }
-        DSEG_TRY(launch_head_final(H2, L.h2_plane, HEAD_H2_PAD, L.Mp, HEAD_H2, m.clf.w, m.clf.b, C, LOGP,
-                                   nullptr, s, FMT_BF16, m.clf.pk.w, m.clf.pk.plane));
-    } else {
-        DSEG_TRY(launch_head_final(FEAT, L.feat_plane, D, L.Mp, D, m.clf.w, m.clf.b, C, LOGP,
-                                   nullptr, s, FMT_BF16, m.clf.pk.w, m.clf.pk.plane));
-    }
+    DSEG_TRY(run_head(env, {Xfin, L.M, L.Mp, L.ntok, FEAT, H1, H2, L.feat_plane, L.h1_plane, L.h2_plane, FMT_BF16, LOGP, nullptr}));
     if (logp_out) DSEG_CHECK_HIP(hipMemcpyAsync(logp_out, LOGP, (size_t)L.Mp * C * 4, hipMemcpyDeviceToDevice, s));
     h->tr_B = B;
     h->tr_H = Hf;

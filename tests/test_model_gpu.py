@@ -445,7 +445,7 @@ def test_g4_960_batch8_frames_are_independent(cuda, precision, tol, flip_frac):
 @pytest.mark.parametrize("precision", ["bf16", "bf16x3"])
 @pytest.mark.parametrize("B", [16, 17])
 def test_two_stream_split_equals_one_stream(cuda, precision, B):
-    """Option 'streams' = 2 (api.hip: dinoseg_forward): a batch of >= 8 frames runs as two half-batches on two streams.  Frames are
+    """Option 'streams' = 2 (forward.hip: dinoseg_forward): a batch of >= 8 frames runs as two half-batches on two streams.  Frames are
     independent (pl_torch_modules.py:253), the kernels and the per-row arithmetic are the same: identical outputs, also for an odd
     batch, also when the call is repeated (workspaces / events reused) and when other work is queued on the caller's stream."""
     import dino_amd
@@ -496,7 +496,7 @@ def test_two_stream_split_equals_one_stream_at_the_benchmark_batch(cuda, precisi
     """32 frames @480 (the headline shape): a whole batch of 901 row panels takes the persistent GEMMs in the split mode where a
     16-frame half on its own (451 panels) would take the 128x128 kernel -- another summation order (the r03 parity line
     read outputs_identical_to_two_streams = false).  Every size-dependent kernel choice of a half-batch is now made for the rows of
-    the whole call (GemmParams::dispatch_rows, forward_impl's disp_M), so the split changes no bit in any precision."""
+    the whole call (GemmParams::dispatch_rows, forward.hip's disp_M), so the split changes no bit in any precision."""
     import dino_amd
     m, _, _ = build(2, precision)
     frames = torch.from_numpy(synthetic_frames(32, 480, seed=91)).cuda()
