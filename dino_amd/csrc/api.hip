@@ -1,5 +1,5 @@
 // C-ABI of libdinoseg_hip.so (see include/dinoseg.h): handle, weight binding / packing, workspaces, options, profiling and the
-// stand-alone ops.  The forward of the DINOSeg hot path is forward.hip, the fine-tune step train_api.hip.  Host code only; kernels
+// stand-alone ops.  The forward of the DINOSeg hot path is forward.hip, the fine-tune step train_api.hip (its backward: backward.hip).  Host code only; kernels
 // live in gemm.hip / attention.hip / elementwise.hip.
 #include <stdarg.h>
 #include <stdio.h>

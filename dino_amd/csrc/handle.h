@@ -1,4 +1,4 @@
-// Internal: the handle behind the C-ABI (shared by api.hip, forward.hip and train_api.hip).
+// Internal: the handle behind the C-ABI (shared by api.hip, forward.hip, train_api.hip and backward.hip).
 #pragma once
 #include <map>
 #include <string>
@@ -127,7 +127,7 @@ struct dinoseg_handle {
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool in_split = false;                 // a split forward is being queued (both halves' launches share the chip)
-    // fine-tune step state (train_api.hip)
+    // fine-tune step state (train_api.hip, backward.hip; the layout of tws: train_ws.h)
     GradRec grad;                          // bound gradient buffers and the transposed weights
     char* tws = nullptr;                  // training workspace: saved activations + backward scratch
     size_t tws_bytes = 0;
@@ -139,7 +139,7 @@ struct dinoseg_handle {
     // n_blocks-1-k, n_blocks + 1 = embeddings; stage_done = number of stages the last backward recorded
     std::vector<hipEvent_t> stage_ev;
     int stage_done = 0;
-    // fork / join events of the weight-gradient side stream (option train_streams = 2: train_api.hip); aux_stream is shared with
+    // fork / join events of the weight-gradient side stream (option train_streams = 2: backward.hip, SideStream); aux_stream is shared with
     // the split forward
     std::vector<hipEvent_t> bw_ev;
     char* twbuf = nullptr;                 // transposed packed weights for the input-gradient GEMMs

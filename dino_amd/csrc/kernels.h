@@ -196,7 +196,7 @@ struct Options {
     int split_min = 8;       // (8 frames @480: +6 %, 12: +16 %, 16: +12 %; 6 frames and fewer: slower split)
     int route_ab = 0;        // A/B switches of dispatch routes that do not change results: bit 0 = 128-row tiles for the residual GEMMs of a small
                              // batch (gemm.hip HALFM off), bit 1 = one wave per row in the LayerNorm backward (train.hip), bit 2 = the weight-
-                             // gradient GEMM's split count not rounded to a multiple of 8 (its XCD-aware grid off: train_api.hip, gemm_tn.hip)
+                             // gradient GEMM's split count not rounded to a multiple of 8 (its XCD-aware grid off: train_ws.h tn_slices, gemm_tn.hip)
     int fp16_patch_planes = 1;      // precision fp16: 1 = the patch embedding on one fp16 plane like the rest of the mode (2466 -> 2486 frames/s,
                                     // 0.0263 / 8 flips -> 0.0218 / 5 on the G3 fixture), 2 = on bf16 hi+lo planes (round 4's first build).
                                     // Refresh-only: read when the weights are packed (the next dinoseg_refresh_weights), never in between
@@ -206,7 +206,7 @@ struct Options {
     int deterministic = 0;   // 1: the fine-tune step sums the loss, the bias and the LayerNorm gamma / beta gradients in a FIXED order (per-block
                              // partials into a scratch area + one ordered pass; the side stream's gemm_tn launches have their own region)
                              // instead of fp32 atomics: two runs from the same state are bit-identical (tests/test_train_gpu.py)
-    int train_streams = 2;   // 2: backward runs the weight-gradient GEMMs of the blocks on the handle's side stream (train_api.hip)
+    int train_streams = 2;   // 2: backward runs the weight-gradient GEMMs of the blocks on the handle's side stream (backward.hip)
     int splitk_tiles = 512;  // weight-gradient GEMMs: partial 128x128 tiles per launch (<= 768, the workspace holds that many)
     int attn_variant = 11 | 1024 | 65536;
                              // bit 0: overflow check on the row sums instead of a per-tile row maximum; bit 1: idle waves skip the

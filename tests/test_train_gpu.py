@@ -563,7 +563,7 @@ def test_deterministic_option_makes_the_fine_tune_step_bit_reproducible(cuda, pr
 
 
 def test_deterministic_bias_only_layers_on_the_side_stream(cuda):
-    """ADVICE r5 (train_api.hip: wgrad_tn): a Linear whose weight is frozen but whose bias trains gets its bias gradient from a column-sum
+    """ADVICE r5 (backward.hip: wgrad_tn): a Linear whose weight is frozen but whose bias trains gets its bias gradient from a column-sum
     pass (transpose_planes) that may be queued on the weight-gradient SIDE stream; in the deterministic mode its partial sums now go to
     that stream's own region of the scratch, not into the region the caller's stream is using at the same moment (LayerNorm backward,
     det_finalize).  Every Linear weight of the backbone frozen, biases and norms trainable: two runs bit-identical, and equal to the

@@ -30,13 +30,16 @@ S8 = ViTConfig(n_blocks=2)
 TINY = ViTConfig(embed_dim=128, num_heads=2, n_blocks=2)
 VITB = ViTConfig(embed_dim=768, num_heads=12, n_blocks=1)
 P16 = ViTConfig(patch=16, pos_grid=14, n_blocks=2, head="linear", n_classes=150)
+NOBLOCK = ViTConfig(n_blocks=0)
+WIDE = ViTConfig(n_blocks=2, n_classes=150)
 
 
 def block_weight(n, p):
     return n.startswith("dino.blocks.") and n.endswith(".weight") and p.dim() == 2
 
 
-# name: (config, precision, frame rows, frame columns, train_streams, which parameters train, through torch.autograd)
+# name: (config, precision, frame rows, frame columns, train_streams, which parameters train, through torch.autograd or "dense" = the
+# fused step on pixel labels of the frame's size[, options set for the case and reset to their defaults (OPTION_DEFAULTS) after it])
 CASES = {
     "vits8 bf16": (S8, "bf16", 64, 64, 2, "all", False),
     "vits8 bf16x3": (S8, "bf16x3", 64, 64, 2, "all", False),
@@ -50,14 +53,33 @@ CASES = {
     "bias-only freeze one stream": (S8, "bf16x3", 64, 64, 1, "no block weights", False),
     "autograd": (S8, "bf16x3", 64, 64, 2, "all", True),
     "autograd one stream bf16": (S8, "bf16", 64, 64, 1, "all", True),
+    "no blocks": (NOBLOCK, "bf16x3", 64, 64, 2, "all", False),              # the final norm hands a null fc2 bias, the block loop is empty
+    "gemm_ln=0 bf16": (S8, "bf16", 64, 64, 2, "all", False, {"gemm_ln": 0}),      # LayerNorm + GEMM fallback of the training forward
+    "gemm_ln=0 bf16x3": (S8, "bf16x3", 64, 64, 2, "all", False, {"gemm_ln": 0}),
+    "mlp head C=150": (WIDE, "bf16x3", 64, 64, 2, "all", False),             # the wide head's dz_ld
+    "64x128": (S8, "bf16x3", 64, 128, 2, "all", False),                      # the rectangular pos-embed scratch in T2
+    "dense": (S8, "bf16x3", 64, 64, 2, "all", "dense"),                      # the dws growth and the dlogp entry
+    "splitk_tiles=1": (S8, "bf16x3", 64, 64, 2, "all", False, {"splitk_tiles": 1}),      # the two ends of the weight gradients' slice count
+    "route_ab=4": (S8, "bf16x3", 64, 64, 2, "all", False, {"route_ab": 4}),
 }
+OPTION_DEFAULTS = {"gemm_ln": 1, "splitk_tiles": 512, "route_ab": 0}
 
 
 def sha(t):
     return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
 
 
-def run(cfg, prec, H, W, streams, train, autograd):
+def run(cfg, prec, H, W, streams, train, autograd, opts={}):
+    for k, v in opts.items():
+        dino_amd.set_option(k, v)
+    try:
+        return run_case(cfg, prec, H, W, streams, train, autograd)
+    finally:
+        for k in opts:
+            dino_amd.set_option(k, OPTION_DEFAULTS[k])
+
+
+def run_case(cfg, prec, H, W, streams, train, autograd):
     dino_amd.set_option("train_streams", streams)
     sd = procedural_state_dict(cfg)
     m = DINOSeg(head=cfg.head, n_blocks=cfg.n_blocks, n_classes=cfg.n_classes, precision=prec, arch=cfg, optimizer=torch.optim.Adam, lr=1e-3)
@@ -68,9 +90,12 @@ def run(cfg, prec, H, W, streams, train, autograd):
     n_patches = (H // cfg.patch) * (W // cfg.patch)
     fr = torch.from_numpy(synthetic_frames(2, H, seed=181, w=W)).cuda()
     lb = torch.from_numpy(synthetic_labels(2, n_patches, cfg.n_classes, seed=182)).cuda()
+    px = torch.from_numpy(synthetic_labels(2, H * W, cfg.n_classes, seed=183)).reshape(2, H, W).cuda()
     out = {}
     for step in range(2):
-        if autograd:
+        if autograd == "dense":
+            loss = m.fused_training_step_dense((fr, px), step)["loss"]
+        elif autograd:
             for p in m.parameters():
                 p.grad = None
             loss = m.training_step((fr, lb), step)["loss"]
