@@ -6,16 +6,16 @@
 //                flip_k == 1 mirrors the view's grid horizontally first: the taps are columns wp_k-1-i0 and wp_k-1-i1, in that
 //                order, with the same lambda ("flip the low-res grid back, then upsample").
 //     lse_k    = m_k + logf(sum_c exp(v_k[c] - m_k)),  m_k = max_c v_k[c]       (a running maximum: one exp per class)
-//     p_k[c]   = exp(v_k[c] - lse_k)                    (the softmax of the interpolated scores: mmseg's protocol; exp = upe_exp below)
+//     p_k[c]   = exp(v_k[c] - lse_k)                    (the softmax of the interpolated scores: mmseg's protocol; exp = up_exp)
 //     s[c]     = p_0[c] + p_1[c] + ... in view order, fp32;   probs[c] = s[c] / K
 //     label    = the FIRST maximum of s over classes;   conf = max_c s[c] / K
 // No atomics: bit-identical from run to run.
 //
-// One workgroup = one 64 x 32 output tile of one frame, wave w rows 8w .. 8w+7, lane l column l, the scalar-branch row walk of
-// upsample.hip.  Two phases inside the launch:
-//   A  per view: the view's footprint is staged in LDS as upsample.hip stages it (cell-major, odd stride, as many classes per pass as
-//      fit), every lane carries a running (max, sum) per pixel and leaves the 8 log-sum-exps of its strip in the caller's scratch
-//      ([K, B, OH, OW] fp32; each lane reads back only what it wrote itself).
+// One workgroup = one 64 x 32 output tile of one frame: the tile, the staging and the strip walk of upsample_common.h.  Two phases
+// inside the launch:
+//   A  per view: the view's footprint is staged in LDS (as many classes per pass as fit), every lane carries a running (max, sum)
+//      per pixel and leaves the 8 log-sum-exps of its strip in the caller's scratch ([K, B, OH, OW] fp32; each lane reads back
+//      only what it wrote itself).
 //   B  per class chunk: the footprints of ALL views are staged side by side; four classes at a time a lane walks the views (view
 //      parameters and the 8 LSEs are fetched once per four classes), adds exp(v - lse) into s[4][8], and keeps the running first
 //      maximum.  4 (+4, +4 C) bytes per pixel are written.
@@ -32,11 +32,6 @@ namespace {
 constexpr int UPE_VT = 8, UPE_XT = 4 * UP_TW, UPE_RT = 4 * UP_TH;     // table words per view: footprint, columns, rows
 constexpr int UPE_TABLE_WORDS = UPE_VT + UPE_XT + UPE_RT;
 constexpr int UPE_CR = 4;                                              // classes per walk over the views in phase B
-constexpr int UPE_LDS_SMALL = 16384, UPE_LDS_LARGE = 40960;           // words: the default 64 KiB, and the CU's whole 160 KiB
-
-// exp of an argument <= 0 (up to rounding): v_exp_f32 of x log2(e), as upsample_loss.hip takes it.  The product's rounding moves the result
-// by at most |x| e^x 2^-24 <= 2.2e-8 ABSOLUTE (|x| e^x <= 1 / e), the instruction by one ulp of a value <= 1: far inside what the sums carry.
-__device__ __forceinline__ float upe_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 
 struct UpEnsPlan {
     int tiles_x, tiles_y, CCB, data_words;
@@ -52,19 +47,11 @@ __global__ __launch_bounds__(256) void upsample_ensemble_kernel(UpEnsViews views
     int* xt = vt + K * UPE_VT;                      // [K][64][4]: the lane's two footprint columns, lambda
     int* rt = xt + K * UPE_XT;                      // [K][32][4]: the row's two footprint rows (in cells), lambda, enters-a-new-row
     float* data = reinterpret_cast<float*>(rt + K * UPE_RT);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int t = blockIdx.x;
-    const int tx = t % tiles_x;
-    t /= tiles_x;
-    const int ty = t % tiles_y, b = t / tiles_y;
-    const int x_first = tx * UP_TW, y_first = ty * UP_TH;
-    const int x_last = (x_first + UP_TW < OW ? x_first + UP_TW : OW) - 1, y_last = (y_first + UP_TH < OH ? y_first + UP_TH : OH) - 1;
-    const int x = x_first + lane, xc = x < OW ? x : OW - 1;     // lanes beyond the frame compute its last column and store nothing
-    const int y0 = y_first + wave * UP_ROWS;
-    const bool active = y0 < OH, x_ok = x < OW;
-    const size_t plane = (size_t)OH * OW;
-    const size_t pix0 = (size_t)y0 * OW + x;
+    const UpTile T = up_tile(tiles_x, tiles_y, OH, OW);
+    const int tid = T.tid, lane = T.lane, wave = T.wave, b = T.b, y0 = T.y0;
+    const int x_first = T.x_first, y_first = T.y_first, x_last = T.x_last, y_last = T.y_last, xc = T.xc;
+    const bool active = T.active, x_ok = T.x_ok;
+    const size_t plane = T.plane, pix0 = T.pix0;
 
     // the coordinate tables: wave w fills views w, w+4, ...
     for (int k = wave; k < K; k += UP_WAVES) {
@@ -114,13 +101,8 @@ __global__ __launch_bounds__(256) void upsample_ensemble_kernel(UpEnsViews views
         const int hp = views.v[k].hp, wp = views.v[k].wp;
         const int fc0 = __builtin_amdgcn_readfirstlane(vt[k * UPE_VT + 0]), fr0 = __builtin_amdgcn_readfirstlane(vt[k * UPE_VT + 1]);
         const int ncols = __builtin_amdgcn_readfirstlane(vt[k * UPE_VT + 2]), ncells = __builtin_amdgcn_readfirstlane(vt[k * UPE_VT + 3]);
-        int CC = data_words / ncells;
-        if (CC > C) CC = C;
-        if ((CC | 1) * ncells > data_words) --CC;   // the stride is odd
-        const int stride = CC | 1;
-        int kw_log2 = 0;
-        while (kw_log2 < 6 && (1 << kw_log2) < CC) ++kw_log2;
-        const int kw = 1 << kw_log2;
+        const UpPass ps = up_pass(data_words, ncells, C);
+        const int CC = ps.CC, stride = ps.stride;
 
         const int* xe = xt + (k * UP_TW + lane) * 4;
         const int off0 = xe[0] * stride, off1 = xe[1] * stride;
@@ -134,44 +116,20 @@ __global__ __launch_bounds__(256) void upsample_ensemble_kernel(UpEnsViews views
             ro1[j] = __builtin_amdgcn_readfirstlane(re[1]) * stride;
             ly[j] = __int_as_float(__builtin_amdgcn_readfirstlane(re[2]));
             adv[j] = __builtin_amdgcn_readfirstlane(re[3]);
-            mx[j] = -3.0e38f;
+            mx[j] = UP_LSE_MX0;
             sum[j] = 0.f;
         }
         for (int c0 = 0; c0 < C; c0 += CC) {
             const int cn = C - c0 < CC ? C - c0 : CC;
             __syncthreads();
-            for (int cell = tid >> kw_log2; cell < ncells; cell += 256 >> kw_log2) {
-                const int r = cell / ncols, col = cell - r * ncols;
-                const float* g = logp + (((size_t)b * hp + fr0 + r) * wp + fc0 + col) * C + c0;
-                float* d = data + cell * stride;
-                for (int q = tid & (kw - 1); q < cn; q += kw) d[q] = g[q];
-            }
+            up_stage(data, logp, b, hp, wp, C, fr0, fc0, ncols, ncells, c0, cn, stride, ps.kw_log2);
             __syncthreads();
             if (!active) continue;
             for (int q = 0; q < cn; ++q) {
                 const float* p = data + q;
-                float a = p[ro0[0] + off0], bb = p[ro0[0] + off1];
-                float h0 = __builtin_fmaf(bb - a, lx, a);
-                a = p[ro1[0] + off0];
-                bb = p[ro1[0] + off1];
-                float h1 = __builtin_fmaf(bb - a, lx, a);
-                float dh = h1 - h0;
+                UpWalk w(p, ro0[0], ro1[0], off0, off1, lx);
 #pragma unroll
-                for (int j = 0; j < UP_ROWS; ++j) {
-                    if (adv[j]) {                   // the next source row: i0 grows by exactly one when OH >= hp
-                        h0 = h1;
-                        a = p[ro1[j] + off0];
-                        bb = p[ro1[j] + off1];
-                        h1 = __builtin_fmaf(bb - a, lx, a);
-                        dh = h1 - h0;
-                    }
-                    const float v = __builtin_fmaf(dh, ly[j], h0);
-                    // running max-subtracted sum: one exp per class, whichever of (v, max) is the larger
-                    const float d = v - mx[j];
-                    const float e = upe_exp(-__builtin_fabsf(d));
-                    sum[j] = d > 0.f ? __builtin_fmaf(sum[j], e, 1.f) : sum[j] + e;
-                    mx[j] = __builtin_fmaxf(mx[j], v);
-                }
+                for (int j = 0; j < UP_ROWS; ++j) up_lse_update(mx[j], sum[j], w.at(p, adv[j], ro1[j], off0, off1, lx, ly[j]));
             }
         }
         if (active && x_ok) {
@@ -191,10 +149,7 @@ __global__ __launch_bounds__(256) void upsample_ensemble_kernel(UpEnsViews views
         idx[j] = 0;
     }
     const float Kf = (float)K;
-    const int stride = CCB | 1;
-    int kw_log2 = 0;
-    while (kw_log2 < 6 && (1 << kw_log2) < CCB) ++kw_log2;
-    const int kw = 1 << kw_log2;
+    const int stride = up_pass_of(CCB).stride, kw_log2 = up_pass_of(CCB).kw_log2;
     for (int c0 = 0; c0 < C; c0 += CCB) {
         const int cn = C - c0 < CCB ? C - c0 : CCB;
         __syncthreads();
@@ -204,12 +159,7 @@ __global__ __launch_bounds__(256) void upsample_ensemble_kernel(UpEnsViews views
             const int fc0 = __builtin_amdgcn_readfirstlane(vt[k * UPE_VT + 0]), fr0 = __builtin_amdgcn_readfirstlane(vt[k * UPE_VT + 1]);
             const int ncols = __builtin_amdgcn_readfirstlane(vt[k * UPE_VT + 2]), ncells = __builtin_amdgcn_readfirstlane(vt[k * UPE_VT + 3]);
             float* vd = data + __builtin_amdgcn_readfirstlane(vt[k * UPE_VT + 4]) * stride;
-            for (int cell = tid >> kw_log2; cell < ncells; cell += 256 >> kw_log2) {
-                const int r = cell / ncols, col = cell - r * ncols;
-                const float* g = logp + (((size_t)b * hp + fr0 + r) * wp + fc0 + col) * C + c0;
-                float* d = vd + cell * stride;
-                for (int q = tid & (kw - 1); q < cn; q += kw) d[q] = g[q];
-            }
+            up_stage(vd, logp, b, hp, wp, C, fr0, fc0, ncols, ncells, c0, cn, stride, kw_log2);
         }
         __syncthreads();
         if (!active) continue;
@@ -241,23 +191,17 @@ __global__ __launch_bounds__(256) void upsample_ensemble_kernel(UpEnsViews views
                 for (int q = 0; q < UPE_CR; ++q) {
                     if (q >= qn) break;
                     const float* p = vd + q;
-                    float a = p[ro0 + off0], bb = p[ro0 + off1];
-                    float h0 = __builtin_fmaf(bb - a, lx, a);
-                    a = p[ro1[0] + off0];
-                    bb = p[ro1[0] + off1];
-                    float h1 = __builtin_fmaf(bb - a, lx, a);
-                    float dh = h1 - h0;
+                    // UpWalk's steps written out: inside this four-class, all-views loop the struct compiles to a stream that
+                    // measures 0.6-0.8 % slower at 150 classes (profiles/upsample_family_ab.md)
+                    float h0 = up_hlerp(p, ro0, off0, off1, lx), h1 = up_hlerp(p, ro1[0], off0, off1, lx), dh = h1 - h0;
 #pragma unroll
                     for (int j = 0; j < UP_ROWS; ++j) {
                         if (adv[j]) {
                             h0 = h1;
-                            a = p[ro1[j] + off0];
-                            bb = p[ro1[j] + off1];
-                            h1 = __builtin_fmaf(bb - a, lx, a);
+                            h1 = up_hlerp(p, ro1[j], off0, off1, lx);
                             dh = h1 - h0;
                         }
-                        const float v = __builtin_fmaf(dh, ly[j], h0);
-                        s[q][j] += upe_exp(v - lse[j]);
+                        s[q][j] += up_exp(__builtin_fmaf(dh, ly[j], h0) - lse[j]);
                     }
                 }
             }
@@ -270,10 +214,7 @@ __global__ __launch_bounds__(256) void upsample_ensemble_kernel(UpEnsViews views
                     if (PROBS) {
                         if (x_ok && y0 + j < OH) probs[((size_t)b * C + c) * plane + pix0 + (size_t)j * OW] = s[q][j] / Kf;
                     }
-                    if (s[q][j] > best[j]) {
-                        best[j] = s[q][j];
-                        idx[j] = c;
-                    }
+                    up_first_max(best[j], idx[j], s[q][j], c);
                 }
             }
         }
@@ -294,40 +235,23 @@ __global__ __launch_bounds__(256) void upsample_ensemble_kernel(UpEnsViews views
 int upsample_ensemble_plan(const char* who, const UpEnsViews& views, int K, int C, int OH, int OW, UpEnsPlan* plan) {
     long long cells = 0, widest = 0;
     for (int k = 0; k < K; ++k) {
-        int max_cols = 1, max_rows = 1;
-        for (int axis = 0; axis < 2; ++axis) {
-            const int o = axis ? OH : OW, i = axis ? views.v[k].hp : views.v[k].wp, step = axis ? UP_TH : UP_TW;
-            int& most = axis ? max_rows : max_cols;
-            for (int first = 0; first < o; first += step) {
-                const int last = (first + step < o ? first + step : o) - 1;
-                int a0, a1, b0, b1;
-                unsigned rem;
-                up_index(first, i, o, &a0, &a1, &rem);
-                up_index(last, i, o, &b0, &b1, &rem);
-                if (b1 - a0 + 1 > most) most = b1 - a0 + 1;
-            }
-        }
-        cells += (long long)max_cols * max_rows;        // <= 65 * 33 per view
-        if ((long long)max_cols * max_rows > widest) widest = (long long)max_cols * max_rows;
+        const long long view = (long long)up_max_footprint(views.v[k].wp, OW, UP_TW) * up_max_footprint(views.v[k].hp, OH, UP_TH);
+        cells += view;                                  // <= 65 * 33 per view
+        if (view > widest) widest = view;
     }
     const int tables = K * UPE_TABLE_WORDS;
-    int CC = 0, budget = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        budget = (pass ? UPE_LDS_LARGE : UPE_LDS_SMALL) - tables;
-        CC = (int)(budget / cells);
-        if (CC > C) CC = C;
-        if ((CC | 1) * cells > budget) --CC;            // the stride is odd: an even CC takes one more word per cell
-        if (CC >= (C < 8 ? C : 8)) break;
-    }
+    long long budget;
+    const UpPass ps = up_pass_two_budgets(tables, cells, C, &budget);
+    const int CC = ps.CC;
     if (CC < 1) {
         dinoseg_set_error("%s: the %d views' footprints of one tile add up to %lld cells, more than the LDS holds (%d words)", who, K, cells,
-                          budget);
+                          (int)budget);
         return -1;
     }
     // phase A stages one view: let it take all its classes in one pass where the default 64 KiB allows
-    long long data_words = cells * (CC | 1);
-    long long want = widest * (C | 1);
-    if (want > UPE_LDS_SMALL - tables) want = UPE_LDS_SMALL - tables;
+    long long data_words = cells * ps.stride;
+    long long want = widest * up_pass_of(C).stride;
+    if (want > UP_LDS_WORDS - tables) want = UP_LDS_WORDS - tables;
     if (want > data_words) data_words = want;
     *plan = {(OW + UP_TW - 1) / UP_TW, (OH + UP_TH - 1) / UP_TH, CC, (int)data_words, (size_t)(tables + data_words) * sizeof(float)};
     return 0;
@@ -377,13 +301,9 @@ int launch_upsample_ensemble(const UpEnsViews& views, int K, int B, int C, int O
     UpEnsPlan pl;
     if (upsample_ensemble_plan("upsample_ensemble", views, K, C, OH, OW, &pl)) return -1;
     static PerDeviceOnce once;
-    if (once.first()) {
-        DSEG_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&upsample_ensemble_kernel<true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, UPE_LDS_LARGE * (int)sizeof(float)));
-        DSEG_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&upsample_ensemble_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, UPE_LDS_LARGE * (int)sizeof(float)));
-        once.mark();
-    }
+    const int rc = up_allow_large_lds(once, "upsample_ensemble_kernel", reinterpret_cast<const void*>(&upsample_ensemble_kernel<true>),
+                                      reinterpret_cast<const void*>(&upsample_ensemble_kernel<false>));
+    if (rc) return rc;
     const unsigned grid = (unsigned)((long long)pl.tiles_x * pl.tiles_y * B);
     float* lse = reinterpret_cast<float*>(scratch);
     if (probs)

@@ -30,8 +30,6 @@ constexpr int UPNLL_IGNORE = -100;          // F.cross_entropy's default ignore_
 constexpr int UPNLL_ACC_BYTES = 256;        // scratch: [0, 256) the accumulators {loss sum, valid pixels}, then lse, then the tile partials
 constexpr int GQ = 32;                      // the gather stages a quadrant in chunks of at most GQ x GQ pixels
 
-__device__ __forceinline__ float upnll_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-
 __device__ __forceinline__ void upnll_finish(const float* acc, float* loss, float* n_valid) {
     const float n = acc[1];
     *loss = n > 0.f ? acc[0] / n : __builtin_nanf("");      // torch: the mean over zero pixels is nan
@@ -43,36 +41,11 @@ __global__ __launch_bounds__(256) void upnll_lse_kernel(const float* __restrict_
                                                         int ignore_index, float* __restrict__ lse_out, float* __restrict__ acc,
                                                         int* __restrict__ flags, float* __restrict__ det) {
     extern __shared__ float up_lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int t = blockIdx.x;
-    const int tx = t % tiles_x;
-    t /= tiles_x;
-    const int ty = t % tiles_y, b = t / tiles_y;
-    const int x_first = tx * UP_TW, y_first = ty * UP_TH;
-    const int x_last = (x_first + UP_TW < OW ? x_first + UP_TW : OW) - 1, y_last = (y_first + UP_TH < OH ? y_first + UP_TH : OH) - 1;
-    const int fc0 = up_coord(x_first, wp, OW).i0, fr0 = up_coord(y_first, hp, OH).i0;
-    const int ncols = up_coord(x_last, wp, OW).i1 - fc0 + 1, nrows = up_coord(y_last, hp, OH).i1 - fr0 + 1;
-    const int ncells = ncols * nrows;
-
-    const int x = x_first + lane, xc = x < OW ? x : OW - 1;
-    const UpCoord cx = up_coord(xc, wp, OW);
-    const int off0 = (cx.i0 - fc0) * stride, off1 = (cx.i1 - fc0) * stride;
-    const float lx = cx.lam;
-    const int y0 = y_first + wave * UP_ROWS;
-    const bool active = y0 < OH, x_ok = x < OW;
-    int ro0[UP_ROWS], ro1[UP_ROWS];
-    float ly[UP_ROWS];
-#pragma unroll
-    for (int j = 0; j < UP_ROWS; ++j) {
-        const int y = y0 + j < OH ? y0 + j : OH - 1;
-        const UpCoord cy = up_coord(y, hp, OH);
-        ro0[j] = (cy.i0 - fr0) * ncols * stride;
-        ro1[j] = (cy.i1 - fr0) * ncols * stride;
-        ly[j] = cy.lam;
-    }
-    const size_t plane = (size_t)OH * OW;
-    const size_t pix0 = (size_t)b * plane + (size_t)y0 * OW + x;
+    const UpTile T = up_tile(tiles_x, tiles_y, OH, OW);
+    const int tid = T.tid, lane = T.lane, wave = T.wave, b = T.b, y0 = T.y0;
+    const bool active = T.active, x_ok = T.x_ok;
+    const UpStrip S = up_strip(T, hp, wp, OH, OW, stride);
+    const size_t pix0 = (size_t)b * T.plane + T.pix0;
     // this lane's labels: -1 = not a valid pixel (outside the frame, ignored, or out of range)
     int tl[UP_ROWS];
     float mx[UP_ROWS], sum[UP_ROWS], ut[UP_ROWS];
@@ -80,7 +53,7 @@ __global__ __launch_bounds__(256) void upnll_lse_kernel(const float* __restrict_
 #pragma unroll
     for (int j = 0; j < UP_ROWS; ++j) {
         tl[j] = -1;
-        mx[j] = -3.0e38f;
+        mx[j] = UP_LSE_MX0;
         sum[j] = 0.f;
         ut[j] = 0.f;
         if (active && x_ok && y0 + j < OH) {
@@ -93,42 +66,20 @@ __global__ __launch_bounds__(256) void upnll_lse_kernel(const float* __restrict_
     }
     if (bad && flags) atomicOr(flags, 1);
 
-    const int kw = 1 << kw_log2;
     for (int c0 = 0; c0 < C; c0 += CC) {
         const int cn = C - c0 < CC ? C - c0 : CC;
         if (c0) __syncthreads();
-        for (int cell = tid >> kw_log2; cell < ncells; cell += 256 >> kw_log2) {
-            const int r = cell / ncols, col = cell - r * ncols;
-            const float* g = logp + (((size_t)b * hp + fr0 + r) * wp + fc0 + col) * C + c0;
-            float* d = up_lds + cell * stride;
-            for (int k = tid & (kw - 1); k < cn; k += kw) d[k] = g[k];
-        }
+        up_stage(up_lds, logp, b, hp, wp, C, S.fr0, S.fc0, S.ncols, S.ncells, c0, cn, stride, kw_log2);
         __syncthreads();
         if (!active) continue;
         for (int k = 0; k < cn; ++k) {
             const float* p = up_lds + k;
-            float a = p[ro0[0] + off0], bb = p[ro0[0] + off1];
-            float h0 = __builtin_fmaf(bb - a, lx, a);
-            a = p[ro1[0] + off0];
-            bb = p[ro1[0] + off1];
-            float h1 = __builtin_fmaf(bb - a, lx, a);
-            float dh = h1 - h0;
+            UpWalk w(p, S.ro0[0], S.ro1[0], S.off0, S.off1, S.lx);
             const int c = c0 + k;
 #pragma unroll
             for (int j = 0; j < UP_ROWS; ++j) {
-                if (j > 0 && ro0[j] != ro0[j - 1]) {
-                    h0 = h1;
-                    a = p[ro1[j] + off0];
-                    bb = p[ro1[j] + off1];
-                    h1 = __builtin_fmaf(bb - a, lx, a);
-                    dh = h1 - h0;
-                }
-                const float v = __builtin_fmaf(dh, ly[j], h0);
-                // running max-subtracted sum: one exp per class, whichever of (v, max) is the larger
-                const float d = v - mx[j];
-                const float e = upnll_exp(-__builtin_fabsf(d));
-                sum[j] = d > 0.f ? __builtin_fmaf(sum[j], e, 1.f) : sum[j] + e;
-                mx[j] = __builtin_fmaxf(mx[j], v);
+                const float v = w.at(p, j > 0 && S.ro0[j] != S.ro0[j - 1], S.ro1[j], S.off0, S.off1, S.lx, S.ly[j]);
+                up_lse_update(mx[j], sum[j], v);
                 if (c == tl[j]) ut[j] = v;
             }
         }
@@ -275,7 +226,7 @@ __global__ __launch_bounds__(256) void upnll_grad_kernel(const float* __restrict
                             const float lx = q_lx[xa + xx], ly = q_ly[ya + yy];
                             const float h0 = __builtin_fmaf(d0, lx, a), h1 = __builtin_fmaf(d1, lx, a2);
                             const float v = __builtin_fmaf(h1 - h0, ly, h0);
-                            const float g = upnll_exp(v - q_lse[ti]) - (tt == k ? 1.f : 0.f);
+                            const float g = up_exp(v - q_lse[ti]) - (tt == k ? 1.f : 0.f);
                             const float w = (qx ? 1.f - lx : lx) * (qy ? 1.f - ly : ly);
                             sacc = __builtin_fmaf(w, g, sacc);
                         }

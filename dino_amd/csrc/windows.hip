@@ -30,7 +30,6 @@ namespace dseg {
 namespace {
 
 constexpr int WM_CR = 4;                                               // classes per walk over the windows
-constexpr int WM_LDS_SMALL = 16384, WM_LDS_LARGE = 40960;             // words: the default 64 KiB, and the CU's whole 160 KiB
 constexpr int WM_MAX_COVERAGE = 4;                                     // windows over one pixel row / column
 
 // one axis of the window rule; s is clamped to max(L - w, 1) on the host (the same origins), so i s + w stays far inside int32
@@ -89,20 +88,12 @@ __global__ __launch_bounds__(256) void window_merge_kernel(const float* __restri
     int* ycnt = colpart + totc_cap;                 // [32]: windows over each row of the tile
     int* tot = ycnt + UP_TH;                        // staged rows, staged columns
     float* data = reinterpret_cast<float*>(tot + 4);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int H = ay.L, W = ax.L;
-    int t = blockIdx.x;
-    const int tx = t % tiles_x;
-    t /= tiles_x;
-    const int ty = t % tiles_y, b = t / tiles_y;
-    const int x_first = tx * UP_TW, y_first = ty * UP_TH;
-    const int x_last = (x_first + UP_TW < W ? x_first + UP_TW : W) - 1, y_last = (y_first + UP_TH < H ? y_first + UP_TH : H) - 1;
-    const int x = x_first + lane, xc = x < W ? x : W - 1;      // lanes beyond the frame compute its last column and store nothing
-    const int y0 = y_first + wave * UP_ROWS;
-    const bool active = y0 < H, x_ok = x < W;
-    const size_t plane = (size_t)H * W;
-    const size_t pix0 = (size_t)y0 * W + x;
+    const UpTile T = up_tile(tiles_x, tiles_y, H, W);
+    const int tid = T.tid, lane = T.lane, wave = T.wave, b = T.b, y0 = T.y0;
+    const int x_first = T.x_first, y_first = T.y_first, x_last = T.x_last, y_last = T.y_last, xc = T.xc;
+    const bool active = T.active, x_ok = T.x_ok;
+    const size_t plane = T.plane, pix0 = T.pix0;
     const int ncell_win = ay.gp * ax.gp;                        // cells of one window's grid
 
     int gy_lo, gy_hi, gx_lo, gx_hi;
@@ -191,17 +182,15 @@ __global__ __launch_bounds__(256) void window_merge_kernel(const float* __restri
         best[j] = -INFINITY;
         idx[j] = 0;
     }
-    const int stride = CC | 1;
+    const int stride = up_pass_of(CC).stride;
     const int rstride = totc * stride;
     const int ncells = totr * totc;
-    int kw_log2 = 0;
-    while (kw_log2 < 6 && (1 << kw_log2) < CC) ++kw_log2;
-    const int kw = 1 << kw_log2;
+    const int kw_log2 = up_pass_of(CC).kw_log2, kw = 1 << kw_log2;    // (after rstride and ncells: kw_log2 first costs one s_waitcnt)
 
     for (int c0 = 0; c0 < C; c0 += CC) {
         const int cn = C - c0 < CC ? C - c0 : CC;
         if (c0) __syncthreads();
-        // stage classes c0 .. c0+cn of every window's footprint: kw lanes walk the classes of one cell (contiguous in memory)
+        // stage classes c0 .. c0+cn of every window's footprint: up_stage's loop, the source cell from the two tables
         for (int cell = tid >> kw_log2; cell < ncells; cell += 256 >> kw_log2) {
             const int r = cell / totc, col = cell - r * totc;
             const float* g = logp + (size_t)(rowpart[r] + colpart[col]) * C + c0;
@@ -244,15 +233,10 @@ __global__ __launch_bounds__(256) void window_merge_kernel(const float* __restri
 #pragma unroll
                         for (int j = 0; j < UP_ROWS; ++j) {
                             if (mode[j] == 0) continue;
-                            if (mode[j] == 3) {
-                                const float a = p[ro0[j] + off0], bb = p[ro0[j] + off1];
-                                h0 = __builtin_fmaf(bb - a, lx, a);
-                            } else if (mode[j] == 2) {
-                                h0 = h1;
-                            }
+                            if (mode[j] == 3) h0 = up_hlerp(p, ro0[j], off0, off1, lx);
+                            else if (mode[j] == 2) h0 = h1;
                             if (mode[j] >= 2) {
-                                const float a = p[ro1[j] + off0], bb = p[ro1[j] + off1];
-                                h1 = __builtin_fmaf(bb - a, lx, a);
+                                h1 = up_hlerp(p, ro1[j], off0, off1, lx);
                                 dh = h1 - h0;
                             }
                             const float v = __builtin_fmaf(dh, ly[j], h0);
@@ -271,10 +255,7 @@ __global__ __launch_bounds__(256) void window_merge_kernel(const float* __restri
                     if (DENSE) {
                         if (x_ok && y0 + j < H) dense[((size_t)b * C + c) * plane + pix0 + (size_t)j * W] = m;
                     }
-                    if (m > best[j]) {
-                        best[j] = m;
-                        idx[j] = c;
-                    }
+                    up_first_max(best[j], idx[j], m, c);
                 }
             }
         }
@@ -382,21 +363,15 @@ int window_merge_plan(const char* who, const WinAxis& ay, const WinAxis& ax, int
     }
     const long long cells = (long long)most_ext[0] * most_ext[1];
     const long long tables = wm_table_words(most_win[0], most_win[1], most_ext[0], most_ext[1]);
-    long long CC = 0, budget = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        budget = (pass ? WM_LDS_LARGE : WM_LDS_SMALL) - tables;
-        CC = budget > 0 ? budget / cells : 0;
-        if (CC > C) CC = C;
-        if ((CC | 1) * cells > budget) --CC;            // the stride is odd: an even CC takes one more word per cell
-        if (CC >= (C < 8 ? C : 8)) break;
-    }
-    if (CC < 1) {
+    long long budget;
+    const UpPass ps = up_pass_two_budgets(tables, cells, C, &budget);
+    if (ps.CC < 1) {
         dinoseg_set_error("%s: the windows' footprints under one tile add up to %lld cells, more than the LDS holds (%lld words)", who,
                           cells, budget);
         return -1;
     }
-    *plan = {(ax.L + UP_TW - 1) / UP_TW, (ay.L + UP_TH - 1) / UP_TH, (int)CC, most_win[0], most_win[1], most_ext[0], most_ext[1],
-             (size_t)(tables + cells * (CC | 1)) * sizeof(float)};
+    *plan = {(ax.L + UP_TW - 1) / UP_TW, (ay.L + UP_TH - 1) / UP_TH, ps.CC, most_win[0], most_win[1], most_ext[0], most_ext[1],
+             (size_t)(tables + cells * ps.stride) * sizeof(float)};
     return 0;
 }
 
@@ -472,13 +447,9 @@ int launch_window_merge(const float* logp, int B, int H, int W, int patch, int w
         window_merge_plan(who, ay, ax, C, &pl))
         return -1;
     static PerDeviceOnce once;
-    if (once.first()) {
-        DSEG_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&window_merge_kernel<true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, WM_LDS_LARGE * (int)sizeof(float)));
-        DSEG_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&window_merge_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, WM_LDS_LARGE * (int)sizeof(float)));
-        once.mark();
-    }
+    const int rc = up_allow_large_lds(once, "window_merge_kernel", reinterpret_cast<const void*>(&window_merge_kernel<true>),
+                                      reinterpret_cast<const void*>(&window_merge_kernel<false>));
+    if (rc) return rc;
     const unsigned grid = (unsigned)((long long)pl.tiles_x * pl.tiles_y * B);
     if (dense)
         hipLaunchKernelGGL(window_merge_kernel<true>, dim3(grid), dim3(256), pl.lds_bytes, s, logp, ay, ax, C, pl.tiles_x, pl.tiles_y,

@@ -16,6 +16,8 @@ CASES = [
     (1, 150, 480, 640, [(30, 40, 0), (60, 80, 1), (90, 120, 0)]),                       # production ratio
     (3, 1, 8, 8, [(1, 1, 0), (1, 1, 1)]),
 ]
+# eight views at the output's own size: the large-LDS path (tests/test_ensemble_gpu.py, tools/upsample_digest.py)
+LARGE_LDS_CASE = (1, 5, 40, 70, [(40, 70, k & 1) for k in range(8)])
 IDS = ["B%d-C%d-%dx%d-K%d" % (c[0], c[1], c[2], c[3], len(c[4])) for c in CASES]
 
 

@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from dino_amd import DINOSeg, ViTConfig, capi, procedural_state_dict, view_sizes
 from dino_amd.weights import synthetic_frames
 
-from .ensemble_util import CASES, IDS, case_data, random_views, reference_probs
+from .ensemble_util import CASES, IDS, LARGE_LDS_CASE, case_data, random_views, reference_probs
 
 pytestmark = pytest.mark.gpu
 S = capi.stream_ptr
@@ -105,7 +105,7 @@ def test_many_views_near_identity_size_take_the_large_lds(cuda):
     """Eight views at the output's own size: under one 64 x 32 tile their footprints add up to 8 * 65 * 33 = 17160 cells, which
     with the coordinate tables is more than 64 KiB even at one class per pass -- the launch asks for more of the CU's LDS.  Two
     tiles on each axis, both ragged; the mirrored views read the frame's other edge."""
-    case = (1, 5, 40, 70, [(40, 70, k & 1) for k in range(8)])
+    case = LARGE_LDS_CASE
     logps = random_views(case)
     check_against_fp64("B1-C5-40x70-K8-identity", case, logps, reference_probs(case, logps))
 
