@@ -133,6 +133,10 @@ SIGNATURES = {
     # the helper kernels on their own (tests/test_helper_ops_gpu.py)
     "dinoseg_op_attn_probs": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _fp, _vp]),
     "dinoseg_op_cls_mask_attn": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _fp, _i32, _vp, _i64, _fp, _vp]),
+    # CLS attention maps at pixel resolution with the cumulative-mass threshold: the launch alone, behind the forward, its token limit
+    "dinoseg_op_cls_attention": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _fp, _fp, _vp]),
+    "dinoseg_cls_attention_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _fp, _fp, _vp]),
+    "dinoseg_cls_attention_max_tokens": (_i32, []),
     "dinoseg_op_cls_rows": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _vp]),
     "dinoseg_op_broadcast_row0": (C.c_int, [_fp, _i32, _i32, _vp]),
     "dinoseg_op_batch_sum_rows": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _vp]),

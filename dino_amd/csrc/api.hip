@@ -1112,6 +1112,42 @@ extern "C" int dinoseg_op_attn_probs(const void* q, const void* k, int64_t qkv_p
                              reinterpret_cast<hipStream_t>(stream), options().op_fmt);
 }
 
+extern "C" int32_t dinoseg_cls_attention_max_tokens(void) { return cls_attention_max_tokens(); }
+
+extern "C" int dinoseg_op_cls_attention(const void* q, const void* k, int64_t qkv_plane, int32_t planes, int32_t B, int32_t heads, int32_t ntok,
+                                        int32_t npad, int32_t hp, int32_t wp, int32_t OH, int32_t OW, float threshold, float* attn_out,
+                                        uint8_t* keep_out, void* stream) {
+    const char* who = "dinoseg_op_cls_attention";
+    if (!q || !k || (!attn_out && !keep_out)) {
+        dinoseg_set_error("%s: null pointer (q, k, and at least one of attn_out / keep_out, are required)", who);
+        return -1;
+    }
+    if (planes != 1 && planes != 2) {
+        dinoseg_set_error("%s: planes=%d must be 1 or 2", who, planes);
+        return -1;
+    }
+    if (cls_attention_check(who, B, heads, ntok, hp, wp, OH, OW, keep_out != nullptr, threshold)) return -1;
+    if (npad < ntok) {
+        dinoseg_set_error("%s: npad=%d is smaller than ntok=%d", who, npad, ntok);
+        return -1;
+    }
+    if ((int64_t)B * heads > INT64_MAX / 64 / npad) {
+        dinoseg_set_error("%s: B*heads*npad*64 (B=%d heads=%d npad=%d) is too large", who, B, heads, npad);
+        return -1;
+    }
+    if (planes == 2 && (qkv_plane < (int64_t)B * heads * npad * 64 || qkv_plane % 8 != 0)) {
+        dinoseg_set_error("%s: qkv_plane=%lld puts the lo plane inside the hi plane of %lld elements, or off a 16-byte boundary", who,
+                          (long long)qkv_plane, (long long)B * heads * npad * 64);
+        return -1;
+    }
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) {
+        dinoseg_set_error("%s: q and k must be 16-byte aligned", who);
+        return -1;
+    }
+    return launch_cls_attention(reinterpret_cast<const bf16_t*>(q), reinterpret_cast<const bf16_t*>(k), qkv_plane, planes, B, heads, ntok, npad,
+                                hp, wp, OH, OW, threshold, attn_out, keep_out, reinterpret_cast<hipStream_t>(stream), options().op_fmt);
+}
+
 extern "C" int dinoseg_op_cls_mask_attn(const void* q, const void* k, const void* v, int64_t qkv_plane, int32_t planes, int32_t heads,
                                         int32_t ntok, int32_t npad, const float* mask, int32_t n_masks, void* ctx, int64_t ctx_plane,
                                         float* probs, void* stream) {

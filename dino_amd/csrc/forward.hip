@@ -1,7 +1,7 @@
 // The inference forward of the DINOSeg hot path on one MI355X (see include/dinoseg.h): dinoseg_forward*, dinoseg_last_selfattention*,
-// dinoseg_forward_mask* and dinoseg_features*.  Host code only: a request (what the call wants back), a per-call context (buffers and
-// sizes), the route of each block as a value (plan_block: the one reader of the options in the block loop), and the stages that
-// enqueue what the route says.  The handle, the weights, the workspaces and the options live in api.hip.
+// dinoseg_cls_attention_hw, dinoseg_forward_mask* and dinoseg_features*.  Host code only: a request (what the call wants back), a
+// per-call context (buffers and sizes), the route of each block as a value (plan_block: the one reader of the options in the block
+// loop), and the stages that enqueue what the route says.  The handle, the weights, the workspaces and the options live in api.hip.
 #include "forward_steps.h"
 
 using namespace dseg;
@@ -16,6 +16,10 @@ struct ForwardRequest {
     int32_t tap_block = -1;             // debug tap: the token rows after prepare_tokens (0) or after block tap_block
     float* tap_out = nullptr;
     float* attn_out = nullptr;          // get_last_selfattention: the probabilities of the last block, then stop
+    float* cls_attn_out = nullptr;      // dinoseg_cls_attention_hw: the CLS row of those probabilities over the patches, enlarged to
+    uint8_t* cls_keep_out = nullptr;    // OH x OW (below), and / or its cumulative-mass threshold at cls_threshold, then stop
+    float cls_threshold = 0.f;
+    bool wants_cls_attention() const { return cls_attn_out || cls_keep_out; }
     const float* cls_mask = nullptr;    // forward_mask / get_last_selfattention(x, cls_mask): the last block on the CLS token through
     int n_masks = 0;                    // each of n_masks masks; the masked probabilities (mask_attn_out) and / or one embedding
     float* mask_attn_out = nullptr;     // per mask (emb_out), then stop
@@ -388,6 +392,12 @@ int forward_impl(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, in
         DSEG_TRY(run_ln_qkv(c, blk, route.qkv));
         if (rq.attn_out && last)        // get_last_selfattention: probabilities of the last block, then stop
             return launch_attn_probs(c.Q, c.K, c.L.qkv_plane, c.P, B, h->cfg.num_heads, c.L.ntok, c.L.npad, rq.attn_out, s, c.FM);
+        if (rq.wants_cls_attention() && last) {
+            DSEG_PROF_ENV(c.env, DINOSEG_PROF_ATTN, DSEG_TRY(launch_cls_attention(c.Q, c.K, c.L.qkv_plane, c.P, B, h->cfg.num_heads, c.L.ntok, c.L.npad,
+                                                                              Hf / h->cfg.patch, Wf / h->cfg.patch, rq.OH, rq.OW,
+                                                                              rq.cls_threshold, rq.cls_attn_out, rq.cls_keep_out, s, c.FM)));
+            return 0;
+        }
         if (rq.cls_mask && last) return run_masked_last_block(c, blk);
         DSEG_TRY(run_attention(c));
         DSEG_TRY(run_block_tail(c, blk, i, route));
@@ -482,6 +492,35 @@ extern "C" int dinoseg_last_selfattention_hw(dinoseg_handle* h, const void* x, i
 extern "C" int dinoseg_last_selfattention(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* attn_out,
                                           void* stream) {
     return dinoseg_last_selfattention_hw(h, x, x_kind, B, r, r, attn_out, stream);
+}
+
+// The forward up to the last block's LayerNorm1 + qkv, then the CLS attention launch (cls_attention.hip).  Everything that launch would
+// refuse is refused here, before the forward enqueues anything.
+extern "C" int dinoseg_cls_attention_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t OH,
+                                        int32_t OW, float threshold, float* attn_out, uint8_t* keep_out, void* stream) {
+    const char* who = "dinoseg_cls_attention_hw";
+    if (!h || !x || B <= 0 || h->cfg.n_blocks < 1) {
+        dinoseg_set_error("%s: bad argument (null handle or frames, B=%d, or a model without blocks)", who, B);
+        return -1;
+    }
+    if (!attn_out && !keep_out) {
+        dinoseg_set_error("%s: null pointer (at least one of attn_out / keep_out is required)", who);
+        return -1;
+    }
+    if (!frame_ok(H, W, h->cfg.patch)) {
+        set_resolution_error(h->cfg.patch);
+        return -1;
+    }
+    const int hp = H / h->cfg.patch, wp = W / h->cfg.patch;
+    if ((long long)hp * wp + 1 > 0x7fffffffll) {
+        dinoseg_set_error("%s: a %dx%d frame has too many tokens", who, H, W);
+        return -1;
+    }
+    if (cls_attention_check(who, B, h->cfg.num_heads, hp * wp + 1, hp, wp, OH, OW, keep_out != nullptr, threshold)) return -1;
+    ForwardRequest rq;
+    rq.cls_attn_out = attn_out; rq.cls_keep_out = keep_out; rq.cls_threshold = threshold;
+    rq.OH = OH; rq.OW = OW;
+    return forward_impl(h, x, x_kind, B, H, W, rq, stream);
 }
 
 extern "C" int dinoseg_forward_mask_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t H, int32_t W, const float* cls_mask,

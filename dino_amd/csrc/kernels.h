@@ -280,6 +280,15 @@ int launch_attn_probs(const bf16_t* q, const bf16_t* k, long plane, int planes, 
 // cm[gt][pred] += 1 over n patches (int64 [C,C], accumulates)
 int launch_cls_mask_attn(const bf16_t* q, const bf16_t* k, const bf16_t* v, long plane, int planes, int heads, int ntok, int npad,
                          const float* mask, int n_masks, bf16_t* ctx, long ctx_plane, float* probs, hipStream_t s, int fmt = 0);
+// CLS attention maps at pixel resolution (cls_attention.hip; the rule: include/dinoseg.h, dinoseg_op_cls_attention): the CLS query row
+// of softmax(q k^T) over all ntok = hp*wp + 1 keys, its patch part enlarged to OH x OW by nearest neighbour -> attn_out fp32 and / or
+// keep_out uint8 (the cumulative-mass threshold) [B, heads, OH, OW].  q, k as launch_attn_probs reads them.  One launch, one workgroup
+// per (frame, head), no atomics, no scratch.  cls_attention_check: the host-side refusals of the shape alone (-1 and a message
+// starting with `who`); cls_attention_max_tokens: the most tokens whose scores fit the LDS of one workgroup.
+int cls_attention_max_tokens();
+int cls_attention_check(const char* who, int B, int heads, int ntok, int hp, int wp, int OH, int OW, bool want_keep, float threshold);
+int launch_cls_attention(const bf16_t* q, const bf16_t* k, long plane, int planes, int B, int heads, int ntok, int npad, int hp, int wp,
+                         int OH, int OW, float threshold, float* attn_out, uint8_t* keep_out, hipStream_t s, int fmt = 0);
 int launch_broadcast_row0(float* X, int D, int n, hipStream_t s);
 int launch_resize_u8(const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw, hipStream_t s);
 int launch_confusion(const int32_t* pred, const int64_t* gt, long n, int C, int64_t* cm, hipStream_t s);

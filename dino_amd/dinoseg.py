@@ -170,6 +170,10 @@ class _ViTParams(nn.Module):
         """vision_transformer.py:273-280; reference call site visualize_attention.py:46."""
         return self._owner().get_last_selfattention(x, cls_mask)
 
+    def cls_attention(self, x, size=None, threshold=None):
+        """The CLS row of ``get_last_selfattention(x)`` over the patches at pixel resolution: ``DINOSeg.cls_attention``."""
+        return self._owner().cls_attention(x, size, threshold)
+
     def get_intermediate_layers(self, x: torch.Tensor, n: int = 1) -> list:
         """vision_transformer.py:282-290: ``norm(x)`` of all tokens after each of the last ``n`` blocks, oldest first (a list of
         [B, N, D] tensors; every block when n exceeds the depth).  One ``dinoseg_features`` call per tap: the library keeps one
@@ -961,6 +965,47 @@ class DINOSeg(nn.Module):
         capi.check(capi.lib().dinoseg_last_selfattention_hw(self._handle, x.data_ptr(), capi.INPUT_F32_CHW, B, H, W, out.data_ptr(),
                                                             self._stream()))
         return out
+
+    @torch.no_grad()
+    def cls_attention(self, x: torch.Tensor, size=None, threshold: Optional[float] = None):
+        """CLS attention maps of the last block at pixel resolution, ``(attn, keep)``: what the reference's visualize_attention.py
+        draws, without the [B, heads, N, N] matrix of ``get_last_selfattention`` (csrc/cls_attention.hip, one launch behind the last
+        block's qkv).  x: uint8 [B,H,W,3] or fp32 [B,3,H,W] frames.  ``attn`` fp32 [B, heads, OH, OW] is
+        ``get_last_selfattention(x)[:, :, 0, 1:]`` on the (H/patch, W/patch) grid, enlarged to ``size = (OH, OW)`` (default the
+        frames' own (H, W); any OH >= H/patch, OW >= W/patch) by nearest neighbour with exact integer coordinates -- for the default
+        size ``F.interpolate(..., scale_factor=patch, mode="nearest")``, so the script's enlarged maps are ``cls_attention(x)[0]``.
+        ``keep`` is None without a threshold, else uint8 [B, heads, OH, OW]: 1 where the patch is in the top ``threshold`` share of
+        the patches' attention mass (0 < threshold < 1).  ``dt_utils.process_attentions(model.dino.get_last_selfattention(x),
+        threshold)`` for frame 0 is ``cls_attention(x, size=(hp, wp), threshold=threshold)``: its ``keep`` when a threshold is given,
+        its ``attn`` otherwise.  The threshold is the reference's sort / cumulative-sum rule in exact integers (include/dinoseg.h,
+        dinoseg_op_cls_attention): a tied group is kept or dropped whole.  Inference only."""
+        kind, B, H, W = self._prep_frames(x)
+        p = self.cfg.patch
+        if H % p != 0 or W % p != 0 or H < p or W < p:
+            raise ValueError(self._resolution_message())
+        if B < 1:
+            raise ValueError("empty batch")
+        hp, wp = H // p, W // p
+        OH, OW = self._out_size(size, (H, W))
+        if OH < hp or OW < wp:
+            raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(hp, wp)}")
+        if threshold is not None:
+            threshold = float(np.float32(threshold))       # the value the library sees
+            if not 0.0 < threshold < 1.0:
+                raise ValueError(f"threshold must be inside (0, 1), got {threshold}")
+        limit = capi.lib().dinoseg_cls_attention_max_tokens()
+        if hp * wp + 1 > limit:
+            raise ValueError(f"a {H}x{W} frame has {hp * wp + 1} tokens, more than the {limit} one launch holds")
+        self._require_gpu()
+        x, kind, B, H, W = self._prep_batch(x)
+        self._sync_weights()
+        heads = self.cfg.num_heads
+        attn = torch.empty((B, heads, OH, OW), dtype=torch.float32, device=x.device)
+        keep = torch.empty((B, heads, OH, OW), dtype=torch.uint8, device=x.device) if threshold is not None else None
+        capi.check(capi.lib().dinoseg_cls_attention_hw(self._handle, x.data_ptr(), kind, B, H, W, OH, OW,
+                                                       0.0 if threshold is None else threshold, attn.data_ptr(), capi.ptr(keep),
+                                                       self._stream()))
+        return attn, keep
 
     # ---- validation metrics (pl_torch_modules.py:302-345) ------------------------------------------
     def validation_step(self, batch, batch_idx=0):

@@ -105,6 +105,20 @@ int dinoseg_forward_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t
 /* dinoseg_last_selfattention at H x W (vision_transformer.py:273-280): attn_out [B, heads, n+1, n+1] */
 int dinoseg_last_selfattention_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W,
                                   float* attn_out, void* stream);
+/* CLS attention maps at pixel resolution: what visualize_attention.py draws (attentions[0, :, 0, 1:] of get_last_selfattention,
+ * enlarged by the patch size with nearest-neighbour) and what dt_utils.process_attentions thresholds, for B frames, without the
+ * [B, heads, n+1, n+1] matrix.  The forward runs up to the last block's LayerNorm1 + qkv; one more launch (dinoseg_op_cls_attention,
+ * where the rule is stated in full) writes
+ *   attn_out fp32  [B, heads, OH, OW]: the CLS query's softmax probabilities of the n patch keys (softmax over all n + 1 keys),
+ *   keep_out uint8 [B, heads, OH, OW]: 1 where the patch belongs to the top `threshold` share of the patches' attention mass,
+ * each nullable, not both; any OH >= hp, OW >= wp (OH = hp, OW = wp: the raw grid; OH = H, OW = W: the script's enlarged maps).
+ * threshold is read only with keep_out and must lie inside (0, 1).  x of either kind.  Everything the launch would refuse -- and
+ * a frame of more than dinoseg_cls_attention_max_tokens() tokens -- is refused before the forward enqueues anything.  Timed under
+ * DINOSEG_PROF_ATTN. */
+int dinoseg_cls_attention_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t OH, int32_t OW,
+                             float threshold, float* attn_out, uint8_t* keep_out, void* stream);
+/* the most tokens (hp*wp + 1) of a frame whose scores fit the LDS of the launch's workgroup */
+int32_t dinoseg_cls_attention_max_tokens(void);
 /* dinoseg_forward_mask at H x W (vision_transformer.py:250-271): cls_mask [n_masks, hp*wp] (the (N, H/8, W/8) masks, row-major),
  * n_masks <= hp*wp; attn_out [heads, n_masks, n+1] */
 int dinoseg_forward_mask_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t H, int32_t W, const float* cls_mask,
@@ -667,6 +681,27 @@ int dinoseg_op_pos_resample_bwd_hw(const float* dpos, int32_t g, int32_t D, int3
  * out fp32 [B, heads, ntok, ntok]. */
 int dinoseg_op_attn_probs(const void* q, const void* k, int64_t qkv_plane, int32_t planes, int32_t B, int32_t heads, int32_t ntok,
                           int32_t npad, float* out, void* stream);
+/* The CLS query row of that softmax at pixel resolution, with dt_utils.process_attentions' cumulative-mass threshold, in one launch
+ * (one workgroup per (frame, head); the N x N matrix is never formed).  q, k as dinoseg_op_attn_probs reads them (rows >= ntok are
+ * never read; the lo plane at + qkv_plane elements, qkv_plane >= B*heads*npad*64 and a multiple of 8; pointers 16-byte aligned);
+ * ntok = hp*wp + 1, at most dinoseg_cls_attention_max_tokens().
+ *   Softmax: s_n = q_0 . k_n in fp32 for every key n < ntok (token 0 is the CLS query); p_n = 2^(s_n - max_n s_n) / sum_n 2^(s_n - max)
+ *     over ALL ntok keys (q carries head_dim^-0.5 log2 e, so this is softmax(q k^T head_dim^-0.5)); the patches are p_1 .. p_{ntok-1},
+ *     patch j - 1 = (row, column) of the hp x wp grid, row-major: get_last_selfattention(x)[b, h, 0, 1:].
+ *   Threshold (only with keep_out; threshold inside (0, 1), else -1): q_j = rint(p_j 2^30) as an unsigned 32-bit integer, T = sum_j q_j
+ *     over the patches, S_le(v) = the sum of the q_j <= v, t = rint(threshold 2^24) (threshold as the fp32 value passed).  Patch j is
+ *     kept iff S_le(q_j) 2^24 > (2^24 - t) T, all in unsigned 64-bit integers (T < 2^31: no overflow).  This is process_attentions'
+ *     rule -- sort ascending, normalise by the patches' own sum, keep where the cumulative sum exceeds 1 - threshold -- made exact:
+ *     integer sums do not depend on their order, so a host restatement reproduces every decision.  It differs from the fp32 sort /
+ *     cumsum in the 2^-30 quantisation and at exact ties: the reference keeps a suffix of a tied group in unspecified sort order, this
+ *     rule keeps the whole group.
+ *   Output: pixel (oy, ox) of the OH x OW map takes patch (sy, sx) = ((oy hp) / OH, (ox wp) / OW), integer division; for integer
+ *     multiples this is F.interpolate(scale_factor=patch, mode="nearest").  Any OH >= hp, OW >= wp.
+ * attn_out fp32 [B, heads, OH, OW], keep_out uint8 (0 / 1) [B, heads, OH, OW]; each nullable, not both.  attn_out is the same bits
+ * with and without keep_out; two runs give the same bits. */
+int dinoseg_op_cls_attention(const void* q, const void* k, int64_t qkv_plane, int32_t planes, int32_t B, int32_t heads, int32_t ntok,
+                             int32_t npad, int32_t hp, int32_t wp, int32_t OH, int32_t OW, float threshold, float* attn_out,
+                             uint8_t* keep_out, void* stream);
 /* Attention.forward(x, cls_mask) for the CLS query of ONE frame (vision_transformer.py:80-107): the CLS row's logits times
  * [0, mask], softmax over all ntok keys, @ V.  q, k, v: [planes][heads, npad, 64] (with one fp16 plane V is bf16, as the fused
  * attention has it); mask fp32 [n_masks][ntok - 1]; ctx: planes [planes][n_masks][heads * 64] (lo at + ctx_plane elements); probs
