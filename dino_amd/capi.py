@@ -37,7 +37,7 @@ class Config(C.Structure):
     ]
 
 
-_vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+_vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _fp = C.c_void_p   # device float* / int32_t* travel as raw addresses
 
 # name -> (restype, argtypes); must list every function include/dinoseg.h declares (checked by tests)
@@ -145,6 +145,10 @@ SIGNATURES = {
     # pixel-resolution output: bilinear upsample + argmax of the log-probs, alone and behind the forward
     "dinoseg_op_upsample_argmax": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _vp]),
     "dinoseg_forward_dense_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _vp]),
+    # image-guided pixel-resolution output (joint bilateral upsample): the cell colours, the upsample + argmax, both behind the forward
+    "dinoseg_op_guide_cells": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _i32, _fp, _vp]),
+    "dinoseg_op_upsample_guided": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _fp, _fp, _vp]),
+    "dinoseg_forward_guided_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _fp, _i32, _i32, _i32, _f64, _f64, _fp, _fp, _fp, _fp, _vp]),
     # pixel-resolution training loss: upsample + cross-entropy + its gradient, alone and as the fine-tune step on pixel labels
     "dinoseg_op_upsample_nll_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "dinoseg_op_upsample_nll": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _i32, _fp, _fp, _fp, _fp, _vp, _vp]),

@@ -588,6 +588,18 @@ extern "C" int dinoseg_op_upsample_argmax(const float* logp, int32_t B, int32_t 
     return launch_upsample_argmax(logp, B, hp, wp, C, OH, OW, labels_out, dense_out, reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int dinoseg_op_guide_cells(const uint8_t* guide, int32_t B, int32_t OH, int32_t OW, int32_t hp, int32_t wp, uint32_t* cells,
+                                      void* stream) {
+    return launch_guide_cells("dinoseg_op_guide_cells", guide, B, OH, OW, hp, wp, cells, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_upsample_guided(const float* logp, const uint8_t* guide, const uint32_t* cells, int32_t B, int32_t hp, int32_t wp,
+                                          int32_t C, int32_t OH, int32_t OW, int32_t radius, double sigma_spatial, double sigma_range,
+                                          int32_t* labels_out, float* dense_out, void* stream) {
+    return launch_upsample_guided("dinoseg_op_upsample_guided", logp, guide, cells, B, hp, wp, C, OH, OW, radius, sigma_spatial, sigma_range,
+                                  labels_out, dense_out, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int64_t dinoseg_op_upsample_ensemble_scratch_bytes(int32_t K, int32_t B, int32_t OH, int32_t OW) {
     return upsample_ensemble_scratch_bytes(K, B, OH, OW);
 }

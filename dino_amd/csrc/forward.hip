@@ -473,6 +473,39 @@ extern "C" int dinoseg_forward_dense_hw(dinoseg_handle* h, const void* x, int32_
     return forward_split(h, x, x_kind, B, H, W, rq, stream);
 }
 
+// The forward into the caller's logp_out, then the two launches of the image-guided upsample (upsample_guided.hip) for the whole batch on
+// the caller's stream, behind the join of the two-stream split.  The forward's own code paths are untouched.  Everything the launches
+// would refuse is refused here, before the forward enqueues anything.
+extern "C" int dinoseg_forward_guided_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W,
+                                         const uint8_t* guide, int32_t OH, int32_t OW, int32_t radius, double sigma_spatial,
+                                         double sigma_range, float* logp_out, uint32_t* cells_scratch, int32_t* labels_out, float* dense_out,
+                                         void* stream) {
+    const char* who = "dinoseg_forward_guided_hw";
+    if (!h || !x || B <= 0) {
+        dinoseg_set_error("%s: bad argument (null handle or frames, or B=%d)", who, B);
+        return -1;
+    }
+    if (!guide || !logp_out || !cells_scratch || (!labels_out && !dense_out)) {
+        dinoseg_set_error("%s: null pointer (guide, logp_out, cells_scratch, and at least one of labels_out / dense_out, are required)", who);
+        return -1;
+    }
+    if (!frame_ok(H, W, h->cfg.patch)) {
+        set_resolution_error(h->cfg.patch);
+        return -1;
+    }
+    const int hp = H / h->cfg.patch, wp = W / h->cfg.patch, C = h->cfg.n_classes;
+    if (upsample_guided_check(who, B, hp, wp, C, OH, OW, radius, sigma_spatial, sigma_range, nullptr)) return -1;
+    if (guide_cells_check(who, B, hp, wp, OH, OW)) return -1;
+    ForwardRequest rq;
+    rq.logp_out = logp_out;
+    DSEG_TRY(forward_split(h, x, x_kind, B, H, W, rq, stream));
+    DeviceGuard guard(h);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    DSEG_TRY(launch_guide_cells(who, guide, B, OH, OW, hp, wp, cells_scratch, s));
+    return launch_upsample_guided(who, logp_out, guide, cells_scratch, B, hp, wp, C, OH, OW, radius, sigma_spatial, sigma_range, labels_out,
+                                  dense_out, s);
+}
+
 extern "C" int dinoseg_forward(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* logp_out,
                                int32_t* argmax_out, int32_t tap_block, float* tap_out, void* stream) {
     return dinoseg_forward_hw(h, x, x_kind, B, r, r, logp_out, argmax_out, tap_block, tap_out, stream);

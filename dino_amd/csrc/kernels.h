@@ -297,6 +297,23 @@ int launch_confusion(const int32_t* pred, const int64_t* gt, long n, int C, int6
 // its shape check alone (-1 and a message starting with `who`): sizes positive, 1 <= C <= 256, OH >= hp, OW >= wp, the integer ranges
 int upsample_check_shape(const char* who, int B, int hp, int wp, int C, int OH, int OW);
 int launch_upsample_argmax(const float* logp, int B, int hp, int wp, int C, int OH, int OW, int32_t* labels, float* dense, hipStream_t s);
+// Image-guided pixel-resolution output (upsample_guided.hip; the rule: include/dinoseg.h, dinoseg_op_upsample_guided): joint bilateral
+// upsampling of logp [B, hp*wp, C] to OH x OW guided by the uint8 frame guide [B, OH, OW, 3].  launch_guide_cells: the rounded mean
+// colour of every cell's pixels, packed uint32 [B, hp, wp].  launch_upsample_guided: per pixel the weighted mean of the (2 radius + 1)^2
+// cells around its own, labels int32 [B, OH, OW] = its first maximum and / or dense fp32 [B, C, OH, OW].  One launch each, no atomics.
+// The checks are the host-side refusals alone (-1 and a message starting with `who`, as the launches' own); upsample_guided_check also
+// plans the launch.
+struct UpGuidedPlan {
+    int tiles_x, tiles_y, CC, stride, kw_log2, col_words;
+    size_t lds_bytes;
+    float a_s, a_r;
+};
+int guide_cells_check(const char* who, int B, int hp, int wp, int OH, int OW);
+int launch_guide_cells(const char* who, const uint8_t* guide, int B, int OH, int OW, int hp, int wp, uint32_t* cells, hipStream_t s);
+int upsample_guided_check(const char* who, int B, int hp, int wp, int C, int OH, int OW, int radius, double sigma_spatial, double sigma_range,
+                          UpGuidedPlan* plan);
+int launch_upsample_guided(const char* who, const float* logp, const uint8_t* guide, const uint32_t* cells, int B, int hp, int wp, int C, int OH, int OW,
+                           int radius, double sigma_spatial, double sigma_range, int32_t* labels, float* dense, hipStream_t s);
 // Pixel-resolution training loss (upsample_loss.hip): loss = F.cross_entropy(that upsample of logp, labels int64 [B, OH, OW]) with the
 // mean over the valid pixels (0 <= label < C; ignore_index and -100 skipped, anything else skipped and flags[0] |= 1), and dlogp
 // [B, hp*wp, C] = d loss / d logp (nullable: loss only), without a [B, C, OH, OW] tensor.  dlogp is a gather in a fixed order (no

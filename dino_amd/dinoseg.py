@@ -305,6 +305,30 @@ def _pair(v, what: str) -> Tuple[int, int]:
         raise ValueError(f"{what} must be an integer or a pair of integers, got {v!r}") from None
 
 
+def guided_params(guided=True, radius=2, sigma_spatial=1.0, sigma_range=0.1):
+    """The validated (radius, sigma_spatial, sigma_range) of an image-guided upsample (``DINOSeg.segment_guided``): ``guided`` is
+    ``True`` (the defaults) or a dict with any of the three keys.  The ranges are the library's (include/dinoseg.h,
+    dinoseg_op_upsample_guided): radius 0..3 cells, sigma_spatial in [0.5, 16] cells, sigma_range in [1e-3, 1e3] of the 0..255
+    range.  Every ``ValueError`` is raised here, before any device use."""
+    if isinstance(guided, dict):
+        unknown = set(guided) - {"radius", "sigma_spatial", "sigma_range"}
+        if unknown:
+            raise ValueError(f"guided takes radius / sigma_spatial / sigma_range, got {sorted(unknown)}")
+        radius = guided.get("radius", radius)
+        sigma_spatial = guided.get("sigma_spatial", sigma_spatial)
+        sigma_range = guided.get("sigma_range", sigma_range)
+    elif guided is not True:
+        raise ValueError(f"guided must be True or a dict of radius / sigma_spatial / sigma_range, got {guided!r}")
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= int(radius) <= 3:
+        raise ValueError(f"radius must be an integer in 0..3, got {radius!r}")
+    sigma_spatial, sigma_range = float(sigma_spatial), float(sigma_range)
+    if not (math.isfinite(sigma_spatial) and 0.5 <= sigma_spatial <= 16.0):
+        raise ValueError(f"sigma_spatial must be in [0.5, 16] (cells), got {sigma_spatial}")
+    if not (math.isfinite(sigma_range) and 1e-3 <= sigma_range <= 1e3):
+        raise ValueError(f"sigma_range must be in [1e-3, 1e3] (of the 0..255 range), got {sigma_range}")
+    return int(radius), sigma_spatial, sigma_range
+
+
 def _axis_coverage(origins: List[int], window: int) -> int:
     """The most windows over one pixel of the axis (attained at a window's first pixel)."""
     most, i = 1, 0
@@ -644,11 +668,83 @@ class DINOSeg(nn.Module):
         (H, W); any OH >= H/patch, OW >= W/patch) and the argmax is taken per pixel -- ``F.interpolate(logp.view(B, hp, wp,
         C).permute(0, 3, 1, 2), size=size, mode="bilinear", align_corners=False).argmax(1)`` with exact coordinates and the first
         maximum -- in one launch behind the head, without the [B,C,OH,OW] transient.  ``want_logp=True`` also returns those
-        interpolated log-probabilities (``dense``, fp32 [B,C,OH,OW]: CRFs, multi-scale averaging).  Inference only."""
+        interpolated log-probabilities (``dense``, fp32 [B,C,OH,OW]: CRFs, multi-scale averaging).  For label boundaries that
+        follow the image's edges without that tensor: ``segment_guided``.  Inference only."""
         self._require_gpu()
         x, kind, B, H, W = self._prep_batch(x)
         OH, OW = self._out_size(size, (H, W))
         labels, dense, _ = self._run_dense(x, kind, B, H, W, OH, OW, want_dense=want_logp)
+        return labels, dense
+
+    # ---- image-guided pixel-resolution output (joint bilateral upsample of the log-probs: csrc/upsample_guided.hip) ----
+    def _guide_plan(self, x: torch.Tensor, guide, size):
+        """The shape checks of ``segment_guided`` without a device: (kind, B, H, W, OH, OW)."""
+        kind, B, H, W = self._prep_frames(x)
+        p = self.cfg.patch
+        if H % p != 0 or W % p != 0 or H < p or W < p:
+            raise ValueError(self._resolution_message())
+        if B < 1:
+            raise ValueError("empty batch")
+        if guide is None:
+            if kind != capi.INPUT_U8_HWC:
+                raise ValueError("fp32 frames carry no image to guide by: pass guide=uint8 [B,OH,OW,3] (or uint8 frames)")
+            OH, OW = self._out_size(size, (H, W))
+        else:
+            if not isinstance(guide, torch.Tensor) or guide.dtype != torch.uint8 or guide.dim() != 4 or guide.shape[3] != 3:
+                raise ValueError(f"expected a uint8 guide [B,OH,OW,3], got {getattr(guide, 'dtype', type(guide).__name__)} "
+                                 f"{tuple(getattr(guide, 'shape', ()))}")
+            if guide.shape[0] != B:
+                raise ValueError(f"the guide has {guide.shape[0]} frames, the batch {B}")
+            OH, OW = self._out_size(size, guide.shape[1:3])
+            if (OH, OW) != tuple(guide.shape[1:3]):
+                raise ValueError(f"size {(OH, OW)} differs from the guide's {tuple(guide.shape[1:3])} (the guide is at the output's size)")
+        if OH < H // p or OW < W // p:
+            raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(H // p, W // p)}")
+        return kind, B, H, W, OH, OW
+
+    def _run_guided(self, x: torch.Tensor, kind: int, B: int, H: int, W: int, guide: torch.Tensor, OH: int, OW: int, params,
+                    want_dense: bool = False):
+        """The forward and the guided upsample of its log-probs in one library call: (labels int32 [B,OH,OW], dense fp32
+        [B,C,OH,OW] or None, low-res log-probs [B*n, C])."""
+        self._sync_weights()
+        C_, dev, p = self.cfg.n_classes, x.device, self.cfg.patch
+        hp, wp = H // p, W // p
+        logp = torch.empty((B * hp * wp, C_), dtype=torch.float32, device=dev)
+        cells = torch.empty((B, hp, wp), dtype=torch.int32, device=dev)
+        labels = torch.empty((B, OH, OW), dtype=torch.int32, device=dev)
+        dense = torch.empty((B, C_, OH, OW), dtype=torch.float32, device=dev) if want_dense else None
+        capi.check(capi.lib().dinoseg_forward_guided_hw(self._handle, x.data_ptr(), kind, B, H, W, guide.data_ptr(), OH, OW, params[0],
+                                                        params[1], params[2], logp.data_ptr(), cells.data_ptr(), labels.data_ptr(),
+                                                        capi.ptr(dense), self._stream()))
+        return labels, dense, logp
+
+    def _guided(self, x: torch.Tensor, guide, size, params, want_dense: bool):
+        kind, B, H, W, OH, OW = self._guide_plan(x, guide, size)
+        self._require_gpu()
+        x, kind, B, H, W = self._prep_batch(x)
+        if guide is not None:
+            guide = guide.to(self.device).contiguous()
+        elif (OH, OW) == (H, W):
+            guide = x
+        else:
+            guide = self._resize_view(x, kind, OH, OW)
+        return self._run_guided(x, kind, B, H, W, guide, OH, OW, params, want_dense)
+
+    @torch.no_grad()
+    def segment_guided(self, x: torch.Tensor, guide: Optional[torch.Tensor] = None, size=None, radius: int = 2,
+                       sigma_spatial: float = 1.0, sigma_range: float = 0.1, want_logp: bool = False):
+        """``segment`` with label boundaries that follow the image: uint8 [B,H,W,3] or fp32 [B,3,H,W] frames -> (labels int32
+        [B,OH,OW], dense or None).  The log-probabilities of the patch grid are enlarged by joint bilateral upsampling (Kopf et al.
+        2007): every output pixel averages the (2 radius + 1)^2 cells around its own with a spatial Gaussian (``sigma_spatial``, in
+        cells) times a Gaussian of the colour distance (``sigma_range``, of the 0..255 range) between the guide at that pixel and
+        the cell's mean colour; the argmax is taken per pixel in the same launch, without the [B,C,OH,OW] transient (the rule:
+        include/dinoseg.h, dinoseg_op_upsample_guided).  ``guide`` is a uint8 image [B,OH,OW,3] at the output's size (``size``
+        defaults to it; a different ``size`` or batch raises).  Without one the frames guide themselves: uint8 frames only (fp32
+        frames raise ``ValueError``), resized by ``dinoseg_op_resize_u8`` when ``size`` is not their own.  ``radius=0`` is the
+        nearest-neighbour enlargement.  ``want_logp=True`` also returns the averaged log-probabilities (fp32 [B,C,OH,OW]).  The
+        defaults are a starting point: their effect on mIoU has not been measured on any dataset.  Inference only."""
+        params = guided_params(True, radius, sigma_spatial, sigma_range)
+        labels, dense, _ = self._guided(x, guide, size, params, want_logp)
         return labels, dense
 
     # ---- multi-scale + flip ensemble at pixel resolution (csrc/upsample_ensemble.hip) ----
@@ -816,13 +912,21 @@ class DINOSeg(nn.Module):
         labels, dense, _ = self._windows(x, window, stride, want_logp, max_windows)
         return labels, dense
 
-    def predict_dense(self, img, size=None, scales=None, flip: bool = False, window=None, stride=None) -> np.ndarray:
+    def predict_dense(self, img, size=None, scales=None, flip: bool = False, window=None, stride=None, guided=None) -> np.ndarray:
         """The pixel-resolution sibling of ``predict()``: the image (PIL.Image or HxWx3 uint8 array) is resized to r x r on the
         device exactly as ``predict()`` does, the log-probabilities are upsampled to ``size`` (default: the IMAGE's own (rows,
         cols)) and the per-pixel argmax comes back as an int64 map.  Eager launches (``predict()`` keeps its captured graph).
         With ``scales`` the labels are those of ``segment_multiscale(resized frame, scales, flip, size)`` instead.
         With ``window`` the image is NOT resized: it is segmented at its own size by ``segment_windows(image, window, stride)``
-        (``size`` other than the image's own, and ``scales``, raise ``ValueError``)."""
+        (``size`` other than the image's own, and ``scales``, raise ``ValueError``).
+        With ``guided`` (``True`` or a dict of ``radius`` / ``sigma_spatial`` / ``sigma_range``) the log-probabilities of the
+        resized frame are enlarged by ``segment_guided``'s rule instead, guided by the ORIGINAL image at its own size (resized
+        only if ``size`` asks for another); ``guided`` with ``window`` or ``scales`` raises ``ValueError``."""
+        gparams = None
+        if guided is not None:
+            if window is not None or scales is not None:
+                raise ValueError("guided cannot be combined with window or scales")
+            gparams = guided_params(guided)
         with torch.no_grad():
             raw = np.asarray(img)
             if raw.dtype != np.uint8 or not raw.flags.c_contiguous:
@@ -839,13 +943,16 @@ class DINOSeg(nn.Module):
             r = self.resolution
             self._require_gpu()
             OH, OW = self._out_size(size, raw.shape[:2])
-            frames = torch.from_numpy(raw).unsqueeze(0).to(self.device)
+            frames = orig = torch.from_numpy(raw).unsqueeze(0).to(self.device)
             if raw.shape[0] != r or raw.shape[1] != r:                           # Resize(r, r) of get_transforms, on the GPU
                 resized = torch.empty((1, r, r, 3), dtype=torch.uint8, device=self.device)
                 capi.check(capi.lib().dinoseg_op_resize_u8(frames.data_ptr(), raw.shape[0], raw.shape[1], resized.data_ptr(), r, r,
                                                           self._stream()))
                 frames = resized
-            if scales is not None:
+            if gparams is not None:
+                guide = orig if (OH, OW) == tuple(raw.shape[:2]) else self._resize_view(orig, capi.INPUT_U8_HWC, OH, OW)
+                labels = self._guided(frames, guide, None, gparams, False)[0]
+            elif scales is not None:
                 labels = self._multiscale(frames, scales, flip, (OH, OW), False, False)[0]
             else:
                 labels, _, _ = self._run_dense(frames, capi.INPUT_U8_HWC, 1, r, r, OH, OW)
@@ -1020,17 +1127,34 @@ class DINOSeg(nn.Module):
                                                        cm.data_ptr(), self._stream()))
         return {"pred": amax, "gt": y, "probs": logp, "confusion": cm}
 
-    def validation_step_dense(self, batch, batch_idx=0, scales=None, flip: bool = False, window=None, stride=None):
+    def validation_step_dense(self, batch, batch_idx=0, scales=None, flip: bool = False, window=None, stride=None, guided=None):
         """``validation_step`` scored per pixel: ``y`` is [B, OH, OW] pixel labels, the prediction is ``segment`` at y's size and
         the confusion matrix counts pixels.  Labels outside [0, n_classes) -- 255 or -100 "void" -- are skipped by the confusion
         kernel.  Same keys as ``validation_step`` ("pred": the pixel labels, "probs": the low-res log-probs), so
         ``validation_epoch_end`` takes its outputs unchanged.  With ``scales`` the prediction is ``segment_multiscale(x, scales,
         flip, size=y's)`` and "probs" the low-res log-probs of the unflipped scale-1.0 view (the first view's without one).
         With ``window`` the prediction is ``segment_windows(x, window, stride)`` on frames of any size, ``y`` has the frames' own
-        H x W, and "probs" is the windows' low-res log-probs [B*G, n, C]; ``window`` with ``scales`` raises ``ValueError``."""
+        H x W, and "probs" is the windows' low-res log-probs [B*G, n, C]; ``window`` with ``scales`` raises ``ValueError``.
+        With ``guided`` (``True`` or a dict of ``radius`` / ``sigma_spatial`` / ``sigma_range``) the prediction is
+        ``segment_guided(x, size=y's)`` on uint8 frames; ``guided`` with ``window`` or ``scales`` raises ``ValueError``."""
         x, y = batch
+        gparams = None
+        if guided is not None:
+            if window is not None or scales is not None:
+                raise ValueError("guided cannot be combined with window or scales")
+            gparams = guided_params(guided)
         if window is not None:
             return self._validation_step_windows(x, y, scales, window, stride)
+        if gparams is not None:
+            if y.dim() != 3 or y.shape[0] != x.shape[0]:
+                raise ValueError(f"expected pixel labels [B={x.shape[0]}, OH, OW], got {tuple(y.shape)}")
+            with torch.no_grad():
+                labels, _, logp = self._guided(x, None, (int(y.shape[1]), int(y.shape[2])), gparams, False)
+                y = y.to(self.device).reshape(-1).long().contiguous()
+                cm = torch.zeros((self.cfg.n_classes, self.cfg.n_classes), dtype=torch.int64, device=self.device)
+                capi.check(capi.lib().dinoseg_op_confusion(labels.data_ptr(), y.data_ptr(), y.numel(), self.cfg.n_classes,
+                                                           cm.data_ptr(), self._stream()))
+            return {"pred": labels, "gt": y, "probs": logp, "confusion": cm}
         self._require_gpu()
         with torch.no_grad():
             xx, kind, B, H, W = self._prep_batch(x)

@@ -190,6 +190,50 @@ int dinoseg_op_upsample_argmax(const float* logp, int32_t B, int32_t hp, int32_t
 int dinoseg_forward_dense_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, int32_t OH, int32_t OW,
                              float* logp_out, int32_t* argmax_out, int32_t* labels_out, float* dense_out, void* stream);
 
+/* ---- image-guided pixel-resolution output: joint bilateral upsampling (Kopf et al. 2007) of the log-probs, guided by the frame the
+ * caller already holds, so that label boundaries follow the image's edges instead of the crossing point between two patch centres ----
+ *
+ *   logp   : fp32 [B, hp*wp, C], the head's output, finite; 1 <= C <= 256
+ *   guide  : uint8 [B, OH, OW, 3] at the OUTPUT's size, OH >= hp, OW >= wp, OH, OW <= 2^20
+ *   radius : R in 0..3;  sigma_spatial in [0.5, 16] (cells);  sigma_range in [1e-3, 1e3] (of the full 0..255 range)
+ * The constants a_s = log2(e) / (2 sigma_spatial^2) and a_r = log2(e) / (2 (255 sigma_range)^2) are computed on the host in fp64 and
+ * rounded once to fp32; the rule is in terms of the rounded values.  All coordinates are integers.
+ *
+ * 1. Cell colours (dinoseg_op_guide_cells).  Output pixel (y, x) belongs to cell ((y hp) / OH, (x wp) / OW) -- the nearest rule of
+ *    dinoseg_op_cls_attention.  Per cell and channel m = (2 sum + n) / (2 n) in integers, sum = the guide summed over the cell's n
+ *    pixels: the rounded mean, 0..255.  cells: uint32 [B, hp, wp] packed R | G << 8 | B << 16.  Integer sums, no atomics.
+ * 2. Taps.  For output pixel (oy, ox): r0 = (oy hp) / OH, c0 = (ox wp) / OW; the taps are the cells (r0 + dr, c0 + dc), dr, dc = -R .. R,
+ *    that lie inside the grid (the others are skipped), in the order dr ascending, then dc ascending.
+ * 3. Spatial term.  my = 2 r OH - ((2 oy + 1) hp - OH) for the tap's row r: an integer, NOT clamped -- the pixel's align_corners=False
+ *    coordinate against the cell centre, in units of 1 / (2 OH) cells.  dy = float(my) / float(2 OH) (correctly rounded), dx likewise;
+ *    s = dy dy + dx dx, each operation rounded to fp32.
+ * 4. Range term.  D = the integer squared RGB distance between guide[b, oy, ox] and the tap's cell colour (<= 195 075); Dmin = the
+ *    smallest D over the pixel's taps.
+ * 5. Weight.  w = exp2(-(s a_s) - float(D - Dmin) a_r), each operation rounded to fp32, exp2 to one ulp.  Subtracting Dmin cancels
+ *    in the quotient below and keeps the largest weight at or above 2^-(a_s 2 (R + 1/2)^2) >= 2^-71: the sum never underflows.
+ *    For R = 0 the single tap's weight is exactly 1.
+ * 6. Value.  acc_k = sum over taps of w L[tap, k] by fmaf in tap order from 0;  W = sum of w in the same order;  V_k = acc_k (1 / W),
+ *    the reciprocal correctly rounded, once per pixel.  dense_out[b, k, oy, ox] = V_k; labels_out = the FIRST maximum of V_k over k.
+ * Consequences: R = 0 is the nearest-neighbour enlargement of logp, bit for bit; a constant guide gives a pure Gaussian enlargement;
+ * nothing is atomic and two runs agree bit for bit; the labels-only launch writes the labels of the launch with dense_out.
+ *
+ * dinoseg_op_guide_cells: step 1 alone, one launch.  dinoseg_op_upsample_guided: steps 2-6 in one launch from the cells of step 1 (for
+ * the same guide and grid), without the [B, C, OH, OW] transient unless dense_out is given; labels_out int32 [B, OH, OW], dense_out fp32
+ * [B, C, OH, OW], at least one.  Refused on the host (-1, a message naming the entry) before anything is launched: null pointers, a
+ * radius outside 0..3, sigmas outside their ranges or not finite, every shape dinoseg_op_upsample_argmax refuses, OH or OW above 2^20,
+ * and a tile footprint ((64 + 2R) x (32 + 2R) cells at ratio 1) that does not fit the LDS.  Stream-ordered, no host synchronisation. */
+int dinoseg_op_guide_cells(const uint8_t* guide, int32_t B, int32_t OH, int32_t OW, int32_t hp, int32_t wp, uint32_t* cells, void* stream);
+int dinoseg_op_upsample_guided(const float* logp, const uint8_t* guide, const uint32_t* cells, int32_t B, int32_t hp, int32_t wp, int32_t C,
+                               int32_t OH, int32_t OW, int32_t radius, double sigma_spatial, double sigma_range, int32_t* labels_out,
+                               float* dense_out, void* stream);
+/* dinoseg_forward_hw into the caller's logp_out [B*n, n_classes] (required), then dinoseg_op_guide_cells into cells_scratch (uint32
+ * [B, hp, wp], required) and dinoseg_op_upsample_guided for the whole batch on the caller's stream (under the two-stream split: behind
+ * the join).  For uint8 frames with OH x OW == H x W, guide may alias x.  Everything the launches would refuse is refused before the
+ * forward enqueues anything.  Stream-ordered, capturable, no host synchronisation, no allocation. */
+int dinoseg_forward_guided_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, const uint8_t* guide,
+                              int32_t OH, int32_t OW, int32_t radius, double sigma_spatial, double sigma_range, float* logp_out,
+                              uint32_t* cells_scratch, int32_t* labels_out, float* dense_out, void* stream);
+
 /* ---- pixel-resolution training loss (what ViT segmenters train on: F.cross_entropy(F.interpolate(scores, size=mask.shape,
  * mode="bilinear", align_corners=False), mask, ignore_index=255)), without the [B, C, OH, OW] transient ----
  *
