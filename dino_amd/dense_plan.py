@@ -1,0 +1,217 @@
+"""The device-free half of ``DINOSeg``'s pixel-resolution modes: everything that decides or refuses from shapes and the patch
+size alone.  Nothing here touches a device or a native handle (``window_origins`` calls a host-only entry of the library), so
+every ``ValueError`` of a pixel-resolution call is raised before the model asks for a GPU.  ``dinoseg.py`` holds the other
+half: the runners that allocate and launch.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import List, NamedTuple, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import capi
+
+ENSEMBLE_MAX_VIEWS = 12        # include/dinoseg.h: dinoseg_op_upsample_ensemble takes 1 .. 12 views
+WINDOW_MAX_COVERAGE = 4        # include/dinoseg.h: dinoseg_op_window_merge takes at most 4 windows over a pixel row / column
+
+
+def view_sizes(H: int, W: int, scales, patch: int) -> List[Tuple[int, int]]:
+    """The frame sizes of a multi-scale protocol: per scale s the H x W frame scaled by s and rounded to the nearest multiple of
+    the patch (halves up, at least one patch): ``H_k = patch * max(1, floor(H * s / patch + 0.5))``, the same for W."""
+    def one(v, s):
+        return patch * max(1, int(math.floor(v * s / patch + 0.5)))
+    return [(one(H, float(s)), one(W, float(s))) for s in scales]
+
+
+def window_origins(L: int, window: int, stride: int) -> List[int]:
+    """The origins of the sliding windows along one axis (mmsegmentation's ``slide_inference``): frame side ``L``, window
+    ``1 <= window <= L``, stride ``>= 1``; ``g = max(L - window + stride - 1, 0) // stride + 1`` windows at ``max(min(i * stride +
+    window, L) - window, 0)`` -- the last one is shifted back to end at ``L``.  The rule lives in the library
+    (``dinoseg_window_origins``, host only: no device needed)."""
+    L, window, stride = int(L), int(window), int(stride)
+    lib = capi.lib()
+    g = lib.dinoseg_window_origins(L, window, stride, None, 0)
+    if g < 1:
+        raise ValueError(f"bad window rule: frame side {L}, window {window}, stride {stride} (1 <= window <= frame side, stride >= 1)")
+    out = (C.c_int32 * g)()
+    if lib.dinoseg_window_origins(L, window, stride, out, g) != g:
+        raise capi.DinosegError(capi.last_error())
+    return list(out)
+
+
+def _pair(v, what: str) -> Tuple[int, int]:
+    try:
+        a, b = (v, v) if isinstance(v, (int, np.integer)) else v
+        return int(a), int(b)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be an integer or a pair of integers, got {v!r}") from None
+
+
+def guided_params(guided=True, radius=2, sigma_spatial=1.0, sigma_range=0.1):
+    """The validated (radius, sigma_spatial, sigma_range) of an image-guided upsample (``DINOSeg.segment_guided``): ``guided`` is
+    ``True`` (the defaults) or a dict with any of the three keys.  The ranges are the library's (include/dinoseg.h,
+    dinoseg_op_upsample_guided): radius 0..3 cells, sigma_spatial in [0.5, 16] cells, sigma_range in [1e-3, 1e3] of the 0..255
+    range.  Every ``ValueError`` is raised here, before any device use."""
+    if isinstance(guided, dict):
+        unknown = set(guided) - {"radius", "sigma_spatial", "sigma_range"}
+        if unknown:
+            raise ValueError(f"guided takes radius / sigma_spatial / sigma_range, got {sorted(unknown)}")
+        radius = guided.get("radius", radius)
+        sigma_spatial = guided.get("sigma_spatial", sigma_spatial)
+        sigma_range = guided.get("sigma_range", sigma_range)
+    elif guided is not True:
+        raise ValueError(f"guided must be True or a dict of radius / sigma_spatial / sigma_range, got {guided!r}")
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= int(radius) <= 3:
+        raise ValueError(f"radius must be an integer in 0..3, got {radius!r}")
+    sigma_spatial, sigma_range = float(sigma_spatial), float(sigma_range)
+    if not (math.isfinite(sigma_spatial) and 0.5 <= sigma_spatial <= 16.0):
+        raise ValueError(f"sigma_spatial must be in [0.5, 16] (cells), got {sigma_spatial}")
+    if not (math.isfinite(sigma_range) and 1e-3 <= sigma_range <= 1e3):
+        raise ValueError(f"sigma_range must be in [1e-3, 1e3] (of the 0..255 range), got {sigma_range}")
+    return int(radius), sigma_spatial, sigma_range
+
+
+def _axis_coverage(origins: List[int], window: int) -> int:
+    """The most windows over one pixel of the axis (attained at a window's first pixel)."""
+    most, i = 1, 0
+    for j, oj in enumerate(origins):
+        while origins[i] + window <= oj:
+            i += 1
+        most = max(most, j - i + 1)
+    return most
+
+
+def resolution_message(patch: int) -> str:
+    # patch 8: the reference's text (pl_torch_modules.py:271-272), byte for byte
+    return "Resolution should be a multiple of 16." if patch == 16 else "Resolution should be a multiple of 8."
+
+
+def frame_layout(x: torch.Tensor, patch: int, multiple: bool = False, one_patch: bool = False, non_empty: bool = False,
+                 u8_only: bool = False) -> Tuple[int, int, int, int]:
+    """The two frame layouts, uint8 [B,H,W,3] and fp32 [B,3,H,W] (any other dtype is read as the second): (input kind, B, H, W).
+    ``multiple``: H and W are multiples of the patch; ``one_patch``: at least one patch each; ``non_empty``: B >= 1;
+    ``u8_only``: only the first layout is taken (``forward_frames``)."""
+    u8 = x.dtype == torch.uint8
+    if u8_only and not (u8 and x.dim() == 4 and x.shape[3] == 3):
+        raise ValueError(f"expected uint8 [B,H,W,3], got {x.dtype} {tuple(x.shape)}")
+    if u8:
+        if x.dim() != 4 or x.shape[3] != 3:
+            raise ValueError(f"expected uint8 [B,H,W,3], got {tuple(x.shape)}")
+        kind, B, H, W = capi.INPUT_U8_HWC, x.shape[0], x.shape[1], x.shape[2]
+    else:
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"expected [B,3,H,W], got {tuple(x.shape)}")
+        kind, B, H, W = capi.INPUT_F32_CHW, x.shape[0], x.shape[2], x.shape[3]
+    if (multiple and (H % patch != 0 or W % patch != 0)) or (one_patch and (H < patch or W < patch)):
+        raise ValueError(resolution_message(patch))
+    if non_empty and B < 1:
+        raise ValueError("empty batch")
+    return kind, B, H, W
+
+
+def label_size(y: torch.Tensor, B: int, own: Optional[Tuple[int, int]] = None) -> Tuple[int, int]:
+    """The (OH, OW) of pixel labels [B, OH, OW]; with ``own`` (sliding windows) they must have that size, the frames'."""
+    if y.dim() != 3 or y.shape[0] != B or (own is not None and tuple(y.shape[1:]) != tuple(own)):
+        want = "OH, OW]" if own is None else f"{own[0]}, {own[1]}] (the frames' own size)"
+        raise ValueError(f"expected pixel labels [B={B}, {want}, got {tuple(y.shape)}")
+    return int(y.shape[1]), int(y.shape[2])
+
+
+def out_size(size, default) -> Tuple[int, int]:
+    OH, OW = (int(v) for v in (default if size is None else size))
+    return OH, OW
+
+
+def window_plan(patch: int, H: int, W: int, window, stride):
+    """The window and stride of a sliding-window call on H x W frames, per axis: ((wh, ww), (sh, sw), (gh, gw)).  Every
+    ``ValueError`` of the protocol is raised here, before any device use."""
+    p = patch
+    if H < p or W < p:
+        raise ValueError(f"frames of {H}x{W} are smaller than one {p}x{p} patch")
+    win, out_s, grid = list(_pair(window, "window")), [], []
+    st = (None, None) if stride is None else _pair(stride, "stride")
+    for axis, L in enumerate((H, W)):
+        w, name = win[axis], ("vertical", "horizontal")[axis]
+        if w < 1:
+            raise ValueError(f"window must be positive, got {tuple(_pair(window, 'window'))}")
+        if w % p != 0:
+            raise ValueError(f"{name} window {w} is not a multiple of the patch ({p})")
+        w = min(w, (L // p) * p)                    # clamped to the largest patch multiple inside the frame
+        s = (2 * w) // 3 if st[axis] is None else st[axis]
+        if s < 1:
+            raise ValueError(f"stride must be positive, got {tuple(st)}")
+        origins = window_origins(L, w, s)
+        cov = _axis_coverage(origins, w)
+        if cov > WINDOW_MAX_COVERAGE:
+            raise ValueError(f"{name} coverage {cov}: window {w} at stride {s} puts {cov} windows over one pixel "
+                             f"{'row' if axis == 0 else 'column'} (at most {WINDOW_MAX_COVERAGE} per axis)")
+        win[axis] = w
+        out_s.append(s)
+        grid.append(len(origins))
+    return tuple(win), tuple(out_s), tuple(grid)
+
+
+def guide_plan(patch: int, x: torch.Tensor, guide, size):
+    """The shape checks of ``segment_guided`` without a device: (kind, B, H, W, OH, OW)."""
+    kind, B, H, W = frame_layout(x, patch, multiple=True, one_patch=True, non_empty=True)
+    if guide is None:
+        if kind != capi.INPUT_U8_HWC:
+            raise ValueError("fp32 frames carry no image to guide by: pass guide=uint8 [B,OH,OW,3] (or uint8 frames)")
+        OH, OW = out_size(size, (H, W))
+    else:
+        if not isinstance(guide, torch.Tensor) or guide.dtype != torch.uint8 or guide.dim() != 4 or guide.shape[3] != 3:
+            raise ValueError(f"expected a uint8 guide [B,OH,OW,3], got {getattr(guide, 'dtype', type(guide).__name__)} "
+                             f"{tuple(getattr(guide, 'shape', ()))}")
+        if guide.shape[0] != B:
+            raise ValueError(f"the guide has {guide.shape[0]} frames, the batch {B}")
+        OH, OW = out_size(size, guide.shape[1:3])
+        if (OH, OW) != tuple(guide.shape[1:3]):
+            raise ValueError(f"size {(OH, OW)} differs from the guide's {tuple(guide.shape[1:3])} (the guide is at the output's size)")
+    if OH < H // patch or OW < W // patch:
+        raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(H // patch, W // patch)}")
+    return kind, B, H, W, OH, OW
+
+
+def multiscale_plan(patch: int, H: int, W: int, scales, flip: bool, size):
+    """The views of ``segment_multiscale`` on H x W frames: ([(H_k, W_k, flip_k)] scale-major, the unflipped view first; their
+    count K; the output's (OH, OW))."""
+    scales = tuple(float(s) for s in scales)
+    K = len(scales) * (2 if flip else 1)
+    if not 1 <= K <= ENSEMBLE_MAX_VIEWS:
+        raise ValueError(f"{len(scales)} scales{' with flip' if flip else ''} are {K} views; the ensemble takes 1 to {ENSEMBLE_MAX_VIEWS}")
+    if any(not (s > 0.0 and math.isfinite(s)) for s in scales):
+        raise ValueError(f"scales must be positive, got {scales}")
+    OH, OW = out_size(size, (H, W))
+    views = [(Hk, Wk, f) for Hk, Wk in view_sizes(H, W, scales, patch) for f in ((0, 1) if flip else (0,))]
+    for Hk, Wk, _ in views:
+        if Hk // patch > OH or Wk // patch > OW:
+            raise ValueError(f"the {Hk}x{Wk} view's grid {Hk // patch}x{Wk // patch} exceeds the output size {OH}x{OW} "
+                             "(upsampling and identity only)")
+    return views, K, (OH, OW)
+
+
+class DenseMode(NamedTuple):
+    """What ``predict_dense`` / ``validation_step_dense`` were asked for.  ``args`` by ``kind``: "bilinear" (), "multiscale"
+    (scales, flip), "windows" (window, stride: checked against the frames by ``window_plan``), "guided" the validated (radius,
+    sigma_spatial, sigma_range)."""
+    kind: str
+    args: tuple = ()
+
+
+def dense_mode(scales=None, flip: bool = False, window=None, stride=None, guided=None) -> DenseMode:
+    """The one mode the five keywords of ``predict_dense`` / ``validation_step_dense`` select, or the ``ValueError`` of a
+    combination that is not one."""
+    if guided is not None:
+        if window is not None or scales is not None:
+            raise ValueError("guided cannot be combined with window or scales")
+        return DenseMode("guided", guided_params(guided))
+    if window is not None:
+        if scales is not None:
+            raise ValueError("window and scales cannot be combined")
+        return DenseMode("windows", (window, stride))
+    if scales is not None:
+        return DenseMode("multiscale", (tuple(scales), bool(flip)))
+    return DenseMode("bilinear")

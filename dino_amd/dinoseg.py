@@ -9,9 +9,8 @@ the model without a ROCm device raises.
 from __future__ import annotations
 
 import ctypes as C
-import math
 import weakref
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, Optional
 
 import numpy as np
 import torch
@@ -19,6 +18,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import capi
+from .dense_plan import (_pair, dense_mode, frame_layout, guide_plan, guided_params, label_size, multiscale_plan, out_size,
+                         resolution_message, view_sizes, window_origins, window_plan)  # noqa: F401  (view_sizes, window_origins: re-exported)
 from .preprocess import resize_linear_u8
 from .weights import VIT_B8, VIT_B16, VIT_S8, VIT_S16, ViTConfig
 
@@ -267,78 +268,6 @@ def dense_nll_loss(logp: torch.Tensor, y: torch.Tensor, grid, ignore_index: int 
 
 
 # --------------------------------------------------------------------------- the model
-ENSEMBLE_MAX_VIEWS = 12        # include/dinoseg.h: dinoseg_op_upsample_ensemble takes 1 .. 12 views
-
-
-def view_sizes(H: int, W: int, scales, patch: int) -> List[Tuple[int, int]]:
-    """The frame sizes of a multi-scale protocol: per scale s the H x W frame scaled by s and rounded to the nearest multiple of
-    the patch (halves up, at least one patch): ``H_k = patch * max(1, floor(H * s / patch + 0.5))``, the same for W."""
-    def one(v, s):
-        return patch * max(1, int(math.floor(v * s / patch + 0.5)))
-    return [(one(H, float(s)), one(W, float(s))) for s in scales]
-
-
-WINDOW_MAX_COVERAGE = 4        # include/dinoseg.h: dinoseg_op_window_merge takes at most 4 windows over a pixel row / column
-
-
-def window_origins(L: int, window: int, stride: int) -> List[int]:
-    """The origins of the sliding windows along one axis (mmsegmentation's ``slide_inference``): frame side ``L``, window
-    ``1 <= window <= L``, stride ``>= 1``; ``g = max(L - window + stride - 1, 0) // stride + 1`` windows at ``max(min(i * stride +
-    window, L) - window, 0)`` -- the last one is shifted back to end at ``L``.  The rule lives in the library
-    (``dinoseg_window_origins``, host only: no device needed)."""
-    L, window, stride = int(L), int(window), int(stride)
-    lib = capi.lib()
-    g = lib.dinoseg_window_origins(L, window, stride, None, 0)
-    if g < 1:
-        raise ValueError(f"bad window rule: frame side {L}, window {window}, stride {stride} (1 <= window <= frame side, stride >= 1)")
-    out = (C.c_int32 * g)()
-    if lib.dinoseg_window_origins(L, window, stride, out, g) != g:
-        raise capi.DinosegError(capi.last_error())
-    return list(out)
-
-
-def _pair(v, what: str) -> Tuple[int, int]:
-    try:
-        a, b = (v, v) if isinstance(v, (int, np.integer)) else v
-        return int(a), int(b)
-    except (TypeError, ValueError):
-        raise ValueError(f"{what} must be an integer or a pair of integers, got {v!r}") from None
-
-
-def guided_params(guided=True, radius=2, sigma_spatial=1.0, sigma_range=0.1):
-    """The validated (radius, sigma_spatial, sigma_range) of an image-guided upsample (``DINOSeg.segment_guided``): ``guided`` is
-    ``True`` (the defaults) or a dict with any of the three keys.  The ranges are the library's (include/dinoseg.h,
-    dinoseg_op_upsample_guided): radius 0..3 cells, sigma_spatial in [0.5, 16] cells, sigma_range in [1e-3, 1e3] of the 0..255
-    range.  Every ``ValueError`` is raised here, before any device use."""
-    if isinstance(guided, dict):
-        unknown = set(guided) - {"radius", "sigma_spatial", "sigma_range"}
-        if unknown:
-            raise ValueError(f"guided takes radius / sigma_spatial / sigma_range, got {sorted(unknown)}")
-        radius = guided.get("radius", radius)
-        sigma_spatial = guided.get("sigma_spatial", sigma_spatial)
-        sigma_range = guided.get("sigma_range", sigma_range)
-    elif guided is not True:
-        raise ValueError(f"guided must be True or a dict of radius / sigma_spatial / sigma_range, got {guided!r}")
-    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= int(radius) <= 3:
-        raise ValueError(f"radius must be an integer in 0..3, got {radius!r}")
-    sigma_spatial, sigma_range = float(sigma_spatial), float(sigma_range)
-    if not (math.isfinite(sigma_spatial) and 0.5 <= sigma_spatial <= 16.0):
-        raise ValueError(f"sigma_spatial must be in [0.5, 16] (cells), got {sigma_spatial}")
-    if not (math.isfinite(sigma_range) and 1e-3 <= sigma_range <= 1e3):
-        raise ValueError(f"sigma_range must be in [1e-3, 1e3] (of the 0..255 range), got {sigma_range}")
-    return int(radius), sigma_spatial, sigma_range
-
-
-def _axis_coverage(origins: List[int], window: int) -> int:
-    """The most windows over one pixel of the axis (attained at a window's first pixel)."""
-    most, i = 1, 0
-    for j, oj in enumerate(origins):
-        while origins[i] + window <= oj:
-            i += 1
-        most = max(most, j - i + 1)
-    return most
-
-
 class DINOSeg(nn.Module):
     """DINO ViT + per-patch segmentation head on MI355X.
 
@@ -578,14 +507,10 @@ class DINOSeg(nn.Module):
         except Exception:
             pass
 
-    def _resolution_message(self) -> str:
-        # patch 8: the reference's text (pl_torch_modules.py:271-272), byte for byte
-        return "Resolution should be a multiple of 16." if self.cfg.patch == 16 else "Resolution should be a multiple of 8."
-
     # ---- reference API ----------------------------------------------------------------------
     def set_resolution(self, resolution=480):
         if resolution % self.cfg.patch != 0:
-            raise ValueError(self._resolution_message())
+            raise ValueError(resolution_message(self.cfg.patch))
         self.transforms = get_transforms(resolution)
         self.resolution = resolution
 
@@ -632,31 +557,29 @@ class DINOSeg(nn.Module):
         """uint8 [B,H,W,3] device frames -> (log-probs or None, int32 argmax [B*(H/8)*(W/8)]).
         The batched form of predict(): normalisation is fused into the patch gather on device."""
         self._require_gpu()
-        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
-            raise ValueError(f"expected uint8 [B,H,W,3], got {frames_u8.dtype} {tuple(frames_u8.shape)}")
-        if frames_u8.shape[1] % self.cfg.patch != 0 or frames_u8.shape[2] % self.cfg.patch != 0:
-            raise ValueError(self._resolution_message())
-        frames_u8 = frames_u8.to(self.device).contiguous()
-        logp, amax, _ = self._run(frames_u8, capi.INPUT_U8_HWC, frames_u8.shape[0], frames_u8.shape[1], frames_u8.shape[2],
-                                  want_logp=want_logp, want_argmax=True)
+        kind, B, H, W = frame_layout(frames_u8, self.cfg.patch, multiple=True, u8_only=True)
+        logp, amax, _ = self._run(self._to_device(frames_u8, kind), kind, B, H, W, want_logp=want_logp, want_argmax=True)
         return logp, amax
 
     # ---- pixel-resolution output (bilinear upsample + argmax of the log-probs, fused: csrc/upsample.hip) ----
-    def _out_size(self, size, default):
-        OH, OW = (int(v) for v in (default if size is None else size))
-        return OH, OW
+    def _alloc_out(self, B: int, OH: int, OW: int, want_dense: bool):
+        """(labels int32 [B,OH,OW], dense fp32 [B,C,OH,OW] or None) on the model's device."""
+        labels = torch.empty((B, OH, OW), dtype=torch.int32, device=self.device)
+        dense = torch.empty((B, self.cfg.n_classes, OH, OW), dtype=torch.float32, device=self.device) if want_dense else None
+        return labels, dense
 
-    def _run_dense(self, x: torch.Tensor, kind: int, B: int, H: int, W: int, OH: int, OW: int, want_dense: bool = False,
-                   want_logp: bool = False):
-        """The forward and the upsample of its log-probs to OH x OW in one library call: (labels int32 [B,OH,OW], dense fp32
+    def _bilinear(self, x: torch.Tensor, size, want_dense: bool = False, want_logp: bool = False):
+        """The forward and the upsample of its log-probs to ``size`` in one library call: (labels int32 [B,OH,OW], dense fp32
         [B,C,OH,OW] or None, low-res log-probs [B*n, C] or None).  Without ``want_logp`` the low-res log-probs stay in the
         library's workspace; the [B,C,OH,OW] tensor exists only when asked for."""
+        kind, B, H, W = frame_layout(x, self.cfg.patch, multiple=True)
+        OH, OW = out_size(size, (H, W))
+        self._require_gpu()
+        x = self._to_device(x, kind)
         self._sync_weights()
-        C_, dev = self.cfg.n_classes, x.device
         n = (H // self.cfg.patch) * (W // self.cfg.patch)
-        labels = torch.empty((B, OH, OW), dtype=torch.int32, device=dev)
-        dense = torch.empty((B, C_, OH, OW), dtype=torch.float32, device=dev) if want_dense else None
-        logp = torch.empty((B * n, C_), dtype=torch.float32, device=dev) if want_logp else None
+        labels, dense = self._alloc_out(B, OH, OW, want_dense)
+        logp = torch.empty((B * n, self.cfg.n_classes), dtype=torch.float32, device=x.device) if want_logp else None
         capi.check(capi.lib().dinoseg_forward_dense_hw(self._handle, x.data_ptr(), kind, B, H, W, OH, OW, capi.ptr(logp), None,
                                                        labels.data_ptr(), capi.ptr(dense), self._stream()))
         return labels, dense, logp
@@ -670,65 +593,31 @@ class DINOSeg(nn.Module):
         maximum -- in one launch behind the head, without the [B,C,OH,OW] transient.  ``want_logp=True`` also returns those
         interpolated log-probabilities (``dense``, fp32 [B,C,OH,OW]: CRFs, multi-scale averaging).  For label boundaries that
         follow the image's edges without that tensor: ``segment_guided``.  Inference only."""
-        self._require_gpu()
-        x, kind, B, H, W = self._prep_batch(x)
-        OH, OW = self._out_size(size, (H, W))
-        labels, dense, _ = self._run_dense(x, kind, B, H, W, OH, OW, want_dense=want_logp)
-        return labels, dense
+        return self._bilinear(x, size, want_dense=want_logp)[:2]
 
     # ---- image-guided pixel-resolution output (joint bilateral upsample of the log-probs: csrc/upsample_guided.hip) ----
-    def _guide_plan(self, x: torch.Tensor, guide, size):
-        """The shape checks of ``segment_guided`` without a device: (kind, B, H, W, OH, OW)."""
-        kind, B, H, W = self._prep_frames(x)
-        p = self.cfg.patch
-        if H % p != 0 or W % p != 0 or H < p or W < p:
-            raise ValueError(self._resolution_message())
-        if B < 1:
-            raise ValueError("empty batch")
-        if guide is None:
-            if kind != capi.INPUT_U8_HWC:
-                raise ValueError("fp32 frames carry no image to guide by: pass guide=uint8 [B,OH,OW,3] (or uint8 frames)")
-            OH, OW = self._out_size(size, (H, W))
-        else:
-            if not isinstance(guide, torch.Tensor) or guide.dtype != torch.uint8 or guide.dim() != 4 or guide.shape[3] != 3:
-                raise ValueError(f"expected a uint8 guide [B,OH,OW,3], got {getattr(guide, 'dtype', type(guide).__name__)} "
-                                 f"{tuple(getattr(guide, 'shape', ()))}")
-            if guide.shape[0] != B:
-                raise ValueError(f"the guide has {guide.shape[0]} frames, the batch {B}")
-            OH, OW = self._out_size(size, guide.shape[1:3])
-            if (OH, OW) != tuple(guide.shape[1:3]):
-                raise ValueError(f"size {(OH, OW)} differs from the guide's {tuple(guide.shape[1:3])} (the guide is at the output's size)")
-        if OH < H // p or OW < W // p:
-            raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(H // p, W // p)}")
-        return kind, B, H, W, OH, OW
-
-    def _run_guided(self, x: torch.Tensor, kind: int, B: int, H: int, W: int, guide: torch.Tensor, OH: int, OW: int, params,
-                    want_dense: bool = False):
+    def _guided(self, x: torch.Tensor, guide, size, params, want_dense: bool = False):
         """The forward and the guided upsample of its log-probs in one library call: (labels int32 [B,OH,OW], dense fp32
-        [B,C,OH,OW] or None, low-res log-probs [B*n, C])."""
-        self._sync_weights()
-        C_, dev, p = self.cfg.n_classes, x.device, self.cfg.patch
-        hp, wp = H // p, W // p
-        logp = torch.empty((B * hp * wp, C_), dtype=torch.float32, device=dev)
-        cells = torch.empty((B, hp, wp), dtype=torch.int32, device=dev)
-        labels = torch.empty((B, OH, OW), dtype=torch.int32, device=dev)
-        dense = torch.empty((B, C_, OH, OW), dtype=torch.float32, device=dev) if want_dense else None
-        capi.check(capi.lib().dinoseg_forward_guided_hw(self._handle, x.data_ptr(), kind, B, H, W, guide.data_ptr(), OH, OW, params[0],
-                                                        params[1], params[2], logp.data_ptr(), cells.data_ptr(), labels.data_ptr(),
-                                                        capi.ptr(dense), self._stream()))
-        return labels, dense, logp
-
-    def _guided(self, x: torch.Tensor, guide, size, params, want_dense: bool):
-        kind, B, H, W, OH, OW = self._guide_plan(x, guide, size)
+        [B,C,OH,OW] or None, low-res log-probs [B*n, C]).  Without a ``guide`` the frames guide themselves, resized when
+        ``size`` is not their own."""
+        kind, B, H, W, OH, OW = guide_plan(self.cfg.patch, x, guide, size)
         self._require_gpu()
-        x, kind, B, H, W = self._prep_batch(x)
+        x = self._to_device(x, kind)
         if guide is not None:
             guide = guide.to(self.device).contiguous()
         elif (OH, OW) == (H, W):
             guide = x
         else:
             guide = self._resize_view(x, kind, OH, OW)
-        return self._run_guided(x, kind, B, H, W, guide, OH, OW, params, want_dense)
+        self._sync_weights()
+        hp, wp = H // self.cfg.patch, W // self.cfg.patch
+        logp = torch.empty((B * hp * wp, self.cfg.n_classes), dtype=torch.float32, device=x.device)
+        cells = torch.empty((B, hp, wp), dtype=torch.int32, device=x.device)
+        labels, dense = self._alloc_out(B, OH, OW, want_dense)
+        capi.check(capi.lib().dinoseg_forward_guided_hw(self._handle, x.data_ptr(), kind, B, H, W, guide.data_ptr(), OH, OW, params[0],
+                                                        params[1], params[2], logp.data_ptr(), cells.data_ptr(), labels.data_ptr(),
+                                                        capi.ptr(dense), self._stream()))
+        return labels, dense, logp
 
     @torch.no_grad()
     def segment_guided(self, x: torch.Tensor, guide: Optional[torch.Tensor] = None, size=None, radius: int = 2,
@@ -743,39 +632,30 @@ class DINOSeg(nn.Module):
         frames raise ``ValueError``), resized by ``dinoseg_op_resize_u8`` when ``size`` is not their own.  ``radius=0`` is the
         nearest-neighbour enlargement.  ``want_logp=True`` also returns the averaged log-probabilities (fp32 [B,C,OH,OW]).  The
         defaults are a starting point: their effect on mIoU has not been measured on any dataset.  Inference only."""
-        params = guided_params(True, radius, sigma_spatial, sigma_range)
-        labels, dense, _ = self._guided(x, guide, size, params, want_logp)
-        return labels, dense
+        return self._guided(x, guide, size, guided_params(True, radius, sigma_spatial, sigma_range), want_logp)[:2]
 
     # ---- multi-scale + flip ensemble at pixel resolution (csrc/upsample_ensemble.hip) ----
-    def _resize_view(self, x: torch.Tensor, kind: int, Hk: int, Wk: int) -> torch.Tensor:
-        """The batch resized to Hk x Wk: F.interpolate for fp32 [B,3,H,W], dinoseg_op_resize_u8 frame by frame for uint8 [B,H,W,3]."""
+    def _resize_view(self, x: torch.Tensor, kind: int, Hk: int, Wk: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The batch resized to Hk x Wk: F.interpolate for fp32 [B,3,H,W], dinoseg_op_resize_u8 frame by frame for uint8 [B,H,W,3]
+        (into ``out`` where the caller owns the destination: the static input of ``predict``'s graph)."""
         if kind != capi.INPUT_U8_HWC:
             return F.interpolate(x, size=(Hk, Wk), mode="bilinear", align_corners=False).contiguous()
         B, H, W = x.shape[0], x.shape[1], x.shape[2]
-        out = torch.empty((B, Hk, Wk, 3), dtype=torch.uint8, device=x.device)
+        if out is None:
+            out = torch.empty((B, Hk, Wk, 3), dtype=torch.uint8, device=x.device)
         for i in range(B):
             capi.check(capi.lib().dinoseg_op_resize_u8(x.data_ptr() + i * H * W * 3, H, W, out.data_ptr() + i * Hk * Wk * 3, Hk, Wk,
                                                       self._stream()))
         return out
 
     def _multiscale(self, x: torch.Tensor, scales, flip: bool, size, want_conf: bool, want_probs: bool):
-        """segment_multiscale, also returning the views' low-res log-probs and their (H_k, W_k, flip_k)."""
-        x, kind, B, H, W = self._prep_batch(x)
-        scales = tuple(float(s) for s in scales)
-        K = len(scales) * (2 if flip else 1)
-        if not 1 <= K <= ENSEMBLE_MAX_VIEWS:
-            raise ValueError(f"{len(scales)} scales{' with flip' if flip else ''} are {K} views; the ensemble takes 1 to {ENSEMBLE_MAX_VIEWS}")
-        if any(not (s > 0.0 and math.isfinite(s)) for s in scales):
-            raise ValueError(f"scales must be positive, got {scales}")
+        """segment_multiscale, also returning the low-res log-probs of the unflipped scale-1.0 view (the first view's without
+        one): what a validation step reports as "probs"."""
         p = self.cfg.patch
-        OH, OW = self._out_size(size, (H, W))
-        views = [(Hk, Wk, f) for Hk, Wk in view_sizes(H, W, scales, p) for f in ((0, 1) if flip else (0,))]
-        for Hk, Wk, _ in views:
-            if Hk // p > OH or Wk // p > OW:
-                raise ValueError(f"the {Hk}x{Wk} view's grid {Hk // p}x{Wk // p} exceeds the output size {OH}x{OW} "
-                                 "(upsampling and identity only)")
+        kind, B, H, W = frame_layout(x, p, multiple=True)
+        views, K, (OH, OW) = multiscale_plan(p, H, W, scales, flip, size)
         self._require_gpu()
+        x = self._to_device(x, kind)
         w_axis = 2 if kind == capi.INPUT_U8_HWC else 3
         logps, xv, cur = [], None, None
         for Hk, Wk, f in views:                         # scale-major, the unflipped view first: one resize per scale
@@ -798,7 +678,8 @@ class DINOSeg(nn.Module):
                                                     i32([v[1] // p for v in views]), i32([v[2] for v in views]), K, B,
                                                     self.cfg.n_classes, OH, OW, labels.data_ptr(), capi.ptr(conf), capi.ptr(probs),
                                                     scratch.data_ptr(), self._stream()))
-        return labels, conf, probs, logps, views
+        own = next((i * (2 if flip else 1) for i, s in enumerate(scales) if float(s) == 1.0), 0)
+        return labels, conf, probs, logps[own]
 
     @torch.no_grad()
     def segment_multiscale(self, x: torch.Tensor, scales=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), flip: bool = True, size=None,
@@ -820,61 +701,19 @@ class DINOSeg(nn.Module):
         unflipped one).  Measured (``tools/ensemble_cost.py``, ViT-S/8 x12 @480, batch 8, fp16): the K forwards in this order
         against the same forwards each repeated at its own resolution differ by -1.0 .. +0.4 ms of 17 (3 views) to 90 ms (12
         views) -- below what the medians resolve; the fused launch itself is 1.1 / 4.8 ms at 150 classes."""
-        labels, conf, probs, _, _ = self._multiscale(x, scales, flip, size, want_conf, want_probs)
-        return labels, conf, probs
+        return self._multiscale(x, scales, flip, size, want_conf, want_probs)[:3]
 
     # ---- sliding-window inference at pixel resolution (csrc/windows.hip) ----
-    def _window_plan(self, H: int, W: int, window, stride):
-        """The window and stride of a sliding-window call on H x W frames, per axis: ((wh, ww), (sh, sw), (gh, gw)).  Every
-        ``ValueError`` of the protocol is raised here, before any device use."""
-        p = self.cfg.patch
-        if H < p or W < p:
-            raise ValueError(f"frames of {H}x{W} are smaller than one {p}x{p} patch")
-        win, out_s, grid = _pair(window, "window"), [], []
-        st = (None, None) if stride is None else _pair(stride, "stride")
-        win = list(win)
-        for axis, L in enumerate((H, W)):
-            w, name = win[axis], ("vertical", "horizontal")[axis]
-            if w < 1:
-                raise ValueError(f"window must be positive, got {tuple(_pair(window, 'window'))}")
-            if w % p != 0:
-                raise ValueError(f"{name} window {w} is not a multiple of the patch ({p})")
-            w = min(w, (L // p) * p)                    # clamped to the largest patch multiple inside the frame
-            s = (2 * w) // 3 if st[axis] is None else st[axis]
-            if s < 1:
-                raise ValueError(f"stride must be positive, got {tuple(st)}")
-            origins = window_origins(L, w, s)
-            cov = _axis_coverage(origins, w)
-            if cov > WINDOW_MAX_COVERAGE:
-                raise ValueError(f"{name} coverage {cov}: window {w} at stride {s} puts {cov} windows over one pixel "
-                                 f"{'row' if axis == 0 else 'column'} (at most {WINDOW_MAX_COVERAGE} per axis)")
-            win[axis] = w
-            out_s.append(s)
-            grid.append(len(origins))
-        return tuple(win), tuple(out_s), tuple(grid)
-
-    def _prep_frames(self, x: torch.Tensor):
-        """The shape check of ``_prep_batch`` for frames of ANY size: (input kind, B, H, W)."""
-        if x.dtype == torch.uint8:
-            if x.dim() != 4 or x.shape[3] != 3:
-                raise ValueError(f"expected uint8 [B,H,W,3], got {tuple(x.shape)}")
-            return capi.INPUT_U8_HWC, x.shape[0], x.shape[1], x.shape[2]
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError(f"expected [B,3,H,W], got {tuple(x.shape)}")
-        return capi.INPUT_F32_CHW, x.shape[0], x.shape[2], x.shape[3]
-
     def _windows(self, x: torch.Tensor, window, stride, want_dense: bool, max_windows: int):
         """segment_windows, also returning the windows' low-res log-probs [B*G, n, C]."""
-        kind, B, H, W = self._prep_frames(x)
-        (wh, ww), (sh, sw), (gh, gw) = self._window_plan(H, W, window, stride)
+        dev, p, C_ = self.device, self.cfg.patch, self.cfg.n_classes
+        kind, B, H, W = frame_layout(x, p, non_empty=True)
+        (wh, ww), (sh, sw), (gh, gw) = window_plan(p, H, W, window, stride)
         max_windows = int(max_windows)
         if max_windows < 1:
             raise ValueError(f"max_windows must be positive, got {max_windows}")
-        if B < 1:
-            raise ValueError("empty batch")
         self._require_gpu()
-        dev, p, C_ = self.device, self.cfg.patch, self.cfg.n_classes
-        x = x.to(dev).contiguous() if kind == capi.INPUT_U8_HWC else x.to(device=dev, dtype=torch.float32).contiguous()
+        x = self._to_device(x, kind)
         self._sync_weights()
         lib, total, n = capi.lib(), B * gh * gw, (wh // p) * (ww // p)
         logp = torch.empty((total, n, C_), dtype=torch.float32, device=dev)
@@ -889,8 +728,7 @@ class DINOSeg(nn.Module):
             capi.check(lib.dinoseg_forward_hw(self._handle, crop.data_ptr(), kind, count, wh, ww,
                                               logp.data_ptr() + 4 * first * n * C_, None, -1, None, self._stream()))
         del crop
-        labels = torch.empty((B, H, W), dtype=torch.int32, device=dev)
-        dense = torch.empty((B, C_, H, W), dtype=torch.float32, device=dev) if want_dense else None
+        labels, dense = self._alloc_out(B, H, W, want_dense)
         capi.check(lib.dinoseg_op_window_merge(logp.data_ptr(), B, H, W, p, wh, ww, sh, sw, C_, labels.data_ptr(), capi.ptr(dense),
                                                self._stream()))
         return labels, dense, logp
@@ -909,8 +747,7 @@ class DINOSeg(nn.Module):
         windows' low-res log-probs and one chunk of cropped windows.  A window or stride that is not positive, a window that is
         not a patch multiple, and more than 4 windows over one pixel row or column (any stride >= window / 3 is fine) raise
         ``ValueError`` before any forward runs.  Inference only."""
-        labels, dense, _ = self._windows(x, window, stride, want_logp, max_windows)
-        return labels, dense
+        return self._windows(x, window, stride, want_logp, max_windows)[:2]
 
     def predict_dense(self, img, size=None, scales=None, flip: bool = False, window=None, stride=None, guided=None) -> np.ndarray:
         """The pixel-resolution sibling of ``predict()``: the image (PIL.Image or HxWx3 uint8 array) is resized to r x r on the
@@ -922,41 +759,47 @@ class DINOSeg(nn.Module):
         With ``guided`` (``True`` or a dict of ``radius`` / ``sigma_spatial`` / ``sigma_range``) the log-probabilities of the
         resized frame are enlarged by ``segment_guided``'s rule instead, guided by the ORIGINAL image at its own size (resized
         only if ``size`` asks for another); ``guided`` with ``window`` or ``scales`` raises ``ValueError``."""
-        gparams = None
-        if guided is not None:
-            if window is not None or scales is not None:
-                raise ValueError("guided cannot be combined with window or scales")
-            gparams = guided_params(guided)
+        mode = dense_mode(scales, flip, window, stride, guided)
+        raw = self._image_u8(img)
+        own, r, guide = tuple(raw.shape[:2]), self.resolution, None
         with torch.no_grad():
-            raw = np.asarray(img)
-            if raw.dtype != np.uint8 or not raw.flags.c_contiguous:
-                raw = np.ascontiguousarray(raw, dtype=np.uint8)
-            if raw.ndim != 3 or raw.shape[2] != 3:
-                raise ValueError(f"expected an HxWx3 image, got {raw.shape}")
-            if window is not None:
-                if scales is not None:
-                    raise ValueError("window and scales cannot be combined")
-                if size is not None and tuple(int(v) for v in size) != tuple(raw.shape[:2]):
-                    raise ValueError(f"with window the image is segmented at its own size {tuple(raw.shape[:2])}, got size={tuple(size)}")
-                labels = self._windows(torch.from_numpy(raw).unsqueeze(0), window, stride, False, 32)[0]
-                return labels[0].cpu().numpy().astype(np.int64)
-            r = self.resolution
-            self._require_gpu()
-            OH, OW = self._out_size(size, raw.shape[:2])
-            frames = orig = torch.from_numpy(raw).unsqueeze(0).to(self.device)
-            if raw.shape[0] != r or raw.shape[1] != r:                           # Resize(r, r) of get_transforms, on the GPU
-                resized = torch.empty((1, r, r, 3), dtype=torch.uint8, device=self.device)
-                capi.check(capi.lib().dinoseg_op_resize_u8(frames.data_ptr(), raw.shape[0], raw.shape[1], resized.data_ptr(), r, r,
-                                                          self._stream()))
-                frames = resized
-            if gparams is not None:
-                guide = orig if (OH, OW) == tuple(raw.shape[:2]) else self._resize_view(orig, capi.INPUT_U8_HWC, OH, OW)
-                labels = self._guided(frames, guide, None, gparams, False)[0]
-            elif scales is not None:
-                labels = self._multiscale(frames, scales, flip, (OH, OW), False, False)[0]
+            frames = torch.from_numpy(raw).unsqueeze(0)
+            if mode.kind == "windows":
+                if size is not None and tuple(int(v) for v in size) != own:
+                    raise ValueError(f"with window the image is segmented at its own size {own}, got size={tuple(size)}")
             else:
-                labels, _, _ = self._run_dense(frames, capi.INPUT_U8_HWC, 1, r, r, OH, OW)
+                self._require_gpu()
+                size = out_size(size, own)
+                frames = orig = frames.to(self.device)
+                if own != (r, r):                                                # Resize(r, r) of get_transforms, on the GPU
+                    frames = self._resize_view(orig, capi.INPUT_U8_HWC, r, r)
+                if mode.kind == "guided":
+                    guide = orig if size == own else self._resize_view(orig, capi.INPUT_U8_HWC, size[0], size[1])
+            labels = self._segment_mode(frames, mode, size, guide=guide)[0]
             return labels[0].cpu().numpy().astype(np.int64)
+
+    def _segment_mode(self, x: torch.Tensor, mode, size, want_logp: bool = False, guide: Optional[torch.Tensor] = None):
+        """The one place that maps a resolved ``dense_mode`` to its runner: (labels int32 [B,OH,OW], None, low-res log-probs).
+        The log-probs are those a validation step reports as "probs" (bilinear: None unless ``want_logp``, which costs that mode
+        an output buffer); sliding windows keep the frames' own size whatever ``size`` says; ``guide`` is the guided mode's."""
+        if mode.kind == "guided":
+            return self._guided(x, guide, size, mode.args)
+        if mode.kind == "windows":
+            return self._windows(x, *mode.args, False, 32)
+        if mode.kind == "multiscale":
+            labels, _, _, logp = self._multiscale(x, *mode.args, size, False, False)
+            return labels, None, logp
+        return self._bilinear(x, size, want_logp=want_logp)
+
+    @staticmethod
+    def _image_u8(img) -> np.ndarray:
+        """A PIL.Image or array as a contiguous uint8 HxWx3 array (``predict`` / ``predict_dense``)."""
+        raw = np.asarray(img)
+        if raw.dtype != np.uint8 or not raw.flags.c_contiguous:
+            raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        if raw.ndim != 3 or raw.shape[2] != 3:
+            raise ValueError(f"expected an HxWx3 image, got {raw.shape}")
+        return raw
 
     def _predict_graph(self, r: int):
         """The single-frame forward of ``predict()`` as a captured HIP graph (one replay instead of ~150 launches: a 12-block
@@ -997,22 +840,14 @@ class DINOSeg(nn.Module):
         (pl_torch_modules.py:276-300, including the non-480 sizes it yields when 480 % (r/8) != 0).  A patch-16 model follows the
         same rule with 16 in place of 8: o = r // 16, blocks of 480 // o."""
         with torch.no_grad():
-            raw = np.asarray(x)
-            if raw.dtype != np.uint8 or not raw.flags.c_contiguous:
-                raw = np.ascontiguousarray(raw, dtype=np.uint8)
-            if raw.ndim != 3 or raw.shape[2] != 3:
-                raise ValueError(f"expected an HxWx3 image, got {raw.shape}")
+            raw = self._image_u8(x)
             r = self.resolution
             self._require_gpu()
             self._sync_weights()
             ent = self._predict_graph(r)
             frames = torch.from_numpy(raw).unsqueeze(0)                           # uint8 on the wire, whatever its size
             if raw.shape[0] != r or raw.shape[1] != r:                           # Resize(r, r) of get_transforms, on the GPU
-                frames = frames.to(self.device)
-                resized = ent["in"] if ent is not None else torch.empty((1, r, r, 3), dtype=torch.uint8, device=self.device)
-                capi.check(capi.lib().dinoseg_op_resize_u8(frames.data_ptr(), raw.shape[0], raw.shape[1], resized.data_ptr(), r, r,
-                                                          self._stream()))
-                frames = resized
+                frames = self._resize_view(frames.to(self.device), capi.INPUT_U8_HWC, r, r, out=None if ent is None else ent["in"])
             elif ent is not None:
                 ent["in"].copy_(frames, non_blocking=True)
             if ent is not None:
@@ -1086,14 +921,10 @@ class DINOSeg(nn.Module):
         threshold)`` for frame 0 is ``cls_attention(x, size=(hp, wp), threshold=threshold)``: its ``keep`` when a threshold is given,
         its ``attn`` otherwise.  The threshold is the reference's sort / cumulative-sum rule in exact integers (include/dinoseg.h,
         dinoseg_op_cls_attention): a tied group is kept or dropped whole.  Inference only."""
-        kind, B, H, W = self._prep_frames(x)
         p = self.cfg.patch
-        if H % p != 0 or W % p != 0 or H < p or W < p:
-            raise ValueError(self._resolution_message())
-        if B < 1:
-            raise ValueError("empty batch")
+        kind, B, H, W = frame_layout(x, p, multiple=True, one_patch=True, non_empty=True)
         hp, wp = H // p, W // p
-        OH, OW = self._out_size(size, (H, W))
+        OH, OW = out_size(size, (H, W))
         if OH < hp or OW < wp:
             raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(hp, wp)}")
         if threshold is not None:
@@ -1104,7 +935,7 @@ class DINOSeg(nn.Module):
         if hp * wp + 1 > limit:
             raise ValueError(f"a {H}x{W} frame has {hp * wp + 1} tokens, more than the {limit} one launch holds")
         self._require_gpu()
-        x, kind, B, H, W = self._prep_batch(x)
+        x = self._to_device(x, kind)
         self._sync_weights()
         heads = self.cfg.num_heads
         attn = torch.empty((B, heads, OH, OW), dtype=torch.float32, device=x.device)
@@ -1121,11 +952,15 @@ class DINOSeg(nn.Module):
         with torch.no_grad():
             xx, kind, B, H, W = self._prep_batch(x)
             logp, amax, _ = self._run(xx, kind, B, H, W, want_logp=True, want_argmax=True)
-            y = y.to(self.device).reshape(-1).long().contiguous()
-            cm = torch.zeros((self.cfg.n_classes, self.cfg.n_classes), dtype=torch.int64, device=self.device)
-            capi.check(capi.lib().dinoseg_op_confusion(amax.data_ptr(), y.data_ptr(), y.numel(), self.cfg.n_classes,
-                                                       cm.data_ptr(), self._stream()))
-        return {"pred": amax, "gt": y, "probs": logp, "confusion": cm}
+            return self._score(amax, y, logp)
+
+    def _score(self, pred: torch.Tensor, y: torch.Tensor, probs: torch.Tensor) -> dict:
+        """A validation step's output: the confusion matrix of int32 predictions against the labels, counted on the device."""
+        y = y.to(self.device).reshape(-1).long().contiguous()
+        cm = torch.zeros((self.cfg.n_classes, self.cfg.n_classes), dtype=torch.int64, device=self.device)
+        capi.check(capi.lib().dinoseg_op_confusion(pred.data_ptr(), y.data_ptr(), y.numel(), self.cfg.n_classes,
+                                                   cm.data_ptr(), self._stream()))
+        return {"pred": pred, "gt": y, "probs": probs, "confusion": cm}
 
     def validation_step_dense(self, batch, batch_idx=0, scales=None, flip: bool = False, window=None, stride=None, guided=None):
         """``validation_step`` scored per pixel: ``y`` is [B, OH, OW] pixel labels, the prediction is ``segment`` at y's size and
@@ -1138,54 +973,12 @@ class DINOSeg(nn.Module):
         With ``guided`` (``True`` or a dict of ``radius`` / ``sigma_spatial`` / ``sigma_range``) the prediction is
         ``segment_guided(x, size=y's)`` on uint8 frames; ``guided`` with ``window`` or ``scales`` raises ``ValueError``."""
         x, y = batch
-        gparams = None
-        if guided is not None:
-            if window is not None or scales is not None:
-                raise ValueError("guided cannot be combined with window or scales")
-            gparams = guided_params(guided)
-        if window is not None:
-            return self._validation_step_windows(x, y, scales, window, stride)
-        if gparams is not None:
-            if y.dim() != 3 or y.shape[0] != x.shape[0]:
-                raise ValueError(f"expected pixel labels [B={x.shape[0]}, OH, OW], got {tuple(y.shape)}")
-            with torch.no_grad():
-                labels, _, logp = self._guided(x, None, (int(y.shape[1]), int(y.shape[2])), gparams, False)
-                y = y.to(self.device).reshape(-1).long().contiguous()
-                cm = torch.zeros((self.cfg.n_classes, self.cfg.n_classes), dtype=torch.int64, device=self.device)
-                capi.check(capi.lib().dinoseg_op_confusion(labels.data_ptr(), y.data_ptr(), y.numel(), self.cfg.n_classes,
-                                                           cm.data_ptr(), self._stream()))
-            return {"pred": labels, "gt": y, "probs": logp, "confusion": cm}
-        self._require_gpu()
+        mode = dense_mode(scales, flip, window, stride, guided)
+        _, B, H, W = frame_layout(x, self.cfg.patch)
+        size = label_size(y, B, own=(H, W) if mode.kind == "windows" else None)
         with torch.no_grad():
-            xx, kind, B, H, W = self._prep_batch(x)
-            if y.dim() != 3 or y.shape[0] != B:
-                raise ValueError(f"expected pixel labels [B={B}, OH, OW], got {tuple(y.shape)}")
-            if scales is not None:
-                labels, _, _, logps, views = self._multiscale(xx, scales, flip, (int(y.shape[1]), int(y.shape[2])), False, False)
-                own = [i for i, (s, v) in enumerate(zip([s for s in scales for _ in range(2 if flip else 1)], views))
-                       if float(s) == 1.0 and v[2] == 0]
-                logp = logps[own[0] if own else 0]
-            else:
-                labels, _, logp = self._run_dense(xx, kind, B, H, W, int(y.shape[1]), int(y.shape[2]), want_logp=True)
-            y = y.to(self.device).reshape(-1).long().contiguous()
-            cm = torch.zeros((self.cfg.n_classes, self.cfg.n_classes), dtype=torch.int64, device=self.device)
-            capi.check(capi.lib().dinoseg_op_confusion(labels.data_ptr(), y.data_ptr(), y.numel(), self.cfg.n_classes,
-                                                       cm.data_ptr(), self._stream()))
-        return {"pred": labels, "gt": y, "probs": logp, "confusion": cm}
-
-    def _validation_step_windows(self, x, y, scales, window, stride):
-        if scales is not None:
-            raise ValueError("window and scales cannot be combined")
-        with torch.no_grad():
-            _, B, H, W = self._prep_frames(x)
-            if y.dim() != 3 or tuple(y.shape) != (B, H, W):
-                raise ValueError(f"expected pixel labels [B={B}, {H}, {W}] (the frames' own size), got {tuple(y.shape)}")
-            labels, _, logp = self._windows(x, window, stride, False, 32)
-            y = y.to(self.device).reshape(-1).long().contiguous()
-            cm = torch.zeros((self.cfg.n_classes, self.cfg.n_classes), dtype=torch.int64, device=self.device)
-            capi.check(capi.lib().dinoseg_op_confusion(labels.data_ptr(), y.data_ptr(), y.numel(), self.cfg.n_classes,
-                                                       cm.data_ptr(), self._stream()))
-        return {"pred": labels, "gt": y, "probs": logp, "confusion": cm}
+            labels, _, logp = self._segment_mode(x, mode, size, want_logp=True)
+            return self._score(labels, y, logp)
 
     def validation_epoch_end(self, outputs, prefix="val"):
         """Balanced accuracy, macro F1 and macro IoU over all patches of the split, from the summed confusion matrices
@@ -1273,20 +1066,12 @@ class DINOSeg(nn.Module):
 
     def _prep_batch(self, x: torch.Tensor):
         """uint8 [B,H,W,3] or fp32 [B,3,H,W] -> (contiguous tensor on the model's device, input kind, B, H, W)."""
-        dev = self.device
-        if x.dtype == torch.uint8:
-            if x.dim() != 4 or x.shape[3] != 3:
-                raise ValueError(f"expected uint8 [B,H,W,3], got {tuple(x.shape)}")
-            kind, B, H, W = capi.INPUT_U8_HWC, x.shape[0], x.shape[1], x.shape[2]
-            x = x.to(dev).contiguous()
-        else:
-            if x.dim() != 4 or x.shape[1] != 3:
-                raise ValueError(f"expected [B,3,H,W], got {tuple(x.shape)}")
-            kind, B, H, W = capi.INPUT_F32_CHW, x.shape[0], x.shape[2], x.shape[3]
-            x = x.to(device=dev, dtype=torch.float32).contiguous()
-        if H % self.cfg.patch != 0 or W % self.cfg.patch != 0:
-            raise ValueError(self._resolution_message())
-        return x, kind, B, H, W
+        kind, B, H, W = frame_layout(x, self.cfg.patch, multiple=True)
+        return self._to_device(x, kind), kind, B, H, W
+
+    def _to_device(self, x: torch.Tensor, kind: int) -> torch.Tensor:
+        """Frames of a checked layout as a contiguous tensor on the model's device (fp32 unless they are uint8)."""
+        return x.to(device=self.device, dtype=torch.uint8 if kind == capi.INPUT_U8_HWC else torch.float32).contiguous()
 
     def check_labels(self) -> None:
         """Raise IndexError if a training step since the last check saw a label outside [0, n_classes) other than the
@@ -1413,10 +1198,9 @@ class DINOSeg(nn.Module):
         ``fused_training_step_dense`` is the same arithmetic in one native call."""
         x, y = batch
         self._require_gpu()
-        if y.dim() != 3 or y.shape[0] != x.shape[0]:
-            raise ValueError(f"expected pixel labels [B={x.shape[0]}, OH, OW], got {tuple(y.shape)}")
+        label_size(y, x.shape[0])
         probs = self(x)
-        H, W = (x.shape[1], x.shape[2]) if x.dtype == torch.uint8 else (x.shape[2], x.shape[3])
+        _, _, H, W = frame_layout(x, self.cfg.patch)
         hp, wp = H // self.cfg.patch, W // self.cfg.patch
         y = y.to(self.device).long().contiguous()
         flags = self.__dict__.get("_dense_flags")
@@ -1439,9 +1223,7 @@ class DINOSeg(nn.Module):
         self._sync_grads("grad")
         x, kind, B, H, W = self._prep_batch(x)
         dev = self.device
-        if y.dim() != 3 or y.shape[0] != B:
-            raise ValueError(f"expected pixel labels [B={B}, OH, OW], got {tuple(y.shape)}")
-        OH, OW = int(y.shape[1]), int(y.shape[2])
+        OH, OW = label_size(y, B)
         hp, wp = H // self.cfg.patch, W // self.cfg.patch
         y = y.to(dev).reshape(-1).long().contiguous()
         loss = torch.zeros((), dtype=torch.float32, device=dev)
@@ -1513,11 +1295,7 @@ class DINOSeg(nn.Module):
         for o in outputs:
             if "confusion" not in o:
                 pred = torch.as_tensor(o["pred"]).to(self.device).reshape(-1).to(torch.int32).contiguous()
-                gt = torch.as_tensor(o["gt"]).to(self.device).reshape(-1).long().contiguous()
-                cm = torch.zeros((self.cfg.n_classes, self.cfg.n_classes), dtype=torch.int64, device=self.device)
-                capi.check(capi.lib().dinoseg_op_confusion(pred.data_ptr(), gt.data_ptr(), gt.numel(), self.cfg.n_classes,
-                                                           cm.data_ptr(), self._stream()))
-                o = {"confusion": cm}
+                o = self._score(pred, torch.as_tensor(o["gt"]), None)
             outs.append(o)
         return self.validation_epoch_end(outs, prefix="train")
 
