@@ -162,6 +162,12 @@ SIGNATURES = {
     "dinoseg_op_window_merge": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _vp]),
     # augmentation of fine-tuning frames and masks from a per-frame table (int32 [B, 36] on the device): warp + colour + labels, blur
     "dinoseg_op_augment": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _fp, _fp, _i32, _fp, _vp]),
+    # video label propagation from patch features: unit rows as fp16 hi + lo planes, the seed from pixel labels, one target frame from
+    # up to 16 context frames (two host tables of device pointers), its scratch size (host only)
+    "dinoseg_op_normalize_tokens": (C.c_int, [_fp, _i32, _i32, _i32, _vp, _vp]),
+    "dinoseg_op_label_cells": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _vp]),
+    "dinoseg_propagate_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "dinoseg_op_propagate": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _fp, _fp, _fp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -642,6 +642,26 @@ extern "C" int dinoseg_op_augment(const uint8_t* frames, const void* masks, int3
                           scratch, reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int dinoseg_op_normalize_tokens(const float* tokens, int32_t B, int32_t n, int32_t D, void* planes, void* stream) {
+    return launch_normalize_tokens(tokens, B, n, D, planes, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_label_cells(const void* labels, int32_t mask_kind, int32_t OH, int32_t OW, int32_t hp, int32_t wp, int32_t C,
+                                      float* seg, void* stream) {
+    return launch_label_cells(labels, mask_kind, OH, OW, hp, wp, C, seg, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int64_t dinoseg_propagate_scratch_bytes(int32_t hp, int32_t wp, int32_t n_ctx, int32_t k) {
+    return propagate_scratch_bytes(hp, wp, n_ctx, k);
+}
+
+extern "C" int dinoseg_op_propagate(const void* target_planes, const void* const* ctx_planes, const float* const* ctx_segs, int32_t n_ctx,
+                                    int32_t hp, int32_t wp, int32_t D, int32_t C, int32_t radius, int32_t k, double tau, float* seg_out,
+                                    int32_t* topk_idx, float* topk_w, void* scratch, void* stream) {
+    return launch_propagate(target_planes, ctx_planes, ctx_segs, n_ctx, hp, wp, D, C, radius, k, tau, seg_out, topk_idx, topk_w, scratch,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int dinoseg_op_confusion(const int32_t* pred, const int64_t* gt, int64_t n, int32_t n_classes, int64_t* cm, void* stream) {
     return launch_confusion(pred, gt, n, n_classes, cm, reinterpret_cast<hipStream_t>(stream));
 }

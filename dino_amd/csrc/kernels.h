@@ -368,6 +368,19 @@ int launch_augment(const uint8_t* frames, const void* masks, int mask_kind, int 
                    int max_radius, int OH, int OW, int out_kind, void* out, int64_t* pixel_labels, int64_t* patch_labels, int patch,
                    float* scratch, hipStream_t s);
 
+// Video label propagation from patch features (propagate.hip; the rule: include/dinoseg.h, dinoseg_op_propagate).
+// launch_normalize_tokens: tokens fp32 [B, 1 + n, D] -> unit rows times 2^10 as fp16 hi + lo planes [B][2][n][D], the CLS row skipped.
+// launch_label_cells: integer pixel labels [OH, OW] (kind 0 uint8, 1 int64) -> class shares per cell, fp32 [n, C].
+// launch_propagate: one target frame from n_ctx <= 16 context frames (host arrays of device pointers, by value to the kernels): the
+// scores launch (one workgroup per query tile and context frame, per-query lists of k in LDS) and the merge launch (weights, gathers).
+// scratch: propagate_scratch_bytes (8 n_ctx n k; -1 for refusable arguments).  No atomics; every refusal is on the host.
+int launch_normalize_tokens(const float* tokens, int B, int n, int D, void* planes, hipStream_t s);
+int launch_label_cells(const void* labels, int mask_kind, int OH, int OW, int hp, int wp, int C, float* seg, hipStream_t s);
+long long propagate_scratch_bytes(int hp, int wp, int n_ctx, int k);
+int launch_propagate(const void* target_planes, const void* const* ctx_planes, const float* const* ctx_segs, int n_ctx, int hp, int wp,
+                     int D, int C, int radius, int k, double tau, float* seg_out, int32_t* topk_idx, float* topk_w, void* scratch,
+                     hipStream_t s);
+
 // ---- fine-tune step (train.hip, attention_bwd.hip) ----
 struct AttnBwdParams {
     const bf16_t* q; const bf16_t* k; const bf16_t* v; long qkv_plane;   // forward operands [planes][B,H,npad,64]

@@ -1,0 +1,465 @@
+// Video label propagation from patch features (the semi-supervised video segmentation protocol of the DINO paper) without the
+// [n_ctx, n, n] affinity.  The rule is stated in full in include/dinoseg.h (dinoseg_op_propagate); in short, every cell of the target
+// frame takes the k best-scoring cells within R cells of itself over all context frames -- score = the inner product of the unit
+// feature rows, order = (score descending, global index ascending) -- and averages their label rows with weights exp((s - s_0) / tau).
+//
+//   normalize_tokens_kernel   one wave per patch token: ||f||^2 and the quotient in fp64, the row scaled by 2^10 and split into fp16
+//                             hi + lo planes [2][n][D] (a unit row's components are about D^-1/2: unscaled, the lo plane would sit in
+//                             fp16 subnormals; scaled, hi + lo carries 22 significand bits down to |f^| = 2^-13).  The CLS row is skipped.
+//   label_cells_kernel        one wave per cell: lane l counts classes l, l + 64, ... over the cell's pixels (every lane reads the same
+//                             pixel: a broadcast), integer counts, no atomics; seg_0 = count / pixels of the cell.
+//   propagate_scores_kernel   one workgroup (4 waves) per (8 x 8 query tile, context frame).  The tile's key window is the tile widened
+//                             by R cells and clipped to the grid (32 x 32 keys at R = 12), walked in blocks of 64 keys.  Per block and
+//                             64-wide slice of D the query tile and the key block (hi and lo, 4 x 8 KiB, 128-byte rows under the
+//                             library's swizzle) are staged in LDS -- the next slice's global loads are in flight under the current
+//                             slice's MFMAs -- and wave (qh, kh) multiplies keys 32 kh .. by queries 32 qh .. : lo.hi + hi.lo + hi.hi on
+//                             v_mfma_f32_32x32x16_f16, fp32 accumulators, slices in ascending order.  Every (key, query) element of an
+//                             MFMA goes through the same arithmetic, so a score depends on the two rows alone.  A lane owns one query
+//                             and 16 keys of the block: the neighbourhood test in integers, then an insertion into the lane's own
+//                             sorted list of k (score, g) in LDS ([slot][thread]: conflict-free), gated by the list's last entry in
+//                             registers.  At the end 64 threads merge the 4 lists of their query (4-way, the total order) into the
+//                             scratch: [n_ctx][n][k] scores and indices.  LDS: 32 KiB + 2 KiB k <= 64 KiB; no atomics; every loop bound
+//                             is a function of the shapes.
+//   propagate_merge_kernel    one wave per query: the n_ctx k <= 256 candidates sit 4 to a lane as 64-bit keys (order-preserving score
+//                             bits, then ~g), k rounds of a wave maximum select rank 0 .. K'-1; weights, W, 1 / W are wave-uniform;
+//                             lanes stride the C classes with k gathers and fmaf each.
+#include "../../include/dinoseg.h"
+#include "common.h"
+#include "kernels.h"
+
+#include <climits>
+#include <cmath>
+
+namespace dseg {
+
+namespace {
+
+constexpr int PRP_TILE = 8;                     // query tile side, 64 queries
+constexpr int PRP_STAGE = 32768;                // Qhi, Qlo, Khi, Klo: 64 rows x 128 B each
+constexpr int PRP_MAX_SIDE = 4096;              // grid side: n <= 2^24, 16 n < 2^31
+constexpr float PRP_UNSCALE = 0x1p-20f;         // planes carry 2^10 f^: products 2^20 <f^, f^>
+constexpr int PRP_EMPTY = INT_MAX;              // g of an empty list slot (score -inf): after every candidate in the total order
+
+__device__ __forceinline__ bool prp_better(float s, int g, float s2, int g2) { return s > s2 || (s == s2 && g < g2); }
+
+__global__ __launch_bounds__(256) void normalize_tokens_kernel(const float* __restrict__ tokens, long long rows, int n, int D,
+                                                               uint16_t* __restrict__ planes) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                            // (a whole wave: no barrier follows)
+    const long long b = row / n, j = row - b * n;
+    const float* src = tokens + ((size_t)b * (n + 1) + 1 + j) * D;
+    double ss = 0.0;
+    for (int d = lane; d < D; d += 64) {
+        const double v = (double)src[d];
+        ss = fma(v, v, ss);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);           // (xor tree: every lane holds the same bits)
+    const double inv = 1024.0 / fmax(sqrt(ss), 1e-12);
+    uint16_t* hi = planes + ((size_t)b * 2 * n + j) * D;
+    uint16_t* lo = hi + (size_t)n * D;
+    for (int d = lane; d < D; d += 64) {
+        const double v = (double)src[d] * inv;
+        const _Float16 h = (_Float16)(float)v;
+        const _Float16 l = (_Float16)(float)(v - (double)(float)h);
+        hi[d] = __builtin_bit_cast(uint16_t, h);
+        lo[d] = __builtin_bit_cast(uint16_t, l);
+    }
+}
+
+__global__ __launch_bounds__(256) void label_cells_kernel(const void* __restrict__ labels, int mask_kind, int OH, int OW, int hp, int wp,
+                                                          int C, float* __restrict__ seg) {
+    const int lane = threadIdx.x & 63;
+    const int cell = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (cell >= hp * wp) return;                                        // (a whole wave: no barrier follows)
+    const int r = cell / wp, c = cell - r * wp;
+    // the pixels y with (y hp) / OH == r: ceil(r OH / hp) .. ceil((r + 1) OH / hp) - 1 (never empty: OH >= hp)
+    const int y0 = (int)(((long long)r * OH + hp - 1) / hp), y1 = (int)(((long long)(r + 1) * OH + hp - 1) / hp);
+    const int x0 = (int)(((long long)c * OW + wp - 1) / wp), x1 = (int)(((long long)(c + 1) * OW + wp - 1) / wp);
+    int cnt[4] = {0, 0, 0, 0};                                          // classes lane, lane + 64, lane + 128, lane + 192
+    for (int y = y0; y < y1; ++y)
+        for (int x = x0; x < x1; ++x) {
+            const size_t at = (size_t)y * OW + x;
+            const long long v = mask_kind == 0 ? (long long)reinterpret_cast<const uint8_t*>(labels)[at]
+                                               : reinterpret_cast<const int64_t*>(labels)[at];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) cnt[i] += v == (long long)(lane + 64 * i) ? 1 : 0;
+        }
+    const float npix = (float)((long long)(y1 - y0) * (x1 - x0));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int cls = lane + 64 * i;
+        if (cls < C) seg[(size_t)cell * C + cls] = __fdiv_rn((float)cnt[i], npix);
+    }
+}
+
+struct PrpCtx {
+    const uint16_t* planes[DINOSEG_PROPAGATE_MAX_CONTEXT];
+    const float* segs[DINOSEG_PROPAGATE_MAX_CONTEXT];
+};
+
+__global__ __launch_bounds__(256) void propagate_scores_kernel(const uint16_t* __restrict__ tq, PrpCtx ctx, int hp, int wp, int D, int R,
+                                                               int k, int tiles_x, float* __restrict__ cand_s, int* __restrict__ cand_g) {
+    extern __shared__ __attribute__((aligned(16))) char prp_lds[];
+    float* ls = reinterpret_cast<float*>(prp_lds + PRP_STAGE);          // [k][256] scores of the lanes' lists, best first
+    int* lg = reinterpret_cast<int*>(prp_lds + PRP_STAGE + k * 1024);   // [k][256] their global indices
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
+    const int qh = wave >> 1, kh = wave & 1;
+    const int n = hp * wp, ci = blockIdx.y;
+    const int r0 = ((int)blockIdx.x / tiles_x) * PRP_TILE, c0 = ((int)blockIdx.x % tiles_x) * PRP_TILE;
+    // the key window: the tile widened by R, clipped to the grid
+    const int wr0 = max(r0 - R, 0), wr1 = min(min(r0 + PRP_TILE - 1, hp - 1) + R, hp - 1);
+    const int wc0 = max(c0 - R, 0), wc1 = min(min(c0 + PRP_TILE - 1, wp - 1) + R, wp - 1);
+    const int ww = wc1 - wc0 + 1, nkeys = ww * (wr1 - wr0 + 1);
+    const int nkb = (nkeys + 63) >> 6, ndc = D >> 6, total = nkb * ndc;
+    const uint16_t* kp = ctx.planes[ci];
+
+    for (int s = 0; s < k; ++s) {
+        ls[s * 256 + tid] = -INFINITY;
+        lg[s * 256 + tid] = PRP_EMPTY;
+    }
+    float thr_s = -INFINITY;                                            // the list's last entry: what a candidate must beat
+    int thr_g = PRP_EMPTY;
+
+    // the lane's query in the selection
+    const int qi = qh * 32 + lr, qr = r0 + (qi >> 3), qc = c0 + (qi & 7);
+    const bool qvalid = qr < hp && qc < wp;
+
+    // staging: thread t moves 16 bytes (chunk t & 7) of rows (t >> 3) and (t >> 3) + 32 of each of the four tiles
+    const int srow = tid >> 3, schunk = tid & 7;
+    size_t qoff[2];
+    int soff[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int row = srow + 32 * h;
+        const int r = min(r0 + (row >> 3), hp - 1), c = min(c0 + (row & 7), wp - 1);   // (a row past the grid re-reads a real one)
+        qoff[h] = (size_t)(r * wp + c) * D + schunk * 8;
+        soff[h] = tile_off_bytes(row, schunk);
+    }
+    const size_t lo_plane = (size_t)n * D;
+    uint4 g_qh0, g_qh1, g_ql0, g_ql1, g_kh0, g_kh1, g_kl0, g_kl1;         // the slice in flight (named: an array would live in scratch)
+    auto key_off = [&](int kb, int h) {
+        int w = kb * 64 + srow + 32 * h;
+        if (w >= nkeys) w = 0;                                          // (a key past the window re-reads a real one; never selected)
+        const int wr = w / ww;
+        return (size_t)((wr0 + wr) * wp + wc0 + (w - wr * ww)) * D + schunk * 8;
+    };
+    auto ld16 = [](const uint16_t* p) { return *reinterpret_cast<const uint4*>(p); };
+    auto fetch = [&](int it) {
+        const int kb = it / ndc;
+        const size_t dofs = (size_t)(it - kb * ndc) * 64, k0 = key_off(kb, 0) + dofs, k1 = key_off(kb, 1) + dofs;
+        g_qh0 = ld16(tq + qoff[0] + dofs);
+        g_qh1 = ld16(tq + qoff[1] + dofs);
+        g_ql0 = ld16(tq + lo_plane + qoff[0] + dofs);
+        g_ql1 = ld16(tq + lo_plane + qoff[1] + dofs);
+        g_kh0 = ld16(kp + k0);
+        g_kh1 = ld16(kp + k1);
+        g_kl0 = ld16(kp + lo_plane + k0);
+        g_kl1 = ld16(kp + lo_plane + k1);
+    };
+
+    // fragment addresses: row lr of the wave's half, chunk 2 s + lh of the 128-byte row
+    int fq[4], fk[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        fq[s] = tile_off_bytes(qh * 32 + lr, s * 2 + lh);
+        fk[s] = 16384 + tile_off_bytes(kh * 32 + lr, s * 2 + lh);
+    }
+
+    f32x16 acc;
+    fetch(0);
+    for (int it = 0; it < total; ++it) {
+        const int kb = it / ndc, dc = it - kb * ndc;
+        __syncthreads();                                                // everyone is done reading the previous slice
+        *reinterpret_cast<uint4*>(prp_lds + soff[0]) = g_qh0;
+        *reinterpret_cast<uint4*>(prp_lds + soff[1]) = g_qh1;
+        *reinterpret_cast<uint4*>(prp_lds + 8192 + soff[0]) = g_ql0;
+        *reinterpret_cast<uint4*>(prp_lds + 8192 + soff[1]) = g_ql1;
+        *reinterpret_cast<uint4*>(prp_lds + 16384 + soff[0]) = g_kh0;
+        *reinterpret_cast<uint4*>(prp_lds + 16384 + soff[1]) = g_kh1;
+        *reinterpret_cast<uint4*>(prp_lds + 24576 + soff[0]) = g_kl0;
+        *reinterpret_cast<uint4*>(prp_lds + 24576 + soff[1]) = g_kl1;
+        __syncthreads();
+        if (it + 1 < total) fetch(it + 1);
+        if (dc == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const bf16x8 qhi = lds_frag(prp_lds + fq[s]), qlo = lds_frag(prp_lds + 8192 + fq[s]);
+            const bf16x8 khi = lds_frag(prp_lds + fk[s]), klo = lds_frag(prp_lds + 8192 + fk[s]);
+            acc = mfma32f<FMT_FP16>(klo, qhi, acc);
+            acc = mfma32f<FMT_FP16>(khi, qlo, acc);
+            acc = mfma32f<FMT_FP16>(khi, qhi, acc);
+        }
+        if (dc != ndc - 1) continue;
+        // the block's scores: register r of this lane is key acc_row(r, lh) of the wave's half, query lr
+        if (qvalid) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int w = kb * 64 + kh * 32 + acc_row(r, lh);
+                if (w >= nkeys) continue;
+                const int wr = w / ww, kr = wr0 + wr, kc = wc0 + (w - wr * ww);
+                if (abs(kr - qr) > R || abs(kc - qc) > R) continue;
+                const float s = acc[r] * PRP_UNSCALE + 0.f;            // (+ 0: a negative zero becomes the positive one)
+                const int g = ci * n + kr * wp + kc;
+                if (!prp_better(s, g, thr_s, thr_g)) continue;
+                int pos = k - 1;                                        // the last entry leaves
+                while (pos > 0) {
+                    const float ps = ls[(pos - 1) * 256 + tid];
+                    const int pg = lg[(pos - 1) * 256 + tid];
+                    if (!prp_better(s, g, ps, pg)) break;
+                    ls[pos * 256 + tid] = ps;
+                    lg[pos * 256 + tid] = pg;
+                    --pos;
+                }
+                ls[pos * 256 + tid] = s;
+                lg[pos * 256 + tid] = g;
+                thr_s = ls[(k - 1) * 256 + tid];
+                thr_g = lg[(k - 1) * 256 + tid];
+            }
+        }
+    }
+    __syncthreads();
+    // 4-way merge of the query's lists (waves (qh, 0) and (qh, 1), both lane halves) under the total order
+    if (tid < 64) {
+        const int q = tid, r = r0 + (q >> 3), c = c0 + (q & 7);
+        if (r < hp && c < wp) {
+            const int t0 = ((q >> 5) * 2) * 64 + (q & 31), t1 = t0 + 32, t2 = t0 + 64, t3 = t0 + 96;
+            int p0 = 0, p1 = 0, p2 = 0, p3 = 0;
+            const size_t out = ((size_t)ci * n + (size_t)r * wp + c) * k;
+            for (int i = 0; i < k; ++i) {
+                // (a list's head index reaches k only after k picks from it: the loop has ended by then)
+                float bs = ls[p0 * 256 + t0];
+                int bg = lg[p0 * 256 + t0], which = 0;
+                const float s1 = ls[p1 * 256 + t1], s2 = ls[p2 * 256 + t2], s3 = ls[p3 * 256 + t3];
+                const int g1 = lg[p1 * 256 + t1], g2 = lg[p2 * 256 + t2], g3 = lg[p3 * 256 + t3];
+                if (prp_better(s1, g1, bs, bg)) { bs = s1; bg = g1; which = 1; }
+                if (prp_better(s2, g2, bs, bg)) { bs = s2; bg = g2; which = 2; }
+                if (prp_better(s3, g3, bs, bg)) { bs = s3; bg = g3; which = 3; }
+                p0 += which == 0;
+                p1 += which == 1;
+                p2 += which == 2;
+                p3 += which == 3;
+                cand_s[out + i] = bs;
+                cand_g[out + i] = bg == PRP_EMPTY ? -1 : bg;
+            }
+        }
+    }
+}
+
+// (score, g) as one unsigned key whose order is the total order: larger = earlier.  0 = no candidate.
+__device__ __forceinline__ unsigned long long prp_key(float s, int g) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, s);
+    const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)o << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)g);
+}
+__device__ __forceinline__ float prp_key_score(unsigned long long key) {
+    const uint32_t o = (uint32_t)(key >> 32);
+    return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
+
+__global__ __launch_bounds__(256) void propagate_merge_kernel(const float* __restrict__ cand_s, const int* __restrict__ cand_g, PrpCtx ctx,
+                                                              int n, int n_ctx, int k, int C, float a, float* __restrict__ seg_out,
+                                                              int32_t* __restrict__ topk_idx, float* __restrict__ topk_w) {
+    __shared__ float sel_w[4][DINOSEG_PROPAGATE_MAX_K];
+    __shared__ int sel_g[4][DINOSEG_PROPAGATE_MAX_K];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int q = blockIdx.x * 4 + wave;
+    const bool valid = q < n;
+    int kept = 0;
+    float W = 0.f;
+    if (valid) {
+        unsigned long long key[4];
+        const int ncand = n_ctx * k;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e = lane + 64 * j;
+            key[j] = 0;
+            if (e < ncand) {
+                const int ci = e / k, i = e - ci * k;
+                const size_t at = ((size_t)ci * n + q) * k + i;
+                const int g = cand_g[at];
+                if (g >= 0) key[j] = prp_key(cand_s[at], g);
+            }
+        }
+        float s0 = 0.f;
+        for (int i = 0; i < k; ++i) {
+            unsigned long long m = key[0];
+#pragma unroll
+            for (int j = 1; j < 4; ++j) m = key[j] > m ? key[j] : m;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long other = __shfl_xor(m, o);
+                m = other > m ? other : m;
+            }
+            if (m == 0) break;                                          // K' = i candidates in all (wave-uniform)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) key[j] = key[j] == m ? 0 : key[j];   // (g is unique: exactly one slot of one lane)
+            const float s = prp_key_score(m);
+            if (i == 0) s0 = s;
+            const float w = __builtin_amdgcn_exp2f((s - s0) * a);
+            W += w;
+            if (lane == 0) {
+                sel_w[wave][i] = w;
+                sel_g[wave][i] = (int)(0xFFFFFFFFu - (uint32_t)m);
+            }
+            kept = i + 1;
+        }
+    }
+    __syncthreads();
+    if (!valid) return;
+    const float inv = __fdiv_rn(1.f, W);
+    for (int c = lane; c < C; c += 64) {
+        float v = 0.f;
+        for (int i = 0; i < kept; ++i) {
+            const int g = sel_g[wave][i], ci = g / n, j = g - ci * n;
+            v = __builtin_fmaf(sel_w[wave][i], ctx.segs[ci][(size_t)j * C + c], v);
+        }
+        seg_out[(size_t)q * C + c] = v * inv;
+    }
+    if (lane < k) {
+        if (topk_idx) topk_idx[(size_t)q * k + lane] = lane < kept ? sel_g[wave][lane] : -1;
+        if (topk_w) topk_w[(size_t)q * k + lane] = lane < kept ? sel_w[wave][lane] * inv : 0.f;
+    }
+}
+
+int prp_grid_check(const char* who, int hp, int wp) {
+    if (hp < 1 || wp < 1 || hp > PRP_MAX_SIDE || wp > PRP_MAX_SIDE) {
+        dinoseg_set_error("%s: patch grid %d x %d (each side 1 .. %d)", who, hp, wp, PRP_MAX_SIDE);
+        return -1;
+    }
+    return 0;
+}
+
+}  // namespace
+
+int launch_normalize_tokens(const float* tokens, int B, int n, int D, void* planes, hipStream_t s) {
+    const char* who = "dinoseg_op_normalize_tokens";
+    if (!tokens || !planes) {
+        dinoseg_set_error("%s: null pointer", who);
+        return -1;
+    }
+    if (B < 1 || n < 1 || n > PRP_MAX_SIDE * PRP_MAX_SIDE || D < 64 || D % 64 != 0 || D > 8192) {
+        dinoseg_set_error("%s: B = %d frames of n = %d cells, width D = %d (positive; D a multiple of 64 up to 8192)", who, B, n, D);
+        return -1;
+    }
+    if ((reinterpret_cast<uintptr_t>(planes) & 15) != 0) {
+        dinoseg_set_error("%s: planes must be 16-byte aligned", who);
+        return -1;
+    }
+    const long long rows = (long long)B * n;
+    if (rows > (1ll << 31) - 4) {
+        dinoseg_set_error("%s: B n = %lld rows exceed the launch range", who, rows);
+        return -1;
+    }
+    hipLaunchKernelGGL(normalize_tokens_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, tokens, rows, n, D,
+                       reinterpret_cast<uint16_t*>(planes));
+    DSEG_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_label_cells(const void* labels, int mask_kind, int OH, int OW, int hp, int wp, int C, float* seg, hipStream_t s) {
+    const char* who = "dinoseg_op_label_cells";
+    if (!labels || !seg) {
+        dinoseg_set_error("%s: null pointer", who);
+        return -1;
+    }
+    if (mask_kind != 0 && mask_kind != 1) {
+        dinoseg_set_error("%s: mask kind %d (0 = uint8, 1 = int64)", who, mask_kind);
+        return -1;
+    }
+    if (C < 1 || C > 256) {
+        dinoseg_set_error("%s: C = %d classes (1 <= C <= 256)", who, C);
+        return -1;
+    }
+    if (prp_grid_check(who, hp, wp)) return -1;
+    if (OH < hp || OW < wp || OH > (1 << 20) || OW > (1 << 20)) {
+        dinoseg_set_error("%s: labels of %d x %d for a grid of %d x %d (OH >= hp, OW >= wp, each side <= 2^20)", who, OH, OW, hp, wp);
+        return -1;
+    }
+    hipLaunchKernelGGL(label_cells_kernel, dim3((unsigned)((hp * wp + 3) / 4)), dim3(256), 0, s, labels, mask_kind, OH, OW, hp, wp, C, seg);
+    DSEG_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+long long propagate_scratch_bytes(int hp, int wp, int n_ctx, int k) {
+    if (hp < 1 || wp < 1 || hp > PRP_MAX_SIDE || wp > PRP_MAX_SIDE || n_ctx < 1 || n_ctx > DINOSEG_PROPAGATE_MAX_CONTEXT || k < 1 ||
+        k > DINOSEG_PROPAGATE_MAX_K)
+        return -1;
+    return (long long)n_ctx * hp * wp * k * 8;                          // fp32 scores, then int32 indices, [n_ctx][n][k] each
+}
+
+int launch_propagate(const void* target_planes, const void* const* ctx_planes, const float* const* ctx_segs, int n_ctx, int hp, int wp,
+                     int D, int C, int radius, int k, double tau, float* seg_out, int32_t* topk_idx, float* topk_w, void* scratch,
+                     hipStream_t s) {
+    const char* who = "dinoseg_op_propagate";
+    if (n_ctx < 1 || n_ctx > DINOSEG_PROPAGATE_MAX_CONTEXT) {
+        dinoseg_set_error("%s: %d context frames (1 <= n_ctx <= %d)", who, n_ctx, DINOSEG_PROPAGATE_MAX_CONTEXT);
+        return -1;
+    }
+    if (!target_planes || !ctx_planes || !ctx_segs || !seg_out || !scratch) {
+        dinoseg_set_error("%s: null pointer (target planes, the two context tables, seg_out and scratch are required)", who);
+        return -1;
+    }
+    PrpCtx ctx = {};
+    for (int i = 0; i < n_ctx; ++i) {
+        if (!ctx_planes[i] || !ctx_segs[i]) {
+            dinoseg_set_error("%s: null planes or seg of context frame %d", who, i);
+            return -1;
+        }
+        if ((reinterpret_cast<uintptr_t>(ctx_planes[i]) & 15) != 0) {
+            dinoseg_set_error("%s: the planes of context frame %d are not 16-byte aligned", who, i);
+            return -1;
+        }
+        ctx.planes[i] = reinterpret_cast<const uint16_t*>(ctx_planes[i]);
+        ctx.segs[i] = ctx_segs[i];
+    }
+    if ((reinterpret_cast<uintptr_t>(target_planes) & 15) != 0 || (reinterpret_cast<uintptr_t>(scratch) & 3) != 0) {
+        dinoseg_set_error("%s: target planes must be 16-byte aligned, scratch 4-byte aligned", who);
+        return -1;
+    }
+    if (prp_grid_check(who, hp, wp)) return -1;
+    if (D < 64 || D % 64 != 0 || D > 8192) {
+        dinoseg_set_error("%s: width D = %d (a multiple of 64 up to 8192)", who, D);
+        return -1;
+    }
+    if (C < 1 || C > 256) {
+        dinoseg_set_error("%s: C = %d classes (1 <= C <= 256)", who, C);
+        return -1;
+    }
+    if (k < 1 || k > DINOSEG_PROPAGATE_MAX_K) {
+        dinoseg_set_error("%s: k = %d (1 <= k <= %d)", who, k, DINOSEG_PROPAGATE_MAX_K);
+        return -1;
+    }
+    if (radius < 0) {
+        dinoseg_set_error("%s: radius %d (>= 0)", who, radius);
+        return -1;
+    }
+    if (!(std::isfinite(tau) && tau > 0.0)) {
+        dinoseg_set_error("%s: temperature %g (finite and positive)", who, tau);
+        return -1;
+    }
+    const float a = (float)(1.4426950408889634074 / tau);
+    if (!std::isfinite(a)) {
+        dinoseg_set_error("%s: temperature %g is too small (log2(e) / tau exceeds fp32)", who, tau);
+        return -1;
+    }
+    const int n = hp * wp;
+    const int R = radius > PRP_MAX_SIDE ? PRP_MAX_SIDE : radius;         // (beyond the grid's side the window is the whole grid)
+    const int tiles_x = (wp + PRP_TILE - 1) / PRP_TILE, tiles_y = (hp + PRP_TILE - 1) / PRP_TILE;
+    float* cand_s = reinterpret_cast<float*>(scratch);
+    int* cand_g = reinterpret_cast<int*>(cand_s + (size_t)n_ctx * n * k);
+    const size_t lds = PRP_STAGE + (size_t)k * 2048;
+    hipLaunchKernelGGL(propagate_scores_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n_ctx), dim3(256), lds, s,
+                       reinterpret_cast<const uint16_t*>(target_planes), ctx, hp, wp, D, R, k, tiles_x, cand_s, cand_g);
+    DSEG_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(propagate_merge_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, cand_s, cand_g, ctx, n, n_ctx, k, C, a,
+                       seg_out, topk_idx, topk_w);
+    DSEG_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // namespace dseg

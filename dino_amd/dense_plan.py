@@ -215,3 +215,93 @@ def dense_mode(scales=None, flip: bool = False, window=None, stride=None, guided
     if scales is not None:
         return DenseMode("multiscale", (tuple(scales), bool(flip)))
     return DenseMode("bilinear")
+
+
+# ---- video label propagation (include/dinoseg.h: dinoseg_op_propagate) ----
+PROPAGATE_MAX_CONTEXT = 16     # context frames of one target frame: frame 0 and up to 15 queued ones
+PROPAGATE_MAX_K = 16
+PROPAGATE_MAX_CLASSES = 256
+
+
+def context_frames(t: int, n_context: int) -> List[int]:
+    """The context list of target frame ``t >= 1``: frame 0 first, then the last ``min(t - 1, n_context)`` frames before ``t``,
+    oldest first (frame 0 never enters the queue): t = 1 -> [0]; t = 2 -> [0, 1]; t = 9, n_context = 7 -> [0, 2 .. 8]."""
+    t, n_context = int(t), int(n_context)
+    if t < 1 or not 0 <= n_context <= PROPAGATE_MAX_CONTEXT - 1:
+        raise ValueError(f"context_frames: target frame {t} (>= 1), n_context {n_context} (0 .. {PROPAGATE_MAX_CONTEXT - 1})")
+    return [0] + list(range(max(1, t - n_context), t))
+
+
+class PropagatePlan(NamedTuple):
+    """What a propagation call was asked for, validated: the frames' layout, the patch grid, the seed's kind ("labels": integer
+    pixel labels [OH0, OW0]; "soft": fp32 [n, C]), the rule's parameters and the output size."""
+    kind: int
+    T: int
+    H: int
+    W: int
+    hp: int
+    wp: int
+    C: int
+    seed: str
+    n_context: int
+    radius: int
+    topk: int
+    temperature: float
+    OH: int
+    OW: int
+    chunk: int
+
+
+def _int_in(v, lo: int, hi: int, what: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"{what} must be an integer in {lo}..{hi}, got {v!r}")
+    return int(v)
+
+
+def propagate_plan(patch: int, frames: torch.Tensor, first, n_classes=None, n_context=7, radius=12, topk=5, temperature=0.1,
+                   size=None, chunk=32) -> PropagatePlan:
+    """The shape and parameter checks of ``DINOSeg.propagate`` / ``LabelPropagator`` without a device.  ``frames`` is the clip
+    (uint8 [T,H,W,3] or fp32 [T,3,H,W]; the propagator passes its first frame as a clip of one); ``first`` the seed of frame 0:
+    integer pixel labels [OH0, OW0] at least as large as the patch grid (``n_classes`` required) or a soft fp32 [n, C].
+    ``radius=None`` is the whole frame.  Every ``ValueError`` is raised here, before any device use."""
+    if not isinstance(frames, torch.Tensor):
+        raise ValueError(f"expected the clip as a tensor, uint8 [T,H,W,3] or fp32 [T,3,H,W], got {type(frames).__name__}")
+    kind, T, H, W = frame_layout(frames, patch, multiple=True, one_patch=True, non_empty=True)
+    hp, wp = H // patch, W // patch
+    n = hp * wp
+    n_context = _int_in(n_context, 0, PROPAGATE_MAX_CONTEXT - 1, "n_context")
+    topk = _int_in(topk, 1, PROPAGATE_MAX_K, "topk")
+    chunk = _int_in(chunk, 1, 1 << 20, "chunk")
+    if radius is None:
+        radius = max(hp, wp)
+    radius = _int_in(radius, 0, 1 << 30, "radius")
+    try:
+        temperature = float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError(f"temperature must be a positive number, got {temperature!r}") from None
+    if not (math.isfinite(temperature) and temperature > 0.0):
+        raise ValueError(f"temperature must be finite and positive, got {temperature}")
+    if n_classes is not None:
+        n_classes = _int_in(n_classes, 1, PROPAGATE_MAX_CLASSES, "n_classes")
+    if not isinstance(first, torch.Tensor) or first.dim() != 2 or first.dtype == torch.bool:
+        raise ValueError("first must be integer pixel labels [OH0, OW0] or a soft fp32 seed [n, C], got "
+                         f"{getattr(first, 'dtype', type(first).__name__)} {tuple(getattr(first, 'shape', ()))}")
+    if first.is_floating_point():
+        if first.shape[0] != n or not 1 <= first.shape[1] <= PROPAGATE_MAX_CLASSES:
+            raise ValueError(f"a soft seed is [n = {n}, C] with 1 <= C <= {PROPAGATE_MAX_CLASSES}, got {tuple(first.shape)}")
+        C, seed = int(first.shape[1]), "soft"
+        if n_classes is not None and n_classes != C:
+            raise ValueError(f"n_classes = {n_classes} differs from the soft seed's {C} columns")
+    else:
+        if n_classes is None:
+            raise ValueError("integer pixel labels need n_classes")
+        if first.shape[0] < hp or first.shape[1] < wp:
+            raise ValueError(f"pixel labels of {tuple(first.shape)} are smaller than the patch grid {(hp, wp)}")
+        C, seed = n_classes, "labels"
+    try:
+        OH, OW = out_size(size, (H, W))
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be a pair (OH, OW), got {size!r}") from None
+    if OH < hp or OW < wp:
+        raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(hp, wp)}")
+    return PropagatePlan(kind, int(T), int(H), int(W), hp, wp, C, seed, n_context, radius, topk, temperature, OH, OW, chunk)

@@ -18,8 +18,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import capi
-from .dense_plan import (_pair, dense_mode, frame_layout, guide_plan, guided_params, label_size, multiscale_plan, out_size,
-                         resolution_message, view_sizes, window_origins, window_plan)  # noqa: F401  (view_sizes, window_origins: re-exported)
+from .dense_plan import (_pair, context_frames, dense_mode, frame_layout, guide_plan, guided_params, label_size, multiscale_plan,
+                         out_size, propagate_plan, resolution_message, view_sizes, window_origins, window_plan)  # noqa: F401  (view_sizes, window_origins: re-exported)
 from .preprocess import resize_linear_u8
 from .weights import VIT_B8, VIT_B16, VIT_S8, VIT_S16, ViTConfig
 
@@ -749,6 +749,40 @@ class DINOSeg(nn.Module):
         ``ValueError`` before any forward runs.  Inference only."""
         return self._windows(x, window, stride, want_logp, max_windows)[:2]
 
+    # ---- video label propagation from patch features (csrc/propagate.hip) ----
+    @torch.no_grad()
+    def propagate(self, frames: torch.Tensor, first: torch.Tensor, n_classes: Optional[int] = None, n_context: int = 7,
+                  radius: Optional[int] = 12, topk: int = 5, temperature: float = 0.1, size=None, n_blocks: int = 0,
+                  chunk: int = 32, want_seg: bool = False):
+        """Label propagation through a clip (the semi-supervised video segmentation protocol of the DINO paper): ``frames`` uint8
+        [T,H,W,3] or fp32 [T,3,H,W], ``first`` the labels of frame 0 -> (labels int32 [T,OH,OW], seg fp32 [T,n,C] or None).
+        ``first`` is either integer pixel labels [OH0, OW0] (any size at least the patch grid; ``n_classes`` required; a label
+        outside [0, n_classes) such as 255 counts for no class) or a soft fp32 [n, C] map over the patch grid, for instance
+        ``exp(forward(x0))``; C is independent of the model's head, and no head weight is used.  Every cell of frame t >= 1 takes
+        the ``topk`` most similar cells (cosine of the final-norm patch tokens after ``n_blocks`` blocks, 0 = all) within
+        ``radius`` cells of itself (``None``: the whole frame) over frame 0 and the ``n_context`` frames before t, and averages
+        their soft label rows with weights ``exp((s - s_max) / temperature)``; that soft map is frame t's context entry, and its
+        bilinear enlargement to ``size`` (default the frames' own) with the first maximum gives the frame's labels (the rule:
+        include/dinoseg.h, dinoseg_op_propagate).  The [n_context, n, n] affinity is never formed.  The backbone runs in batches
+        of ``chunk`` frames; only the small propagate launches are sequential.  ``LabelPropagator`` is the streaming form.
+        Inference only."""
+        plan = propagate_plan(self.cfg.patch, frames, first, n_classes, n_context, radius, topk, temperature, size, chunk)
+        if not 0 <= n_blocks <= self.cfg.n_blocks:
+            raise ValueError(f"intermediate must be in [0, {self.cfg.n_blocks}]")
+        self._require_gpu()
+        x = self._to_device(frames, plan.kind)
+        runner = _PropagateRunner(self, plan)
+        labels = torch.empty((plan.T, plan.OH, plan.OW), dtype=torch.int32, device=self.device)
+        seg = torch.empty((plan.T, plan.hp * plan.wp, plan.C), dtype=torch.float32, device=self.device) if want_seg else None
+        for c0 in range(0, plan.T, plan.chunk):
+            tokens = self.features(x[c0:c0 + plan.chunk], n_blocks)
+            for i in range(tokens.shape[0]):
+                t = c0 + i
+                seg_t = runner.seed(tokens[i:i + 1], first, labels[t]) if t == 0 else runner.step(tokens[i:i + 1], labels[t])
+                if want_seg:
+                    seg[t].copy_(seg_t)
+        return labels, seg
+
     def predict_dense(self, img, size=None, scales=None, flip: bool = False, window=None, stride=None, guided=None) -> np.ndarray:
         """The pixel-resolution sibling of ``predict()``: the image (PIL.Image or HxWx3 uint8 array) is resized to r x r on the
         device exactly as ``predict()`` does, the log-probabilities are upsampled to ``size`` (default: the IMAGE's own (rows,
@@ -1426,3 +1460,120 @@ class DINOSeg(nn.Module):
     def load_from_checkpoint(cls, checkpoint_path, map_location=None, **overrides):
         from .ckpt import load_checkpoint
         return load_checkpoint(cls, checkpoint_path, map_location=map_location, **overrides)
+
+
+# --------------------------------------------------------------------------- video label propagation
+class _PropagateRunner:
+    """The launches of label propagation for one clip or stream, shared by ``DINOSeg.propagate`` and ``LabelPropagator``: a device
+    ring of plane and seg slots (frame 0's, ``n_context`` queued frames' and the one the target frame is written into, which then
+    takes the oldest queued frame's place), the scratch, and the two host pointer tables of ``dinoseg_op_propagate``."""
+
+    def __init__(self, model: "DINOSeg", plan):
+        self.model, self.plan = model, plan
+        n, D, dev = plan.hp * plan.wp, model.cfg.embed_dim, model.device
+        slots = plan.n_context + 2
+        self.planes = torch.empty((slots, 2, n, D), dtype=torch.float16, device=dev)
+        self.segs = torch.empty((slots, n, plan.C), dtype=torch.float32, device=dev)
+        lib = capi.lib()
+        nbytes = lib.dinoseg_propagate_scratch_bytes(plan.hp, plan.wp, plan.n_context + 1, plan.topk)
+        if nbytes < 0:
+            raise capi.DinosegError(f"dinoseg_propagate_scratch_bytes refused grid {plan.hp}x{plan.wp}, {plan.n_context + 1} context "
+                                    f"frames, k = {plan.topk}")
+        self.scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        self.queue: list = []                       # slots of the queued frames, oldest first
+        self.free = list(range(1, slots))           # slot 0 is frame 0's
+        self.t = 0
+
+    def _labels(self, seg: torch.Tensor, labels_out: torch.Tensor) -> None:
+        p = self.plan
+        capi.check(capi.lib().dinoseg_op_upsample_argmax(seg.data_ptr(), 1, p.hp, p.wp, p.C, p.OH, p.OW, labels_out.data_ptr(), None,
+                                                         self.model._stream()))
+
+    def _normalize(self, tokens: torch.Tensor, slot: int) -> None:
+        p = self.plan
+        capi.check(capi.lib().dinoseg_op_normalize_tokens(tokens.data_ptr(), 1, p.hp * p.wp, self.model.cfg.embed_dim,
+                                                          self.planes[slot].data_ptr(), self.model._stream()))
+
+    def seed(self, tokens: torch.Tensor, first: torch.Tensor, labels_out: torch.Tensor) -> torch.Tensor:
+        """Frame 0: its planes, its seg from ``first`` (slot 0) and its labels; returns the seg [n, C] (the slot itself)."""
+        p, dev = self.plan, self.model.device
+        self._normalize(tokens, 0)
+        if p.seed == "soft":
+            self.segs[0].copy_(first.to(device=dev, dtype=torch.float32))
+        else:
+            kind = 0 if first.dtype == torch.uint8 else 1
+            y = first.to(device=dev, dtype=torch.uint8 if kind == 0 else torch.int64).contiguous()
+            capi.check(capi.lib().dinoseg_op_label_cells(y.data_ptr(), kind, y.shape[0], y.shape[1], p.hp, p.wp, p.C,
+                                                         self.segs[0].data_ptr(), self.model._stream()))
+        self._labels(self.segs[0], labels_out)
+        self.t = 1
+        return self.segs[0]
+
+    def step(self, tokens: torch.Tensor, labels_out: torch.Tensor) -> torch.Tensor:
+        """Target frame ``self.t`` from its context (``context_frames``): returns its seg [n, C], a ring slot that stays valid
+        for the next ``n_context`` steps."""
+        p = self.plan
+        slot = self.free.pop()
+        self._normalize(tokens, slot)
+        ctx = [0] + self.queue                      # frame 0, then the queued frames oldest first
+        assert len(ctx) == len(context_frames(self.t, p.n_context))
+        planes = (C.c_void_p * len(ctx))(*[self.planes[s].data_ptr() for s in ctx])
+        segs = (C.c_void_p * len(ctx))(*[self.segs[s].data_ptr() for s in ctx])
+        capi.check(capi.lib().dinoseg_op_propagate(self.planes[slot].data_ptr(), planes, segs, len(ctx), p.hp, p.wp,
+                                                   self.model.cfg.embed_dim, p.C, p.radius, p.topk, p.temperature,
+                                                   self.segs[slot].data_ptr(), None, None, self.scratch.data_ptr(),
+                                                   self.model._stream()))
+        self._labels(self.segs[slot], labels_out)
+        if p.n_context > 0:
+            self.queue.append(slot)
+            if len(self.queue) > p.n_context:
+                self.free.append(self.queue.pop(0))
+        else:
+            self.free.append(slot)
+        self.t += 1
+        return self.segs[slot]
+
+
+class LabelPropagator:
+    """The streaming form of ``DINOSeg.propagate`` for a camera: ``LabelPropagator(model, first_frame, first, ...)`` seeds frame 0
+    (``first_frame`` uint8 [H,W,3] or fp32 [3,H,W], or the same with a leading batch of one; ``first`` as in ``propagate``), then
+    ``step(frame) -> (labels int32 [OH,OW], seg fp32 [n,C] or None)`` labels every later frame from frame 0 and the ``n_context``
+    frames before it.  Frame 0's own labels are ``labels0``.  Device memory: a ring of ``n_context + 2`` plane and seg slots (the
+    extra one receives the target frame) and the scratch of ``dinoseg_op_propagate``; a step allocates its frame's tokens and its
+    outputs.  Frame by frame this gives what ``propagate(chunk=1)`` gives, bit for bit.  Inference only."""
+
+    def __init__(self, model: DINOSeg, first_frame: torch.Tensor, first: torch.Tensor, n_classes: Optional[int] = None,
+                 n_context: int = 7, radius: Optional[int] = 12, topk: int = 5, temperature: float = 0.1, size=None,
+                 n_blocks: int = 0, want_seg: bool = False):
+        x = self._one(first_frame)
+        self.plan = propagate_plan(model.cfg.patch, x, first, n_classes, n_context, radius, topk, temperature, size, 1)
+        if not 0 <= n_blocks <= model.cfg.n_blocks:
+            raise ValueError(f"intermediate must be in [0, {model.cfg.n_blocks}]")
+        model._require_gpu()
+        self.model, self.n_blocks, self.want_seg = model, n_blocks, want_seg
+        with torch.no_grad():
+            self._runner = _PropagateRunner(model, self.plan)
+            self.labels0 = torch.empty((self.plan.OH, self.plan.OW), dtype=torch.int32, device=model.device)
+            seg0 = self._runner.seed(model.features(model._to_device(x, self.plan.kind), n_blocks), first, self.labels0)
+            self.seg0 = seg0.clone() if want_seg else None
+
+    @staticmethod
+    def _one(frame) -> torch.Tensor:
+        if not isinstance(frame, torch.Tensor) or frame.dim() not in (3, 4):
+            raise ValueError(f"expected one frame, uint8 [H,W,3] or fp32 [3,H,W], got {getattr(frame, 'shape', type(frame).__name__)}")
+        x = frame[None] if frame.dim() == 3 else frame
+        if x.shape[0] != 1:
+            raise ValueError(f"expected one frame, got a batch of {x.shape[0]}")
+        return x
+
+    @torch.no_grad()
+    def step(self, frame: torch.Tensor):
+        p = self.plan
+        x = self._one(frame)
+        kind, _, H, W = frame_layout(x, self.model.cfg.patch, multiple=True, one_patch=True)
+        if (kind, H, W) != (p.kind, p.H, p.W):
+            raise ValueError(f"the stream's frames are {'uint8' if p.kind == capi.INPUT_U8_HWC else 'fp32'} {p.H}x{p.W}, got "
+                             f"{x.dtype} {H}x{W}")
+        labels = torch.empty((p.OH, p.OW), dtype=torch.int32, device=self.model.device)
+        seg = self._runner.step(self.model.features(self.model._to_device(x, kind), self.n_blocks), labels)
+        return labels, (seg.clone() if self.want_seg else None)

@@ -378,6 +378,61 @@ int dinoseg_op_augment(const uint8_t* frames, const void* masks, int32_t mask_ki
                        const dinoseg_augment_frame* table, int32_t max_radius, int32_t OH, int32_t OW, int32_t out_kind, void* out,
                        int64_t* pixel_labels, int64_t* patch_labels, int32_t patch, float* scratch, void* stream);
 
+/* ---- video label propagation from patch features (the semi-supervised video segmentation protocol of the DINO paper: one labelled
+ * frame, every later frame takes its labels from the nearest patch features of the frames before it), without the [n_ctx, n, n]
+ * affinity.  No reference counterpart: the reference labels one frame at a time.  propagate.hip.
+ *
+ * Notation: hp x wp the patch grid, n = hp wp cells row-major, D the embedding width (a multiple of 64), C the number of label
+ * classes, 1 .. 256, independent of the model's head; R >= 0 the neighbourhood radius in cells, k in 1 .. 16, tau > 0 the temperature.
+ * Context list of target frame t >= 1 (the caller's, DINOSeg.propagate): frame 0 first, then the last min(t - 1, n_context) frames
+ * before t, oldest first: t = 1 -> [0]; t = 2 -> [0, 1]; t = 9, n_context = 7 -> [0, 2 .. 8].  Frame 0 never enters the queue; at most
+ * 1 + n_context <= 16 context frames.
+ *
+ * 1. Features (dinoseg_op_normalize_tokens).  The patch tokens of dinoseg_features_hw without the CLS row; f^ = f / max(||f||_2, 1e-12).
+ *    The operand planes hold 2^10 f^ as fp16 hi + lo (hi = fp16(v), lo = fp16(v - hi), the norm and the quotient in fp64):
+ *    [B][2][n][D] 16-bit elements, hi plane then lo plane per frame.
+ * 2. Candidates.  The candidates of query cell q = (r, c) are the cells j = (r', c') of every context frame with |r' - r| <= R and
+ *    |c' - c| <= R inside the grid (integer test per pair).  Candidate j of the ci-th context frame has the global index g = ci n + j.
+ *    Its score s = <f^_t[q], f^_ctx[j]> is accumulated in fp32 from the planes (lo.hi + hi.lo + hi.hi, D in ascending slices of 64) and
+ *    is a function of the two rows alone, not of where the pair sits in a tile: bit-equal rows give bit-equal scores.  A score of -0 is
+ *    taken as +0.  |s - the fp64 value| <= (D + 16) 2^-24.
+ * 3. Selection.  The K' = min(k, #candidates) candidates that come first in the total order (score descending, then g ascending):
+ *    rank 0 .. K'-1.  The order is total, so the result does not depend on how the lists are merged.
+ * 4. Weights.  w_i = exp2((s_i - s_0) a) in fp32, a = log2(e) / tau computed in fp64 on the host and rounded once to fp32;
+ *    W = sum w_i in rank order.
+ * 5. Value.  V[c] = (sum_i w_i seg[g_i, c]) (1 / W), by fmaf in rank order from 0, the reciprocal (correctly rounded) taken once;
+ *    seg_out[q, :] = V, fp32 [n, C].  This soft map, not its argmax, is what later frames use as context.
+ * 6. Pixel labels: dinoseg_op_upsample_argmax applied to seg_out, unchanged.
+ *
+ * The seed (dinoseg_op_label_cells): integer pixel labels [OH, OW] (OH >= hp, OW >= wp; mask_kind 0 = uint8, 1 = int64, as
+ * dinoseg_op_augment) -> seg fp32 [n, C].  Pixel (y, x) belongs to cell ((y hp) / OH, (x wp) / OW), the nearest rule of
+ * dinoseg_op_guide_cells; seg[cell, c] = float(count_c) / float(n_cell) with integer counts (no atomics); a pixel whose label is
+ * outside [0, C) (255, -100) counts in n_cell and in no class.
+ *
+ * In exact arithmetic and without ties this is the DINO script's computation (exp(bmm / 0.1) times the neighbourhood mask, topk over
+ * all context candidates, renormalise, segs @ aff; defaults n_context 7, R 12, k 5, tau 0.1).  Deviations: exact ties at the cut keep
+ * exactly k candidates by index (the script keeps the whole tied group); the script's per-class min-max rescale of the enlarged map is
+ * not done; the enlargement uses this library's exact coordinates.
+ *
+ * dinoseg_op_propagate: steps 2 - 5 for one target frame in two launches (per (8 x 8 query tile, context frame) the scores on MFMAs
+ * and a per-query list of k in LDS; then the merge of the context frames' lists, the weights and the k gathers).  ctx_planes /
+ * ctx_segs are HOST arrays of n_ctx device pointers (planes of step 1, seg fp32 [n, C]); they travel to the kernels by value.
+ * scratch: dinoseg_propagate_scratch_bytes(hp, wp, n_ctx, k) bytes of device memory (8 n_ctx n k; host only, -1 for refusable
+ * arguments).  Optional debug outputs: topk_idx int32 [n, k] (g in rank order, -1 beyond K') and topk_w fp32 [n, k] (w_i / W, 0
+ * beyond K').  R above the grid's sides is the whole grid.  No atomics, no synchronisation between workgroups; two runs agree bit for
+ * bit.  Refused on the host (-1, the message names the entry) before anything is launched: null pointers; C outside 1 .. 256; k
+ * outside 1 .. 16; n_ctx outside 1 .. 16; R < 0; tau not finite or not positive; non-positive sizes or grid sides above 4096; D not a
+ * multiple of 64 or above 8192; planes not 16-byte aligned.  Stream-ordered, no host synchronisation, no allocation. */
+#define DINOSEG_PROPAGATE_MAX_CONTEXT 16
+#define DINOSEG_PROPAGATE_MAX_K 16
+int dinoseg_op_normalize_tokens(const float* tokens, int32_t B, int32_t n, int32_t D, void* planes, void* stream);
+int dinoseg_op_label_cells(const void* labels, int32_t mask_kind, int32_t OH, int32_t OW, int32_t hp, int32_t wp, int32_t C, float* seg,
+                           void* stream);
+int64_t dinoseg_propagate_scratch_bytes(int32_t hp, int32_t wp, int32_t n_ctx, int32_t k);
+int dinoseg_op_propagate(const void* target_planes, const void* const* ctx_planes, const float* const* ctx_segs, int32_t n_ctx,
+                         int32_t hp, int32_t wp, int32_t D, int32_t C, int32_t radius, int32_t k, double tau, float* seg_out,
+                         int32_t* topk_idx, float* topk_w, void* scratch, void* stream);
+
 /* ---- fine-tune step (replaces DINOSeg.training_step + autograd + optimizer.step, pl_torch_modules.py:258-268) ---- */
 
 /* Bind (or, with NULL, unbind) the fp32 gradient buffer of a parameter, same shape as the bound weight.  A parameter
