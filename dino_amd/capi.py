@@ -168,6 +168,12 @@ SIGNATURES = {
     "dinoseg_op_label_cells": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _vp]),
     "dinoseg_propagate_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "dinoseg_op_propagate": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _fp, _fp, _fp, _vp, _vp]),
+    # spherical k-means over patch features: the scratch size (host only), centroid rows -> unit rows + planes, one assignment pass
+    # (scores on request, objective and moved slots), one centroid update
+    "dinoseg_kmeans_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "dinoseg_op_kmeans_init": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _vp, _vp]),
+    "dinoseg_op_kmeans_assign": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _fp, _fp, _fp, _vp, _vp, _vp]),
+    "dinoseg_op_kmeans_update": (C.c_int, [_vp, _i32, _i32, _vp, _fp, _vp, _i32, _i32, _fp, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

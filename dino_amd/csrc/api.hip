@@ -662,6 +662,27 @@ extern "C" int dinoseg_op_propagate(const void* target_planes, const void* const
                             reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int64_t dinoseg_kmeans_scratch_bytes(int32_t B, int32_t n, int32_t K, int32_t D) { return kmeans_scratch_bytes(B, n, K, D); }
+
+extern "C" int dinoseg_op_kmeans_init(const float* rows, int32_t K, int32_t D, int32_t normalize, float* centroids, void* planes,
+                                      void* stream) {
+    return launch_kmeans_init(rows, K, D, normalize, centroids, planes, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_kmeans_assign(const void* points, int32_t B, int32_t n, const void* centroid_planes, int32_t K, int32_t D,
+                                        const int32_t* prev_assign, int32_t* assign, float* best, float* scores, float* objective,
+                                        int32_t* moved, void* scratch, void* stream) {
+    return launch_kmeans_assign(points, B, n, centroid_planes, K, D, prev_assign, assign, best, scores, objective, moved, scratch,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_kmeans_update(const void* points, int32_t B, int32_t n, const int32_t* assign, const float* prev_centroids,
+                                        const void* prev_planes, int32_t K, int32_t D, float* centroids, void* planes, int32_t* counts,
+                                        void* scratch, void* stream) {
+    return launch_kmeans_update(points, B, n, assign, prev_centroids, prev_planes, K, D, centroids, planes, counts, scratch,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int dinoseg_op_confusion(const int32_t* pred, const int64_t* gt, int64_t n, int32_t n_classes, int64_t* cm, void* stream) {
     return launch_confusion(pred, gt, n, n_classes, cm, reinterpret_cast<hipStream_t>(stream));
 }

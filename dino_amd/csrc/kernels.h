@@ -381,6 +381,19 @@ int launch_propagate(const void* target_planes, const void* const* ctx_planes, c
                      int D, int C, int radius, int k, double tau, float* seg_out, int32_t* topk_idx, float* topk_w, void* scratch,
                      hipStream_t s);
 
+// Spherical k-means over patch features (kmeans.hip; the rule: include/dinoseg.h, dinoseg_op_kmeans_assign).  Points are the planes of
+// launch_normalize_tokens for B frames of n cells, clustered jointly; centroids are fp32 [K, D] rows plus planes [2][K][D].
+// launch_kmeans_init: fp32 rows -> (unit) fp32 rows and their planes.  launch_kmeans_assign: the assign launch (scores on MFMAs, the
+// running pair in registers, scores [N, K] on request) and, when a record slot is given, the one-workgroup records launch.
+// launch_kmeans_update: the partial launch (one workgroup per (range, cluster), members gathered in index order) and the finalize launch
+// (ranges in range order, fp64 norm, row and planes).  scratch: kmeans_scratch_bytes (-1 for refusable arguments).  No atomics.
+long long kmeans_scratch_bytes(int B, int n, int K, int D);
+int launch_kmeans_init(const float* rows, int K, int D, int normalize, float* centroids, void* planes, hipStream_t s);
+int launch_kmeans_assign(const void* points, int B, int n, const void* centroid_planes, int K, int D, const int32_t* prev_assign,
+                         int32_t* assign, float* best, float* scores, float* objective, int32_t* moved, void* scratch, hipStream_t s);
+int launch_kmeans_update(const void* points, int B, int n, const int32_t* assign, const float* prev_centroids, const void* prev_planes,
+                         int K, int D, float* centroids, void* planes, int32_t* counts, void* scratch, hipStream_t s);
+
 // ---- fine-tune step (train.hip, attention_bwd.hip) ----
 struct AttnBwdParams {
     const bf16_t* q; const bf16_t* k; const bf16_t* v; long qkv_plane;   // forward operands [planes][B,H,npad,64]

@@ -305,3 +305,80 @@ def propagate_plan(patch: int, frames: torch.Tensor, first, n_classes=None, n_co
     if OH < hp or OW < wp:
         raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(hp, wp)}")
     return PropagatePlan(kind, int(T), int(H), int(W), hp, wp, C, seed, n_context, radius, topk, temperature, OH, OW, chunk)
+
+
+# ---- unsupervised segmentation: spherical k-means over patch features (include/dinoseg.h: dinoseg_op_kmeans_assign) ----
+KMEANS_MAX_K = 256             # the class limit of dinoseg_op_upsample_argmax
+
+
+class KMeansPlan(NamedTuple):
+    """What a clustering call was asked for, validated: the frames' layout, the patch grid, the number of points N = B n, the rule's
+    parameters, how the centroids start ("sample": K distinct points drawn on the host; "rows": the caller's fp32 [k, D]) and the
+    output size."""
+    kind: int
+    B: int
+    H: int
+    W: int
+    hp: int
+    wp: int
+    N: int
+    k: int
+    iters: int
+    init: str
+    seed: int
+    n_init: int
+    OH: int
+    OW: int
+    chunk: int
+
+
+def sample_indices(N: int, k: int, seed: int) -> torch.Tensor:
+    """The K distinct point indices of ``init="sample"``: the head of a seeded host permutation (the library has no device random
+    numbers), int64 [k]."""
+    N, k = int(N), int(k)
+    if not 1 <= k <= N:
+        raise ValueError(f"init='sample' draws k = {k} distinct points out of N = {N}")
+    return torch.randperm(N, generator=torch.Generator().manual_seed(int(seed)))[:k]
+
+
+def _centroid_rows(rows, k, embed_dim: int, what: str) -> int:
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.dtype != torch.float32 or rows.shape[1] != embed_dim or \
+            not 1 <= rows.shape[0] <= KMEANS_MAX_K or (k is not None and rows.shape[0] != k):
+        want = "1.." + str(KMEANS_MAX_K) if k is None else str(k)
+        raise ValueError(f"{what} must be {'the string sample or ' if what == 'init' else ''}fp32 rows [{want}, {embed_dim}], got "
+                         f"{getattr(rows, 'dtype', type(rows).__name__)} {tuple(getattr(rows, 'shape', ()))}")
+    return int(rows.shape[0])
+
+
+def kmeans_plan(patch: int, embed_dim: int, x: torch.Tensor, k, iters=10, init="sample", seed=0, n_init=1, size=None,
+                chunk=32) -> KMeansPlan:
+    """The shape and parameter checks of ``DINOSeg.cluster`` / ``DINOSeg.assign_clusters`` without a device.  ``x`` is the batch or clip
+    (uint8 [B,H,W,3] or fp32 [B,3,H,W], H and W multiples of the patch size); ``init`` is ``"sample"`` or fp32 rows [k, D].
+    ``assign_clusters`` passes its centroids as ``init`` with ``k=None`` and ``iters=0``.  Every ``ValueError`` is raised here, before
+    any device use."""
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"expected the frames as a tensor, uint8 [B,H,W,3] or fp32 [B,3,H,W], got {type(x).__name__}")
+    kind, B, H, W = frame_layout(x, patch, multiple=True, one_patch=True, non_empty=True)
+    hp, wp = H // patch, W // patch
+    N = int(B) * hp * wp
+    if k is not None:
+        k = _int_in(k, 1, KMEANS_MAX_K, "k")
+    iters = _int_in(iters, 0, 1 << 20, "iters")
+    n_init = _int_in(n_init, 1, 1 << 20, "n_init")
+    seed = _int_in(seed, -(1 << 62), 1 << 62, "seed")
+    chunk = _int_in(chunk, 1, 1 << 20, "chunk")
+    if isinstance(init, str):
+        if init != "sample" or k is None:
+            raise ValueError(f"init must be 'sample' or fp32 rows [k, {embed_dim}], got {init!r}")
+        if k > N:
+            raise ValueError(f"init='sample' draws k = {k} distinct points, but the frames have only N = {N} patch cells")
+        how = "sample"
+    else:
+        k, how = _centroid_rows(init, k, embed_dim, "init" if k is not None else "centroids"), "rows"
+    try:
+        OH, OW = out_size(size, (H, W))
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be a pair (OH, OW), got {size!r}") from None
+    if OH < hp or OW < wp:
+        raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(hp, wp)}")
+    return KMeansPlan(kind, int(B), int(H), int(W), hp, wp, N, k, iters, how, seed, n_init, OH, OW, chunk)

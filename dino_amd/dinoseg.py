@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import weakref
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -18,8 +18,9 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import capi
-from .dense_plan import (_pair, context_frames, dense_mode, frame_layout, guide_plan, guided_params, label_size, multiscale_plan,
-                         out_size, propagate_plan, resolution_message, view_sizes, window_origins, window_plan)  # noqa: F401  (view_sizes, window_origins: re-exported)
+from .dense_plan import (_pair, context_frames, dense_mode, frame_layout, guide_plan, guided_params, kmeans_plan, label_size,
+                         multiscale_plan, out_size, propagate_plan, resolution_message, sample_indices, view_sizes, window_origins,
+                         window_plan)  # noqa: F401  (view_sizes, window_origins: re-exported)
 from .preprocess import resize_linear_u8
 from .weights import VIT_B8, VIT_B16, VIT_S8, VIT_S16, ViTConfig
 
@@ -782,6 +783,80 @@ class DINOSeg(nn.Module):
                 if want_seg:
                     seg[t].copy_(seg_t)
         return labels, seg
+
+    # ---- unsupervised segmentation: spherical k-means over patch features (csrc/kmeans.hip) ----
+    def _point_planes(self, x: torch.Tensor, plan, n_blocks: int) -> torch.Tensor:
+        """The unit patch rows of every frame as fp16 hi + lo planes [B, 2, n, D]: the backbone in batches of ``plan.chunk``, each
+        batch normalised into its slice of one buffer."""
+        n, D = plan.hp * plan.wp, self.cfg.embed_dim
+        planes = torch.empty((plan.B, 2, n, D), dtype=torch.float16, device=self.device)
+        for c0 in range(0, plan.B, plan.chunk):
+            tokens = self.features(x[c0:c0 + plan.chunk], n_blocks)
+            capi.check(capi.lib().dinoseg_op_normalize_tokens(tokens.data_ptr(), tokens.shape[0], n, D, planes[c0:].data_ptr(),
+                                                              self._stream()))
+        return planes
+
+    def _cluster_labels(self, scores: torch.Tensor, plan) -> torch.Tensor:
+        labels = torch.empty((plan.B, plan.OH, plan.OW), dtype=torch.int32, device=self.device)
+        capi.check(capi.lib().dinoseg_op_upsample_argmax(scores.data_ptr(), plan.B, plan.hp, plan.wp, plan.k, plan.OH, plan.OW,
+                                                         labels.data_ptr(), None, self._stream()))
+        return labels
+
+    @torch.no_grad()
+    def cluster(self, x: torch.Tensor, k: int, iters: int = 10, init="sample", seed: int = 0, n_init: int = 1, size=None,
+                n_blocks: int = 0, chunk: int = 32, want_scores: bool = False) -> "ClusterResult":
+        """Unsupervised segmentation: spherical k-means over the patch tokens of a batch or clip (the k-means baseline of STEGO and
+        of "Deep ViT Features as Dense Visual Descriptors").  ``x`` uint8 [B,H,W,3] or fp32 [B,3,H,W], H and W multiples of the
+        patch size -> ``ClusterResult(labels int32 [B,OH,OW], centroids fp32 [k,D], counts int32 [k], objective fp32 [iters+1],
+        moved int32 [iters+1], scores fp32 [B,n,k] or None)``.  All B n cells are clustered jointly, so a cluster id means the same
+        thing in every frame.  Every cell goes to the centroid with the largest cosine (the lowest id on an exact tie); a centroid
+        becomes the unit row of the sum of its cells; an empty cluster keeps its centroid (the rule: include/dinoseg.h,
+        dinoseg_op_kmeans_assign).  ``init="sample"`` starts from ``k`` distinct cells drawn on the host from ``seed``; an fp32
+        [k, D] tensor starts from its rows, normalised.  ``iters`` (assign, update) pairs run without a host synchronisation and
+        without an early stop, then one final assignment against the final centroids gives the scores whose bilinear enlargement
+        to ``size`` (default the frames' own) with the first maximum is ``labels``; ``iters=0`` labels by the initial centroids.
+        ``objective[t]`` is the sum of the cells' best cosines in pass t, ``moved[t]`` the number of cells that changed cluster
+        (all of them in pass 0), ``counts`` the cluster sizes of the last update (zeros for ``iters=0``).  With ``n_init > 1`` the
+        runs use seeds ``seed, seed + 1, ...`` and the one with the largest final objective wins (the first on a tie).  No head
+        weight is used.  Inference only."""
+        plan = kmeans_plan(self.cfg.patch, self.cfg.embed_dim, x, k, iters, init, seed, n_init, size, chunk)
+        if not 0 <= n_blocks <= self.cfg.n_blocks:
+            raise ValueError(f"intermediate must be in [0, {self.cfg.n_blocks}]")
+        self._require_gpu()
+        planes = self._point_planes(self._to_device(x, plan.kind), plan, n_blocks)
+        runner = _KMeansRunner(self, plan, planes)
+        best = None
+        for r in range(plan.n_init):
+            if plan.init == "sample":
+                idx = sample_indices(plan.N, plan.k, plan.seed + r).to(self.device)
+                flat = planes.permute(0, 2, 1, 3).reshape(plan.N, 2, -1)[idx].float()        # the sampled points: (hi + lo) 2^-10
+                rows = ((flat[:, 0] + flat[:, 1]) * 2.0 ** -10).contiguous()
+            else:
+                rows = init.to(device=self.device, dtype=torch.float32).contiguous()
+            run = runner.run(rows)
+            final = float(run.objective[-1])                                                 # the run's one read of its records
+            if best is None or final > best[0]:
+                best = (final, run)
+        run = best[1]
+        labels = self._cluster_labels(run.scores, plan)
+        scores = run.scores.view(plan.B, plan.hp * plan.wp, plan.k) if want_scores else None
+        return ClusterResult(labels, run.centroids, run.counts, run.objective, run.moved, scores)
+
+    @torch.no_grad()
+    def assign_clusters(self, x: torch.Tensor, centroids: torch.Tensor, size=None, n_blocks: int = 0, want_scores: bool = False):
+        """The streaming form of ``cluster`` for a camera: frames ``x`` (as in ``cluster``) and unit centroids fp32 [k, D], as
+        ``cluster`` returns them -> (labels int32 [B,OH,OW], scores fp32 [B,n,k] or None).  Features, normalisation, one assignment
+        launch, the enlargement.  The centroids are taken as they are (not normalised again), so ``cluster``'s own centroids give
+        the labels of its final pass bit for bit.  Inference only."""
+        plan = kmeans_plan(self.cfg.patch, self.cfg.embed_dim, x, None, 0, centroids, 0, 1, size, max(int(x.shape[0]), 1))
+        if not 0 <= n_blocks <= self.cfg.n_blocks:
+            raise ValueError(f"intermediate must be in [0, {self.cfg.n_blocks}]")
+        self._require_gpu()
+        planes = self._point_planes(self._to_device(x, plan.kind), plan, n_blocks)
+        runner = _KMeansRunner(self, plan, planes)
+        scores = runner.assign_only(centroids.to(device=self.device, dtype=torch.float32).contiguous())
+        labels = self._cluster_labels(scores, plan)
+        return labels, (scores.view(plan.B, plan.hp * plan.wp, plan.k) if want_scores else None)
 
     def predict_dense(self, img, size=None, scales=None, flip: bool = False, window=None, stride=None, guided=None) -> np.ndarray:
         """The pixel-resolution sibling of ``predict()``: the image (PIL.Image or HxWx3 uint8 array) is resized to r x r on the
@@ -1577,3 +1652,80 @@ class LabelPropagator:
         labels = torch.empty((p.OH, p.OW), dtype=torch.int32, device=self.model.device)
         seg = self._runner.step(self.model.features(self.model._to_device(x, kind), self.n_blocks), labels)
         return labels, (seg.clone() if self.want_seg else None)
+
+
+# --------------------------------------------------------------------------- unsupervised segmentation (spherical k-means)
+class ClusterResult(NamedTuple):
+    """What ``DINOSeg.cluster`` returns: pixel labels int32 [B, OH, OW], unit centroids fp32 [k, D], the cluster sizes of the last
+    update int32 [k], per pass the objective fp32 [iters + 1] and the number of cells that changed cluster int32 [iters + 1], and the
+    final pass's scores fp32 [B, n, k] when asked for."""
+    labels: torch.Tensor
+    centroids: torch.Tensor
+    counts: torch.Tensor
+    objective: torch.Tensor
+    moved: torch.Tensor
+    scores: Optional[torch.Tensor]
+
+
+class _KMeansRun(NamedTuple):
+    centroids: torch.Tensor
+    counts: torch.Tensor
+    objective: torch.Tensor
+    moved: torch.Tensor
+    scores: torch.Tensor
+
+
+class _KMeansRunner:
+    """The launches of spherical k-means over one planes buffer, shared by ``DINOSeg.cluster`` and ``DINOSeg.assign_clusters``: the
+    scratch of ``dinoseg_kmeans_scratch_bytes`` and the per-point outputs are allocated once; every run owns its centroids, records
+    and scores."""
+
+    def __init__(self, model: "DINOSeg", plan, planes: torch.Tensor):
+        self.model, self.plan, self.planes = model, plan, planes
+        self.n, self.D, dev = plan.hp * plan.wp, model.cfg.embed_dim, model.device
+        nbytes = capi.lib().dinoseg_kmeans_scratch_bytes(plan.B, self.n, plan.k, self.D)
+        if nbytes < 0:
+            raise capi.DinosegError(f"dinoseg_kmeans_scratch_bytes refused {plan.B} frames of {self.n} cells, k = {plan.k}, "
+                                    f"width {self.D}")
+        self.scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        self.assign = torch.empty((plan.N,), dtype=torch.int32, device=dev)
+        self.best = torch.empty((plan.N,), dtype=torch.float32, device=dev)
+
+    def _init(self, rows: torch.Tensor, normalize: bool):
+        k, dev = self.plan.k, self.model.device
+        cent = torch.empty((k, self.D), dtype=torch.float32, device=dev)
+        cplanes = torch.empty((2, k, self.D), dtype=torch.float16, device=dev)
+        capi.check(capi.lib().dinoseg_op_kmeans_init(rows.data_ptr(), k, self.D, int(normalize), cent.data_ptr(), cplanes.data_ptr(),
+                                                     self.model._stream()))
+        return cent, cplanes
+
+    def _assign(self, cplanes, prev, scores, objective, moved, t: int) -> None:
+        p = self.plan
+        capi.check(capi.lib().dinoseg_op_kmeans_assign(
+            self.planes.data_ptr(), p.B, self.n, cplanes.data_ptr(), p.k, self.D, capi.ptr(prev), self.assign.data_ptr(),
+            self.best.data_ptr(), capi.ptr(scores), None if objective is None else objective[t:].data_ptr(),
+            None if moved is None else moved[t:].data_ptr(), self.scratch.data_ptr(), self.model._stream()))
+
+    def run(self, rows: torch.Tensor) -> _KMeansRun:
+        """init, ``iters`` times (assign, update), the final assign with scores; no host synchronisation in between"""
+        p, dev = self.plan, self.model.device
+        cent, cplanes = self._init(rows, True)
+        counts = torch.zeros((p.k,), dtype=torch.int32, device=dev)
+        objective = torch.empty((p.iters + 1,), dtype=torch.float32, device=dev)
+        moved = torch.empty((p.iters + 1,), dtype=torch.int32, device=dev)
+        scores = torch.empty((p.N, p.k), dtype=torch.float32, device=dev)
+        for t in range(p.iters):
+            self._assign(cplanes, self.assign if t > 0 else None, None, objective, moved, t)
+            capi.check(capi.lib().dinoseg_op_kmeans_update(
+                self.planes.data_ptr(), p.B, self.n, self.assign.data_ptr(), cent.data_ptr(), cplanes.data_ptr(), p.k, self.D,
+                cent.data_ptr(), cplanes.data_ptr(), counts.data_ptr(), self.scratch.data_ptr(), self.model._stream()))
+        self._assign(cplanes, self.assign if p.iters > 0 else None, scores, objective, moved, p.iters)
+        return _KMeansRun(cent, counts, objective, moved, scores)
+
+    def assign_only(self, centroids: torch.Tensor) -> torch.Tensor:
+        """one assignment against centroids taken as they are -> scores [N, k]"""
+        p = self.plan
+        _, cplanes = self._init(centroids, False)
+        scores = torch.empty((p.N, p.k), dtype=torch.float32, device=self.model.device)
+        self._assign(cplanes, None, scores, None, None, 0)
+        return scores

@@ -433,6 +433,63 @@ int dinoseg_op_propagate(const void* target_planes, const void* const* ctx_plane
                          int32_t hp, int32_t wp, int32_t D, int32_t C, int32_t radius, int32_t k, double tau, float* seg_out,
                          int32_t* topk_idx, float* topk_w, void* scratch, void* stream);
 
+/* ---- unsupervised segmentation: spherical k-means over patch features (the k-means baseline of STEGO and of "Deep ViT Features as
+ * Dense Visual Descriptors": cluster the patch tokens of a batch or clip, get segments whose ids mean the same in every frame).  No
+ * reference counterpart: the reference trains on hand-labelled frames.  kmeans.hip.
+ *
+ * Notation: B frames of n cells, N = B n points, point i = frame i / n, cell i % n; D the embedding width (a multiple of 64 in
+ * 64 .. 8192); K centroids, 1 .. 256 (the class limit of dinoseg_op_upsample_argmax); E = (D + 16) 2^-24.
+ *
+ * 1. Points.  The planes of dinoseg_op_normalize_tokens, [B][2][n][D] fp16 hi / lo scaled by 2^10.  The point is DEFINED as
+ *    x_i = (hi_i + lo_i) 2^-10, which is exact in fp32: no rounding of the normalisation enters the rule.  All N points are clustered
+ *    jointly.
+ * 2. Centroids.  K rows, kept as fp32 [K][D] and as planes [2][K][D] in the same format: 2^10 c = hi + lo with hi = fp16(2^10 c),
+ *    lo = fp16(2^10 c - hi), the split of the fp32 row.  The assignment reads the planes alone: c_j there is (hi_j + lo_j) 2^-10.
+ *    dinoseg_op_kmeans_init writes both from caller rows [K, D]: with normalize = 1 the row is c = fp32(row / max(||row||_2, 1e-12)),
+ *    the norm (fma in fp64) and the quotient in fp64 as dinoseg_op_normalize_tokens does them; with normalize = 0 the row is taken as
+ *    it is (centroids that an update wrote are unit rows already and keep their bits).  centroids may be rows itself.
+ * 3. Assignment (dinoseg_op_kmeans_assign).  s_ij = <x_i, c_j>, accumulated in fp32 from the planes with the arithmetic of
+ *    dinoseg_op_propagate (lo.hi + hi.lo + hi.hi on v_mfma_f32_32x32x16_f16, D in ascending slices of 64): a function of the two rows
+ *    alone, |s_ij - the fp64 value| <= E; a score of -0 is taken as +0.  a_i = argmax_j s_ij, the lowest j on an exact tie; best_i =
+ *    s_{i, a_i}.  The running (score, index) pair stays in registers; scores fp32 [N, K] is written only when the pointer is given.
+ * 4. Records.  *objective = sum_i best_i in fp32 in a fixed order (per tile of 64 points an xor tree, then the tiles strided over 256
+ *    threads and a binary tree); *moved = #{i : prev_assign[i] != a_i}, exact, = N when prev_assign is NULL.  Either slot may be NULL.
+ *    prev_assign may be assign itself.
+ * 5. Update (dinoseg_op_kmeans_update).  m_j = sum over {i : a_i = j} of x_i in fp32, in an order that is a function of the shapes and
+ *    the assignment: the points are cut into R = min(ceil(N / 256), Rmax) ranges of ceil(N / R), Rmax = 4096 / K clamped to
+ *    16 .. 64; inside a range the members of a cluster
+ *    are taken in index order, 1024 assignments at a time, dealt round-robin to G = 256 / T thread groups (T the power of two >= D / 8,
+ *    8 .. 256), each group adds its members in order, the groups are added in group order, the ranges in range order.  No
+ *    floating-point atomic, no synchronisation between workgroups beyond kernel boundaries; two runs agree bit for bit.
+ *    |m_j[d] - the exact sum| <= (n_j + 16) 2^-24 sum_i |x_i[d]|.  c_j = fp32(m_j / ||m_j||), the norm (fma in fp64) and the quotient in
+ *    fp64; the row and its planes are written.  n_j = 0 or ||m_j|| = 0: the previous row and planes are copied bit for bit.
+ *    counts[j] = n_j.  centroids / planes may be prev_centroids / prev_planes themselves.
+ * 6. Pixel labels: dinoseg_op_upsample_argmax applied to scores [B, n, K], unchanged.
+ *
+ * The loop is the caller's (DINOSeg.cluster): init, then iters times (assign, update) with the record slots objective + t, moved + t of
+ * device arrays, then one final assign that writes scores and slot iters.  Nothing stops early and nothing synchronises with the host.
+ *
+ * Deviations from sklearn's KMeans / the usual script: cosine (spherical) k-means, so the centroid is renormalised and the objective
+ * is the sum of cosines (larger is better); seeding is by distinct sampled points (no k-means++); an empty cluster keeps its centroid
+ * (sklearn relocates it); a fixed number of iterations, no tolerance test; ties go to the lowest index.
+ *
+ * scratch: dinoseg_kmeans_scratch_bytes(B, n, K, D) = 4 R K (D + 1) + 8 ceil(N / 64) bytes of device memory, 16-byte aligned, the same
+ * buffer for assign and update (R as in step 5, at most 64): R partial centroid sets fp32 [R][K][D], their counts int32 [R][K], and per tile of 64 points one fp32
+ * objective share and one int32 moved count.  Nothing of size N K or N D.  Host only; -1 for refusable arguments.
+ *
+ * Refused on the host (-1, the message names the entry) before anything is launched: null pointers (scores, objective, moved and
+ * prev_assign are optional); D not a multiple of 64 in 64 .. 8192; K outside 1 .. 256; B or n below 1; B n above 2^31 - 256; points,
+ * planes or scratch not 16-byte aligned, a 32-bit array not 4-byte aligned; normalize outside {0, 1}.  Stream-ordered, no allocation. */
+#define DINOSEG_KMEANS_MAX_K 256
+int64_t dinoseg_kmeans_scratch_bytes(int32_t B, int32_t n, int32_t K, int32_t D);
+int dinoseg_op_kmeans_init(const float* rows, int32_t K, int32_t D, int32_t normalize, float* centroids, void* planes, void* stream);
+int dinoseg_op_kmeans_assign(const void* points, int32_t B, int32_t n, const void* centroid_planes, int32_t K, int32_t D,
+                             const int32_t* prev_assign, int32_t* assign, float* best, float* scores, float* objective, int32_t* moved,
+                             void* scratch, void* stream);
+int dinoseg_op_kmeans_update(const void* points, int32_t B, int32_t n, const int32_t* assign, const float* prev_centroids,
+                             const void* prev_planes, int32_t K, int32_t D, float* centroids, void* planes, int32_t* counts,
+                             void* scratch, void* stream);
+
 /* ---- fine-tune step (replaces DINOSeg.training_step + autograd + optimizer.step, pl_torch_modules.py:258-268) ---- */
 
 /* Bind (or, with NULL, unbind) the fp32 gradient buffer of a parameter, same shape as the bound weight.  A parameter
