@@ -174,6 +174,12 @@ SIGNATURES = {
     "dinoseg_op_kmeans_init": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _vp, _vp]),
     "dinoseg_op_kmeans_assign": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _fp, _fp, _fp, _vp, _vp, _vp]),
     "dinoseg_op_kmeans_update": (C.c_int, [_vp, _i32, _i32, _vp, _fp, _vp, _i32, _i32, _fp, _vp, _vp, _vp, _vp]),
+    # normalized cut on a 1-bit patch graph: the graph's size and the cell limit (host only), planes -> bit graph + degree, every
+    # pass of the deflated lazy power iteration and the partition in one launch
+    "dinoseg_ncut_graph_bytes": (_i64, [_i32, _i32]),
+    "dinoseg_ncut_max_cells": (_i32, []),
+    "dinoseg_op_ncut_graph": (C.c_int, [_vp, _i32, _i32, _i32, _f64, _vp, _vp, _vp]),
+    "dinoseg_op_ncut_iterate": (C.c_int, [_vp, _vp, _i32, _i32, _f64, _fp, _i32, _fp, _fp, _vp, _fp, _fp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -683,6 +683,22 @@ extern "C" int dinoseg_op_kmeans_update(const void* points, int32_t B, int32_t n
                                 reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int64_t dinoseg_ncut_graph_bytes(int32_t B, int32_t n) { return ncut_graph_bytes(B, n); }
+
+extern "C" int32_t dinoseg_ncut_max_cells(void) { return ncut_max_cells(); }
+
+extern "C" int dinoseg_op_ncut_graph(const void* planes, int32_t B, int32_t n, int32_t D, double tau, void* graph, int32_t* degree,
+                                     void* stream) {
+    return launch_ncut_graph(planes, B, n, D, tau, graph, degree, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_ncut_iterate(const void* graph, const int32_t* degree, int32_t B, int32_t n, double eps, const float* z_in,
+                                       int32_t iters, float* z_out, float* rho, uint8_t* fg, float* eigvec, float* margin,
+                                       int32_t* seed_cell, void* stream) {
+    return launch_ncut_iterate(graph, degree, B, n, eps, z_in, iters, z_out, rho, fg, eigvec, margin, seed_cell,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int dinoseg_op_confusion(const int32_t* pred, const int64_t* gt, int64_t n, int32_t n_classes, int64_t* cm, void* stream) {
     return launch_confusion(pred, gt, n, n_classes, cm, reinterpret_cast<hipStream_t>(stream));
 }

@@ -394,6 +394,17 @@ int launch_kmeans_assign(const void* points, int B, int n, const void* centroid_
 int launch_kmeans_update(const void* points, int B, int n, const int32_t* assign, const float* prev_centroids, const void* prev_planes,
                          int K, int D, float* centroids, void* planes, int32_t* counts, void* scratch, hipStream_t s);
 
+// Normalized cut on a 1-bit patch graph (ncut.hip; the rule: include/dinoseg.h, dinoseg_op_ncut_graph).  Points are the planes of
+// launch_normalize_tokens; every frame is its own graph.  launch_ncut_graph: one workgroup per (frame, 64 queries), three MFMA
+// accumulators per tile, ballots -> the row-major bit graph [B][n][ceil(n / 64)] uint64 and the exact degree.  launch_ncut_iterate: one
+// workgroup of 1024 threads per frame, every pass in one launch, the vectors in LDS -> z_out, rho [B][iters], fg, eigvec, margin
+// (optional), seed_cell.  ncut_graph_bytes: -1 for refusable arguments.  ncut_max_cells: what the vectors leave of the LDS.  No atomics.
+long long ncut_graph_bytes(int B, int n);
+int ncut_max_cells();
+int launch_ncut_graph(const void* planes, int B, int n, int D, double tau, void* graph, int32_t* degree, hipStream_t s);
+int launch_ncut_iterate(const void* graph, const int32_t* degree, int B, int n, double eps, const float* z_in, int iters, float* z_out,
+                        float* rho, uint8_t* fg, float* eigvec, float* margin, int32_t* seed_cell, hipStream_t s);
+
 // ---- fine-tune step (train.hip, attention_bwd.hip) ----
 struct AttnBwdParams {
     const bf16_t* q; const bf16_t* k; const bf16_t* v; long qkv_plane;   // forward operands [planes][B,H,npad,64]

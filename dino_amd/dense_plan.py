@@ -382,3 +382,65 @@ def kmeans_plan(patch: int, embed_dim: int, x: torch.Tensor, k, iters=10, init="
     if OH < hp or OW < wp:
         raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(hp, wp)}")
     return KMeansPlan(kind, int(B), int(H), int(W), hp, wp, N, k, iters, how, seed, n_init, OH, OW, chunk)
+
+
+# ---- unsupervised foreground masks: normalized cut on a 1-bit patch graph (include/dinoseg.h: dinoseg_op_ncut_graph) ----
+NCUT_MAX_CELLS = 10160         # dinoseg_ncut_max_cells(): what the vectors z, xv, r, u leave of the 160 KiB of LDS (checked by tests)
+NCUT_MAX_ITERS = 4096
+
+
+class NcutPlan(NamedTuple):
+    """What a normalized-cut call was asked for, validated: the frames' layout, the patch grid, the rule's parameters (``tau`` as the
+    fp32 value the graph launch compares against) and the output size."""
+    kind: int
+    B: int
+    H: int
+    W: int
+    hp: int
+    wp: int
+    tau: float
+    eps: float
+    iters: int
+    seed: int
+    OH: int
+    OW: int
+    chunk: int
+
+
+def ncut_start(n: int, seed: int) -> torch.Tensor:
+    """The start vector of the power iteration: a seeded host normal vector, fp32 [n] (the library has no device random numbers).
+    Every frame of a call starts from the same vector."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"the start vector has n = {n} cells (positive)")
+    return torch.randn(n, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float32)
+
+
+def ncut_plan(patch: int, x: torch.Tensor, tau=0.2, eps=1e-5, iters=64, seed=0, size=None, chunk=32) -> NcutPlan:
+    """The shape and parameter checks of ``DINOSeg.ncut`` without a device.  ``x`` is the batch (uint8 [B,H,W,3] or fp32 [B,3,H,W], H
+    and W multiples of the patch size).  Every ``ValueError`` is raised here, before any device use."""
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"expected the frames as a tensor, uint8 [B,H,W,3] or fp32 [B,3,H,W], got {type(x).__name__}")
+    kind, B, H, W = frame_layout(x, patch, multiple=True, one_patch=True, non_empty=True)
+    hp, wp = H // patch, W // patch
+    for v in (tau, eps):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"tau and eps must be numbers, got {tau!r} and {eps!r}")
+    tau32, eps = float(np.float32(tau)), float(eps)                     # tau is rounded once to fp32, here
+    if not (math.isfinite(tau32) and -1.0 < tau32 < 1.0):
+        raise ValueError(f"tau = {tau!r} must be finite and inside (-1, 1)")
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"eps = {eps!r} must be inside [0, 1)")
+    iters = _int_in(iters, 0, NCUT_MAX_ITERS, "iters")
+    seed = _int_in(seed, -(1 << 62), 1 << 62, "seed")
+    chunk = _int_in(chunk, 1, 1 << 20, "chunk")
+    if hp * wp > NCUT_MAX_CELLS:
+        raise ValueError(f"the patch grid {(hp, wp)} has {hp * wp} cells; the vectors of at most {NCUT_MAX_CELLS} fit the LDS of the "
+                         f"one workgroup that iterates a frame")
+    try:
+        OH, OW = out_size(size, (H, W))
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be a pair (OH, OW), got {size!r}") from None
+    if OH < hp or OW < wp:
+        raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(hp, wp)}")
+    return NcutPlan(kind, int(B), int(H), int(W), hp, wp, tau32, eps, iters, seed, OH, OW, chunk)

@@ -19,8 +19,8 @@ from torch import nn
 
 from . import capi
 from .dense_plan import (_pair, context_frames, dense_mode, frame_layout, guide_plan, guided_params, kmeans_plan, label_size,
-                         multiscale_plan, out_size, propagate_plan, resolution_message, sample_indices, view_sizes, window_origins,
-                         window_plan)  # noqa: F401  (view_sizes, window_origins: re-exported)
+                         multiscale_plan, ncut_plan, ncut_start, out_size, propagate_plan, resolution_message, sample_indices,
+                         view_sizes, window_origins, window_plan)  # noqa: F401  (view_sizes, window_origins: re-exported)
 from .preprocess import resize_linear_u8
 from .weights import VIT_B8, VIT_B16, VIT_S8, VIT_S16, ViTConfig
 
@@ -857,6 +857,48 @@ class DINOSeg(nn.Module):
         scores = runner.assign_only(centroids.to(device=self.device, dtype=torch.float32).contiguous())
         labels = self._cluster_labels(scores, plan)
         return labels, (scores.view(plan.B, plan.hp * plan.wp, plan.k) if want_scores else None)
+
+    # ---- unsupervised foreground masks: normalized cut on a 1-bit patch graph (csrc/ncut.hip) ----
+    @torch.no_grad()
+    def ncut(self, x: torch.Tensor, tau: float = 0.2, eps: float = 1e-5, iters: int = 64, seed: int = 0, size=None, n_blocks: int = 0,
+             chunk: int = 32, want_graph: bool = False) -> "NcutResult":
+        """Unsupervised foreground masks: the spectral bipartition of every frame's patch-similarity graph (TokenCut, "Deep
+        Spectral Methods").  ``x`` uint8 [B,H,W,3] or fp32 [B,3,H,W], H and W multiples of the patch size -> ``NcutResult(labels
+        int32 [B,OH,OW] with 1 = foreground, fg uint8 [B,n], eigvec fp32 [B,n] (foreground positive), seed_cell int32 [B], rho
+        fp32 [B,iters], degree int32 [B,n], graph uint64 [B,n,ceil(n/64)] or None)``.  Every frame is its own graph; frames are
+        independent.  Two cells are joined when the cosine of their tokens exceeds ``tau``; a joined pair weighs 1, any other pair
+        ``eps``; ``iters`` lazy power iterations with the known top vector deflated approach the second eigenvector of the
+        normalised graph (``rho`` records the Rayleigh quotient of every pass; nothing stops early), started from
+        ``ncut_start(n, seed)``; the cells on the side of the cell with the largest entry are the foreground, and the bilinear
+        enlargement of the signed margin to ``size`` (default the frames' own) gives ``labels`` (the rule:
+        include/dinoseg.h, dinoseg_op_ncut_graph).  No n x n matrix of floats is formed: the graph is n^2 bits.  No head weight is
+        used.  Inference only."""
+        plan = ncut_plan(self.cfg.patch, x, tau, eps, iters, seed, size, chunk)
+        if not 0 <= n_blocks <= self.cfg.n_blocks:
+            raise ValueError(f"intermediate must be in [0, {self.cfg.n_blocks}]")
+        self._require_gpu()
+        lib, dev, B, n, D = capi.lib(), self.device, plan.B, plan.hp * plan.wp, self.cfg.embed_dim
+        planes = self._point_planes(self._to_device(x, plan.kind), plan, n_blocks)
+        nbytes = lib.dinoseg_ncut_graph_bytes(B, n)
+        if nbytes < 0:
+            raise capi.DinosegError(f"dinoseg_ncut_graph_bytes refused {B} frames of {n} cells")
+        graph = torch.empty((B, n, nbytes // (8 * B * n)), dtype=torch.int64, device=dev)
+        degree = torch.empty((B, n), dtype=torch.int32, device=dev)
+        capi.check(lib.dinoseg_op_ncut_graph(planes.data_ptr(), B, n, D, plan.tau, graph.data_ptr(), degree.data_ptr(), self._stream()))
+        z = ncut_start(n, plan.seed).to(dev).expand(B, n).contiguous()
+        rho = torch.empty((B, plan.iters), dtype=torch.float32, device=dev)
+        fg = torch.empty((B, n), dtype=torch.uint8, device=dev)
+        eigvec = torch.empty((B, n), dtype=torch.float32, device=dev)
+        margin = torch.empty((B, n), dtype=torch.float32, device=dev)
+        seed_cell = torch.empty((B,), dtype=torch.int32, device=dev)
+        capi.check(lib.dinoseg_op_ncut_iterate(graph.data_ptr(), degree.data_ptr(), B, n, plan.eps, z.data_ptr(), plan.iters,
+                                               z.data_ptr(), rho.data_ptr() if plan.iters else None, fg.data_ptr(), eigvec.data_ptr(),
+                                               margin.data_ptr(), seed_cell.data_ptr(), self._stream()))
+        two = torch.stack((torch.zeros_like(margin), margin), dim=2).contiguous()      # the two-class map [B, n, 2] = (0, margin)
+        labels = torch.empty((B, plan.OH, plan.OW), dtype=torch.int32, device=dev)
+        capi.check(lib.dinoseg_op_upsample_argmax(two.data_ptr(), B, plan.hp, plan.wp, 2, plan.OH, plan.OW, labels.data_ptr(), None,
+                                                  self._stream()))
+        return NcutResult(labels, fg, eigvec, seed_cell, rho, degree, graph.view(torch.uint64) if want_graph else None)
 
     def predict_dense(self, img, size=None, scales=None, flip: bool = False, window=None, stride=None, guided=None) -> np.ndarray:
         """The pixel-resolution sibling of ``predict()``: the image (PIL.Image or HxWx3 uint8 array) is resized to r x r on the
@@ -1729,3 +1771,18 @@ class _KMeansRunner:
         scores = torch.empty((p.N, p.k), dtype=torch.float32, device=self.model.device)
         self._assign(cplanes, None, scores, None, None, 0)
         return scores
+
+
+# --------------------------------------------------------------------------- unsupervised foreground masks (normalized cut)
+class NcutResult(NamedTuple):
+    """What ``DINOSeg.ncut`` returns: pixel labels int32 [B, OH, OW] (1 = foreground), the cell partition uint8 [B, n], the
+    sign-fixed eigenvector fp32 [B, n] (foreground positive), the cell with the largest entry int32 [B], the Rayleigh record of
+    every pass fp32 [B, iters], the set bits per row int32 [B, n], and the row-major bit graph uint64 [B, n, ceil(n / 64)] when asked
+    for."""
+    labels: torch.Tensor
+    fg: torch.Tensor
+    eigvec: torch.Tensor
+    seed_cell: torch.Tensor
+    rho: torch.Tensor
+    degree: torch.Tensor
+    graph: Optional[torch.Tensor]

@@ -490,6 +490,66 @@ int dinoseg_op_kmeans_update(const void* points, int32_t B, int32_t n, const int
                              const void* prev_planes, int32_t K, int32_t D, float* centroids, void* planes, int32_t* counts,
                              void* scratch, void* stream);
 
+/* ---- unsupervised foreground masks: normalized cut on a 1-bit patch graph (the spectral bipartition of TokenCut and of "Deep
+ * Spectral Methods": which cells are the object and which the background, in this frame alone, with no label, no head, no k and no
+ * other frame).  No reference counterpart.  ncut.hip.  No n x n matrix of floats exists: a frame's graph is n^2 bits.
+ *
+ * Notation, per frame (frames are independent; every frame is its own graph): n cells, 1 .. dinoseg_ncut_max_cells(); D the embedding
+ * width (a multiple of 64 in 64 .. 8192); W = ceil(n / 64) words per row; E = (D + 16) 2^-24.
+ *
+ * 1. Points.  The planes of dinoseg_op_normalize_tokens, [B][2][n][D] fp16 hi / lo scaled by 2^10; x_i = (hi_i + lo_i) 2^-10 as
+ *    dinoseg_op_kmeans_assign defines it.
+ * 2. Scores.  s_ij = <x_i, x_j> from the planes on v_mfma_f32_32x32x16_f16, D in ascending slices of 64, fp32 accumulators.  The three
+ *    products are kept in THREE accumulators and combined once as (c_lo.hi + c_hi.lo) + c_hi.hi, c_a.b = sum_d a_i[d] b_j[d].  This
+ *    deliberately differs from the single chain lo.hi + hi.lo + hi.hi of dinoseg_op_propagate and dinoseg_op_kmeans_assign: with this
+ *    grouping s_ij and s_ji are the same bits (the two cross terms swap roles, fp32 addition commutes), so the graph is symmetric bit
+ *    for bit.  s_ij is a function of the two rows alone; |s_ij - the fp64 value| <= E; a score of -0 is taken as +0.
+ * 3. Graph (dinoseg_op_ncut_graph).  bit(i, j) = s_ij > tau, tau rounded once to fp32 on the host.  graph: [B][n][W] uint64 words, row
+ *    major, key j at bit j % 64 of word j / 64; pad bits are zero.  degree[i] = cnt_i = popcount(row i), exact (int32 [B][n]).
+ *    This is the only launch that touches the planes.
+ * 4. Weights.  W = eps 11^T + (1 - eps) Bits (TokenCut's binary affinity: 1 above tau, eps below).  d_i = fp32(eps (n - cnt_i) + cnt_i),
+ *    formed in fp64; r_i = fp32(1 / sqrt(d_i)) (0 where d_i = 0); u_i = fp32(sqrt(d_i) / sqrt(sum_j d_j)), the known top eigenvector of
+ *    M = D^-1/2 W D^-1/2 (0 where the sum is 0).  The iteration runs on (I + M) / 2, whose spectrum lies in [0, 1]: a negative
+ *    eigenvalue of the non-PSD threshold graph can never win.
+ * 5. Deflate and normalise, DN(z): c = <u, z>; q_i = fp32(z_i - c u_i); z_i <- fp32(q_i / ||q||), or 0 everywhere where ||q|| = 0
+ *    (one-cell grids and complete graphs fall under this case).
+ * 6. One pass (dinoseg_op_ncut_iterate), from a prepared z = DN(.):
+ *      xv_j = z_j r_j (fp32);  S = sum_j xv_j;  t_i = the sum of xv_j over the set bits of row i, in fp32 in a fixed order: key j
+ *      belongs to lane j % 64, a lane adds its keys in ascending order from 0, the 64 lanes are added in an xor tree (offsets 32, 16, .., 1);
+ *      y_i = fp32(r_i (eps S + (1 - eps) t_i));  rho = <z, y>;  p_i = (z_i + y_i) / 2 (fp32);  z' = DN(p).
+ *    The global sums S, rho, c, ||q||^2 and the mean of step 7 are fp64 in a fixed order that depends on n only (thread t of 1024 adds
+ *    cells t, t + 1024, .. in order -- rho: wave w of 16 adds rows w, w + 16, .. --, an xor tree per wave, the 16 waves in order).
+ *    |t_i - the exact sum| <= (cnt_i + 16) 2^-24 sum over the set bits of |xv_j|.
+ *    The call: z_0 = DN(z_in); iters passes, rho[b][t] = the pass's Rayleigh record <z, y> = <z, M z> of the unit z it started from;
+ *    z_out = the last z'.  Every pass after the first prepares its input once more, DN(z'), exactly as a fresh call would prepare z_out: a call
+ *    with iters = T equals T calls with iters = 1 chained through z_out, bit for bit.  iters = 0 does step 7 on z_0.
+ * 7. Result.  v_i = z_i r_i (fp32); avg = the mean of v (fp64); seed_cell = argmax |v_i|, the lowest index on a tie; sigma = +1 if
+ *    v_seed > avg, else -1; margin_i = fp32(sigma (v_i - avg)); fg_i = margin_i > 0; eigvec = sigma v.  This is TokenCut's
+ *    bipartition and seed rule: the side that holds the largest |v| is the foreground.
+ * 8. Pixel labels: dinoseg_op_upsample_argmax, unchanged, applied to the two-class map [B, n, 2] = (0, margin_i); the first maximum
+ *    makes ties go to background.
+ *
+ * Deviations from TokenCut: the points are the tokens of dinoseg_features_hw, not last-block keys; a fixed number of lazy power
+ * iterations replaces the dense generalized eigh; no connected component around the seed is taken and no box is produced.
+ *
+ * dinoseg_ncut_graph_bytes(B, n) = 8 B n ceil(n / 64); dinoseg_ncut_max_cells() = what the four vectors z, xv, r, u leave of the 160 KiB
+ * of LDS of the one workgroup that iterates a frame (10 160; the 480 x 640 camera at patch 8 has 4800; 960 x 960 at patch 8, 14 400,
+ * does not fit).  Host only; the size query answers -1 for refusable arguments.
+ *
+ * dinoseg_op_ncut_iterate: z_in / z_out fp32 [B][n] (z_out may be z_in); rho fp32 [B][iters] (may be NULL with iters = 0); fg uint8
+ * [B][n]; eigvec fp32 [B][n]; margin fp32 [B][n] or NULL; seed_cell int32 [B].  One workgroup of 1024 threads per frame runs every
+ * pass in one launch; no synchronisation between workgroups, no scratch, no host synchronisation; bit-identical from run to run.
+ *
+ * Refused on the host (-1, the message names the entry) before anything is launched: null pointers (margin is optional, rho with
+ * iters = 0); D not a multiple of 64 in 64 .. 8192; B or n below 1; n above dinoseg_ncut_max_cells(); tau not finite or outside
+ * (-1, 1); eps outside [0, 1); iters outside 0 .. 4096; planes not 16-byte aligned, the graph not 8-byte aligned, a 32-bit array not
+ * 4-byte aligned.  Stream-ordered, no allocation. */
+int64_t dinoseg_ncut_graph_bytes(int32_t B, int32_t n);
+int32_t dinoseg_ncut_max_cells(void);
+int dinoseg_op_ncut_graph(const void* planes, int32_t B, int32_t n, int32_t D, double tau, void* graph, int32_t* degree, void* stream);
+int dinoseg_op_ncut_iterate(const void* graph, const int32_t* degree, int32_t B, int32_t n, double eps, const float* z_in, int32_t iters,
+                            float* z_out, float* rho, uint8_t* fg, float* eigvec, float* margin, int32_t* seed_cell, void* stream);
+
 /* ---- fine-tune step (replaces DINOSeg.training_step + autograd + optimizer.step, pl_torch_modules.py:258-268) ---- */
 
 /* Bind (or, with NULL, unbind) the fp32 gradient buffer of a parameter, same shape as the bound weight.  A parameter
