@@ -180,6 +180,11 @@ SIGNATURES = {
     "dinoseg_ncut_max_cells": (_i32, []),
     "dinoseg_op_ncut_graph": (C.c_int, [_vp, _i32, _i32, _i32, _f64, _vp, _vp, _vp]),
     "dinoseg_op_ncut_iterate": (C.c_int, [_vp, _vp, _i32, _i32, _f64, _fp, _i32, _fp, _fp, _vp, _fp, _fp, _vp, _vp]),
+    "dinoseg_ncut_split_max_cells": (_i32, []),
+    "dinoseg_ncut_split_graph_bytes": (_i64, [_i32, _i32]),
+    "dinoseg_ncut_split_scratch_bytes": (_i64, [_i32, _i32]),
+    "dinoseg_op_ncut_graph_split": (C.c_int, [_vp, _i32, _i32, _i32, _f64, _vp, _vp, _vp]),
+    "dinoseg_op_ncut_iterate_split": (C.c_int, [_vp, _vp, _i32, _i32, _f64, _fp, _i32, _i32, _fp, _fp, _vp, _fp, _fp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -699,6 +699,24 @@ extern "C" int dinoseg_op_ncut_iterate(const void* graph, const int32_t* degree,
                                reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int32_t dinoseg_ncut_split_max_cells(void) { return ncut_split_max_cells(); }
+
+extern "C" int64_t dinoseg_ncut_split_graph_bytes(int32_t B, int32_t n) { return ncut_split_graph_bytes(B, n); }
+
+extern "C" int64_t dinoseg_ncut_split_scratch_bytes(int32_t B, int32_t n) { return ncut_split_scratch_bytes(B, n); }
+
+extern "C" int dinoseg_op_ncut_graph_split(const void* planes, int32_t B, int32_t n, int32_t D, double tau, void* graph, int32_t* degree,
+                                           void* stream) {
+    return launch_ncut_graph_split(planes, B, n, D, tau, graph, degree, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_ncut_iterate_split(const void* graph, const int32_t* degree, int32_t B, int32_t n, double eps, const float* z_in,
+                                             int32_t iters, int32_t rows_per_group, float* z_out, float* rho, uint8_t* fg, float* eigvec,
+                                             float* margin, int32_t* seed_cell, void* scratch, void* stream) {
+    return launch_ncut_iterate_split(graph, degree, B, n, eps, z_in, iters, rows_per_group, z_out, rho, fg, eigvec, margin, seed_cell,
+                                     scratch, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int dinoseg_op_confusion(const int32_t* pred, const int64_t* gt, int64_t n, int32_t n_classes, int64_t* cm, void* stream) {
     return launch_confusion(pred, gt, n, n_classes, cm, reinterpret_cast<hipStream_t>(stream));
 }

@@ -404,6 +404,16 @@ int ncut_max_cells();
 int launch_ncut_graph(const void* planes, int B, int n, int D, double tau, void* graph, int32_t* degree, hipStream_t s);
 int launch_ncut_iterate(const void* graph, const int32_t* degree, int B, int n, double eps, const float* z_in, int iters, float* z_out,
                         float* rho, uint8_t* fg, float* eigvec, float* margin, int32_t* seed_cell, hipStream_t s);
+// The same rule and the same bits with a frame's rows dealt to many workgroups (ncut_split.hip; the addendum in include/dinoseg.h):
+// one launch per pass ordered by the stream alone, xv the only vector in LDS, z / y / r / u in a scratch of ncut_split_scratch_bytes.
+// launch_ncut_graph_split (ncut.hip) is launch_ncut_graph's kernel under the split cell limit.
+int ncut_split_max_cells();
+long long ncut_split_graph_bytes(int B, int n);
+long long ncut_split_scratch_bytes(int B, int n);
+int launch_ncut_graph_split(const void* planes, int B, int n, int D, double tau, void* graph, int32_t* degree, hipStream_t s);
+int launch_ncut_iterate_split(const void* graph, const int32_t* degree, int B, int n, double eps, const float* z_in, int iters,
+                              int rows_per_group, float* z_out, float* rho, uint8_t* fg, float* eigvec, float* margin, int32_t* seed_cell,
+                              void* scratch, hipStream_t s);
 
 // ---- fine-tune step (train.hip, attention_bwd.hip) ----
 struct AttnBwdParams {

@@ -21,6 +21,7 @@
 //                         conflict-free ds_read_b32 of xv[64 w + l] (shared by the two rows a wave walks at a time) and one select on
 //                         the word itself as the lane mask, added in ascending w; the 64 lanes meet in an xor tree.  The global sums (S, rho, <u, z>, ||q||^2, the mean) are fp64:
 //                         thread t adds its cells t, t + 1024, ... in order, an xor tree per wave, the 16 waves in wave order.
+// (ncut_split.hip runs the same passes with a frame's rows dealt to many workgroups, one launch per pass, bit for bit the same.)
 #include "../../include/dinoseg.h"
 #include "common.h"
 #include "kernels.h"
@@ -361,13 +362,13 @@ __global__ __launch_bounds__(NC_THREADS) void ncut_iterate_kernel(const unsigned
 
 bool nc_misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
-int nc_shape_check(const char* who, int B, int n) {
+int nc_shape_check(const char* who, int B, int n, int max_cells = NC_MAX_CELLS) {
     if (B < 1 || n < 1) {
         dinoseg_set_error("%s: B = %d frames of n = %d cells (positive)", who, B, n);
         return -1;
     }
-    if (n > NC_MAX_CELLS) {
-        dinoseg_set_error("%s: n = %d cells exceed the %d whose vectors fit the LDS of one workgroup", who, n, NC_MAX_CELLS);
+    if (n > max_cells) {
+        dinoseg_set_error("%s: n = %d cells exceed the %d whose vectors fit the LDS of one workgroup", who, n, max_cells);
         return -1;
     }
     if ((long long)B * ((n + NC_TILE - 1) / NC_TILE) > NC_MAX_GRID) {
@@ -386,8 +387,11 @@ long long ncut_graph_bytes(int B, int n) {
     return 8ll * B * n * ((n + 63) / 64);
 }
 
-int launch_ncut_graph(const void* planes, int B, int n, int D, double tau, void* graph, int32_t* degree, hipStream_t s) {
-    const char* who = "dinoseg_op_ncut_graph";
+namespace {
+
+// the graph launch under the cell limit of the entry `who`: the kernel itself has no limit of its own
+int nc_launch_graph(const char* who, int max_cells, const void* planes, int B, int n, int D, double tau, void* graph, int32_t* degree,
+                    hipStream_t s) {
     if (!planes || !graph || !degree) {
         dinoseg_set_error("%s: null pointer", who);
         return -1;
@@ -396,7 +400,7 @@ int launch_ncut_graph(const void* planes, int B, int n, int D, double tau, void*
         dinoseg_set_error("%s: width D = %d (a multiple of 64 up to 8192)", who, D);
         return -1;
     }
-    if (nc_shape_check(who, B, n)) return -1;
+    if (nc_shape_check(who, B, n, max_cells)) return -1;
     if (!std::isfinite(tau) || !(tau > -1.0 && tau < 1.0)) {
         dinoseg_set_error("%s: tau = %g (finite, inside (-1, 1))", who, tau);
         return -1;
@@ -410,6 +414,16 @@ int launch_ncut_graph(const void* planes, int B, int n, int D, double tau, void*
                        (float)tau, tiles, reinterpret_cast<unsigned long long*>(graph), degree);
     DSEG_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+}  // namespace
+
+int launch_ncut_graph(const void* planes, int B, int n, int D, double tau, void* graph, int32_t* degree, hipStream_t s) {
+    return nc_launch_graph("dinoseg_op_ncut_graph", NC_MAX_CELLS, planes, B, n, D, tau, graph, degree, s);
+}
+
+int launch_ncut_graph_split(const void* planes, int B, int n, int D, double tau, void* graph, int32_t* degree, hipStream_t s) {
+    return nc_launch_graph("dinoseg_op_ncut_graph_split", ncut_split_max_cells(), planes, B, n, D, tau, graph, degree, s);
 }
 
 int launch_ncut_iterate(const void* graph, const int32_t* degree, int B, int n, double eps, const float* z_in, int iters, float* z_out,

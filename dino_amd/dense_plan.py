@@ -386,12 +386,14 @@ def kmeans_plan(patch: int, embed_dim: int, x: torch.Tensor, k, iters=10, init="
 
 # ---- unsupervised foreground masks: normalized cut on a 1-bit patch graph (include/dinoseg.h: dinoseg_op_ncut_graph) ----
 NCUT_MAX_CELLS = 10160         # dinoseg_ncut_max_cells(): what the vectors z, xv, r, u leave of the 160 KiB of LDS (checked by tests)
+NCUT_SPLIT_MAX_CELLS = 40640   # dinoseg_ncut_split_max_cells(): what the one vector xv leaves of the 160 KiB of LDS of a row workgroup
 NCUT_MAX_ITERS = 4096
 
 
 class NcutPlan(NamedTuple):
     """What a normalized-cut call was asked for, validated: the frames' layout, the patch grid, the rule's parameters (``tau`` as the
-    fp32 value the graph launch compares against) and the output size."""
+    fp32 value the graph launch compares against), the output size, and ``split``: 0 for the one-workgroup launch, -1 for the split
+    launches with the library's choice of rows per workgroup, R >= 1 for the split launches with R rows per workgroup."""
     kind: int
     B: int
     H: int
@@ -405,6 +407,7 @@ class NcutPlan(NamedTuple):
     OH: int
     OW: int
     chunk: int
+    split: int = 0
 
 
 def ncut_start(n: int, seed: int) -> torch.Tensor:
@@ -416,9 +419,11 @@ def ncut_start(n: int, seed: int) -> torch.Tensor:
     return torch.randn(n, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float32)
 
 
-def ncut_plan(patch: int, x: torch.Tensor, tau=0.2, eps=1e-5, iters=64, seed=0, size=None, chunk=32) -> NcutPlan:
+def ncut_plan(patch: int, x: torch.Tensor, tau=0.2, eps=1e-5, iters=64, seed=0, size=None, chunk=32, split=False) -> NcutPlan:
     """The shape and parameter checks of ``DINOSeg.ncut`` without a device.  ``x`` is the batch (uint8 [B,H,W,3] or fp32 [B,3,H,W], H
-    and W multiples of the patch size).  Every ``ValueError`` is raised here, before any device use."""
+    and W multiples of the patch size).  ``split``: ``False`` for the one-workgroup launch, ``True`` for the split launches with the
+    library's choice of rows per workgroup, an int >= 1 for that many rows per workgroup.  Every ``ValueError`` is raised here, before
+    any device use."""
     if not isinstance(x, torch.Tensor):
         raise ValueError(f"expected the frames as a tensor, uint8 [B,H,W,3] or fp32 [B,3,H,W], got {type(x).__name__}")
     kind, B, H, W = frame_layout(x, patch, multiple=True, one_patch=True, non_empty=True)
@@ -434,7 +439,16 @@ def ncut_plan(patch: int, x: torch.Tensor, tau=0.2, eps=1e-5, iters=64, seed=0, 
     iters = _int_in(iters, 0, NCUT_MAX_ITERS, "iters")
     seed = _int_in(seed, -(1 << 62), 1 << 62, "seed")
     chunk = _int_in(chunk, 1, 1 << 20, "chunk")
-    if hp * wp > NCUT_MAX_CELLS:
+    if isinstance(split, (bool, np.bool_)):
+        split = -1 if split else 0
+    elif isinstance(split, (int, np.integer)) and split >= 1:
+        split = min(int(split), NCUT_SPLIT_MAX_CELLS)                   # (rows per workgroup beyond the frame's rows: the whole frame)
+    else:
+        raise ValueError(f"split must be False, True or a number of rows per workgroup >= 1, got {split!r}")
+    if split and hp * wp > NCUT_SPLIT_MAX_CELLS:
+        raise ValueError(f"the patch grid {(hp, wp)} has {hp * wp} cells; with split, the one vector of at most {NCUT_SPLIT_MAX_CELLS} "
+                         f"(NCUT_SPLIT_MAX_CELLS) fits the LDS of a row workgroup")
+    if not split and hp * wp > NCUT_MAX_CELLS:
         raise ValueError(f"the patch grid {(hp, wp)} has {hp * wp} cells; the vectors of at most {NCUT_MAX_CELLS} fit the LDS of the "
                          f"one workgroup that iterates a frame")
     try:
@@ -443,4 +457,4 @@ def ncut_plan(patch: int, x: torch.Tensor, tau=0.2, eps=1e-5, iters=64, seed=0, 
         raise ValueError(f"size must be a pair (OH, OW), got {size!r}") from None
     if OH < hp or OW < wp:
         raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(hp, wp)}")
-    return NcutPlan(kind, int(B), int(H), int(W), hp, wp, tau32, eps, iters, seed, OH, OW, chunk)
+    return NcutPlan(kind, int(B), int(H), int(W), hp, wp, tau32, eps, iters, seed, OH, OW, chunk, split)

@@ -861,7 +861,7 @@ class DINOSeg(nn.Module):
     # ---- unsupervised foreground masks: normalized cut on a 1-bit patch graph (csrc/ncut.hip) ----
     @torch.no_grad()
     def ncut(self, x: torch.Tensor, tau: float = 0.2, eps: float = 1e-5, iters: int = 64, seed: int = 0, size=None, n_blocks: int = 0,
-             chunk: int = 32, want_graph: bool = False) -> "NcutResult":
+             chunk: int = 32, want_graph: bool = False, split=False) -> "NcutResult":
         """Unsupervised foreground masks: the spectral bipartition of every frame's patch-similarity graph (TokenCut, "Deep
         Spectral Methods").  ``x`` uint8 [B,H,W,3] or fp32 [B,3,H,W], H and W multiples of the patch size -> ``NcutResult(labels
         int32 [B,OH,OW] with 1 = foreground, fg uint8 [B,n], eigvec fp32 [B,n] (foreground positive), seed_cell int32 [B], rho
@@ -872,28 +872,39 @@ class DINOSeg(nn.Module):
         ``ncut_start(n, seed)``; the cells on the side of the cell with the largest entry are the foreground, and the bilinear
         enlargement of the signed margin to ``size`` (default the frames' own) gives ``labels`` (the rule:
         include/dinoseg.h, dinoseg_op_ncut_graph).  No n x n matrix of floats is formed: the graph is n^2 bits.  No head weight is
-        used.  Inference only."""
-        plan = ncut_plan(self.cfg.patch, x, tau, eps, iters, seed, size, chunk)
+        used.  Inference only.  ``split`` (``True``, or the rows per workgroup) deals every frame's rows to many workgroups, one launch
+        per pass: the same bits in every field, a fraction of the latency, and grids of up to ``NCUT_SPLIT_MAX_CELLS`` cells (960 x
+        960 at patch 8 fits) where the default stops at ``NCUT_MAX_CELLS``."""
+        plan = ncut_plan(self.cfg.patch, x, tau, eps, iters, seed, size, chunk, split)
         if not 0 <= n_blocks <= self.cfg.n_blocks:
             raise ValueError(f"intermediate must be in [0, {self.cfg.n_blocks}]")
         self._require_gpu()
         lib, dev, B, n, D = capi.lib(), self.device, plan.B, plan.hp * plan.wp, self.cfg.embed_dim
         planes = self._point_planes(self._to_device(x, plan.kind), plan, n_blocks)
-        nbytes = lib.dinoseg_ncut_graph_bytes(B, n)
+        graph_bytes, graph_op = ((lib.dinoseg_ncut_split_graph_bytes, lib.dinoseg_op_ncut_graph_split) if plan.split else
+                                 (lib.dinoseg_ncut_graph_bytes, lib.dinoseg_op_ncut_graph))
+        nbytes = graph_bytes(B, n)
         if nbytes < 0:
             raise capi.DinosegError(f"dinoseg_ncut_graph_bytes refused {B} frames of {n} cells")
         graph = torch.empty((B, n, nbytes // (8 * B * n)), dtype=torch.int64, device=dev)
         degree = torch.empty((B, n), dtype=torch.int32, device=dev)
-        capi.check(lib.dinoseg_op_ncut_graph(planes.data_ptr(), B, n, D, plan.tau, graph.data_ptr(), degree.data_ptr(), self._stream()))
+        capi.check(graph_op(planes.data_ptr(), B, n, D, plan.tau, graph.data_ptr(), degree.data_ptr(), self._stream()))
         z = ncut_start(n, plan.seed).to(dev).expand(B, n).contiguous()
         rho = torch.empty((B, plan.iters), dtype=torch.float32, device=dev)
         fg = torch.empty((B, n), dtype=torch.uint8, device=dev)
         eigvec = torch.empty((B, n), dtype=torch.float32, device=dev)
         margin = torch.empty((B, n), dtype=torch.float32, device=dev)
         seed_cell = torch.empty((B,), dtype=torch.int32, device=dev)
-        capi.check(lib.dinoseg_op_ncut_iterate(graph.data_ptr(), degree.data_ptr(), B, n, plan.eps, z.data_ptr(), plan.iters,
-                                               z.data_ptr(), rho.data_ptr() if plan.iters else None, fg.data_ptr(), eigvec.data_ptr(),
-                                               margin.data_ptr(), seed_cell.data_ptr(), self._stream()))
+        if plan.split:
+            scratch = torch.empty((lib.dinoseg_ncut_split_scratch_bytes(B, n),), dtype=torch.uint8, device=dev)
+            capi.check(lib.dinoseg_op_ncut_iterate_split(graph.data_ptr(), degree.data_ptr(), B, n, plan.eps, z.data_ptr(), plan.iters,
+                                                         max(plan.split, 0), z.data_ptr(), rho.data_ptr() if plan.iters else None,
+                                                         fg.data_ptr(), eigvec.data_ptr(), margin.data_ptr(), seed_cell.data_ptr(),
+                                                         scratch.data_ptr(), self._stream()))
+        else:
+            capi.check(lib.dinoseg_op_ncut_iterate(graph.data_ptr(), degree.data_ptr(), B, n, plan.eps, z.data_ptr(), plan.iters,
+                                                   z.data_ptr(), rho.data_ptr() if plan.iters else None, fg.data_ptr(), eigvec.data_ptr(),
+                                                   margin.data_ptr(), seed_cell.data_ptr(), self._stream()))
         two = torch.stack((torch.zeros_like(margin), margin), dim=2).contiguous()      # the two-class map [B, n, 2] = (0, margin)
         labels = torch.empty((B, plan.OH, plan.OW), dtype=torch.int32, device=dev)
         capi.check(lib.dinoseg_op_upsample_argmax(two.data_ptr(), B, plan.hp, plan.wp, 2, plan.OH, plan.OW, labels.data_ptr(), None,

@@ -550,6 +550,51 @@ int dinoseg_op_ncut_graph(const void* planes, int32_t B, int32_t n, int32_t D, d
 int dinoseg_op_ncut_iterate(const void* graph, const int32_t* degree, int32_t B, int32_t n, double eps, const float* z_in, int32_t iters,
                             float* z_out, float* rho, uint8_t* fg, float* eigvec, float* margin, int32_t* seed_cell, void* stream);
 
+/* Addendum: the same rule with a frame's rows dealt to many workgroups (ncut_split.hip).  Opt-in; the entries above are unchanged.
+ *
+ * The rule is steps 1-8 above, word for word, and every order of summation in it is a function of n alone: the split entries give
+ * THE SAME BITS as the entries above in every output wherever both accept n.  Only two things differ: which workgroup computes a
+ * row's t_i and y_i (t_i depends on the row and on xv alone, so the owner does not matter), and the cell limit.
+ *
+ * dinoseg_op_ncut_iterate_split issues iters + 2 plain launches on the caller's stream, ordered by the stream alone -- no grid
+ * barrier, no cooperative launch, no flag, no atomic, no graph capture, no host synchronisation:
+ *   weights    one workgroup per frame: r and u (step 4) into the scratch;
+ *   pass t     (iters launches) B x (ceil(n / R) + [t > 0]) workgroups of 1024 threads, R = rows per workgroup.  Every row workgroup
+ *              redundantly prepares the pass's input in its own LDS, in the thread-ownership order of step 6, from the previous
+ *              launch's z and y in the scratch -- p = (z + y) / 2, DN(p), DN once more (pass 0: DN(z_in)), xv = z r, S -- so all
+ *              hold the same bits; it then walks its R rows and writes their y_i, and its rows' z_i, into the OTHER half of the
+ *              ping-pong scratch (workgroups of the same launch still read the old half).  The extra workgroup of a frame forms
+ *              rho[t - 1], a record that never feeds back, from the previous launch's z and y in the rule's order;
+ *   result     one workgroup per frame: the last p, DN(p) (iters = 0: DN(z_in)), rho[iters - 1] and step 7.  z_out may be z_in for
+ *              every iters, 0 included: nothing before this launch writes z_out, and here every element is read and written by
+ *              one thread.
+ *
+ * dinoseg_ncut_split_max_cells() = (160 KiB - 1024 bytes of reduction slots - the 256-byte pad that the last word's pad lanes read)
+ * / 4 bytes = 40 640: the one fp32 vector a row workgroup keeps in LDS is xv; every other vector element belongs to one thread and
+ * lives in the scratch.  960 x 960 at patch 8 has 14 400 cells.  dinoseg_ncut_split_graph_bytes(B, n) = 8 B n ceil(n / 64);
+ * dinoseg_ncut_split_scratch_bytes(B, n) = 24 B n: six fp32 vectors per frame, the two halves of z and of y, r and u.  Nothing scales
+ * with n^2.  Both answer -1 for B or n below 1, n above the split limit, or B ceil(n / 64) beyond the launch range.  The scratch
+ * holds nothing between calls.
+ *
+ * rows_per_group: 0 = the library's choice, the smallest multiple of 32 (every wave walks whole pairs of rows) at which the B
+ * ceil(n / R) row workgroups of a pass are at most 256, one per compute unit: all of them run at once and the redundant preparation
+ * is paid once per pass; but never more than 256 rows (measured faster at batch 32 than one round of larger groups).  >= 1 is
+ * taken as given (above n: n).  The bits do not depend on it.
+ *
+ * dinoseg_op_ncut_graph_split runs the graph launch of dinoseg_op_ncut_graph unchanged; only the host's cell limit differs.
+ *
+ * Refused (-1, the message names the entry, nothing is launched): everything the entries above refuse, with
+ * dinoseg_ncut_split_max_cells() as the cell limit; a null scratch or one not 16-byte aligned; rows_per_group below 0; B (ceil(n / R)
+ * + 1) beyond the launch range. */
+int32_t dinoseg_ncut_split_max_cells(void);
+int64_t dinoseg_ncut_split_graph_bytes(int32_t B, int32_t n);
+int64_t dinoseg_ncut_split_scratch_bytes(int32_t B, int32_t n);
+int dinoseg_op_ncut_graph_split(const void* planes, int32_t B, int32_t n, int32_t D, double tau, void* graph, int32_t* degree,
+                                void* stream);
+int dinoseg_op_ncut_iterate_split(const void* graph, const int32_t* degree, int32_t B, int32_t n, double eps, const float* z_in,
+                                  int32_t iters, int32_t rows_per_group, float* z_out, float* rho, uint8_t* fg, float* eigvec,
+                                  float* margin, int32_t* seed_cell, void* scratch, void* stream);
+
 /* ---- fine-tune step (replaces DINOSeg.training_step + autograd + optimizer.step, pl_torch_modules.py:258-268) ---- */
 
 /* Bind (or, with NULL, unbind) the fp32 gradient buffer of a parameter, same shape as the bound weight.  A parameter
