@@ -185,6 +185,10 @@ SIGNATURES = {
     "dinoseg_ncut_split_scratch_bytes": (_i64, [_i32, _i32]),
     "dinoseg_op_ncut_graph_split": (C.c_int, [_vp, _i32, _i32, _i32, _f64, _vp, _vp, _vp]),
     "dinoseg_op_ncut_iterate_split": (C.c_int, [_vp, _vp, _i32, _i32, _f64, _fp, _i32, _i32, _fp, _fp, _vp, _fp, _fp, _vp, _vp, _vp]),
+    # connected components of a label map and their object table: the scratch size (host only); labels -> ids, count, first, label,
+    # area, box, status
+    "dinoseg_components_scratch_bytes": (_i64, [_i32, _i32, _i32]),
+    "dinoseg_op_components": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

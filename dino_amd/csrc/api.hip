@@ -717,6 +717,15 @@ extern "C" int dinoseg_op_ncut_iterate_split(const void* graph, const int32_t* d
                                      scratch, reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int64_t dinoseg_components_scratch_bytes(int32_t B, int32_t H, int32_t W) { return components_scratch_bytes(B, H, W); }
+
+extern "C" int dinoseg_op_components(const int32_t* labels, int32_t B, int32_t H, int32_t W, int32_t connectivity, int32_t ignore,
+                                     int32_t max_objects, int32_t* ids, int32_t* count, int32_t* first, int32_t* label, int32_t* area,
+                                     int32_t* box, int32_t* status, void* scratch, void* stream) {
+    return launch_components(labels, B, H, W, connectivity, ignore, max_objects, ids, count, first, label, area, box, status, scratch,
+                             reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int dinoseg_op_confusion(const int32_t* pred, const int64_t* gt, int64_t n, int32_t n_classes, int64_t* cm, void* stream) {
     return launch_confusion(pred, gt, n, n_classes, cm, reinterpret_cast<hipStream_t>(stream));
 }

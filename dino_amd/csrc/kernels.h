@@ -415,6 +415,14 @@ int launch_ncut_iterate_split(const void* graph, const int32_t* degree, int B, i
                               int rows_per_group, float* z_out, float* rho, uint8_t* fg, float* eigvec, float* margin, int32_t* seed_cell,
                               void* scratch, hipStream_t s);
 
+// Connected components of label maps and their object table (components.hip; the rule: include/dinoseg.h, dinoseg_op_components): a
+// union-find per 64 x 32 tile in LDS, unions across tile edges by integer atomicMin, roots and per-segment root masks, a prefix sum per
+// frame, ids and the table.  Five plain launches ordered by the stream.  components_scratch_bytes: -1 for refusable arguments.
+long long components_scratch_bytes(int B, int H, int W);
+int launch_components(const int32_t* labels, int B, int H, int W, int connectivity, int ignore, int max_objects, int32_t* ids,
+                      int32_t* count, int32_t* first, int32_t* label, int32_t* area, int32_t* box, int32_t* status, void* scratch,
+                      hipStream_t s);
+
 // ---- fine-tune step (train.hip, attention_bwd.hip) ----
 struct AttnBwdParams {
     const bf16_t* q; const bf16_t* k; const bf16_t* v; long qkv_plane;   // forward operands [planes][B,H,npad,64]

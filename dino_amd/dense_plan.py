@@ -458,3 +458,45 @@ def ncut_plan(patch: int, x: torch.Tensor, tau=0.2, eps=1e-5, iters=64, seed=0, 
     if OH < hp or OW < wp:
         raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(hp, wp)}")
     return NcutPlan(kind, int(B), int(H), int(W), hp, wp, tau32, eps, iters, seed, OH, OW, chunk, split)
+
+
+# ---- connected components of a label map and their object table (include/dinoseg.h: dinoseg_op_components) ----
+COMPONENTS_MAX_SIDE = 8192            # DINOSEG_COMPONENTS_MAX_SIDE
+COMPONENTS_MAX_OBJECTS = 1 << 20      # DINOSEG_COMPONENTS_MAX_OBJECTS
+
+
+class ComponentsPlan(NamedTuple):
+    """What a connected-components call was asked for, validated: the frames' shape (``promoted``: the caller gave one [H, W] map),
+    the rule's parameters (``ignore`` as the operator takes it: -1 for "negatives only") and the rows of the object table."""
+    B: int
+    H: int
+    W: int
+    connectivity: int
+    ignore: int
+    max_objects: int
+    promoted: bool
+
+
+def components_plan(labels: torch.Tensor, connectivity=4, ignore=None, max_objects=256) -> ComponentsPlan:
+    """The shape and parameter checks of ``DINOSeg.components`` without a device.  ``labels``: a map [B, H, W] or [H, W] of any
+    integer dtype (bool and uint8 included) whose values fit int32.  Every ``ValueError`` is raised here, before any device use."""
+    if not isinstance(labels, torch.Tensor):
+        raise ValueError(f"expected the label map as a tensor, integer [B,H,W] or [H,W], got {type(labels).__name__}")
+    if labels.is_floating_point() or labels.is_complex():
+        raise ValueError(f"the label map must have an integer dtype (bool and uint8 included), got {labels.dtype}")
+    if labels.dim() not in (2, 3):
+        raise ValueError(f"the label map must be [B,H,W] or [H,W], got {tuple(labels.shape)}")
+    promoted = labels.dim() == 2
+    B, H, W = (1, *labels.shape) if promoted else labels.shape
+    B, H, W = int(B), int(H), int(W)
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"the label map {tuple(labels.shape)} is empty")
+    if H > COMPONENTS_MAX_SIDE or W > COMPONENTS_MAX_SIDE:
+        raise ValueError(f"frames of {H} x {W} exceed {COMPONENTS_MAX_SIDE} (COMPONENTS_MAX_SIDE) along a side")
+    if B * H * W >= 1 << 31:
+        raise ValueError(f"{B} frames of {H} x {W} hold {B * H * W} pixels; linear indices must stay below 2^31")
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or int(connectivity) not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    ignore = -1 if ignore is None else _int_in(ignore, -(1 << 31), (1 << 31) - 1, "ignore")
+    max_objects = _int_in(max_objects, 1, COMPONENTS_MAX_OBJECTS, "max_objects")
+    return ComponentsPlan(B, H, W, int(connectivity), ignore, max_objects, promoted)

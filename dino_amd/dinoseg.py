@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import capi
-from .dense_plan import (_pair, context_frames, dense_mode, frame_layout, guide_plan, guided_params, kmeans_plan, label_size,
+from .dense_plan import (_pair, components_plan, context_frames, dense_mode, frame_layout, guide_plan, guided_params, kmeans_plan, label_size,
                          multiscale_plan, ncut_plan, ncut_start, out_size, propagate_plan, resolution_message, sample_indices,
                          view_sizes, window_origins, window_plan)  # noqa: F401  (view_sizes, window_origins: re-exported)
 from .preprocess import resize_linear_u8
@@ -875,6 +875,10 @@ class DINOSeg(nn.Module):
         used.  Inference only.  ``split`` (``True``, or the rows per workgroup) deals every frame's rows to many workgroups, one launch
         per pass: the same bits in every field, a fraction of the latency, and grids of up to ``NCUT_SPLIT_MAX_CELLS`` cells (960 x
         960 at patch 8 fits) where the default stops at ``NCUT_MAX_CELLS``."""
+        return self._ncut(x, tau, eps, iters, seed, size, n_blocks, chunk, want_graph, split)[0]
+
+    def _ncut(self, x, tau, eps, iters, seed, size, n_blocks, chunk, want_graph, split):
+        """``ncut`` -> (its result, the signed margin fp32 [B, n] its labels were formed from, the plan)"""
         plan = ncut_plan(self.cfg.patch, x, tau, eps, iters, seed, size, chunk, split)
         if not 0 <= n_blocks <= self.cfg.n_blocks:
             raise ValueError(f"intermediate must be in [0, {self.cfg.n_blocks}]")
@@ -905,11 +909,82 @@ class DINOSeg(nn.Module):
             capi.check(lib.dinoseg_op_ncut_iterate(graph.data_ptr(), degree.data_ptr(), B, n, plan.eps, z.data_ptr(), plan.iters,
                                                    z.data_ptr(), rho.data_ptr() if plan.iters else None, fg.data_ptr(), eigvec.data_ptr(),
                                                    margin.data_ptr(), seed_cell.data_ptr(), self._stream()))
+        labels = self._margin_labels(margin, plan.hp, plan.wp, plan.OH, plan.OW)
+        return NcutResult(labels, fg, eigvec, seed_cell, rho, degree, graph.view(torch.uint64) if want_graph else None), margin, plan
+
+    def _margin_labels(self, margin: torch.Tensor, hp: int, wp: int, OH: int, OW: int) -> torch.Tensor:
+        """Pixel labels int32 [B, OH, OW] of a signed cell margin fp32 [B, hp wp]: the bilinear enlargement of the two-class map
+        (0, margin) with the first maximum (ties go to background)."""
+        B = margin.shape[0]
         two = torch.stack((torch.zeros_like(margin), margin), dim=2).contiguous()      # the two-class map [B, n, 2] = (0, margin)
-        labels = torch.empty((B, plan.OH, plan.OW), dtype=torch.int32, device=dev)
-        capi.check(lib.dinoseg_op_upsample_argmax(two.data_ptr(), B, plan.hp, plan.wp, 2, plan.OH, plan.OW, labels.data_ptr(), None,
-                                                  self._stream()))
-        return NcutResult(labels, fg, eigvec, seed_cell, rho, degree, graph.view(torch.uint64) if want_graph else None)
+        labels = torch.empty((B, OH, OW), dtype=torch.int32, device=self.device)
+        capi.check(capi.lib().dinoseg_op_upsample_argmax(two.data_ptr(), B, hp, wp, 2, OH, OW, labels.data_ptr(), None, self._stream()))
+        return labels
+
+    # ---- connected components of a label map and their object table (csrc/components.hip) ----
+    @torch.no_grad()
+    def components(self, labels: torch.Tensor, connectivity: int = 4, ignore=None, max_objects: int = 256) -> "ComponentsResult":
+        """Objects of a label map: its connected components, numbered in raster order of their first pixels, and per component
+        the first pixel, the label, the area and the box.  ``labels``: a map [B,H,W] or [H,W] (taken as one frame) of any integer
+        dtype whose values fit int32, on the device or on the host -- the ``labels`` of ``segment*``, ``cluster`` and ``ncut`` as
+        they come -> ``ComponentsResult(ids int32 [B,H,W], count int32 [B], first int32 [B,M], label int32 [B,M], area int32
+        [B,M], box int32 [B,M,4])`` with M = ``max_objects``.  A pixel is void (id -1) when its label is negative or equals
+        ``ignore``; two pixels belong together when a path of 4-neighbours (``connectivity=8``: 8-neighbours) of one label joins
+        them.  ``count`` is the true number of components, however large; the table describes the first ``min(count, M)`` of them
+        (``box`` = (x0, y0, x1, y1), half-open) and holds first = label = -1, area = 0, box = 0 behind them (the rule:
+        include/dinoseg.h, dinoseg_op_components).  The conversion to int32 and the copy to the device are torch's; nothing
+        synchronises with the host.  Inference only."""
+        plan = components_plan(labels, connectivity, ignore, max_objects)
+        self._require_gpu()
+        lib, dev, B, H, W, M = capi.lib(), self.device, plan.B, plan.H, plan.W, plan.max_objects
+        lab = labels.to(device=dev, dtype=torch.int32).contiguous()
+        nbytes = lib.dinoseg_components_scratch_bytes(B, H, W)
+        if nbytes < 0:
+            raise capi.DinosegError(f"dinoseg_components_scratch_bytes refused {B} frames of {H} x {W}")
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        ids = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+        count, status = (torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(2))
+        first, label, area = (torch.empty((B, M), dtype=torch.int32, device=dev) for _ in range(3))
+        box = torch.empty((B, M, 4), dtype=torch.int32, device=dev)
+        capi.check(lib.dinoseg_op_components(lab.data_ptr(), B, H, W, plan.connectivity, plan.ignore, M, ids.data_ptr(), count.data_ptr(),
+                                             first.data_ptr(), label.data_ptr(), area.data_ptr(), box.data_ptr(), status.data_ptr(),
+                                             scratch.data_ptr(), self._stream()))
+        return ComponentsResult(ids, count, first, label, area, box)
+
+    @torch.no_grad()
+    def discover(self, x: torch.Tensor, tau: float = 0.2, eps: float = 1e-5, iters: int = 64, seed: int = 0, size=None, n_blocks: int = 0,
+                 chunk: int = 32, split=True, connectivity: int = 4) -> "DiscoverResult":
+        """Unsupervised single-object discovery (TokenCut's ``detect_box``): ``ncut``, then the connected component of the
+        foreground cells that holds the seed cell, its box and its mask.  Arguments as ``ncut`` -> ``DiscoverResult(labels int32
+        [B,OH,OW] with 1 = the object, box int32 [B,4] = (x0, y0, x1, y1) half-open in the coordinates of the frame (H, W) whatever
+        ``size`` is, found uint8 [B], cells uint8 [B,n], area int32 [B] in cells, ncut NcutResult)``.  ``cells`` is the component
+        of ``ncut.fg`` on the patch grid (``connectivity=4``, scipy.ndimage.label's default, as TokenCut has it) around
+        ``ncut.seed_cell``; ``box`` is the component's cell box times the patch size; ``labels`` is the enlargement of the margin
+        with every cell outside ``cells`` pushed to the background side.  ``found`` is 0 where the seed cell itself is background
+        (a one-cell grid, a constant vector): then ``cells`` is empty and ``box`` and ``area`` are 0.  No host synchronisation.
+        Inference only."""
+        if isinstance(connectivity, bool) or connectivity not in (4, 8):
+            raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+        res, margin, plan = self._ncut(x, tau, eps, iters, seed, size, n_blocks, chunk, False, split)
+        return DiscoverResult(*self._discover_from(margin, res.fg, res.seed_cell, plan.hp, plan.wp, plan.OH, plan.OW, connectivity), res)
+
+    def _discover_from(self, margin: torch.Tensor, fg: torch.Tensor, seed_cell: torch.Tensor, hp: int, wp: int, OH: int, OW: int,
+                       connectivity: int = 4):
+        """``discover`` from the cut on: (margin fp32 [B,n], fg uint8 [B,n], seed_cell int32 [B]) on the device -> (labels, box,
+        found, cells, area)."""
+        B, n, p = fg.shape[0], hp * wp, self.cfg.patch
+        comp = self.components(fg.view(B, hp, wp), connectivity, ignore=0, max_objects=n)
+        at = seed_cell.to(torch.int64).view(B, 1)
+        k = torch.gather(comp.ids.view(B, n), 1, at)                                   # the seed's component, -1 on a background seed
+        found = torch.gather(fg, 1, at).view(B)
+        cells = (comp.ids.view(B, n) == k) & (k >= 0)
+        row = k.clamp(min=0)
+        hit = (k >= 0).view(B)
+        box = torch.gather(comp.box, 1, row.view(B, 1, 1).expand(B, 1, 4)).view(B, 4) * p
+        box = torch.where(hit.view(B, 1), box, torch.zeros_like(box))
+        area = torch.where(hit, torch.gather(comp.area, 1, row).view(B), torch.zeros_like(comp.count))
+        labels = self._margin_labels(torch.where(cells, margin, -margin.abs()), hp, wp, OH, OW)
+        return labels, box, found, cells.to(torch.uint8), area
 
     def predict_dense(self, img, size=None, scales=None, flip: bool = False, window=None, stride=None, guided=None) -> np.ndarray:
         """The pixel-resolution sibling of ``predict()``: the image (PIL.Image or HxWx3 uint8 array) is resized to r x r on the
@@ -1797,3 +1872,28 @@ class NcutResult(NamedTuple):
     rho: torch.Tensor
     degree: torch.Tensor
     graph: Optional[torch.Tensor]
+
+
+# --------------------------------------------------------------------------- objects of a label map (connected components)
+class ComponentsResult(NamedTuple):
+    """What ``DINOSeg.components`` returns: per pixel the number of its component int32 [B, H, W] (-1 on void pixels), the number of
+    components int32 [B], and the table of the first M of them: the first pixel's linear index, the label, the area, and the half-open
+    box (x0, y0, x1, y1), int32 [B, M] / [B, M, 4]; rows behind the last component hold first = label = -1, area = 0, box = 0."""
+    ids: torch.Tensor
+    count: torch.Tensor
+    first: torch.Tensor
+    label: torch.Tensor
+    area: torch.Tensor
+    box: torch.Tensor
+
+
+class DiscoverResult(NamedTuple):
+    """What ``DINOSeg.discover`` returns: pixel labels int32 [B, OH, OW] (1 = the object), its box int32 [B, 4] = (x0, y0, x1, y1)
+    half-open in frame coordinates, whether the seed cell is foreground uint8 [B], the object's cells uint8 [B, n], their number int32
+    [B], and the cut they were taken from."""
+    labels: torch.Tensor
+    box: torch.Tensor
+    found: torch.Tensor
+    cells: torch.Tensor
+    area: torch.Tensor
+    ncut: NcutResult

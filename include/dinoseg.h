@@ -595,6 +595,51 @@ int dinoseg_op_ncut_iterate_split(const void* graph, const int32_t* degree, int3
                                   int32_t iters, int32_t rows_per_group, float* z_out, float* rho, uint8_t* fg, float* eigvec,
                                   float* margin, int32_t* seed_cell, void* scratch, void* stream);
 
+/* ---- connected components of a label map and their object table (what scipy.ndimage.label plus find_objects give on the host: how
+ * many objects a label map holds, which pixels each one owns, its area and its box).  No reference counterpart.  components.hip.
+ * Everything is an integer; the result is a function of the input alone, bit for bit, from run to run.
+ *
+ * Input: labels int32 [B][H][W]; connectivity 4 or 8; ignore int32.
+ *
+ * 1. Void.  A pixel is void when its label is negative or equals `ignore` (ignore = -1: negatives only).
+ * 2. Joined.  Two non-void pixels of one frame are joined when they are 4-neighbours ((x +- 1, y) or (x, y +- 1)) and carry the same
+ *    label; with connectivity = 8 also when they are diagonal neighbours ((x +- 1, y +- 1)) with the same label.
+ * 3. Components are the classes of the transitive closure of "joined".  Frames never interact.
+ * 4. The first pixel of a component is its pixel with the smallest linear index y W + x.
+ * 5. The components of a frame are numbered 0, 1, .. in ascending order of their first pixels (raster order, the order of
+ *    scipy.ndimage.label on a one-class map).
+ *
+ * Output:
+ *   ids     int32 [B][H][W]   the number of the pixel's component, -1 on void pixels;
+ *   count   int32 [B]         the true number of components of the frame, however large;
+ *   the object table of M = max_objects rows per frame: first int32 [B][M] (the first pixel's linear index), label int32 [B][M]
+ *   (the component's label), area int32 [B][M] (its pixel count), box int32 [B][M][4] = (x0, y0, x1, y1), half-open: x0 / y0 the
+ *   smallest x / y of any of its pixels, x1 / y1 the largest plus one.  Row k < min(count, M) describes component k; rows from
+ *   min(count, M) on hold first = -1, label = -1, area = 0, box = 0.  ids and count do not depend on M;
+ *   status  int32 [B]         0.  (1 would say that a loop of the launches below ran into its step cap, which their invariant rules
+ *                             out: every parent slot only ever receives a smaller index, so every chain strictly descends.)
+ *
+ * Launches (five, plain, on the caller's stream behind a memset of status; ordered by the stream alone: no cooperative launch, no grid
+ * barrier, no flag between workgroups, no host synchronisation, no allocation): a union-find per 64 x 32 tile in LDS rooted at the
+ * tile's smallest index; unions across tile edges by integer atomicMin on the parent array (the fixed point -- every component rooted
+ * at its smallest index -- is unique, so the arrival order does not show); every pixel's root and, per row segment of 64 pixels, the
+ * bit mask of the pixels that are roots; per frame the prefix sum of the masks' popcounts (segments are in raster order) and count;
+ * ids = the prefix of the root's segment + the popcount of its mask below the root, and the table by integer add / min / max, one per
+ * wave and distinct component.  No floating-point atomic anywhere.
+ *
+ * scratch: dinoseg_components_scratch_bytes(B, H, W) = 4 B H W + 12 B H ceil(W / 64) bytes rounded up to 16, 16-byte aligned device
+ * memory (the parent array, the masks, the prefixes); it holds nothing between calls.  Host only; -1 for refusable arguments.
+ *
+ * Refused on the host (-1, the message names the entry) before anything is launched: a null pointer; B, H or W below 1; H or W above
+ * 8192; B H W >= 2^31; max_objects outside 1 .. 2^20; connectivity outside {4, 8}; a 32-bit array not 4-byte aligned or the scratch
+ * not 16-byte aligned. */
+#define DINOSEG_COMPONENTS_MAX_SIDE 8192
+#define DINOSEG_COMPONENTS_MAX_OBJECTS (1 << 20)
+int64_t dinoseg_components_scratch_bytes(int32_t B, int32_t H, int32_t W);
+int dinoseg_op_components(const int32_t* labels, int32_t B, int32_t H, int32_t W, int32_t connectivity, int32_t ignore,
+                          int32_t max_objects, int32_t* ids, int32_t* count, int32_t* first, int32_t* label, int32_t* area, int32_t* box,
+                          int32_t* status, void* scratch, void* stream);
+
 /* ---- fine-tune step (replaces DINOSeg.training_step + autograd + optimizer.step, pl_torch_modules.py:258-268) ---- */
 
 /* Bind (or, with NULL, unbind) the fp32 gradient buffer of a parameter, same shape as the bound weight.  A parameter
