@@ -6,15 +6,12 @@
 //   kmeans_init_kernel        one wave per centroid row: ||row||^2 and the quotient in fp64 (or the row as it is), the fp32 row and
 //                             its split 2^10 c = hi + lo into planes [2][K][D].
 //   kmeans_assign_kernel      one workgroup (4 waves) per tile of 64 consecutive points.  The centroid planes are walked in blocks of
-//                             64 rows; per block and 64-wide slice of D the point tile and the centroid block (hi and lo, 4 x 8 KiB,
-//                             128-byte rows under the library's swizzle) are staged in LDS -- the next slice's global loads are in
-//                             flight under the current slice's MFMAs -- and wave (qh, kh) multiplies centroids 32 kh .. by points
-//                             32 qh .. with the arithmetic of propagate_scores_kernel: lo.hi + hi.lo + hi.hi on
-//                             v_mfma_f32_32x32x16_f16, fp32 accumulators, slices in ascending order.  A lane owns one point and 16
-//                             centroids of the block in ascending order; its running (score, index) pair stays in registers (a strict
-//                             > keeps the lower index).  The four pairs of a point meet in LDS under the total order (score
-//                             descending, index ascending).  The [N, K] scores are stored only on request.  The tile's objective
-//                             share (xor tree over the 64 points) and its count of changed points go to the scratch.
+//                             64 rows by the family's pair walk (pair_common.h); wave (qh, kh) multiplies centroids 32 kh .. by points
+//                             32 qh .. with the arithmetic of propagate_scores_kernel: lo.hi + hi.lo + hi.hi into one accumulator.  A
+//                             lane owns one point and 16 centroids of the block in ascending order; its running (score, index) pair
+//                             stays in registers (a strict > keeps the lower index).  The four pairs of a point meet in LDS under the
+//                             total order (score descending, index ascending).  The [N, K] scores are stored only on request.  The
+//                             tile's objective share (xor tree over the 64 points) and its count of changed points go to the scratch.
 //   kmeans_records_kernel     one workgroup: the tiles' shares in a fixed order -> objective and moved.
 //   kmeans_partial_kernel     one workgroup per (range of points, cluster), R = min(ceil(N / 256), 4096 / K clamped to 16 .. 64) ranges
 //                             (measured: 64 ranges at K = 256 were 16 384 workgroups with a row or two each and took 86 us): the
@@ -28,6 +25,7 @@
 #include "../../include/dinoseg.h"
 #include "common.h"
 #include "kernels.h"
+#include "pair_common.h"
 
 #include <climits>
 
@@ -35,9 +33,7 @@ namespace dseg {
 
 namespace {
 
-constexpr int KM_TILE = 64;                     // points of an assign workgroup
-constexpr int KM_STAGE = 32768;                 // Phi, Plo, Chi, Clo: 64 rows x 128 B each
-constexpr float KM_UNSCALE = 0x1p-20f;          // planes carry 2^10 x: products 2^20 <x, c>
+constexpr int KM_TILE = PAIR_TILE;              // points of an assign workgroup
 constexpr int KM_MAX_RANGES = 64;               // point ranges of the update: partial centroid sets in the scratch
 constexpr int KM_MIN_RANGES = 16;               // ... the cap at large K
 constexpr int KM_RANGE_WGS = 4096;              // ... R K stays near this many workgroups
@@ -45,17 +41,13 @@ constexpr int KM_RANGE_MIN = 256;               // a range holds at least this m
 constexpr int KM_CHUNK = 1024;                  // assignments scanned per list
 constexpr long long KM_MAX_POINTS = (1ll << 31) - 256;
 
-__device__ __forceinline__ bool km_better(float s, int j, float s2, int j2) { return s > s2 || (s == s2 && j < j2); }
-
 // the fp32 row element and its planes: c = fp32(q), 2^10 c = hi + lo
 __device__ __forceinline__ void km_write_unit(double q, float* c, uint16_t* hi, uint16_t* lo) {
     const float c32 = (float)q;
-    const double v = (double)c32 * 1024.0;
-    const _Float16 h = (_Float16)(float)v;
-    const _Float16 l = (_Float16)(float)(v - (double)(float)h);
+    const UnitSplit v = split_unit((double)c32 * 1024.0);
     *c = c32;
-    *hi = __builtin_bit_cast(uint16_t, h);
-    *lo = __builtin_bit_cast(uint16_t, l);
+    *hi = v.hi;
+    *lo = v.lo;
 }
 
 // rows may be the centroids themselves: every element is read and written by the same lane, and the norm is complete before the first write
@@ -72,8 +64,7 @@ __global__ __launch_bounds__(256) void kmeans_init_kernel(const float* rows, int
             const double v = (double)src[d];
             ss = fma(v, v, ss);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);       // (xor tree: every lane holds the same bits)
+        ss = wave_sum_f64(ss);
         inv = 1.0 / fmax(sqrt(ss), 1e-12);
     }
     float* c = centroids + (size_t)row * D;
@@ -87,98 +78,54 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const uint16_t* __re
                                                             const uint16_t* __restrict__ cplanes, int K, int D, const int32_t* prev,
                                                             int32_t* assign, float* __restrict__ best, float* __restrict__ scores,
                                                             float* __restrict__ tile_obj, int32_t* __restrict__ tile_moved) {
-    __shared__ __attribute__((aligned(16))) char km_lds[KM_STAGE];
+    __shared__ __attribute__((aligned(16))) char km_lds[PAIR_STAGE];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
     const int qh = wave >> 1, kh = wave & 1;
     const int i0 = (int)blockIdx.x * KM_TILE;                           // (N <= 2^31 - 256: i0 + 63 fits)
-    const int nkb = (K + 63) >> 6, ndc = D >> 6, total = nkb * ndc;
 
     // the lane's point in the selection
     const int pi = i0 + qh * 32 + lr;
     const bool pvalid = pi < N;
 
-    // staging: thread t moves 16 bytes (chunk t & 7) of rows (t >> 3) and (t >> 3) + 32 of each of the four tiles
-    const int srow = tid >> 3, schunk = tid & 7;
-    size_t poff[2];
-    int soff[2];
+    // the tile's points as the walk stages them (pair_common.h)
+    size_t prow[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const int row = srow + 32 * h;
-        const int i = min(i0 + row, N - 1);                             // (a row past the last point re-reads a real one)
+        const int i = min(i0 + pair_stage_row(h), N - 1);               // (a row past the last point re-reads a real one)
         const int b = i / n, c = i - b * n;
-        poff[h] = ((size_t)b * 2 * n + c) * D + schunk * 8;
-        soff[h] = tile_off_bytes(row, schunk);
+        prow[h] = ((size_t)b * 2 * n + c) * D;
     }
-    const size_t p_lo = (size_t)n * D, c_lo = (size_t)K * D;
-    uint4 g_ph0, g_ph1, g_pl0, g_pl1, g_ch0, g_ch1, g_cl0, g_cl1;         // the slice in flight (named: an array would live in scratch)
-    auto ld16 = [](const uint16_t* p) { return *reinterpret_cast<const uint4*>(p); };
-    auto fetch = [&](int it) {
-        const int kb = it / ndc;
-        const size_t dofs = (size_t)(it - kb * ndc) * 64;
-        // (a centroid row past K re-reads a real one; never selected)
-        const size_t c0 = (size_t)min(kb * 64 + srow, K - 1) * D + schunk * 8 + dofs;
-        const size_t c1 = (size_t)min(kb * 64 + srow + 32, K - 1) * D + schunk * 8 + dofs;
-        g_ph0 = ld16(points + poff[0] + dofs);
-        g_ph1 = ld16(points + poff[1] + dofs);
-        g_pl0 = ld16(points + p_lo + poff[0] + dofs);
-        g_pl1 = ld16(points + p_lo + poff[1] + dofs);
-        g_ch0 = ld16(cplanes + c0);
-        g_ch1 = ld16(cplanes + c1);
-        g_cl0 = ld16(cplanes + c_lo + c0);
-        g_cl1 = ld16(cplanes + c_lo + c1);
-    };
-
-    // fragment addresses: row lr of the wave's half, chunk 2 s + lh of the 128-byte row
-    int fq[4], fk[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        fq[s] = tile_off_bytes(qh * 32 + lr, s * 2 + lh);
-        fk[s] = 16384 + tile_off_bytes(kh * 32 + lr, s * 2 + lh);
-    }
+    // (a centroid row past K re-reads a real one; never selected)
+    auto centroid_row = [&](int j) { return (size_t)min(j, K - 1) * D; };
 
     float bs = -INFINITY;                                               // the lane's running pair
     int bj = INT_MAX;
     f32x16 acc;
-    fetch(0);
-    for (int it = 0; it < total; ++it) {
-        const int kb = it / ndc, dc = it - kb * ndc;
-        __syncthreads();                                                // everyone is done reading the previous slice
-        *reinterpret_cast<uint4*>(km_lds + soff[0]) = g_ph0;
-        *reinterpret_cast<uint4*>(km_lds + soff[1]) = g_ph1;
-        *reinterpret_cast<uint4*>(km_lds + 8192 + soff[0]) = g_pl0;
-        *reinterpret_cast<uint4*>(km_lds + 8192 + soff[1]) = g_pl1;
-        *reinterpret_cast<uint4*>(km_lds + 16384 + soff[0]) = g_ch0;
-        *reinterpret_cast<uint4*>(km_lds + 16384 + soff[1]) = g_ch1;
-        *reinterpret_cast<uint4*>(km_lds + 24576 + soff[0]) = g_cl0;
-        *reinterpret_cast<uint4*>(km_lds + 24576 + soff[1]) = g_cl1;
-        __syncthreads();
-        if (it + 1 < total) fetch(it + 1);
-        if (dc == 0) {
+    auto zero = [&]() {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const bf16x8 phi = lds_frag(km_lds + fq[s]), plo = lds_frag(km_lds + 8192 + fq[s]);
-            const bf16x8 chi = lds_frag(km_lds + fk[s]), clo = lds_frag(km_lds + 8192 + fk[s]);
-            acc = mfma32f<FMT_FP16>(clo, phi, acc);
-            acc = mfma32f<FMT_FP16>(chi, plo, acc);
-            acc = mfma32f<FMT_FP16>(chi, phi, acc);
-        }
-        if (dc != ndc - 1) continue;
-        // the block's scores: register r of this lane is centroid acc_row(r, lh) of the wave's half (ascending in r), point lr
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    };
+    auto slice = [&](bf16x8 phi, bf16x8 plo, bf16x8 chi, bf16x8 clo) {
+        acc = mfma32f<FMT_FP16>(clo, phi, acc);
+        acc = mfma32f<FMT_FP16>(chi, plo, acc);
+        acc = mfma32f<FMT_FP16>(chi, phi, acc);
+    };
+    // the block's scores: register r of this lane is centroid acc_row(r, lh) of the wave's half (ascending in r), point lr
+    auto select = [&](int kb) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int j = kb * 64 + kh * 32 + acc_row(r, lh);
             if (j >= K) continue;
-            const float s = acc[r] * KM_UNSCALE + 0.f;                 // (+ 0: a negative zero becomes the positive one)
+            const float s = acc[r] * PAIR_UNSCALE + 0.f;                // (+ 0: a negative zero becomes the positive one)
             if (scores && pvalid) scores[(size_t)pi * K + j] = s;
             if (s > bs) {                                               // (strict: the lower index keeps an exact tie)
                 bs = s;
                 bj = j;
             }
         }
-    }
+    };
+    pair_walk(km_lds, points, (size_t)n * D, prow, cplanes, (size_t)K * D, (K + 63) >> 6, D >> 6, centroid_row, [](int) {}, zero, slice,
+              select);
     __syncthreads();                                                    // the staging area becomes the four pairs of every point
     float* ms = reinterpret_cast<float*>(km_lds);
     int* mj = reinterpret_cast<int*>(km_lds + 1024);
@@ -193,7 +140,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const uint16_t* __re
         for (int o = 32; o <= 96; o += 32) {
             const float s2 = ms[t0 + o];
             const int j2 = mj[t0 + o];
-            if (km_better(s2, j2, s, j)) { s = s2; j = j2; }
+            if (better(s2, j2, s, j)) { s = s2; j = j2; }
         }
         const int i = i0 + tid;
         float o = 0.f;
@@ -362,8 +309,7 @@ __global__ __launch_bounds__(256) void kmeans_finalize_kernel(const float* __res
         m_lds[d] = m;
         ss = fma((double)m, (double)m, ss);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    ss = wave_sum_f64(ss);
     if (lane == 0) wss[wave] = ss;
     __syncthreads();
     ss = ((wss[0] + wss[1]) + wss[2]) + wss[3];

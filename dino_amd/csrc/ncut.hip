@@ -6,92 +6,51 @@
 // order of summation is a function of n alone.
 //
 //   ncut_graph_kernel     one workgroup (4 waves) per (frame, tile of 64 query cells).  The frame's own rows are walked as key blocks
-//                         of 64; per block and 64-wide slice of D the query tile and the key block (hi and lo, 4 x 8 KiB, 128-byte
-//                         rows under the library's swizzle) are staged in LDS -- the next slice's global loads are in flight under
-//                         the current slice's MFMAs -- and wave (qh, kh) multiplies queries 32 qh .. by keys 32 kh .. on
-//                         v_mfma_f32_32x32x16_f16 into THREE accumulators, lo.hi, hi.lo and hi.hi, combined once per block as
-//                         (lo.hi + hi.lo) + hi.hi: s_ij and s_ji are the same bits (the cross terms swap roles, fp32 addition
-//                         commutes), so the graph is symmetric bit for bit.  A lane owns one key and 16 queries; one ballot per
-//                         accumulator register turns 64 decisions into two half words (two queries x 32 keys), the four waves' halves
-//                         meet in LDS, and 64 threads store the block's word of their query and add its popcount to the degree they
-//                         keep in a register.  A query's whole row belongs to one workgroup: no atomics.
-//   ncut_iterate_kernel   one workgroup of 1024 threads per frame runs every pass in one launch.  z, xv = z r, r and u live in LDS.
-//                         The row sums: rows are dealt to the 16 waves, a row's words are wave-uniform (scalar loads; the frame's
-//                         graph is read once per pass and stays in L2 / Infinity Cache), lane l owns keys l, l + 64, ...: per word one
-//                         conflict-free ds_read_b32 of xv[64 w + l] (shared by the two rows a wave walks at a time) and one select on
-//                         the word itself as the lane mask, added in ascending w; the 64 lanes meet in an xor tree.  The global sums (S, rho, <u, z>, ||q||^2, the mean) are fp64:
-//                         thread t adds its cells t, t + 1024, ... in order, an xor tree per wave, the 16 waves in wave order.
+//                         of 64 by the family's pair walk (pair_common.h); wave (qh, kh) multiplies queries 32 qh .. by keys 32 kh ..
+//                         into THREE accumulators, lo.hi, hi.lo and hi.hi, combined once per block as (lo.hi + hi.lo) + hi.hi: s_ij
+//                         and s_ji are the same bits (the cross terms swap roles, fp32 addition commutes), so the graph is symmetric
+//                         bit for bit.  A lane owns one key and 16 queries; one ballot per accumulator register turns 64 decisions
+//                         into two half words (two queries x 32 keys), the four waves' halves meet in LDS, and 64 threads store the
+//                         block's word of their query and add its popcount to the degree they keep in a register.  A query's whole
+//                         row belongs to one workgroup: no atomics.
+//   ncut_iterate_kernel   one workgroup of 1024 threads per frame runs every pass in one launch.  z, xv = z r, r and u live in LDS;
+//                         the frame's graph is read once per pass and stays in L2 / Infinity Cache.  The weights, the deflation, the
+//                         row sums, the global sums and the result are the pieces of ncut_common.h, which states their orders of
+//                         summation; this kernel's own are rho (a wave chains its rows in order by fp64 fma, the 16 waves in wave
+//                         order) and p = (z + y) / 2.
 // (ncut_split.hip runs the same passes with a frame's rows dealt to many workgroups, one launch per pass, bit for bit the same.)
 #include "../../include/dinoseg.h"
 #include "common.h"
 #include "kernels.h"
+#include "ncut_common.h"
+#include "pair_common.h"
 
-#include <climits>
 #include <cmath>
 
 namespace dseg {
 
 namespace {
 
-constexpr int NC_TILE = 64;                     // query cells of a graph workgroup
-constexpr int NC_STAGE = 32768;                 // Qhi, Qlo, Khi, Klo: 64 rows x 128 B each
-constexpr float NC_UNSCALE = 0x1p-20f;          // planes carry 2^10 x: products 2^20 <x_i, x_j>
-constexpr int NC_THREADS = 1024, NC_WAVES = NC_THREADS / 64;
-constexpr int NC_LDS_BYTES = 160 * 1024;        // the CU's whole LDS
-constexpr int NC_FIXED_BYTES = 1024;            // the reduction slots: 2 x 16 fp64, 16 fp32 + 16 int32
 constexpr int NC_VECTORS = 4;                   // z, xv, r, u
-constexpr int NC_PAD_BYTES = 256;               // the last word's pad lanes read up to 63 floats past a vector: they stay inside
-constexpr int NC_MAX_CELLS = (NC_LDS_BYTES - NC_FIXED_BYTES - NC_PAD_BYTES) / (4 * NC_VECTORS);      // 10 160
-constexpr int NC_DEFAULT_LDS_BYTES = 64 * 1024; // beyond it a launch needs the opt-in
-constexpr int NC_MAX_ITERS = 4096;
-constexpr long long NC_MAX_GRID = 0x7fffffffll;
+constexpr int NC_MAX_CELLS = nc_cell_limit(NC_VECTORS);
+static_assert(NC_MAX_CELLS == 10160, "the one-workgroup entries publish this limit");
+constexpr const char* NC_FITS = "vectors fit the LDS of one workgroup";
 
 __global__ __launch_bounds__(256) void ncut_graph_kernel(const uint16_t* __restrict__ planes, int n, int D, float tau, int tiles,
                                                          unsigned long long* __restrict__ graph, int32_t* __restrict__ degree) {
-    __shared__ __attribute__((aligned(16))) char nc_lds[NC_STAGE];
+    __shared__ __attribute__((aligned(16))) char nc_lds[PAIR_STAGE];
     __shared__ uint32_t halfw[NC_TILE * 2];                             // [query][key half] of the block just finished
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31;
     const int qh = wave >> 1, kh = wave & 1;
     const int b = (int)blockIdx.x / tiles, i0 = ((int)blockIdx.x - b * tiles) * NC_TILE;
-    const int nkb = (n + 63) >> 6, ndc = D >> 6, total = nkb * ndc;
+    const int nkb = (n + 63) >> 6;
     const uint16_t* fr = planes + (size_t)b * 2 * n * D;                // the frame's hi plane [n][D]; its lo plane follows
     const size_t p_lo = (size_t)n * D;
 
-    // staging: thread t moves 16 bytes (chunk t & 7) of rows (t >> 3) and (t >> 3) + 32 of each of the four tiles
-    const int srow = tid >> 3, schunk = tid & 7;
-    size_t qoff[2];
-    int soff[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int row = srow + 32 * h;
-        qoff[h] = (size_t)min(i0 + row, n - 1) * D + schunk * 8;        // (a row past the last cell re-reads a real one; never stored)
-        soff[h] = tile_off_bytes(row, schunk);
-    }
-    uint4 g_qh0, g_qh1, g_ql0, g_ql1, g_kh0, g_kh1, g_kl0, g_kl1;         // the slice in flight (named: an array would live in scratch)
-    auto ld16 = [](const uint16_t* p) { return *reinterpret_cast<const uint4*>(p); };
-    auto fetch = [&](int it) {
-        const int kb = it / ndc;
-        const size_t dofs = (size_t)(it - kb * ndc) * 64;
-        // (a key row past n re-reads a real one; its decision is forced to 0)
-        const size_t k0 = (size_t)min(kb * 64 + srow, n - 1) * D + schunk * 8 + dofs;
-        const size_t k1 = (size_t)min(kb * 64 + srow + 32, n - 1) * D + schunk * 8 + dofs;
-        g_qh0 = ld16(fr + qoff[0] + dofs);
-        g_qh1 = ld16(fr + qoff[1] + dofs);
-        g_ql0 = ld16(fr + p_lo + qoff[0] + dofs);
-        g_ql1 = ld16(fr + p_lo + qoff[1] + dofs);
-        g_kh0 = ld16(fr + k0);
-        g_kh1 = ld16(fr + k1);
-        g_kl0 = ld16(fr + p_lo + k0);
-        g_kl1 = ld16(fr + p_lo + k1);
-    };
-
-    // fragment addresses: row lr of the wave's half, chunk 2 s + lh of the 128-byte row
-    int fq[4], fk[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        fq[s] = tile_off_bytes(qh * 32 + lr, s * 2 + lh);
-        fk[s] = 16384 + tile_off_bytes(kh * 32 + lr, s * 2 + lh);
-    }
+    // the tile's query rows as the walk stages them (pair_common.h); a row past the last cell re-reads a real one and is never stored,
+    // a key row past n re-reads a real one and its decision is forced to 0
+    const size_t qrow[2] = {(size_t)min(i0 + pair_stage_row(0), n - 1) * D, (size_t)min(i0 + pair_stage_row(1), n - 1) * D};
+    auto key_row = [&](int j) { return (size_t)min(j, n - 1) * D; };
     // lane l < 32 carries the half word of query l of the wave's half: accumulator register my_r of lane half my_h is that query
     const int my_r = (lr & 3) + 4 * (lr >> 3), my_h = (lr >> 2) & 1;
 
@@ -107,65 +66,39 @@ __global__ __launch_bounds__(256) void ncut_graph_kernel(const uint16_t* __restr
     };
 
     f32x16 acc_lh, acc_hl, acc_hh;
-    fetch(0);
-    for (int it = 0; it < total; ++it) {
-        const int kb = it / ndc, dc = it - kb * ndc;
-        __syncthreads();                                                // everyone is done reading the previous slice; halfw is complete
-        if (dc == 0 && kb > 0) flush(kb - 1);
-        *reinterpret_cast<uint4*>(nc_lds + soff[0]) = g_qh0;
-        *reinterpret_cast<uint4*>(nc_lds + soff[1]) = g_qh1;
-        *reinterpret_cast<uint4*>(nc_lds + 8192 + soff[0]) = g_ql0;
-        *reinterpret_cast<uint4*>(nc_lds + 8192 + soff[1]) = g_ql1;
-        *reinterpret_cast<uint4*>(nc_lds + 16384 + soff[0]) = g_kh0;
-        *reinterpret_cast<uint4*>(nc_lds + 16384 + soff[1]) = g_kh1;
-        *reinterpret_cast<uint4*>(nc_lds + 24576 + soff[0]) = g_kl0;
-        *reinterpret_cast<uint4*>(nc_lds + 24576 + soff[1]) = g_kl1;
-        __syncthreads();
-        if (it + 1 < total) fetch(it + 1);
-        if (dc == 0) {
+    // (the walk's first barrier of a block completes halfw of the block before)
+    auto flush_previous = [&](int kb) {
+        if (kb > 0) flush(kb - 1);
+    };
+    auto zero = [&]() {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                acc_lh[r] = 0.f;
-                acc_hl[r] = 0.f;
-                acc_hh[r] = 0.f;
-            }
+        for (int r = 0; r < 16; ++r) {
+            acc_lh[r] = 0.f;
+            acc_hl[r] = 0.f;
+            acc_hh[r] = 0.f;
         }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const bf16x8 qhi = lds_frag(nc_lds + fq[s]), qlo = lds_frag(nc_lds + 8192 + fq[s]);
-            const bf16x8 khi = lds_frag(nc_lds + fk[s]), klo = lds_frag(nc_lds + 8192 + fk[s]);
-            acc_lh = mfma32f<FMT_FP16>(qlo, khi, acc_lh);
-            acc_hl = mfma32f<FMT_FP16>(qhi, klo, acc_hl);
-            acc_hh = mfma32f<FMT_FP16>(qhi, khi, acc_hh);
-        }
-        if (dc != ndc - 1) continue;
-        // the block's decisions: register r of this lane is query acc_row(r, lh) of the wave's half, key lr of the wave's half
+    };
+    auto slice = [&](bf16x8 qhi, bf16x8 qlo, bf16x8 khi, bf16x8 klo) {
+        acc_lh = mfma32f<FMT_FP16>(qlo, khi, acc_lh);
+        acc_hl = mfma32f<FMT_FP16>(qhi, klo, acc_hl);
+        acc_hh = mfma32f<FMT_FP16>(qhi, khi, acc_hh);
+    };
+    // the block's decisions: register r of this lane is query acc_row(r, lh) of the wave's half, key lr of the wave's half
+    auto decide = [&](int kb) {
         const bool kvalid = kb * 64 + kh * 32 + lr < n;                 // (pad bits are zero)
         uint32_t mine = 0;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float s = ((acc_lh[r] + acc_hl[r]) + acc_hh[r]) * NC_UNSCALE + 0.f;      // (+ 0: a negative zero becomes the positive one)
+            const float s = ((acc_lh[r] + acc_hl[r]) + acc_hh[r]) * PAIR_UNSCALE + 0.f;    // (+ 0: a negative zero becomes the positive one)
             const unsigned long long m = __ballot(kvalid && s > tau);   // low half: query acc_row(r, 0), high half: acc_row(r, 1)
             if (r == my_r) mine = my_h ? (uint32_t)(m >> 32) : (uint32_t)m;
         }
         if (lane < 32) halfw[(qh * 32 + lane) * 2 + kh] = mine;         // (read after the next barrier, rewritten after the one after it)
-    }
+    };
+    pair_walk(nc_lds, fr, p_lo, qrow, fr, p_lo, nkb, D >> 6, key_row, flush_previous, zero, slice, decide);
     __syncthreads();
     flush(nkb - 1);
     if (tid < NC_TILE && qi < n) degree[(size_t)b * n + qi] = cnt;
-}
-
-// x where the lane's bit of the wave-uniform word is set, else 0: the word itself is the lane mask of one select
-__device__ __forceinline__ float nc_pick(unsigned long long word, float x) {
-    float r;
-    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(x), "s"(word));
-    return r;
-}
-
-__device__ __forceinline__ double nc_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);             // (xor tree: every lane holds the same bits)
-    return v;
 }
 
 // z_in may be z_out: element i of both belongs to thread i % 1024, which reads at the start and writes at the end
@@ -174,10 +107,7 @@ __global__ __launch_bounds__(NC_THREADS) void ncut_iterate_kernel(const unsigned
                                                                   int iters, float* z_out, float* __restrict__ rho,
                                                                   uint8_t* __restrict__ fg, float* __restrict__ eigvec,
                                                                   float* __restrict__ margin, int32_t* __restrict__ seed_cell) {
-    extern __shared__ __attribute__((aligned(16))) char nci_lds[];
-    double* slots = reinterpret_cast<double*>(nci_lds);                // [2][16]: the waves' sums, two uses alternating
-    float* amax = reinterpret_cast<float*>(nci_lds + 256);             // [16] the waves' largest |v|
-    int* aidx = reinterpret_cast<int*>(nci_lds + 320);                 // [16] ... and its cell
+    extern __shared__ __attribute__((aligned(16))) char nci_lds[];     // the slots (ncut_common.h), then the vectors
     float* z = reinterpret_cast<float*>(nci_lds + NC_FIXED_BYTES);     // [n] the iterate
     float* xv = z + n;                                                  // [n] z r (a word's pad lanes read past it, inside the allocation; never selected)
     float* rr = xv + n;                                                 // [n] r = 1 / sqrt(d)
@@ -186,51 +116,11 @@ __global__ __launch_bounds__(NC_THREADS) void ncut_iterate_kernel(const unsigned
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.x, W = (n + 63) >> 6;
     const size_t base = (size_t)b * n;
-    int flip = 0;
-    // the global sum of one value per thread: xor tree per wave, the waves in wave order; the barrier inside also publishes LDS writes
-    auto block_sum = [&](double v) {
-        double* s = slots + 16 * flip;
-        flip ^= 1;
-        v = nc_wave_sum(v);
-        if (lane == 0) s[wave] = v;
-        __syncthreads();
-        double t = s[0];
-#pragma unroll
-        for (int w = 1; w < NC_WAVES; ++w) t += s[w];
-        return t;
-    };
+    NcBlockSum block_sum{reinterpret_cast<double*>(nci_lds), 0, lane, wave};
 
-    // r, u and the start vector
-    double part = 0.0;
-    for (int i = tid; i < n; i += NC_THREADS) {
-        const int c = degree[base + i];
-        const float d = (float)(eps * (double)(n - c) + (double)c);
-        rr[i] = d > 0.f ? (float)(1.0 / sqrt((double)d)) : 0.f;
-        u[i] = d;
-        z[i] = z_in[base + i];
-        part += (double)d;
-    }
-    const double dsum = block_sum(part);
-    const double dnorm = sqrt(dsum);
-    for (int i = tid; i < n; i += NC_THREADS) u[i] = dnorm > 0.0 ? (float)(sqrt((double)u[i]) / dnorm) : 0.f;
-
-    // z <- (z - <u, z> u) / || . ||; every element is its thread's own
-    auto deflate_normalise = [&]() {
-        double c = 0.0;
-        for (int i = tid; i < n; i += NC_THREADS) c = fma((double)u[i], (double)z[i], c);
-        c = block_sum(c);
-        double ss = 0.0;
-        for (int i = tid; i < n; i += NC_THREADS) {
-            const float q = (float)((double)z[i] - c * (double)u[i]);
-            z[i] = q;
-            ss = fma((double)q, (double)q, ss);
-        }
-        ss = block_sum(ss);
-        const double nrm = sqrt(ss);
-        for (int i = tid; i < n; i += NC_THREADS) z[i] = nrm > 0.0 ? (float)((double)z[i] / nrm) : 0.f;
-    };
-
-    deflate_normalise();
+    for (int i = tid; i < n; i += NC_THREADS) z[i] = z_in[base + i];
+    nc_weights(degree + base, n, eps, rr, u, tid, block_sum);
+    nc_deflate_normalise(z, u, n, tid, block_sum);
     for (int t = 0; t < iters; ++t) {
         double S = 0.0;
         for (int i = tid; i < n; i += NC_THREADS) {
@@ -241,59 +131,14 @@ __global__ __launch_bounds__(NC_THREADS) void ncut_iterate_kernel(const unsigned
         S = block_sum(S);
         const double epsS = eps * S, om = 1.0 - eps;
         double rp = 0.0;                                                // the wave's share of rho, its rows in order
-        auto finish = [&](int i, float ti) {                            // (ti: the xor tree left the same bits in every lane)
+        nc_row_walk(graph + base * W, W, 0, n, xv, lane, wave, [&](int i, float ti) {
             const float zi = z[i];
             const float y = (float)((double)rr[i] * (epsS + om * (double)ti));
             rp = fma((double)zi, (double)y, rp);
             if (lane == 0) z[i] = 0.5f * (zi + y);
-        };
-        // two rows of the wave at a time, i and i + 16: one read of xv serves both, and two streams of words are in flight
-        for (int i = wave; i < n; i += 2 * NC_WAVES) {
-            const bool two = i + NC_WAVES < n;
-            const unsigned long long* row_a = graph + (base + i) * W;
-            const unsigned long long* row_b = two ? row_a + (size_t)NC_WAVES * W : row_a;   // (no second row: the first again, unused)
-            float acc_a = 0.f, acc_b = 0.f;
-            int w = 0;
-            if (W >= 8) {                                               // eight words at a time, the next eight in flight
-                unsigned long long cur_a[8], cur_b[8], nxt_a[8], nxt_b[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    cur_a[k] = row_a[k];
-                    cur_b[k] = row_b[k];
-                }
-                for (; w + 8 <= W; w += 8) {
-                    const int ahead = w + 16 <= W ? w + 8 : 0;          // (past the last group: re-read the first)
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        nxt_a[k] = row_a[ahead + k];
-                        nxt_b[k] = row_b[ahead + k];
-                    }
-                    float x[8];
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) x[k] = xv[(w + k) * 64 + lane];
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        acc_a += nc_pick(cur_a[k], x[k]);
-                        acc_b += nc_pick(cur_b[k], x[k]);
-                    }
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        cur_a[k] = nxt_a[k];
-                        cur_b[k] = nxt_b[k];
-                    }
-                }
-            }
-            for (; w < W; ++w) {
-                const float x = xv[w * 64 + lane];
-                acc_a += nc_pick(row_a[w], x);
-                acc_b += nc_pick(row_b[w], x);
-            }
-            finish(i, wave_sum(acc_a));
-            if (two) finish(i + NC_WAVES, wave_sum(acc_b));
-        }
+        });
         {                                                               // rho: the waves' shares in wave order
-            double* s = slots + 16 * flip;
-            flip ^= 1;
+            double* s = block_sum.next();
             if (lane == 0) s[wave] = rp;
             __syncthreads();                                            // ... and the rows' p are visible to their threads
             if (tid == 0) {
@@ -303,74 +148,14 @@ __global__ __launch_bounds__(NC_THREADS) void ncut_iterate_kernel(const unsigned
                 rho[(size_t)b * iters + t] = (float)r;
             }
         }
-        deflate_normalise();
+        nc_deflate_normalise(z, u, n, tid, block_sum);
         // the next pass prepares its input as a fresh call would prepare z_out: T chained calls and one call of T passes are the same bits
-        if (t + 1 < iters) deflate_normalise();
+        if (t + 1 < iters) nc_deflate_normalise(z, u, n, tid, block_sum);
     }
-
-    // the result: v = z r, its mean, the seed, the sign, the partition
-    double vs = 0.0;
-    float ba = -1.f;
-    int bi = INT_MAX;
-    for (int i = tid; i < n; i += NC_THREADS) {
-        const float v = z[i] * rr[i];
-        xv[i] = v;
-        vs += (double)v;
-        const float a = fabsf(v);
-        if (a > ba) {                                                   // (strict: the lower cell keeps an exact tie)
-            ba = a;
-            bi = i;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float a2 = __shfl_xor(ba, o);
-        const int i2 = __shfl_xor(bi, o);
-        if (a2 > ba || (a2 == ba && i2 < bi)) {
-            ba = a2;
-            bi = i2;
-        }
-    }
-    if (lane == 0) {
-        amax[wave] = ba;
-        aidx[wave] = bi;
-    }
-    const double avg = block_sum(vs) / (double)n;                       // (its barrier publishes xv, amax and aidx)
-    ba = amax[0];
-    bi = aidx[0];
-#pragma unroll
-    for (int w = 1; w < NC_WAVES; ++w) {
-        const float a2 = amax[w];
-        const int i2 = aidx[w];
-        if (a2 > ba || (a2 == ba && i2 < bi)) {
-            ba = a2;
-            bi = i2;
-        }
-    }
-    if (bi == INT_MAX) bi = 0;                                          // (no |v| compared greater than -1: not a finite input)
-    const float sigma = (double)xv[bi] > avg ? 1.f : -1.f;
-    if (tid == 0) seed_cell[b] = bi;
-    for (int i = tid; i < n; i += NC_THREADS) {
-        const float v = xv[i];
-        const float m = (float)((double)sigma * ((double)v - avg));
-        z_out[base + i] = z[i];
-        eigvec[base + i] = sigma * v;
-        fg[base + i] = m > 0.f ? 1 : 0;
-        if (margin) margin[base + i] = m;
-    }
+    nc_result(nci_lds, z, rr, n, tid, block_sum, z_out + base, eigvec + base, fg + base, margin ? margin + base : nullptr, seed_cell + b);
 }
 
-bool nc_misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
-int nc_shape_check(const char* who, int B, int n, int max_cells = NC_MAX_CELLS) {
-    if (B < 1 || n < 1) {
-        dinoseg_set_error("%s: B = %d frames of n = %d cells (positive)", who, B, n);
-        return -1;
-    }
-    if (n > max_cells) {
-        dinoseg_set_error("%s: n = %d cells exceed the %d whose vectors fit the LDS of one workgroup", who, n, max_cells);
-        return -1;
-    }
+int nc_grid_check(const char* who, int B, int n) {
     if ((long long)B * ((n + NC_TILE - 1) / NC_TILE) > NC_MAX_GRID) {
         dinoseg_set_error("%s: B = %d frames of n = %d cells exceed the launch range", who, B, n);
         return -1;
@@ -400,7 +185,7 @@ int nc_launch_graph(const char* who, int max_cells, const void* planes, int B, i
         dinoseg_set_error("%s: width D = %d (a multiple of 64 up to 8192)", who, D);
         return -1;
     }
-    if (nc_shape_check(who, B, n, max_cells)) return -1;
+    if (nc_cells_check(who, B, n, max_cells, NC_FITS) || nc_grid_check(who, B, n)) return -1;
     if (!std::isfinite(tau) || !(tau > -1.0 && tau < 1.0)) {
         dinoseg_set_error("%s: tau = %g (finite, inside (-1, 1))", who, tau);
         return -1;
@@ -429,28 +214,8 @@ int launch_ncut_graph_split(const void* planes, int B, int n, int D, double tau,
 int launch_ncut_iterate(const void* graph, const int32_t* degree, int B, int n, double eps, const float* z_in, int iters, float* z_out,
                         float* rho, uint8_t* fg, float* eigvec, float* margin, int32_t* seed_cell, hipStream_t s) {
     const char* who = "dinoseg_op_ncut_iterate";
-    if (!graph || !degree || !z_in || !z_out || !fg || !eigvec || !seed_cell) {
-        dinoseg_set_error("%s: null pointer (only margin, and rho with iters = 0, are optional)", who);
-        return -1;
-    }
-    if (nc_shape_check(who, B, n)) return -1;
-    if (iters < 0 || iters > NC_MAX_ITERS) {
-        dinoseg_set_error("%s: iters = %d (0 .. %d)", who, iters, NC_MAX_ITERS);
-        return -1;
-    }
-    if (iters > 0 && !rho) {
-        dinoseg_set_error("%s: null pointer (rho is required with iters > 0)", who);
-        return -1;
-    }
-    if (!(eps >= 0.0 && eps < 1.0)) {
-        dinoseg_set_error("%s: eps = %g (inside [0, 1))", who, eps);
-        return -1;
-    }
-    if (nc_misaligned(graph, 7) || nc_misaligned(degree, 3) || nc_misaligned(z_in, 3) || nc_misaligned(z_out, 3) || nc_misaligned(rho, 3) ||
-        nc_misaligned(eigvec, 3) || nc_misaligned(margin, 3) || nc_misaligned(seed_cell, 3)) {
-        dinoseg_set_error("%s: the graph must be 8-byte aligned, a 32-bit array 4-byte aligned", who);
-        return -1;
-    }
+    const NcIterateArgs args{graph, degree, B, n, eps, z_in, iters, z_out, rho, fg, eigvec, margin, seed_cell};
+    if (nc_iterate_check(who, args, false, nullptr, NC_MAX_CELLS, NC_FITS, [&]() { return nc_grid_check(who, B, n); })) return -1;
     const size_t lds = (size_t)NC_FIXED_BYTES + NC_PAD_BYTES + (size_t)n * 4 * NC_VECTORS;
     if (lds > NC_DEFAULT_LDS_BYTES) {
         static PerDeviceOnce once;

@@ -9,23 +9,22 @@
 //   label_cells_kernel        one wave per cell: lane l counts classes l, l + 64, ... over the cell's pixels (every lane reads the same
 //                             pixel: a broadcast), integer counts, no atomics; seg_0 = count / pixels of the cell.
 //   propagate_scores_kernel   one workgroup (4 waves) per (8 x 8 query tile, context frame).  The tile's key window is the tile widened
-//                             by R cells and clipped to the grid (32 x 32 keys at R = 12), walked in blocks of 64 keys.  Per block and
-//                             64-wide slice of D the query tile and the key block (hi and lo, 4 x 8 KiB, 128-byte rows under the
-//                             library's swizzle) are staged in LDS -- the next slice's global loads are in flight under the current
-//                             slice's MFMAs -- and wave (qh, kh) multiplies keys 32 kh .. by queries 32 qh .. : lo.hi + hi.lo + hi.hi on
-//                             v_mfma_f32_32x32x16_f16, fp32 accumulators, slices in ascending order.  Every (key, query) element of an
-//                             MFMA goes through the same arithmetic, so a score depends on the two rows alone.  A lane owns one query
-//                             and 16 keys of the block: the neighbourhood test in integers, then an insertion into the lane's own
-//                             sorted list of k (score, g) in LDS ([slot][thread]: conflict-free), gated by the list's last entry in
-//                             registers.  At the end 64 threads merge the 4 lists of their query (4-way, the total order) into the
-//                             scratch: [n_ctx][n][k] scores and indices.  LDS: 32 KiB + 2 KiB k <= 64 KiB; no atomics; every loop bound
-//                             is a function of the shapes.
+//                             by R cells and clipped to the grid (32 x 32 keys at R = 12), walked in blocks of 64 keys by the family's
+//                             pair walk (pair_common.h); wave (qh, kh) multiplies keys 32 kh .. by queries 32 qh .. : lo.hi + hi.lo +
+//                             hi.hi into one accumulator.  Every (key, query) element of an MFMA goes through the same arithmetic, so
+//                             a score depends on the two rows alone.  A lane owns one query and 16 keys of the block: the
+//                             neighbourhood test in integers, then an insertion into the lane's own sorted list of k (score, g) in
+//                             LDS ([slot][thread]: conflict-free), gated by the list's last entry in registers.  At the end 64
+//                             threads merge the 4 lists of their query (4-way, the total order) into the scratch: [n_ctx][n][k]
+//                             scores and indices.  LDS: 32 KiB + 2 KiB k <= 64 KiB; no atomics; every loop bound is a function of
+//                             the shapes.
 //   propagate_merge_kernel    one wave per query: the n_ctx k <= 256 candidates sit 4 to a lane as 64-bit keys (order-preserving score
 //                             bits, then ~g), k rounds of a wave maximum select rank 0 .. K'-1; weights, W, 1 / W are wave-uniform;
 //                             lanes stride the C classes with k gathers and fmaf each.
 #include "../../include/dinoseg.h"
 #include "common.h"
 #include "kernels.h"
+#include "pair_common.h"
 
 #include <climits>
 #include <cmath>
@@ -35,12 +34,8 @@ namespace dseg {
 namespace {
 
 constexpr int PRP_TILE = 8;                     // query tile side, 64 queries
-constexpr int PRP_STAGE = 32768;                // Qhi, Qlo, Khi, Klo: 64 rows x 128 B each
 constexpr int PRP_MAX_SIDE = 4096;              // grid side: n <= 2^24, 16 n < 2^31
-constexpr float PRP_UNSCALE = 0x1p-20f;         // planes carry 2^10 f^: products 2^20 <f^, f^>
 constexpr int PRP_EMPTY = INT_MAX;              // g of an empty list slot (score -inf): after every candidate in the total order
-
-__device__ __forceinline__ bool prp_better(float s, int g, float s2, int g2) { return s > s2 || (s == s2 && g < g2); }
 
 __global__ __launch_bounds__(256) void normalize_tokens_kernel(const float* __restrict__ tokens, long long rows, int n, int D,
                                                                uint16_t* __restrict__ planes) {
@@ -54,17 +49,14 @@ __global__ __launch_bounds__(256) void normalize_tokens_kernel(const float* __re
         const double v = (double)src[d];
         ss = fma(v, v, ss);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);           // (xor tree: every lane holds the same bits)
+    ss = wave_sum_f64(ss);
     const double inv = 1024.0 / fmax(sqrt(ss), 1e-12);
     uint16_t* hi = planes + ((size_t)b * 2 * n + j) * D;
     uint16_t* lo = hi + (size_t)n * D;
     for (int d = lane; d < D; d += 64) {
-        const double v = (double)src[d] * inv;
-        const _Float16 h = (_Float16)(float)v;
-        const _Float16 l = (_Float16)(float)(v - (double)(float)h);
-        hi[d] = __builtin_bit_cast(uint16_t, h);
-        lo[d] = __builtin_bit_cast(uint16_t, l);
+        const UnitSplit v = split_unit((double)src[d] * inv);
+        hi[d] = v.hi;
+        lo[d] = v.lo;
     }
 }
 
@@ -102,8 +94,8 @@ struct PrpCtx {
 __global__ __launch_bounds__(256) void propagate_scores_kernel(const uint16_t* __restrict__ tq, PrpCtx ctx, int hp, int wp, int D, int R,
                                                                int k, int tiles_x, float* __restrict__ cand_s, int* __restrict__ cand_g) {
     extern __shared__ __attribute__((aligned(16))) char prp_lds[];
-    float* ls = reinterpret_cast<float*>(prp_lds + PRP_STAGE);          // [k][256] scores of the lanes' lists, best first
-    int* lg = reinterpret_cast<int*>(prp_lds + PRP_STAGE + k * 1024);   // [k][256] their global indices
+    float* ls = reinterpret_cast<float*>(prp_lds + PAIR_STAGE);          // [k][256] scores of the lanes' lists, best first
+    int* lg = reinterpret_cast<int*>(prp_lds + PAIR_STAGE + k * 1024);   // [k][256] their global indices
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
     const int qh = wave >> 1, kh = wave & 1;
     const int n = hp * wp, ci = blockIdx.y;
@@ -112,13 +104,15 @@ __global__ __launch_bounds__(256) void propagate_scores_kernel(const uint16_t* _
     const int wr0 = max(r0 - R, 0), wr1 = min(min(r0 + PRP_TILE - 1, hp - 1) + R, hp - 1);
     const int wc0 = max(c0 - R, 0), wc1 = min(min(c0 + PRP_TILE - 1, wp - 1) + R, wp - 1);
     const int ww = wc1 - wc0 + 1, nkeys = ww * (wr1 - wr0 + 1);
-    const int nkb = (nkeys + 63) >> 6, ndc = D >> 6, total = nkb * ndc;
+    const int nkb = (nkeys + 63) >> 6;
     const uint16_t* kp = ctx.planes[ci];
 
     for (int s = 0; s < k; ++s) {
         ls[s * 256 + tid] = -INFINITY;
         lg[s * 256 + tid] = PRP_EMPTY;
     }
+    float* my_ls = ls + tid;                                            // the lane's own list: slot s at [s * 256]
+    int* my_lg = lg + tid;
     float thr_s = -INFINITY;                                            // the list's last entry: what a candidate must beat
     int thr_g = PRP_EMPTY;
 
@@ -126,102 +120,58 @@ __global__ __launch_bounds__(256) void propagate_scores_kernel(const uint16_t* _
     const int qi = qh * 32 + lr, qr = r0 + (qi >> 3), qc = c0 + (qi & 7);
     const bool qvalid = qr < hp && qc < wp;
 
-    // staging: thread t moves 16 bytes (chunk t & 7) of rows (t >> 3) and (t >> 3) + 32 of each of the four tiles
-    const int srow = tid >> 3, schunk = tid & 7;
-    size_t qoff[2];
-    int soff[2];
+    // the tile's query rows as the walk stages them (pair_common.h)
+    size_t qrow[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const int row = srow + 32 * h;
+        const int row = pair_stage_row(h);
         const int r = min(r0 + (row >> 3), hp - 1), c = min(c0 + (row & 7), wp - 1);   // (a row past the grid re-reads a real one)
-        qoff[h] = (size_t)(r * wp + c) * D + schunk * 8;
-        soff[h] = tile_off_bytes(row, schunk);
+        qrow[h] = (size_t)(r * wp + c) * D;
     }
-    const size_t lo_plane = (size_t)n * D;
-    uint4 g_qh0, g_qh1, g_ql0, g_ql1, g_kh0, g_kh1, g_kl0, g_kl1;         // the slice in flight (named: an array would live in scratch)
-    auto key_off = [&](int kb, int h) {
-        int w = kb * 64 + srow + 32 * h;
+    auto key_row = [&](int w) {
         if (w >= nkeys) w = 0;                                          // (a key past the window re-reads a real one; never selected)
         const int wr = w / ww;
-        return (size_t)((wr0 + wr) * wp + wc0 + (w - wr * ww)) * D + schunk * 8;
+        return (size_t)((wr0 + wr) * wp + wc0 + (w - wr * ww)) * D;
     };
-    auto ld16 = [](const uint16_t* p) { return *reinterpret_cast<const uint4*>(p); };
-    auto fetch = [&](int it) {
-        const int kb = it / ndc;
-        const size_t dofs = (size_t)(it - kb * ndc) * 64, k0 = key_off(kb, 0) + dofs, k1 = key_off(kb, 1) + dofs;
-        g_qh0 = ld16(tq + qoff[0] + dofs);
-        g_qh1 = ld16(tq + qoff[1] + dofs);
-        g_ql0 = ld16(tq + lo_plane + qoff[0] + dofs);
-        g_ql1 = ld16(tq + lo_plane + qoff[1] + dofs);
-        g_kh0 = ld16(kp + k0);
-        g_kh1 = ld16(kp + k1);
-        g_kl0 = ld16(kp + lo_plane + k0);
-        g_kl1 = ld16(kp + lo_plane + k1);
-    };
-
-    // fragment addresses: row lr of the wave's half, chunk 2 s + lh of the 128-byte row
-    int fq[4], fk[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        fq[s] = tile_off_bytes(qh * 32 + lr, s * 2 + lh);
-        fk[s] = 16384 + tile_off_bytes(kh * 32 + lr, s * 2 + lh);
-    }
 
     f32x16 acc;
-    fetch(0);
-    for (int it = 0; it < total; ++it) {
-        const int kb = it / ndc, dc = it - kb * ndc;
-        __syncthreads();                                                // everyone is done reading the previous slice
-        *reinterpret_cast<uint4*>(prp_lds + soff[0]) = g_qh0;
-        *reinterpret_cast<uint4*>(prp_lds + soff[1]) = g_qh1;
-        *reinterpret_cast<uint4*>(prp_lds + 8192 + soff[0]) = g_ql0;
-        *reinterpret_cast<uint4*>(prp_lds + 8192 + soff[1]) = g_ql1;
-        *reinterpret_cast<uint4*>(prp_lds + 16384 + soff[0]) = g_kh0;
-        *reinterpret_cast<uint4*>(prp_lds + 16384 + soff[1]) = g_kh1;
-        *reinterpret_cast<uint4*>(prp_lds + 24576 + soff[0]) = g_kl0;
-        *reinterpret_cast<uint4*>(prp_lds + 24576 + soff[1]) = g_kl1;
-        __syncthreads();
-        if (it + 1 < total) fetch(it + 1);
-        if (dc == 0) {
+    auto zero = [&]() {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        }
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    };
+    auto slice = [&](bf16x8 qhi, bf16x8 qlo, bf16x8 khi, bf16x8 klo) {
+        acc = mfma32f<FMT_FP16>(klo, qhi, acc);
+        acc = mfma32f<FMT_FP16>(khi, qlo, acc);
+        acc = mfma32f<FMT_FP16>(khi, qhi, acc);
+    };
+    // the block's scores: register r of this lane is key acc_row(r, lh) of the wave's half, query lr
+    auto select = [&](int kb) {
+        if (!qvalid) return;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const bf16x8 qhi = lds_frag(prp_lds + fq[s]), qlo = lds_frag(prp_lds + 8192 + fq[s]);
-            const bf16x8 khi = lds_frag(prp_lds + fk[s]), klo = lds_frag(prp_lds + 8192 + fk[s]);
-            acc = mfma32f<FMT_FP16>(klo, qhi, acc);
-            acc = mfma32f<FMT_FP16>(khi, qlo, acc);
-            acc = mfma32f<FMT_FP16>(khi, qhi, acc);
-        }
-        if (dc != ndc - 1) continue;
-        // the block's scores: register r of this lane is key acc_row(r, lh) of the wave's half, query lr
-        if (qvalid) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int w = kb * 64 + kh * 32 + acc_row(r, lh);
-                if (w >= nkeys) continue;
-                const int wr = w / ww, kr = wr0 + wr, kc = wc0 + (w - wr * ww);
-                if (abs(kr - qr) > R || abs(kc - qc) > R) continue;
-                const float s = acc[r] * PRP_UNSCALE + 0.f;            // (+ 0: a negative zero becomes the positive one)
-                const int g = ci * n + kr * wp + kc;
-                if (!prp_better(s, g, thr_s, thr_g)) continue;
-                int pos = k - 1;                                        // the last entry leaves
-                while (pos > 0) {
-                    const float ps = ls[(pos - 1) * 256 + tid];
-                    const int pg = lg[(pos - 1) * 256 + tid];
-                    if (!prp_better(s, g, ps, pg)) break;
-                    ls[pos * 256 + tid] = ps;
-                    lg[pos * 256 + tid] = pg;
-                    --pos;
-                }
-                ls[pos * 256 + tid] = s;
-                lg[pos * 256 + tid] = g;
-                thr_s = ls[(k - 1) * 256 + tid];
-                thr_g = lg[(k - 1) * 256 + tid];
+        for (int r = 0; r < 16; ++r) {
+            const int w = kb * 64 + kh * 32 + acc_row(r, lh);
+            if (w >= nkeys) continue;
+            const int wr = w / ww, kr = wr0 + wr, kc = wc0 + (w - wr * ww);
+            if (abs(kr - qr) > R || abs(kc - qc) > R) continue;
+            const float s = acc[r] * PAIR_UNSCALE + 0.f;                // (+ 0: a negative zero becomes the positive one)
+            const int g = ci * n + kr * wp + kc;
+            if (!better(s, g, thr_s, thr_g)) continue;
+            int pos = k - 1;                                            // the last entry leaves
+            while (pos > 0) {
+                const float ps = my_ls[(pos - 1) * 256];
+                const int pg = my_lg[(pos - 1) * 256];
+                if (!better(s, g, ps, pg)) break;
+                my_ls[pos * 256] = ps;
+                my_lg[pos * 256] = pg;
+                --pos;
             }
+            my_ls[pos * 256] = s;
+            my_lg[pos * 256] = g;
+            thr_s = my_ls[(k - 1) * 256];
+            thr_g = my_lg[(k - 1) * 256];
         }
-    }
+    };
+    pair_walk(prp_lds, tq, (size_t)n * D, qrow, kp, (size_t)n * D, nkb, D >> 6, key_row, [](int) {}, zero, slice, select);
     __syncthreads();
     // 4-way merge of the query's lists (waves (qh, 0) and (qh, 1), both lane halves) under the total order
     if (tid < 64) {
@@ -236,9 +186,9 @@ __global__ __launch_bounds__(256) void propagate_scores_kernel(const uint16_t* _
                 int bg = lg[p0 * 256 + t0], which = 0;
                 const float s1 = ls[p1 * 256 + t1], s2 = ls[p2 * 256 + t2], s3 = ls[p3 * 256 + t3];
                 const int g1 = lg[p1 * 256 + t1], g2 = lg[p2 * 256 + t2], g3 = lg[p3 * 256 + t3];
-                if (prp_better(s1, g1, bs, bg)) { bs = s1; bg = g1; which = 1; }
-                if (prp_better(s2, g2, bs, bg)) { bs = s2; bg = g2; which = 2; }
-                if (prp_better(s3, g3, bs, bg)) { bs = s3; bg = g3; which = 3; }
+                if (better(s1, g1, bs, bg)) { bs = s1; bg = g1; which = 1; }
+                if (better(s2, g2, bs, bg)) { bs = s2; bg = g2; which = 2; }
+                if (better(s3, g3, bs, bg)) { bs = s3; bg = g3; which = 3; }
                 p0 += which == 0;
                 p1 += which == 1;
                 p2 += which == 2;
@@ -452,7 +402,7 @@ int launch_propagate(const void* target_planes, const void* const* ctx_planes, c
     const int tiles_x = (wp + PRP_TILE - 1) / PRP_TILE, tiles_y = (hp + PRP_TILE - 1) / PRP_TILE;
     float* cand_s = reinterpret_cast<float*>(scratch);
     int* cand_g = reinterpret_cast<int*>(cand_s + (size_t)n_ctx * n * k);
-    const size_t lds = PRP_STAGE + (size_t)k * 2048;
+    const size_t lds = PAIR_STAGE + (size_t)k * 2048;
     hipLaunchKernelGGL(propagate_scores_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n_ctx), dim3(256), lds, s,
                        reinterpret_cast<const uint16_t*>(target_planes), ctx, hp, wp, D, R, k, tiles_x, cand_s, cand_g);
     DSEG_CHECK_HIP(hipGetLastError());
