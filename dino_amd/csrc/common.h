@@ -144,10 +144,13 @@ __device__ __forceinline__ float wave_sum(float v) {
 // Exact-form GELU 0.5*x*(1+erf(x/sqrt2)) (nn.GELU() default, vision_transformer.py:50,55) with erfc by
 // Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7) written without cancellation:
 //   1 + erf(z) = 2 - t*P(t)*exp(-z^2) for z >= 0,  = t*P(t)*exp(-z^2) for z < 0,  t = 1/(1 + 0.3275911 |z|).
+// p is held as 0.32759112f, one fp32 step above the nearest to 0.3275911: 1/sqrt2 and log2(e) both round down in fp32, which
+// raises erfc by up to 1.4e-8 and takes the function as compiled to 1.53e-7 near |x| = 1.26; the step in p offsets it, so that
+// |gelu_erf - gelu| <= 0.5 |x| 1.5e-7 holds with the constants the kernels hold (1.42e-7; tests/test_gelu_formula_cpu.py).
 // ~14 VALU ops (one v_rcp, one v_exp) instead of libm erff's ~60.
 __device__ __forceinline__ float gelu_erf(float x) {
     const float z = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
+    const float t = __builtin_amdgcn_rcpf(fmaf(0.32759112f, z, 1.0f));
     float pl = fmaf(1.061405429f, t, -1.453152027f);
     pl = fmaf(pl, t, 1.421413741f);
     pl = fmaf(pl, t, -0.284496736f);
@@ -170,10 +173,11 @@ __device__ __forceinline__ float gelu_fast(float x) {
     return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
-// d/dx of the exact GELU: Phi(x) + x * phi(x), same erfc approximation (shares the exponential).
+// d/dx of the exact GELU: Phi(x) + x * phi(x), same erfc approximation with the same p (shares the exponential): Phi within 0.75e-7,
+// the whole within 0.9e-7 with the constants as held (tests/test_gelu_formula_cpu.py::test_erf_form_derivative).
 __device__ __forceinline__ float gelu_erf_grad(float x) {
     const float z = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
+    const float t = __builtin_amdgcn_rcpf(fmaf(0.32759112f, z, 1.0f));
     float pl = fmaf(1.061405429f, t, -1.453152027f);
     pl = fmaf(pl, t, 1.421413741f);
     pl = fmaf(pl, t, -0.284496736f);

@@ -433,7 +433,7 @@ __global__ __launch_bounds__(mf3::THREADS, 1) void mlp_fused3_kernel(MlpFused3Pa
         // ---- the GELU of a tile's 16 accumulator values per lane, one instruction per MFMA gap and element: element n starts at gap
         // 5 n of its carrier step (F1 of the next tile) and runs on into the first gaps of its own fc2 step (gaps 72 ..); the
         // exact-erf form of common.h's gelu_erf (Abramowitz & Stegun 7.1.26) as max(x, 0) - |x| (P(t) / 2) exp(-x^2 / 2),
-        // t = 1 / (1 + 0.3275911 |x| / sqrt 2), then the hi + lo split of each pair of values
+        // t = 1 / (1 + 0.3275911 |x| / sqrt 2) (p as common.h holds it, 0.32759112f), then the hi + lo split of each pair of values
         constexpr int GELU_OPS = 14;                                  // value complete after op 13
         constexpr int OP_SAT = GELU_OPS, OP_HI = OP_SAT + 1, OP_R = OP_HI + 1, OP_LO = OP_R + 1;      // (pairs: at the odd element)
         constexpr int GELU_STRIDE = 5, GELU_END = 15 * GELU_STRIDE + OP_LO;      // last gap with GELU work (92)
@@ -445,7 +445,7 @@ __global__ __launch_bounds__(mf3::THREADS, 1) void mlp_fused3_kernel(MlpFused3Pa
             if (MF3_ABL & 1) {
                 if constexpr (I == 0) ex[N] = s[N];
             } else {
-                if constexpr (I == 0) ea[N] = fmaf(0.3275911f * 0.70710678118654752440f, __builtin_fabsf(s[N]), 1.0f);
+                if constexpr (I == 0) ea[N] = fmaf(0.32759112f * 0.70710678118654752440f, __builtin_fabsf(s[N]), 1.0f);
                 if constexpr (I == 1) eb[N] = s[N] * s[N];
                 if constexpr (I == 2) ea[N] = __builtin_amdgcn_rcpf(ea[N]);
                 if constexpr (I == 3) eb[N] = eb[N] * (-0.5f * 1.44269504088896340736f);

@@ -796,7 +796,12 @@ int dinoseg_op_ln_gemm(const float* X, const float* gamma, const float* beta, fl
  * X fp32 [M, 384] updated in place.  Replaces Block.forward's `x = x + self.mlp(self.norm2(x))` (vision_transformer.py:135 ->
  * :59-65): LayerNorm2, fc1, exact GELU (fitted form of the bf16 mode), fc2, residual add; the hidden activation stays on chip.
  * Wp = both weights re-packed in MFMA fragment order by dinoseg_op_pack_mlp (dinoseg_op_mlp_fused_pack_elems(D, F) bf16
- * elements; 0 = unsupported shape). */
+ * elements; 0 = unsupported shape).
+ * Range with fp16 operands (option "op_fmt" 1; the same holds for dinoseg_op_proj_mlp_fused, dinoseg_op_block_tail_fused and the
+ * mlp_fused4.hip entries below): the hidden activation is NOT saturated -- a pre-activation beyond 65504 is stored as inf and the row
+ * comes back NaN (0 x inf in fc2); up to 65504 it is exact.  b1 reaches the accumulator as three fp16 pieces: |b1| <= 65504, and an
+ * |b1| < 0.5 may lose up to 2^-25.  dinoseg_op_gemm's GELU epilogue, dinoseg_op_gemm_rs and the hi + lo entries (mlp_fused3.hip) saturate at
+ * +-65504 instead.  Measured and not changed: profiles/fused_gelu_saturation_ab.md; DESIGN.md (precision modes). */
 int64_t dinoseg_op_mlp_fused_pack_elems(int32_t D, int32_t F);
 int dinoseg_op_pack_mlp(const float* W1, const float* W2, int32_t D, int32_t F, void* dst, void* stream);
 int dinoseg_op_mlp_fused(float* X, const float* gamma, const float* beta, float eps, const void* Wp, const float* b1,
