@@ -189,6 +189,13 @@ SIGNATURES = {
     # area, box, status
     "dinoseg_components_scratch_bytes": (_i64, [_i32, _i32, _i32]),
     "dinoseg_op_components": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # multi-object discovery (recursive normalized cuts): the scratch size (host only); graph &= alive and the degree; the seed's
+    # component of a round -> cells, found, area, box, a score channel, alive; the K rounds on the stream (it destroys the graph)
+    "dinoseg_maskcut_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "dinoseg_op_ncut_mask": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
+    "dinoseg_op_maskcut_select": (C.c_int, [_vp, _vp, _fp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _fp, _vp]),
+    "dinoseg_op_maskcut": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f64, _fp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _fp, _vp, _vp,
+                                     _fp, _fp, _vp, _fp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

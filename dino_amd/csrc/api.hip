@@ -726,6 +726,27 @@ extern "C" int dinoseg_op_components(const int32_t* labels, int32_t B, int32_t H
                              reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int64_t dinoseg_maskcut_scratch_bytes(int32_t B, int32_t hp, int32_t wp, int32_t K) { return maskcut_scratch_bytes(B, hp, wp, K); }
+
+extern "C" int dinoseg_op_ncut_mask(void* graph, int32_t* degree, const void* alive, int32_t B, int32_t n, void* stream) {
+    return launch_ncut_mask(graph, degree, alive, B, n, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_maskcut_select(const int32_t* ids, const uint8_t* fg, const float* margin, const int32_t* seed_cell, void* alive,
+                                         int32_t B, int32_t hp, int32_t wp, int32_t K, int32_t t, uint8_t* cells, uint8_t* found,
+                                         int32_t* area, int32_t* box, float* score, void* stream) {
+    return launch_maskcut_select(ids, fg, margin, seed_cell, alive, B, hp, wp, K, t, cells, found, area, box, score,
+                                 reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_maskcut(void* graph, int32_t* degree, int32_t B, int32_t hp, int32_t wp, double eps, const float* z_start,
+                                  int32_t iters, int32_t rows_per_group, int32_t connectivity, int32_t K, uint8_t* cells, uint8_t* found,
+                                  int32_t* area, int32_t* box, float* score, int32_t* count, uint8_t* fg, float* margin, float* eigvec,
+                                  int32_t* seed_cell, float* rho, void* scratch, void* stream) {
+    return launch_maskcut(graph, degree, B, hp, wp, eps, z_start, iters, rows_per_group, connectivity, K, cells, found, area, box, score,
+                          count, fg, margin, eigvec, seed_cell, rho, scratch, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int dinoseg_op_confusion(const int32_t* pred, const int64_t* gt, int64_t n, int32_t n_classes, int64_t* cm, void* stream) {
     return launch_confusion(pred, gt, n, n_classes, cm, reinterpret_cast<hipStream_t>(stream));
 }

@@ -423,6 +423,19 @@ int launch_components(const int32_t* labels, int B, int H, int W, int connectivi
                       int32_t* count, int32_t* first, int32_t* label, int32_t* area, int32_t* box, int32_t* status, void* scratch,
                       hipStream_t s);
 
+// Multi-object discovery: K rounds of the split cut with the found object painted out between rounds (maskcut.hip; the rule:
+// include/dinoseg.h, dinoseg_op_maskcut).  launch_ncut_mask: graph &= alive in place and the exact degree, one wave per row.
+// launch_maskcut_select: the seed's component -> cells, found, area, box, the score channel t + 1, alive &= ~cells; one workgroup per
+// frame.  launch_maskcut: the K rounds -- mask, launch_ncut_iterate_split, candidates, launch_components, select -- on the stream; it
+// destroys the graph.  maskcut_scratch_bytes: -1 for refusable arguments.
+long long maskcut_scratch_bytes(int B, int hp, int wp, int K);
+int launch_ncut_mask(void* graph, int32_t* degree, const void* alive, int B, int n, hipStream_t s);
+int launch_maskcut_select(const int32_t* ids, const uint8_t* fg, const float* margin, const int32_t* seed_cell, void* alive, int B, int hp,
+                          int wp, int K, int t, uint8_t* cells, uint8_t* found, int32_t* area, int32_t* box, float* score, hipStream_t s);
+int launch_maskcut(void* graph, int32_t* degree, int B, int hp, int wp, double eps, const float* z_start, int iters, int rows_per_group,
+                   int connectivity, int K, uint8_t* cells, uint8_t* found, int32_t* area, int32_t* box, float* score, int32_t* count,
+                   uint8_t* fg, float* margin, float* eigvec, int32_t* seed_cell, float* rho, void* scratch, hipStream_t s);
+
 // ---- fine-tune step (train.hip, attention_bwd.hip) ----
 struct AttnBwdParams {
     const bf16_t* q; const bf16_t* k; const bf16_t* v; long qkv_plane;   // forward operands [planes][B,H,npad,64]

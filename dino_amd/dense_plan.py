@@ -500,3 +500,31 @@ def components_plan(labels: torch.Tensor, connectivity=4, ignore=None, max_objec
     ignore = -1 if ignore is None else _int_in(ignore, -(1 << 31), (1 << 31) - 1, "ignore")
     max_objects = _int_in(max_objects, 1, COMPONENTS_MAX_OBJECTS, "max_objects")
     return ComponentsPlan(B, H, W, int(connectivity), ignore, max_objects, promoted)
+
+
+# ---- multi-object discovery: recursive normalized cuts (include/dinoseg.h: dinoseg_op_maskcut) ----
+MASKCUT_MAX_OBJECTS = 16              # DINOSEG_MASKCUT_MAX_OBJECTS
+
+
+class MaskCutPlan(NamedTuple):
+    """What a multi-object discovery call was asked for, validated: the plan of every round's cut (split launches only), the
+    number of rounds and the connectivity of the component around the seed."""
+    ncut: NcutPlan
+    max_objects: int
+    connectivity: int
+
+
+def maskcut_plan(patch: int, x: torch.Tensor, max_objects=3, tau=0.2, eps=1e-5, iters=64, seed=0, size=None, chunk=32, split=True,
+                 connectivity=4) -> MaskCutPlan:
+    """The shape and parameter checks of ``DINOSeg.discover_all`` without a device: those of ``ncut_plan`` with ``split``, then
+    ``max_objects`` in 1 .. ``MASKCUT_MAX_OBJECTS``, ``connectivity`` 4 or 8, and ``split=False`` refused (the rounds run on the split
+    launches only).  Every ``ValueError`` is raised here, before any device use."""
+    if isinstance(split, (bool, np.bool_)) and not split:
+        raise ValueError("discover_all runs on the split launches only: split must be True or a number of rows per workgroup >= 1")
+    plan = ncut_plan(patch, x, tau, eps, iters, seed, size, chunk, split)
+    max_objects = _int_in(max_objects, 1, MASKCUT_MAX_OBJECTS, "max_objects")
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or int(connectivity) not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    if plan.hp > COMPONENTS_MAX_SIDE or plan.wp > COMPONENTS_MAX_SIDE:
+        raise ValueError(f"the patch grid {(plan.hp, plan.wp)} exceeds {COMPONENTS_MAX_SIDE} (COMPONENTS_MAX_SIDE) along a side")
+    return MaskCutPlan(plan, max_objects, int(connectivity))

@@ -19,7 +19,7 @@ from torch import nn
 
 from . import capi
 from .dense_plan import (_pair, components_plan, context_frames, dense_mode, frame_layout, guide_plan, guided_params, kmeans_plan, label_size,
-                         multiscale_plan, ncut_plan, ncut_start, out_size, propagate_plan, resolution_message, sample_indices,
+                         maskcut_plan, multiscale_plan, ncut_plan, ncut_start, out_size, propagate_plan, resolution_message, sample_indices,
                          view_sizes, window_origins, window_plan)  # noqa: F401  (view_sizes, window_origins: re-exported)
 from .preprocess import resize_linear_u8
 from .weights import VIT_B8, VIT_B16, VIT_S8, VIT_S16, ViTConfig
@@ -986,6 +986,57 @@ class DINOSeg(nn.Module):
         labels = self._margin_labels(torch.where(cells, margin, -margin.abs()), hp, wp, OH, OW)
         return labels, box, found, cells.to(torch.uint8), area
 
+    # ---- multi-object discovery: recursive normalized cuts (csrc/maskcut.hip) ----
+    @torch.no_grad()
+    def discover_all(self, x: torch.Tensor, max_objects: int = 3, tau: float = 0.2, eps: float = 1e-5, iters: int = 64, seed: int = 0,
+                     size=None, n_blocks: int = 0, chunk: int = 32, split=True, connectivity: int = 4,
+                     want_graph: bool = False) -> "MaskCutResult":
+        """Unsupervised multi-object discovery (MaskCut, the discovery step of CutLER): K = ``max_objects`` rounds of ``discover``
+        on one graph, the cells of every found object painted out of the graph before the next cut.  Arguments as ``discover`` ->
+        ``MaskCutResult(labels int32 [B,OH,OW] with 0 = background and t + 1 = the object of round t, count int32 [B], found uint8
+        [B,K], box int32 [B,K,4] = (x0, y0, x1, y1) half-open in the coordinates of the frame, area int32 [B,K] in cells, cells
+        uint8 [B,K,n], seed_cell int32 [B,K], rho fp32 [B,K,iters], graph uint64 [B,n,ceil(n/64)] or None)``.  Round 0 is
+        ``discover(split=True)``.  A painted cell stays in the graph as a node joined to nothing (every pair with it weighs ``eps``);
+        every round starts from ``ncut_start(n, seed)``; a round whose seed cell is background or already painted finds nothing
+        (``found`` 0, empty ``cells``, ``box`` and ``area`` 0) and, since nothing stops early, every later round repeats it; ``count``
+        is the number of rounds that found an object (the rule: include/dinoseg.h, dinoseg_op_maskcut).  The rounds run on the split
+        launches only: ``split=False`` raises ``ValueError``.  ``want_graph`` returns the ORIGINAL graph (a copy: the rounds consume
+        theirs).  MaskCut's corner reversal, its IoU and area rejections and its CRF are not done.  No host synchronisation.
+        Inference only."""
+        mplan = maskcut_plan(self.cfg.patch, x, max_objects, tau, eps, iters, seed, size, chunk, split, connectivity)
+        plan, K = mplan.ncut, mplan.max_objects
+        if not 0 <= n_blocks <= self.cfg.n_blocks:
+            raise ValueError(f"intermediate must be in [0, {self.cfg.n_blocks}]")
+        self._require_gpu()
+        lib, dev, B, n, D = capi.lib(), self.device, plan.B, plan.hp * plan.wp, self.cfg.embed_dim
+        planes = self._point_planes(self._to_device(x, plan.kind), plan, n_blocks)
+        nbytes, sbytes = lib.dinoseg_ncut_split_graph_bytes(B, n), lib.dinoseg_maskcut_scratch_bytes(B, plan.hp, plan.wp, K)
+        if nbytes < 0 or sbytes < 0:
+            raise capi.DinosegError(f"dinoseg_maskcut_scratch_bytes refused {B} frames of {plan.hp} x {plan.wp} cells")
+        graph = torch.empty((B, n, nbytes // (8 * B * n)), dtype=torch.int64, device=dev)
+        degree = torch.empty((B, n), dtype=torch.int32, device=dev)
+        capi.check(lib.dinoseg_op_ncut_graph_split(planes.data_ptr(), B, n, D, plan.tau, graph.data_ptr(), degree.data_ptr(), self._stream()))
+        original = graph.clone().view(torch.uint64) if want_graph else None
+        z = ncut_start(n, plan.seed).to(dev).expand(B, n).contiguous()
+        scratch = torch.empty((sbytes,), dtype=torch.uint8, device=dev)
+        cells, fg = (torch.empty((B, K, n), dtype=torch.uint8, device=dev) for _ in range(2))
+        margin, eigvec = (torch.empty((B, K, n), dtype=torch.float32, device=dev) for _ in range(2))
+        found = torch.empty((B, K), dtype=torch.uint8, device=dev)
+        area, seed_cell = (torch.empty((B, K), dtype=torch.int32, device=dev) for _ in range(2))
+        box = torch.empty((B, K, 4), dtype=torch.int32, device=dev)
+        score = torch.empty((B, n, K + 1), dtype=torch.float32, device=dev)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        rho = torch.empty((B, K, plan.iters), dtype=torch.float32, device=dev)
+        capi.check(lib.dinoseg_op_maskcut(graph.data_ptr(), degree.data_ptr(), B, plan.hp, plan.wp, plan.eps, z.data_ptr(), plan.iters,
+                                          max(plan.split, 0), mplan.connectivity, K, cells.data_ptr(), found.data_ptr(), area.data_ptr(),
+                                          box.data_ptr(), score.data_ptr(), count.data_ptr(), fg.data_ptr(), margin.data_ptr(),
+                                          eigvec.data_ptr(), seed_cell.data_ptr(), rho.data_ptr() if plan.iters else None,
+                                          scratch.data_ptr(), self._stream()))
+        labels = torch.empty((B, plan.OH, plan.OW), dtype=torch.int32, device=dev)
+        capi.check(lib.dinoseg_op_upsample_argmax(score.data_ptr(), B, plan.hp, plan.wp, K + 1, plan.OH, plan.OW, labels.data_ptr(), None,
+                                                  self._stream()))
+        return MaskCutResult(labels, count, found, box * self.cfg.patch, area, cells, seed_cell, rho, original)
+
     def predict_dense(self, img, size=None, scales=None, flip: bool = False, window=None, stride=None, guided=None) -> np.ndarray:
         """The pixel-resolution sibling of ``predict()``: the image (PIL.Image or HxWx3 uint8 array) is resized to r x r on the
         device exactly as ``predict()`` does, the log-probabilities are upsampled to ``size`` (default: the IMAGE's own (rows,
@@ -1897,3 +1948,20 @@ class DiscoverResult(NamedTuple):
     cells: torch.Tensor
     area: torch.Tensor
     ncut: NcutResult
+
+
+class MaskCutResult(NamedTuple):
+    """What ``DINOSeg.discover_all`` returns for K = ``max_objects`` rounds: pixel labels int32 [B, OH, OW] (0 = background, t + 1 =
+    the object of round t), the number of rounds that found an object int32 [B], and per round whether it did uint8 [B, K], the
+    object's box int32 [B, K, 4] = (x0, y0, x1, y1) half-open in frame coordinates, its cells' number int32 [B, K], the cells uint8
+    [B, K, n], the cut's seed cell int32 [B, K] and Rayleigh record fp32 [B, K, iters]; the ORIGINAL bit graph uint64 [B, n,
+    ceil(n / 64)] when asked for."""
+    labels: torch.Tensor
+    count: torch.Tensor
+    found: torch.Tensor
+    box: torch.Tensor
+    area: torch.Tensor
+    cells: torch.Tensor
+    seed_cell: torch.Tensor
+    rho: torch.Tensor
+    graph: Optional[torch.Tensor]

@@ -640,6 +640,67 @@ int dinoseg_op_components(const int32_t* labels, int32_t B, int32_t H, int32_t W
                           int32_t max_objects, int32_t* ids, int32_t* count, int32_t* first, int32_t* label, int32_t* area, int32_t* box,
                           int32_t* status, void* scratch, void* stream);
 
+/* ---- multi-object discovery: recursive normalized cuts (MaskCut, the discovery step of CutLER: cut the graph, keep the connected
+ * component around the seed cell, paint its cells out of the graph, cut again).  No reference counterpart.  maskcut.hip.  The cut is
+ * dinoseg_op_ncut_iterate_split and the components are dinoseg_op_components, both unchanged; what is new is the glue that makes a
+ * round a function of the previous one on the device.  On the 1-bit graph "paint the object out" is graph &= alive and the degree a
+ * popcount, so everything new is an integer or a sign operation: the result is a function of the input alone, bit for bit.
+ *
+ * Per frame (frames are independent): n = hp wp cells, W = ceil(n / 64), K = max_objects rounds t = 0 .. K - 1.  State: alive, one
+ * bit per cell, [B][W] uint64 words, cell i at bit i % 64 of word i / 64, pad bits zero.  Before round 0 every cell is alive and
+ * score[b][i][0] = 0 is written (once).
+ *
+ * 1. Mask (dinoseg_op_ncut_mask).  graph[i][w] <- alive_i ? graph[i][w] & alive[w] : 0, in place; degree[i] = popcount of the new row,
+ *    exact.  Pad bits stay zero; a symmetric graph stays symmetric.  Bits are only ever cleared, so masking the previous round's
+ *    graph with the new alive equals masking the original graph: one graph buffer serves all rounds.  Dead cells stay in the graph
+ *    as nodes joined to nothing: every pair with a dead cell weighs eps, which is what MaskCut's feats * (1 - painting) gives under
+ *    TokenCut's binary affinity.  Steps 4-7 of dinoseg_op_ncut_graph apply to the masked graph unchanged, with n the FULL cell count.
+ * 2. Cut.  dinoseg_op_ncut_iterate_split on the masked graph and degree.  Every round starts from the SAME start vector z_start,
+ *    which no round writes.  Its result is fg_t, margin_t, seed_cell_t, eigvec_t, rho_t.
+ * 3. Candidates.  cand_i = (fg_t[i] != 0 && alive_i) ? 1 : 0 as int32 [B][hp][wp]; ids = the ids of dinoseg_op_components on it with
+ *    ignore = 0 and the connectivity given (its table is not used).
+ * 4. Select (dinoseg_op_maskcut_select).  s = seed_cell_t.  k = ids[s] where 0 <= s < n, alive_s and fg_t[s] != 0, else -1;
+ *    found_t = k >= 0 (a dead seed or a background seed gives 0).  cells_t[i] = found_t && ids[i] == k.  area_t = the count of cells_t;
+ *    box_t = (x0, y0, x1, y1), half-open, in CELLS (x = i % wp, y = i / wp), all four 0 when not found.  alive &= ~cells_t.
+ *    score[b][i][t + 1] = cells_t[i] ? margin_t[i] : -|margin_t[i]| (margin_t[i] with the sign bit set: the bits of torch.where(cells,
+ *    margin, -margin.abs())).  No other channel of score is touched.  Nothing is summed in floating point; the area and the box are
+ *    integer add / min / max in one workgroup per frame.
+ * 5. Pixel labels: dinoseg_op_upsample_argmax, unchanged, on score [B, n, K + 1]: 0 is background, t + 1 is object t, ties go to the
+ *    lower index.
+ * 6. No early stop (there is no host synchronisation).  A round with found_t = 0 leaves alive unchanged, so every later round repeats
+ *    it bit for bit.  count[b] = the number of rounds with found = 1.
+ *
+ * Deviations from MaskCut: the points are the tokens of dinoseg_features_hw, not last-block keys; the lazy power iteration replaces
+ * eigh; the three-corner reversal of the partition, the IoU > 0.5 rejection, the 1 % area rejection and the CRF post-processing are
+ * not done; a not-found round does not end the loop, it repeats.
+ *
+ * dinoseg_op_maskcut runs the K rounds on the caller's stream: an init launch; per round the mask launch, the iters + 2 launches of
+ * the split cut, one launch that forms cand and copies the round's fg / margin / eigvec / seed_cell / rho into slot t of the
+ * caller's arrays, the launches of dinoseg_op_components, the select launch; at the end one launch for count.  Nothing synchronises
+ * with the host, nothing allocates, there are no flags and no atomics of its own.  IT DESTROYS THE CALLER'S GRAPH AND DEGREE: after
+ * the call they are those of the last round's mask.  Outputs: cells uint8 [B][K][n]; found uint8 [B][K]; area int32 [B][K]; box
+ * int32 [B][K][4]; score fp32 [B][n][K + 1]; count int32 [B]; fg uint8 [B][K][n]; margin, eigvec fp32 [B][K][n]; seed_cell int32
+ * [B][K]; rho fp32 [B][K][iters] (may be NULL with iters = 0).  z_start fp32 [B][n].
+ *
+ * dinoseg_maskcut_scratch_bytes(B, hp, wp, K): the split scratch, the components scratch and its one-row table, alive, cand, ids,
+ * the working z and the round's working fg / margin / eigvec / seed_cell / rho (rho at the 4096 passes the cut accepts), each part
+ * rounded up to 16 bytes; it does not grow with K.  Host only; -1 for refusable arguments.  The scratch holds nothing between calls.
+ *
+ * Refused (-1, the message names the entry, nothing is launched, the outputs, the scratch and the graph stay untouched): a null
+ * pointer (rho with iters = 0 is optional); everything dinoseg_op_ncut_iterate_split refuses about B, n, eps, iters and
+ * rows_per_group and dinoseg_op_components about B, hp, wp; K outside 1 .. 16; t outside 0 .. K - 1; connectivity not 4 or 8; the
+ * graph or alive not 8-byte aligned, a 32-bit array not 4-byte aligned, the scratch not 16-byte aligned. */
+#define DINOSEG_MASKCUT_MAX_OBJECTS 16
+int64_t dinoseg_maskcut_scratch_bytes(int32_t B, int32_t hp, int32_t wp, int32_t K);
+int dinoseg_op_ncut_mask(void* graph, int32_t* degree, const void* alive, int32_t B, int32_t n, void* stream);
+int dinoseg_op_maskcut_select(const int32_t* ids, const uint8_t* fg, const float* margin, const int32_t* seed_cell, void* alive, int32_t B,
+                              int32_t hp, int32_t wp, int32_t K, int32_t t, uint8_t* cells, uint8_t* found, int32_t* area, int32_t* box,
+                              float* score, void* stream);
+int dinoseg_op_maskcut(void* graph, int32_t* degree, int32_t B, int32_t hp, int32_t wp, double eps, const float* z_start, int32_t iters,
+                       int32_t rows_per_group, int32_t connectivity, int32_t K, uint8_t* cells, uint8_t* found, int32_t* area,
+                       int32_t* box, float* score, int32_t* count, uint8_t* fg, float* margin, float* eigvec, int32_t* seed_cell,
+                       float* rho, void* scratch, void* stream);
+
 /* ---- fine-tune step (replaces DINOSeg.training_step + autograd + optimizer.step, pl_torch_modules.py:258-268) ---- */
 
 /* Bind (or, with NULL, unbind) the fp32 gradient buffer of a parameter, same shape as the bound weight.  A parameter
