@@ -959,7 +959,11 @@ int dinoseg_op_block_tail_fused(float* X, const void* ctx, const void* Wproj, co
  * q, k, v: [planes][B,heads,npad,64]; ctx: bf16 planes [planes][B*ntok][heads*64]; lse (optional): fp32 [B,heads,ntok], log2 domain.
  * Pad rows: rows ntok..npad of q, k and v are read with the 64-row tiles they share with real rows and must hold FINITE values -- any
  * finite values, zero is not required.  Every kernel masks them: a pad key gets probability 0 and 0 x finite = 0, so they never
- * reach ctx or lse (bit for bit: tests/test_forward_containment_gpu.py); a NaN or Inf there may (0 x Inf). */
+ * reach ctx or lse (bit for bit: tests/test_forward_containment_gpu.py); a NaN or Inf there may (0 x Inf).
+ * On inputs whose scores are integers, whose values are small integers and whose sums fit 24 bits, every route is exact: where the row
+ * sum is a power of two ctx carries the round-to-nearest-even planes of the exact quotient bit for bit, elsewhere each element lies within
+ * the store format's half ulp plus 4 * 2^-24 of it (tests/test_attention_probes_gpu.py).  lse lies within 2 fp32 ulps at the magnitude of
+ * the hardware log2's result (assumed, not documented) plus one ulp of lse itself, at any integer shift of the scores up to +-200. */
 int dinoseg_op_attention(const void* q, const void* k, const void* v, int64_t qkv_plane, void* ctx, int64_t ctx_plane,
                          float* lse, int32_t B, int32_t heads, int32_t ntok, int32_t npad, int32_t planes, void* stream);
 
