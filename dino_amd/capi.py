@@ -79,6 +79,8 @@ SIGNATURES = {
     "dinoseg_op_nll_loss_grad": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _fp, _fp, _fp, _vp, _i64, _i32, _vp]),
     "dinoseg_op_pos_resample_bwd_hw": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _fp, _fp, _vp]),
     "dinoseg_set_option": (C.c_int, [C.c_char_p, _i32]),
+    "dinoseg_get_option": (C.c_int, [C.c_char_p, C.POINTER(_i32)]),
+    "dinoseg_option_name": (C.c_char_p, [_i32]),
     "dinoseg_profile": (C.c_int, [_vp, _i32]),
     "dinoseg_profile_read": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(_i32)]),
     "dinoseg_op_pack": (C.c_int, [_fp, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _vp]),

@@ -822,6 +822,25 @@ extern "C" int dinoseg_set_option(const char* key, int32_t value) {
     return -1;
 }
 
+extern "C" int dinoseg_get_option(const char* key, int32_t* value) {
+    if (!key || !value) {
+        dinoseg_set_error("dinoseg_get_option: null argument");
+        return -1;
+    }
+    for (const OptionRow& row : OPTION_TABLE) {
+        if (strcmp(key, row.name) != 0) continue;
+        *value = row.member ? dseg::options().*row.member : 0;
+        return 0;
+    }
+    dinoseg_set_error("dinoseg_get_option: unknown key '%s'", key);
+    return -1;
+}
+
+extern "C" const char* dinoseg_option_name(int32_t index) {
+    const int32_t n = (int32_t)(sizeof(OPTION_TABLE) / sizeof(OPTION_TABLE[0]));
+    return index >= 0 && index < n ? OPTION_TABLE[index].name : nullptr;
+}
+
 // ------------------------------------------------------------------------------------------------ profiling
 extern "C" int dinoseg_profile(dinoseg_handle* h, int32_t level) {
     if (!h || level < 0 || level > 2) {

@@ -807,8 +807,23 @@ int dinoseg_profile_read(dinoseg_handle* h, float* ms_sum, int32_t* counts);
  *                of a small batch; bit 1: the one-wave-per-row LayerNorm backward; bit 2: the weight-gradient GEMM's 2-D grid);
  *   "attn_variant", "gemm_dbg", "attn_dbg": kernel A/B and timing-ablation switches (tools/bench_ops.py; attn_variant's bits:
  *                dino_amd/csrc/kernels.h -- default 11 | 1024 | 65536: from four rounds of workgroups on the attention runs its tile loop
- *                as a generated assembly pipeline, attention_za.hip, bit-identical to the compiled kernel). */
+ *                as a generated assembly pipeline, attention_za.hip, bit-identical to the compiled kernel);
+ *   "mlp_fused_min_rows" 12000 [default], "mlp_fused3_min_rows" 10000 [default]: the fewest token rows at which "mlp_fused" = 1 takes the
+ *                fused launch, on one plane / on hi + lo planes;
+ *   "qkv_fused3" 1 [default], "qkv_fused4" 1 [default]: "qkv_fused" for the hi + lo launch / for the one-wave-per-SIMD launch;
+ *   "mlp_fused4" 0 [default] / 1: one-plane modes -- the fused projection + MLP launch with one wave per SIMD (read at refresh and at
+ *                every forward: setting it between two refreshes can switch the route off, never on);
+ *   "gemm_rs"    3 [default]: the row-stationary streaming GEMMs (embed_dim 768, one plane, >= "gemm_rs_min_rows" rows, default 24000),
+ *                a bit per linear: 1 = mlp.fc1, 2 = attn.qkv, 4 = attn.proj and mlp.fc2 (stored & 7; read like "mlp_fused4");
+ *   "gemm_rs_ln" 1 [default] / 0: ... with the LayerNorm in front of qkv / fc1 in the kernel's prologue (read at refresh only);
+ *   "mlp_stagger" 0 [default], "mlp_grid" 0 [default]: experiment switches of the fused MLP launch (dino_amd/csrc/kernels.h).
+ * A value is stored normalised (a flag as 0 / 1, "gemm_rs" & 7, "split_min" >= 2, "fp16_patch_planes" 1 or 2); a refused one ("op_fmt"
+ * outside 0 / 1, an unknown key) returns -1 and stores nothing. */
 int dinoseg_set_option(const char* key, int32_t value);
+/* Reads the stored (normalised) value of one key of dinoseg_set_option into *value; -1 for an unknown key or a null pointer, *value untouched. */
+int dinoseg_get_option(const char* key, int32_t* value);
+/* The key in row `index` (0 ..) of the option table, NULL outside it: enumerates the keys of dinoseg_set_option / dinoseg_get_option. */
+const char* dinoseg_option_name(int32_t index);
 
 /* Bytes of library-owned device memory a (B, r) forward needs (activations + packed weights). */
 int64_t dinoseg_workspace_bytes(const dinoseg_handle* h, int32_t B, int32_t r);

@@ -1,10 +1,32 @@
 """Helpers for the -m gpu parity tests: everything goes through the C-ABI (dino_amd.capi)."""
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 import torch
 
+import dino_amd
 from dino_amd import capi
+
+# the options dinoseg_refresh_weights reads (which packed copies it lays out): the comment above struct Options in dino_amd/csrc/kernels.h
+REFRESH_OPTIONS = ("fp16_patch_planes", "mlp_fused4", "gemm_rs", "gemm_rs_ln")
+
+
+@contextlib.contextmanager
+def route_options(*models, **kw):
+    """dino_amd.options(**kw) for models that are alive: where kw holds an option that is read at the refresh, every model refreshes
+    its weights after the set and again after the restore."""
+    def invalidate():
+        if any(k in REFRESH_OPTIONS for k in kw):
+            for m in models:
+                m.invalidate_weights()
+    try:
+        with dino_amd.options(**kw):
+            invalidate()
+            yield
+    finally:
+        invalidate()
 
 
 def pack(x: torch.Tensor, planes: int, rows_pad: int = None, cols_pad: int = None) -> torch.Tensor:

@@ -47,14 +47,12 @@ W1024p16 and the ViT-S reference of BF16_PATCH_GRAD_PARENT itself -- were 0.8 ..
 is within 1e-5 of 0 in the oracle took the other side of its kink.  The labels of tests/arch_util.py leave such patches out
 (kink_patches); nothing about that depends on the width.
 """
-import contextlib
-
 import numpy as np
 import pytest
 import torch
 
 import dino_amd
-from dino_amd import DINOSeg, capi
+from dino_amd import DINOSeg, capi, options
 from dino_amd.weights import tensor_shapes
 from oracle import dinoseg_oracle as O
 from tests import arch_util as A
@@ -62,10 +60,8 @@ from tests import arch_util as A
 pytestmark = pytest.mark.gpu
 TOL = 1e-3                                      # the parity modes' bar (BASELINE.json north_star)
 MARGIN = 2e-3                                   # argmax is compared where the reference's top-2 margin exceeds this
-ATTN_VARIANT_DEFAULT = 11 | 1024 | 65536        # kernels.h: Options::attn_variant
-OPTION_DEFAULTS = {"gemm_ln": 1, "gemm_big": 1, "gemm_rs_min_rows": 24000, "mlp_fused": 1, "streams": 2, "split_min": 8,
-                   "attn_variant": ATTN_VARIANT_DEFAULT, "deterministic": 0, "train_streams": 2}
-# every route a config of the matrix can take, forced at this tiny shape (an option that does not apply to a config leaves its route alone)
+# every route a config of the matrix can take, forced at this tiny shape (an option that does not apply to a config leaves its route alone);
+# a callable value is evaluated when the route runs (bits on top of the option's current value)
 ROUTES = [
     ("default", {}),
     ("gemm_ln=0", {"gemm_ln": 0}),                                      # LayerNorm launch + GEMM
@@ -75,7 +71,7 @@ ROUTES = [
     ("gemm_rs", {"gemm_rs_min_rows": 1}),                               # the row-stationary GEMMs (embed_dim 768, one plane)
     ("mlp_fused=2", {"mlp_fused": 2}),                                  # the fused MLP launches where F = 1536, the fallback elsewhere
     ("split", {"streams": 2, "split_min": 2}),                          # one frame per stream
-    ("attn_za", {"attn_variant": ATTN_VARIANT_DEFAULT | 2048}),         # the assembly attention at every grid size
+    ("attn_za", {"attn_variant": lambda: dino_amd.get_option("attn_variant") | 2048}),      # the assembly attention at every grid size
 ]
 SIDE_TAGS = ["W256", "W640r2", "W896r1", "W1024p16", "Sr1"]
 DET_TAGS = ["W896r1", "W1024p16"]
@@ -85,18 +81,6 @@ LR = 1e-3
 # bf16 fine-tune step: relative L2 error of the patch weight gradient of embed_dim 384, ratio 4 (MLP head, 7 classes, the frames and
 # labels of the matrix) on the parent commit against the same oracle, by (patch, depth): 64 x 64 at patch 8, 96 x 96 at patch 16
 BF16_PATCH_GRAD_PARENT = {(8, 2): 6.97e-2, (16, 2): 9.34e-2, (8, 0): 6.13e-2}       # (bf16x3 on the same models: 3.4e-5, 2.6e-5, 1.3e-5)
-
-
-@contextlib.contextmanager
-def options(**kw):
-    """The given options for the body, the kernels.h defaults on the way out."""
-    try:
-        for k, v in kw.items():
-            dino_amd.set_option(k, v)
-        yield
-    finally:
-        for k in kw:
-            dino_amd.set_option(k, OPTION_DEFAULTS[k])
 
 
 def build(tag, precision, **kw):
@@ -139,7 +123,7 @@ def test_forward_on_every_route(cuda, tag, precision):
     f8, x = A.tensor(A.frames(tag)).cuda(), A.pixels(tag).cuda()
     outs = {}
     for name, opts in ROUTES:
-        with options(**opts):
+        with options(**{k: v() if callable(v) else v for k, v in opts.items()}):
             lp8, am8 = m.forward_frames(f8)
             with torch.no_grad():
                 lp = m(x)

@@ -10,9 +10,9 @@ import numpy as np
 import pytest
 import torch
 
-from dino_amd import capi
+from dino_amd import capi, options
 from tests import attention_probe_util as P
-from tests.test_forward_containment_gpu import ATTN_KERNELS, ATTN_LONG, ATTN_LONG_KERNELS, DT, QSCALE, options, to_planes
+from tests.test_forward_containment_gpu import ATTN_KERNELS, ATTN_LONG, ATTN_LONG_KERNELS, DT, QSCALE, attn_variant_of, to_planes
 
 pytestmark = pytest.mark.gpu
 S = capi.stream_ptr
@@ -25,10 +25,10 @@ _cases, _planes = {}, {}
 
 def _route(name):
     """(attn_variant, planes, Q / K / ctx fp16, V fp16, wants an lse, what its reference trails the row maximum by)"""
-    variant, planes, fmt, v_bf16, want_lse, _, _ = ATTN_KERNELS[name]
+    _, planes, fmt, v_bf16, want_lse, _, _ = ATTN_KERNELS[name]
     v_fp16 = fmt == "fp16" and planes == 2 and not v_bf16
     running = name.startswith(("ref", "default"))
-    return variant, planes, fmt == "fp16", v_fp16, want_lse, (14 if fmt == "fp16" else 16) if running else 0
+    return attn_variant_of(name), planes, fmt == "fp16", v_fp16, want_lse, (14 if fmt == "fp16" else 16) if running else 0
 
 
 def _shapes(name):

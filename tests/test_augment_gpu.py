@@ -314,13 +314,10 @@ def test_fit_without_an_augmenter_equals_a_pass_through_hook(cuda, tmp_path):
     vf, vm = U.random_batch(6, 64, 96)
     data = [(torch.from_numpy(vf[i:i + 2]), torch.from_numpy(vm[i:i + 2]).long()) for i in (0, 2, 4)]
     hist = []
-    dino_amd.set_option("deterministic", 1)
-    try:
+    with dino_amd.options(deterministic=1):
         for hook in (None, lambda model, x, y: (x, y)):
             m = build(ViTConfig(**SMALL), lr=1e-3, optimizer=torch.optim.Adam, freeze_backbone=False, max_epochs=2, write_path=str(tmp_path))
             hist.append(m.fit(train_dataloader=data[:2], val_dataloader=data[2:], augment=hook)["history"])
-    finally:
-        dino_amd.set_option("deterministic", 0)
     assert len(hist[0]) == 2 and len(hist[1]) == 2
     for a, b in zip(*hist):
         assert a.keys() == b.keys() and np.isfinite(a["train_loss"])

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import dino_amd
 from dino_amd import capi
 from tests.gpu_util import pack, seeded, unpack
 
@@ -23,8 +24,6 @@ LOG2E = 1.4426950408889634
 SENT = 12345.0                      # fp32 sentinel of outputs a kernel must not touch
 SENT16 = 0x7F7F                     # bf16 sentinel (a large finite value)
 EPI_PLAIN, EPI_BF16, EPI_DGELU, EPI_DRELU = 0, 6, 8, 9
-ATTN_VARIANT_DEFAULT = 11 | 1024 | 65536     # include/dinoseg.h
-ROUTE_AB_DEFAULT = 0
 
 
 def planes64(p: torch.Tensor) -> torch.Tensor:
@@ -416,16 +415,11 @@ def test_layernorm_backward(cuda, D, M, ntok, drop_cls, accumulate, planes, rout
     cs = torch.zeros(D + 1, device="cuda")
     dg[D] = db[D] = cs[D] = SENT
     dxp = torch.full((2, M, D), SENT16, dtype=torch.int16, device="cuda")
-    if route:
-        capi.check(lib.dinoseg_set_option(b"route_ab", route))
-    try:
+    with dino_amd.options(**({"route_ab": route} if route else {})):
         capi.check(lib.dinoseg_op_layernorm_bwd2(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), eps, M, D, dx.data_ptr(), accumulate,
                                                  dg.data_ptr(), db.data_ptr(), drop_cls, ntok, dxp.data_ptr(), M * D, planes,
                                                  cs.data_ptr(), S()))
         torch.cuda.synchronize()
-    finally:
-        if route:
-            capi.check(lib.dinoseg_set_option(b"route_ab", ROUTE_AB_DEFAULT))
     # fp64 restatement (native_layer_norm_backward)
     xd, gd = x.double(), gamma.double()
     dyd = torch.zeros((M, D), dtype=torch.float64, device="cuda")
@@ -484,16 +478,11 @@ def _attn_bwd_run(B, H, ntok, planes, seed, variant=None):
                                         lse.data_ptr(), B, H, ntok, npad, planes, S()))
     scratch = torch.zeros(2 * B * H * npad, device="cuda")
     dqkv = torch.full((planes, B * ntok, 3 * H * 64), SENT16, dtype=torch.int16, device="cuda")
-    if variant is not None:
-        capi.check(lib.dinoseg_set_option(b"attn_variant", variant))
-    try:
+    with dino_amd.options(**({} if variant is None else {"attn_variant": variant})):
         capi.check(lib.dinoseg_op_attention_bwd(qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), plane, dop.data_ptr(), ctx.data_ptr(),
                                                 B * ntok * H * 64, lse.data_ptr(), scratch.data_ptr(), dqkv.data_ptr(),
                                                 B * ntok * 3 * H * 64, B, H, ntok, npad, planes, S()))
         torch.cuda.synchronize()
-    finally:
-        if variant is not None:
-            capi.check(lib.dinoseg_set_option(b"attn_variant", ATTN_VARIANT_DEFAULT))
     return qp, kp, vp, dop, dqkv, npad
 
 
@@ -551,5 +540,5 @@ def test_attention_backward_dq_8_wave_route_is_bit_identical_to_4_wave(cuda):
     ncu = torch.cuda.get_device_properties(0).multi_processor_count
     assert ((B * H + 7) // 8 * 8) * ((ntok + 127) // 128) >= 2 * ncu, "shape no longer selects the 8-wave dQ kernel"
     *_, d8, _ = _attn_bwd_run(B, H, ntok, 1, seed=77)
-    *_, d4, _ = _attn_bwd_run(B, H, ntok, 1, seed=77, variant=ATTN_VARIANT_DEFAULT | 64)
+    *_, d4, _ = _attn_bwd_run(B, H, ntok, 1, seed=77, variant=dino_amd.get_option("attn_variant") | 64)
     assert torch.equal(d8, d4), f"{int((d8 != d4).sum())} elements differ between the 8-wave and the 4-wave dQ route"

@@ -207,8 +207,7 @@ def test_segment_under_the_two_stream_split(cuda, precision):
     m = build(ViTConfig(n_blocks=2), precision)
     for B in (8, 9):
         frames = torch.from_numpy(synthetic_frames(B, 64, seed=41 + B)).cuda()
-        dino_amd.set_option("streams", 1)
-        try:
+        with dino_amd.options(streams=1):
             want, lp, _ = op_on_frames(m, frames, 100, 131)
             one, one_d = m.segment(frames, size=(100, 131), want_logp=True)
             dino_amd.set_option("streams", 2)
@@ -216,8 +215,6 @@ def test_segment_under_the_two_stream_split(cuda, precision):
                 two, two_d = m.segment(frames, size=(100, 131), want_logp=True)
                 assert torch.equal(two, one) and torch.equal(two_d, one_d)
             lean, _ = m.segment(frames, size=(100, 131))            # log-probs in the two workspaces
-        finally:
-            dino_amd.set_option("streams", 2)
         assert torch.equal(one, want) and torch.equal(lean, want)
 
 

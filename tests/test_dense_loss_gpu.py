@@ -186,13 +186,10 @@ def test_loss_only_call_and_determinism(cuda):
     dev, td = logp.cuda(), t.cuda()
     runs = [run_op(dev, td, shape) for _ in range(3)]
     assert torch.equal(runs[0][1], runs[1][1]) and torch.equal(runs[0][1], runs[2][1])
-    dino_amd.set_option("deterministic", 1)
-    try:
+    with dino_amd.options(deterministic=1):
         det = [run_op(dev, td, shape) for _ in range(3)]
         only, none, _ = run_op(dev, td, shape, want_grad=False)
         torch.cuda.synchronize()
-    finally:
-        dino_amd.set_option("deterministic", 0)
     assert none is None
     for l, d, _ in det:
         assert torch.equal(l, det[0][0]) and torch.equal(d, runs[0][1])
@@ -209,14 +206,11 @@ def test_writes_stay_inside_the_outputs(cuda):
     big = torch.full((n + 2 * pad,), -7.25, device="cuda")
     lbuf = torch.full((257,), -7.25, device="cuda")
     for det in (0, 1):
-        dino_amd.set_option("deterministic", det)
-        try:
+        with dino_amd.options(deterministic=det):
             big.fill_(-7.25)
             lbuf.fill_(-7.25)
             _, d, _ = run_op(logp.cuda(), t.cuda(), shape, loss=lbuf[128:129], dlogp=big[pad:pad + n].view(B, hp * wp, C))
             torch.cuda.synchronize()
-        finally:
-            dino_amd.set_option("deterministic", 0)
         assert bool((big[:pad] == -7.25).all()) and bool((big[pad + n:] == -7.25).all())
         assert bool((lbuf[:128] == -7.25).all()) and bool((lbuf[129:] == -7.25).all())
         assert torch.isfinite(lbuf[128]) and bool((d != -7.25).all())
@@ -226,8 +220,7 @@ def test_op_is_graph_capturable(cuda):
     shape = (2, 8, 16, 33, 100, 131)
     logp, t = random_case(shape, seed=41)
     dev, td = logp.cuda(), t.cuda()
-    dino_amd.set_option("deterministic", 1)
-    try:
+    with dino_amd.options(deterministic=1):
         eager_loss, eager_d, _ = run_op(dev, td, shape)
         loss = torch.zeros((1,), device="cuda")
         d = torch.zeros_like(eager_d)
@@ -244,8 +237,6 @@ def test_op_is_graph_capturable(cuda):
         d.fill_(-1.0)
         g.replay()
         torch.cuda.synchronize()
-    finally:
-        dino_amd.set_option("deterministic", 0)
     assert torch.equal(loss, eager_loss) and torch.equal(d, eager_d)
 
 
@@ -280,8 +271,7 @@ def test_fused_step_equals_its_three_parts(cuda):
     B, H, W, hp, wp, C = 2, 64, 96, 8, 12, 7
     shape = (B, hp, wp, C, H, W)
     lib = capi.lib()
-    dino_amd.set_option("deterministic", 1)
-    try:
+    with dino_amd.options(deterministic=1):
         out = m.fused_training_step_dense((frames, y))
         want = {k: p.grad.clone() for k, p in m.named_parameters()}
         assert all(torch.isfinite(v).all() for v in want.values()) and float(want["clf.layer_3.weight"].abs().max()) > 0
@@ -290,8 +280,6 @@ def test_fused_step_equals_its_three_parts(cuda):
         loss, dlogp, _ = run_op(logp, y.contiguous(), shape)
         capi.check(lib.dinoseg_backward(m._handle, dlogp.data_ptr(), S()))
         torch.cuda.synchronize()
-    finally:
-        dino_amd.set_option("deterministic", 0)
     assert torch.equal(logp, out["probs"]) and torch.equal(loss.reshape(()), out["loss"])
     for k, p in m.named_parameters():
         assert torch.equal(p.grad, want[k]), k
@@ -380,8 +368,7 @@ def test_dense_step_is_graph_capturable(cuda):
     m, frames, y = small_model_and_batch()
     B, H, W = 2, 64, 96
     yf = y.reshape(-1).contiguous()
-    dino_amd.set_option("deterministic", 1)
-    try:
+    with dino_amd.options(deterministic=1):
         eager = m.fused_training_step_dense((frames, y))
         want = {k: p.grad.clone() for k, p in m.named_parameters()}
         loss = torch.zeros((), device="cuda")
@@ -402,8 +389,6 @@ def test_dense_step_is_graph_capturable(cuda):
             p.grad.fill_(7.0)
         g.replay()
         torch.cuda.synchronize()
-    finally:
-        dino_amd.set_option("deterministic", 0)
     assert torch.equal(loss, eager["loss"])
     for k, p in m.named_parameters():
         assert torch.equal(p.grad, want[k]), k

@@ -11,14 +11,14 @@ entry takes is larger than the minimal one, and the gaps of the inputs hold fini
 The attention kernels additionally run with finite garbage in the pad rows ntok..npad of Q, K and V -- one pad key per head a multiple of
 a real query, a log2-domain score near +100 -- and must give the bits of the run on zero pad rows: the pad rows need not be zero (the
 contract of include/dinoseg.h)."""
-import contextlib
 import math
 
 import numpy as np
 import pytest
 import torch
 
-from dino_amd import capi
+import dino_amd
+from dino_amd import capi, options
 from oracle import dinoseg_oracle as O
 from tests.gpu_util import Guarded, pack_slabs, seeded, strided_planes, untouched
 from tests.test_ops_gpu import _ln_ref, _mlp3_case, _one_plane, _pack_mlp4, _pack_rs, _q1, _split_planes, pack_mlp
@@ -27,24 +27,9 @@ pytestmark = pytest.mark.gpu
 S = capi.stream_ptr
 LOG2E = 1.4426950408889634
 QSCALE = 0.125 * LOG2E
-ATTN_VARIANT_DEFAULT = 11 | 1024 | 65536        # kernels.h: Options::attn_variant
-# what options() restores: the defaults of struct Options in dino_amd/csrc/kernels.h -- keep the two in step
-OPTION_DEFAULTS = {"attn_variant": ATTN_VARIANT_DEFAULT, "op_fmt": 0, "op_v_bf16": 0, "gemm_big": 1, "route_ab": 0}
 DT = {"bf16": torch.bfloat16, "fp16": torch.float16}
 M_EDGES = [1, 77, 128 * 5 + 33]         # one row; one partial tile; five tiles and a ragged sixth
 M_PERSISTENT = 128 * 300 + 19           # more items than workgroups (the persistent kernels), ragged last item
-
-
-@contextlib.contextmanager
-def options(**kw):
-    lib = capi.lib()
-    try:
-        for k, v in kw.items():
-            capi.check(lib.dinoseg_set_option(k.encode(), v))
-        yield
-    finally:
-        for k in kw:
-            capi.check(lib.dinoseg_set_option(k.encode(), OPTION_DEFAULTS[k]))
 
 
 def to_planes(x, dt, planes):
@@ -68,7 +53,8 @@ def _ends(M):
 
 
 # ------------------------------------------------------------------------------------------------ attention
-# name -> (attn_variant, planes, Q / K / ctx format, op_v_bf16, LSE output, ctx bar, lse bar).  The bars are those of the kernel's existing
+# name -> (attn_variant, planes, Q / K / ctx format, op_v_bf16, LSE output, ctx bar, lse bar); attn_variant None = the library's default, which
+# attn_variant_of() reads.  The bars are those of the kernel's existing
 # test: test_attention / test_attention_kernel_variants (1.2e-2 / 6e-3 on one bf16 plane, 1e-4 / 1e-4 on hi + lo planes),
 # test_attention_za_is_bit_identical_to_the_compiled_kernel (2e-2), test_attention_za_hi_lo_planes_bit_identical (1e-4 / 5e-3),
 # test_attention_key_split_for_small_grids (1.5e-2), test_fp16_gpu.py::test_attention_fp16_qk (1.2e-2: the default route without an LSE,
@@ -82,20 +68,20 @@ ATTN_KERNELS.update({
     "z256-bf16": (11 | 512 | 4096, 1, "bf16", 0, True, 2e-2, 6e-3),                        # attn_fwd_z_kernel<1, 4, 8>
     "za32-bf16": (11 | 512 | 1024 | 2048, 1, "bf16", 0, True, 2e-2, 6e-3),                 # attention_za.hip, 32 queries per wave
     "za64-bf16": (11 | 512 | 1024 | 2048 | 65536, 1, "bf16", 0, True, 2e-2, 6e-3),         # ... 64 queries per wave
-    "split-bf16": (ATTN_VARIANT_DEFAULT, 1, "bf16", 0, False, 1.5e-2, None),               # attn_fwd_zs_kernel<., 2 / 3> from 193 / 2048 tokens on
+    "split-bf16": (None, 1, "bf16", 0, False, 1.5e-2, None),               # attn_fwd_zs_kernel<., 2 / 3> from 193 / 2048 tokens on
     "z-bf16x3": (11 | 16, 2, "bf16", 0, True, 1e-4, 5e-3),                                 # attn_fwd_z_kernel<2, 3, 12>
     "za-bf16x3": (11 | 16 | 1024 | 2048, 2, "bf16", 0, True, 1e-4, 5e-3),                  # attention_za.hip, hi + lo body
     # the default options with an LSE (the training forward): launch_attention keeps attention.hip VAR 3 then, the kernel of ref3-bf16x3,
     # reached here through the default dispatch; the default hi + lo INFERENCE route (no LSE, large grids) is attention_za.hip = za-bf16x3
-    "default-bf16x3": (ATTN_VARIANT_DEFAULT, 2, "bf16", 0, True, 1e-4, 1e-4),
+    "default-bf16x3": (None, 2, "bf16", 0, True, 1e-4, 1e-4),
     "z128-fp16": (11 | 512, 1, "fp16", 0, False, 1.2e-2, None),                            # fp16 Q / K, bf16 V
     "z256-fp16": (11 | 512 | 4096, 1, "fp16", 0, False, 2e-2, None),
     "za32-fp16": (11 | 512 | 1024 | 2048, 1, "fp16", 0, False, 2e-2, None),
     "za64-fp16": (11 | 512 | 1024 | 2048 | 65536, 1, "fp16", 0, False, 2e-2, None),
-    "split-fp16": (ATTN_VARIANT_DEFAULT, 1, "fp16", 0, False, 1.2e-2, None),
+    "split-fp16": (None, 1, "fp16", 0, False, 1.2e-2, None),
     "z-fp16x3-vbf16": (11 | 16, 2, "fp16", 1, False, 1e-4, None),                          # fp16 hi + lo Q / K / ctx, bf16 hi + lo V
     "za-fp16x3-vbf16": (11 | 16 | 1024 | 2048, 2, "fp16", 1, False, 1e-4, None),
-    "ref3-fp16x3": (ATTN_VARIANT_DEFAULT, 2, "fp16", 0, False, 1e-5, None),                # attention.hip, every operand fp16 hi + lo
+    "ref3-fp16x3": (None, 2, "fp16", 0, False, 1e-5, None),                # attention.hip, every operand fp16 hi + lo
 })
 ATTN_SHAPES = [(1, 1, 1), (1, 3, 65), (2, 2, 197), (1, 1, 257), (2, 5, 300)]
 ATTN_LONG = (1, 1, 2051)       # 33 key tiles with 3 valid keys in the last, a last q-tile with 3 valid rows: the three-group split, 256-query forms
@@ -103,6 +89,11 @@ ATTN_LONG_KERNELS = ("z256-bf16", "za32-bf16", "za64-bf16", "split-bf16", "za-bf
                      "za-fp16x3-vbf16")
 PAD_SHAPES = [(1, 3, 65), (1, 1, 257), (2, 2, 197)]
 _attn_cache = {}
+
+
+def attn_variant_of(name):
+    variant = ATTN_KERNELS[name][0]
+    return dino_amd.get_option("attn_variant") if variant is None else variant
 
 
 def _attn_operands(B, H, ntok, planes, fmt, v_bf16):
@@ -144,7 +135,7 @@ def _attn_operands(B, H, ntok, planes, fmt, v_bf16):
 def _attn_run(name, B, H, ntok, qkv, guarded):
     """one dinoseg_op_attention launch, ctx and lse between guard bands; guarded: every stride larger than minimal, else the exact layout.
     Returns (ctx planes [planes, B*ntok, H*64] int16, lse [B*H*ntok] or None, guards untouched)"""
-    variant, planes, fmt, v_bf16, want_lse, _, _ = ATTN_KERNELS[name]
+    _, planes, fmt, v_bf16, want_lse, _, _ = ATTN_KERNELS[name]
     npad = (ntok + 63) // 64 * 64
     ctx = Guarded(planes, B * ntok, H * 64, torch.int16, exact=not guarded)
     lse = Guarded(1, 1, B * H * ntok, torch.float32, band=4096) if want_lse else None
@@ -153,7 +144,7 @@ def _attn_run(name, B, H, ntok, qkv, guarded):
         (qp, kp, vp), qkv_plane = [x[1] for x in keep], keep[0][2]
     else:
         (qp, kp, vp), qkv_plane = [t.data_ptr() for t in qkv], B * H * npad * 64
-    with options(attn_variant=variant, op_fmt=int(fmt == "fp16"), op_v_bf16=v_bf16):
+    with options(attn_variant=attn_variant_of(name), op_fmt=int(fmt == "fp16"), op_v_bf16=v_bf16):
         capi.check(capi.lib().dinoseg_op_attention(qp, kp, vp, qkv_plane, ctx.ptr(), ctx.plane, lse.ptr() if lse else None, B, H, ntok, npad,
                                                    planes, S()))
         torch.cuda.synchronize()

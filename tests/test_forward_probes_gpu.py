@@ -27,14 +27,13 @@ mlp_fused2.hip and gemm_ln12.hip hand the bias to the accumulator as three 16-bi
 bits) and for fp16 down to its subnormal grid, 2^-24 -- an fp16 bias loses at most 2^-25 (pre_err below, times |gelu'| <= 1.13), and
 a bias beyond 65504 cannot be given at all: there the saturation probe reaches 76 800 through the fc1 product instead.
 """
-import contextlib
 import math
 
 import numpy as np
 import pytest
 import torch
 
-from dino_amd import capi
+from dino_amd import capi, options
 from tests import probe_util as P
 
 pytestmark = pytest.mark.gpu
@@ -62,18 +61,6 @@ def zeros(*shape):
 
 def i16(*shape):
     return torch.zeros(shape, dtype=torch.int16, device="cuda")
-
-
-@contextlib.contextmanager
-def options(**kv):
-    lib = capi.lib()
-    try:
-        for k, v in kv.items():
-            capi.check(lib.dinoseg_set_option(k.encode(), int(v)))
-        yield
-    finally:
-        for k, v in (("op_fmt", 0), ("gemm_big", 1), ("op_v_bf16", 0)):
-            capi.check(lib.dinoseg_set_option(k.encode(), v))
 
 
 def planes_of(kind):

@@ -6,13 +6,13 @@ runs split (bf16 hi+lo).  Op tests: against fp64 on the operands the kernel saw,
 test_ops_gpu.py (the stand-alone ops take the format from option `op_fmt`).  Model tests: against the goldens captured from the
 reference (vision_transformer.py:237-248, pl_torch_modules.py:239-256); the bounds are 1.5x what was measured on MI355X.
 """
-import contextlib
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import dino_amd
 from dino_amd import DINOSeg, ViTConfig, capi, procedural_state_dict
 from dino_amd.weights import synthetic_frames, synthetic_labels
 from oracle import dinoseg_oracle as O
@@ -26,14 +26,9 @@ FP16_MAX = 65504.0
 S = capi.stream_ptr
 
 
-@contextlib.contextmanager
 def fp16_ops():
     """Stand-alone ops (dinoseg_op_*) with single-plane fp16 operands."""
-    capi.check(capi.lib().dinoseg_set_option(b"op_fmt", 1))
-    try:
-        yield
-    finally:
-        capi.check(capi.lib().dinoseg_set_option(b"op_fmt", 0))
+    return dino_amd.options(op_fmt=1)
 
 
 def q16(x: torch.Tensor) -> torch.Tensor:
@@ -83,8 +78,7 @@ def test_gemm_resid_and_gelu(cuda, M, N, K):
     for big in (0, 2):
         if big == 2 and (N % 384 != 0 or K % 32 != 0):
             continue
-        capi.check(lib.dinoseg_set_option(b"gemm_big", big))
-        try:
+        with dino_amd.options(gemm_big=big):
             with fp16_ops():
                 Ap, Wp = pack(A, 1), pack(W, 1)
                 X = X0.clone()
@@ -94,8 +88,6 @@ def test_gemm_resid_and_gelu(cuda, M, N, K):
                 capi.check(lib.dinoseg_op_gemm(Ap.data_ptr(), M * K, K, Wp.data_ptr(), N * K, M, N, K, 1, capi.EPI_GELU, bias.data_ptr(),
                                                None, outp.data_ptr(), M * N, N, S()))
                 torch.cuda.synchronize()
-        finally:
-            capi.check(lib.dinoseg_set_option(b"gemm_big", 1))
         # same quantised operands, fp32 accumulation: only summation-order noise remains
         assert float((X - X0 - base).abs().max()) <= 3e-6 * scale * max(1.0, (K / 64) ** 0.5), big
         want = O.gelu_erf(base.cpu()).cuda()
@@ -136,14 +128,11 @@ def test_qkv_layout_q_k_fp16_v_bf16(cuda, route, B, ntok):
         slack = 2.0          # the kernel's own fp32 LayerNorm can move an fp16 rounding point of A
     else:
         A0 = seeded((M_, D), 5)
-        capi.check(lib.dinoseg_set_option(b"gemm_big", 2 if route == "gemm_big" else 0))
-        try:
+        with dino_amd.options(gemm_big=2 if route == "gemm_big" else 0):
             with fp16_ops():
                 Ap, Wp = pack(A0, 1), pack(W, 1)
                 capi.check(lib.dinoseg_op_qkv_gemm(Ap.data_ptr(), M_ * D, Wp.data_ptr(), 3 * D * D, bias.data_ptr(), B, ntok, npad, H, 1,
                                                    qscale, q.data_ptr(), k.data_ptr(), v.data_ptr(), plane, S()))
-        finally:
-            capi.check(lib.dinoseg_set_option(b"gemm_big", 1))
         A = q16(A0)
         slack = 1.0
     torch.cuda.synchronize()
@@ -294,18 +283,12 @@ def test_g3_vits8_480_one_wave_fused_mlp_is_bounded(cuda, golden_dir, L, precisi
     g = load(golden_dir, f"g3_vits8_L{L}_r480")
     m, _, _ = build(L, precision)
     frames = torch.from_numpy(synthetic_frames(1, 480, seed=int(g["frame_seed"]))).cuda()
-    lib = capi.lib()
     out = {}
-    try:
-        for f4 in (1, 0):      # (the option is read when the weights are packed -- at the first forward of this model -- and at every forward)
-            for k, v in (("mlp_fused", 2), ("proj_fused", 1), ("qkv_fused", 0), ("mlp_fused4", f4)):
-                capi.check(lib.dinoseg_set_option(k.encode(), v))
+    for f4 in (1, 0):      # (the option is read when the weights are packed -- at the first forward of this model -- and at every forward)
+        with dino_amd.options(mlp_fused=2, proj_fused=1, qkv_fused=0, mlp_fused4=f4):
             lp, am = m.forward_frames(frames)
             torch.cuda.synchronize()
-            out[f4] = (lp.cpu(), am.cpu().long())
-    finally:
-        for k, v in (("mlp_fused", 1), ("proj_fused", 1), ("qkv_fused", 0), ("mlp_fused4", 0)):
-            capi.check(lib.dinoseg_set_option(k.encode(), v))
+        out[f4] = (lp.cpu(), am.cpu().long())
     lp, am = out[1]
     assert torch.isfinite(lp).all()
     err = float((lp - torch.from_numpy(g["logp"])).abs().max())
@@ -325,15 +308,9 @@ def test_g3_vits8_480_fp16_mode_is_bounded(cuda, golden_dir, L, mlp_fused, proj_
     g = load(golden_dir, f"g3_vits8_L{L}_r480")
     m, _, _ = build(L, "fp16")
     frames = torch.from_numpy(synthetic_frames(1, 480, seed=int(g["frame_seed"]))).cuda()
-    lib = capi.lib()
-    for k, v in (("mlp_fused", mlp_fused), ("proj_fused", proj_fused), ("qkv_fused", qkv_fused), ("gemm_ln", gemm_ln)):
-        capi.check(lib.dinoseg_set_option(k.encode(), v))
-    try:
+    with dino_amd.options(mlp_fused=mlp_fused, proj_fused=proj_fused, qkv_fused=qkv_fused, gemm_ln=gemm_ln):
         lp, am = m.forward_frames(frames)
         torch.cuda.synchronize()
-    finally:
-        for k, v in (("mlp_fused", 1), ("proj_fused", 1), ("qkv_fused", 0), ("gemm_ln", 1)):
-            capi.check(lib.dinoseg_set_option(k.encode(), v))
     assert torch.isfinite(lp).all()
     err = float((lp.cpu() - torch.from_numpy(g["logp"])).abs().max())
     flips = int((am.cpu().long() != torch.from_numpy(g["argmax"].astype(np.int64))).sum())
@@ -443,8 +420,7 @@ def test_gemm_hi_lo_planes_fp16(cuda):
     scale = float(ref.abs().max())
     X0 = seeded((M, N), 4)
     for big in (0, 2):
-        capi.check(lib.dinoseg_set_option(b"gemm_big", big))
-        try:
+        with dino_amd.options(gemm_big=big):
             with fp16_ops():
                 Ap, Wp = pack(A, 2), pack(W, 2)
                 X = X0.clone()
@@ -454,8 +430,6 @@ def test_gemm_hi_lo_planes_fp16(cuda):
                 capi.check(lib.dinoseg_op_gemm(Ap.data_ptr(), M * K, K, Wp.data_ptr(), N * K, M, N, K, 2, capi.EPI_RELU, bias.data_ptr(),
                                                None, outp.data_ptr(), M * N, N, S()))
                 torch.cuda.synchronize()
-        finally:
-            capi.check(lib.dinoseg_set_option(b"gemm_big", 1))
         err = float((X - X0 - ref).abs().max())
         assert err <= 3e-6 * scale, (big, err / scale)          # (bf16 hi + lo: 4e-5; fp32 summation noise at K = 1536 is ~1e-6)
         got = un16(outp)
@@ -559,14 +533,10 @@ def test_fp16x3_holds_the_flat_bar_under_outliers(cuda, chan, head):
     m = DINOSeg(head=cfg.head, n_blocks=3, n_classes=cfg.n_classes, precision="fp16x3", arch=cfg)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
     m = m.to("cuda:0")
-    lib = capi.lib()
     for big in (1, 0):
-        capi.check(lib.dinoseg_set_option(b"gemm_big", big))
-        try:
+        with dino_amd.options(gemm_big=big):
             lp, am = m.forward_frames(torch.from_numpy(frames_np).cuda())
             torch.cuda.synchronize()
-        finally:
-            capi.check(lib.dinoseg_set_option(b"gemm_big", 1))
         assert torch.isfinite(lp).all()
         err = float((lp.cpu() - ref).abs().max())
         print(f"outliers x{chan:g} / x{head:g} fp16x3 (gemm_big={big}): max|dlogp| {err:.3e}")

@@ -17,10 +17,8 @@ CASES = [(p, s) for p in ("bf16", "bf16x3") for s in (1, 2)]
 
 @contextlib.contextmanager
 def stepping(precision, streams):
-    """The model and its batch, with the options of the case set and the defaults restored on the way out."""
-    dino_amd.set_option("deterministic", 1)
-    dino_amd.set_option("train_streams", streams)
-    try:
+    """The model and its batch, with the options of the case set for the body."""
+    with dino_amd.options(deterministic=1, train_streams=streams):
         sd = procedural_state_dict(CFG)
         m = DINOSeg(head=CFG.head, n_blocks=CFG.n_blocks, n_classes=CFG.n_classes, precision=precision, arch=CFG)
         m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
@@ -29,9 +27,6 @@ def stepping(precision, streams):
         lb = torch.from_numpy(synthetic_labels(2, 64, CFG.n_classes, seed=172)).cuda()
         yield m, (fr, lb)
         torch.cuda.synchronize()
-    finally:
-        dino_amd.set_option("deterministic", 0)
-        dino_amd.set_option("train_streams", 2)
 
 
 @pytest.mark.parametrize("precision,streams", CASES)

@@ -9,13 +9,13 @@ Errors are max |err| / max |ref| (Adam: relative to the summed magnitudes of eac
 `helper_ops` line: the kernel's error, the restatement's, their ratio and the bar (profiles/helper_ops_parity_lines.txt holds a run).
 For 16-bit outputs the kernel's error contains the rounding of the output format, so the ratio can pass 4 there while the bar holds.
 """
-import contextlib
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
+import dino_amd
 from dino_amd import DINOSeg, ViTConfig, capi, procedural_state_dict
 from dino_amd.weights import synthetic_frames
 from oracle import dinoseg_oracle as O
@@ -31,13 +31,8 @@ FMT = {"bf16": 0, "fp16": 1}
 ULP16 = {("bf16", 1): 2.0 ** -8, ("bf16", 2): 2.0 ** -15, ("fp16", 1): 2.0 ** -11, ("fp16", 2): 2.0 ** -22}
 
 
-@contextlib.contextmanager
 def op_fmt(fmt):
-    capi.check(capi.lib().dinoseg_set_option(b"op_fmt", FMT[fmt]))
-    try:
-        yield
-    finally:
-        capi.check(capi.lib().dinoseg_set_option(b"op_fmt", 0))
+    return dino_amd.options(op_fmt=FMT[fmt])
 
 
 def unpack64(p, fmt):

@@ -135,12 +135,124 @@ def test_handle_lifecycle_and_errors_without_gpu():
         assert lib.dinoseg_create(ctypes.byref(cfg), ctypes.byref(h)) == 0 and lib.dinoseg_destroy(h) == 0
     cfg = capi.Config(384, 6, 1, 8, 4, 7, capi.HEAD_MLP, 28, 1e-6, 4)
     assert lib.dinoseg_create(ctypes.byref(cfg), ctypes.byref(h)) == -1
-    assert lib.dinoseg_set_option(b"op_fmt", 2) == -1 and "op_fmt" in capi.last_error()
-    assert lib.dinoseg_set_option(b"op_fmt", 0) == 0 and lib.dinoseg_set_option(b"mlp_variant", 1) == 0
-    assert lib.dinoseg_set_option(b"no_such_option", 1) == -1
+    with dino_amd.options():
+        assert lib.dinoseg_set_option(b"op_fmt", 2) == -1 and "op_fmt" in capi.last_error()
+        assert lib.dinoseg_set_option(b"op_fmt", 0) == 0 and lib.dinoseg_set_option(b"mlp_variant", 1) == 0
+        assert lib.dinoseg_set_option(b"no_such_option", 1) == -1
     assert set(dino_amd.dinoseg._PRECISIONS) == {"bf16", "bf16x3", "fp16", "fp16x3"}
     with pytest.raises(ValueError, match="precision"):
         DINOSeg(precision="fp32")
+
+
+# Every key of dinoseg_set_option with its default: the one place outside dino_amd/csrc/kernels.h (struct Options) where the defaults
+# stand.  Everything else reads them (dino_amd.get_option) or restores what it found (dino_amd.options).
+KERNELS_H_DEFAULTS = {
+    "gemm_ln": 1, "gemm_big": 1, "gemm_dbg": 0, "attn_dbg": 0, "mlp_fused": 1, "mlp_fused_min_rows": 12000, "mlp_fused3_min_rows": 10000,
+    "mlp_stagger": 0, "mlp_grid": 0, "qkv_fused": 0, "mlp_fused4": 0, "qkv_fused4": 1, "qkv_fused3": 1, "gemm_rs": 3,
+    "gemm_rs_min_rows": 24000, "gemm_rs_ln": 1, "proj_fused": 1, "streams": 2, "split_min": 8, "route_ab": 0, "fp16_patch_planes": 1,
+    "op_v_bf16": 0, "op_fmt": 0, "deterministic": 0, "train_streams": 2, "splitk_tiles": 512, "attn_variant": 66571,       # bits 0, 1, 3, 10 and 16
+    "mlp_variant": 0,
+}
+OPTION_FLAGS = ("op_v_bf16", "deterministic", "gemm_rs_ln", "qkv_fused3", "qkv_fused4", "mlp_fused4")      # stored as 0 / 1
+
+
+def _get(key):
+    """(return code, value) of dinoseg_get_option; the value starts as a sentinel"""
+    out = ctypes.c_int32(-77)
+    return capi.lib().dinoseg_get_option(key, ctypes.byref(out)), out.value
+
+
+def test_option_get_reads_what_set_stored():
+    """dinoseg_get_option returns the stored, normalised value of every key."""
+    lib = capi.lib()
+    before = {k: dino_amd.get_option(k) for k in dino_amd.option_names()}
+    with dino_amd.options():
+        for name in dino_amd.option_names():
+            key = name.encode()
+            for v in ((0, 1) if name == "op_fmt" else (0, 1, 2, 1000, -3)):
+                assert lib.dinoseg_set_option(key, v) == 0, (name, v)
+                want = {"mlp_variant": 0, "gemm_rs": v & 7, "split_min": max(v, 2), "fp16_patch_planes": 1 if v == 1 else 2}.get(
+                    name, int(v != 0) if name in OPTION_FLAGS else v)
+                assert _get(key) == (0, want), (name, v)
+        for name, v, want in (("deterministic", 5, 1), ("split_min", 1, 2), ("gemm_rs", 15, 7), ("fp16_patch_planes", 3, 2),
+                              ("mlp_variant", 9, 0)):
+            assert lib.dinoseg_set_option(name.encode(), v) == 0 and _get(name.encode()) == (0, want), name
+        assert lib.dinoseg_set_option(b"op_fmt", 1) == 0
+        assert lib.dinoseg_set_option(b"op_fmt", 2) == -1 and "op_fmt" in capi.last_error()
+        assert _get(b"op_fmt") == (0, 1)                      # a refused value stores nothing
+    assert {k: dino_amd.get_option(k) for k in dino_amd.option_names()} == before
+
+
+def test_option_get_refusals():
+    lib = capi.lib()
+    assert _get(b"no_such_option") == (-1, -77)               # the output is untouched
+    assert "dinoseg_get_option: unknown key 'no_such_option'" in capi.last_error()
+    assert _get(None) == (-1, -77)
+    assert "dinoseg_get_option: null argument" in capi.last_error()
+    assert lib.dinoseg_get_option(b"streams", None) == -1
+    assert "dinoseg_get_option: null argument" in capi.last_error()
+    with pytest.raises(capi.DinosegError, match="no_such_option"):
+        dino_amd.get_option("no_such_option")
+
+
+def test_option_enumeration():
+    """dinoseg_option_name walks the table: 28 unique names, NULL on both sides, each accepted by get and set and documented."""
+    lib = capi.lib()
+    names = dino_amd.option_names()
+    assert len(names) == 28 and len(set(names)) == 28
+    assert lib.dinoseg_option_name(-1) is None and lib.dinoseg_option_name(len(names)) is None
+    assert [lib.dinoseg_option_name(i).decode() for i in range(len(names))] == names
+    with open(capi.HEADER_PATH) as f:
+        text = f.read()
+    comment = text[text.index("/* Process-wide switches."):text.index("int dinoseg_set_option(")]
+    for name in names:
+        rc, value = _get(name.encode())
+        assert rc == 0 and lib.dinoseg_set_option(name.encode(), value) == 0, name
+        assert f'"{name}"' in comment, f"include/dinoseg.h: the dinoseg_set_option comment does not name {name}"
+
+
+def test_option_defaults_in_a_fresh_process():
+    """A process that has set nothing reads KERNELS_H_DEFAULTS, key by key (a changed default in kernels.h is an edit of that table)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = "import json, dino_amd; print(json.dumps({k: dino_amd.get_option(k) for k in dino_amd.option_names()}))"
+    out = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    got = json.loads(out.stdout.strip().splitlines()[-1])
+    assert len(KERNELS_H_DEFAULTS) == 28 and got == KERNELS_H_DEFAULTS
+
+
+def test_option_scope_restores_every_key():
+    """dino_amd.options: after a normal body, after a body that raises, after a bare set_option of a key it was not given, nested on
+    one key, and when one of its own values is refused."""
+    state = lambda: {k: dino_amd.get_option(k) for k in dino_amd.option_names()}
+    outside = state()
+    with dino_amd.options(streams=1):
+        before = state()
+        with dino_amd.options(streams=3, deterministic=1):
+            assert (dino_amd.get_option("streams"), dino_amd.get_option("deterministic")) == (3, 1)
+        assert state() == before
+        with pytest.raises(KeyError):
+            with dino_amd.options(gemm_ln=0):
+                assert dino_amd.get_option("gemm_ln") == 0
+                raise KeyError("body")
+        assert state() == before
+        with dino_amd.options(gemm_ln=2):
+            dino_amd.set_option("mlp_fused", 0)
+            dino_amd.set_option("gemm_ln", 0)
+        assert state() == before
+        with dino_amd.options(split_min=4):
+            with dino_amd.options(split_min=6):
+                assert dino_amd.get_option("split_min") == 6
+            assert dino_amd.get_option("split_min") == 4
+        assert state() == before
+        with pytest.raises(capi.DinosegError, match="op_fmt"):
+            with dino_amd.options(gemm_big=0, op_fmt=2, gemm_ln=0):
+                raise AssertionError("the body must not run")
+        assert state() == before
+    assert state() == outside
 
 
 def test_native_name_and_shape_table_matches_tensor_shapes():

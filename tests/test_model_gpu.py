@@ -76,15 +76,8 @@ def test_g3_vits8_480_bf16_mode_is_bounded(cuda, golden_dir, L, mlp_fused, proj_
     g = load(golden_dir, f"g3_vits8_L{L}_r480")
     m, _, _ = build(L, "bf16")
     frames = torch.from_numpy(synthetic_frames(1, 480, seed=int(g["frame_seed"]))).cuda()
-    dino_amd.set_option("mlp_fused", mlp_fused)
-    dino_amd.set_option("proj_fused", proj_fused)
-    dino_amd.set_option("qkv_fused", qkv_fused)
-    try:
+    with dino_amd.options(mlp_fused=mlp_fused, proj_fused=proj_fused, qkv_fused=qkv_fused):
         lp, am = m.forward_frames(frames)
-    finally:
-        dino_amd.set_option("mlp_fused", 1)
-        dino_amd.set_option("proj_fused", 1)
-        dino_amd.set_option("qkv_fused", 0)
     err = float((lp.cpu() - torch.from_numpy(g["logp"])).abs().max())
     differ = am.cpu().numpy() != g["argmax"].astype(np.int32)
     print(f"L={L} bf16 mode (mlp_fused={mlp_fused} proj_fused={proj_fused} qkv_fused={qkv_fused}): max|dlogp|={err:.3e} "
@@ -452,12 +445,11 @@ def test_two_stream_split_equals_one_stream(cuda, precision, B):
     m, _, _ = build(2, precision)
     m.set_resolution(112)
     frames = torch.from_numpy(synthetic_frames(B, 112, seed=77)).cuda()
-    dino_amd.set_option("streams", 1)                          # the reference: the whole batch on the caller's stream
-    lp1, am1 = m.forward_frames(frames)
-    lp1, am1 = lp1.clone(), am1.clone()
-    small1 = m.forward_frames(frames[:3])[0].clone()
-    dino_amd.set_option("streams", 2)
-    try:
+    with dino_amd.options(streams=1):                          # the reference: the whole batch on the caller's stream
+        lp1, am1 = m.forward_frames(frames)
+        lp1, am1 = lp1.clone(), am1.clone()
+        small1 = m.forward_frames(frames[:3])[0].clone()
+    with dino_amd.options(streams=2):
         noise = torch.randn(2048, 2048, device="cuda")
         for _ in range(3):
             noise = noise @ noise * 1e-3                       # the fork must wait for what is already queued, the join for both halves
@@ -465,8 +457,6 @@ def test_two_stream_split_equals_one_stream(cuda, precision, B):
             assert torch.equal(lp2, lp1) and torch.equal(am2, am1)
         small, _ = m.forward_frames(frames[:3])                # below split_min: the ordinary path
         assert torch.equal(small, small1)
-    finally:
-        dino_amd.set_option("streams", 2)                      # the library default
 
 
 def test_two_stream_split_equals_one_stream_fused_routes(cuda):
@@ -477,8 +467,7 @@ def test_two_stream_split_equals_one_stream_fused_routes(cuda):
     import dino_amd
     m, _, _ = build(2, "bf16")
     frames = torch.from_numpy(synthetic_frames(9, 480, seed=79)).cuda()
-    dino_amd.set_option("streams", 1)
-    try:
+    with dino_amd.options(streams=1):
         lp1, am1 = m.forward_frames(frames)
         lp1, am1 = lp1.clone(), am1.clone()
         dino_amd.set_option("streams", 2)
@@ -487,8 +476,6 @@ def test_two_stream_split_equals_one_stream_fused_routes(cuda):
             assert torch.equal(lp2, lp1) and torch.equal(am2, am1)
         single, _ = m.forward_frames(frames[4:5])            # one frame: unfused route (3601 rows)
         assert float((single - lp1.reshape(9, 3600, -1)[4]).abs().max()) <= 0.2
-    finally:
-        dino_amd.set_option("streams", 2)
 
 
 @pytest.mark.parametrize("precision", ["bf16x3", "fp16x3", "fp16", "bf16"])
@@ -500,16 +487,13 @@ def test_two_stream_split_equals_one_stream_at_the_benchmark_batch(cuda, precisi
     import dino_amd
     m, _, _ = build(2, precision)
     frames = torch.from_numpy(synthetic_frames(32, 480, seed=91)).cuda()
-    dino_amd.set_option("streams", 1)
-    try:
+    with dino_amd.options(streams=1):
         lp1, am1 = m.forward_frames(frames)
         lp1, am1 = lp1.clone(), am1.clone()
         dino_amd.set_option("streams", 2)
         lp2, am2 = m.forward_frames(frames)
         assert torch.isfinite(lp1).all()
         assert torch.equal(lp2, lp1) and torch.equal(am2, am1)
-    finally:
-        dino_amd.set_option("streams", 2)
 
 
 def test_fused_routes_agree_on_random_shapes(cuda):
@@ -527,28 +511,23 @@ def test_fused_routes_agree_on_random_shapes(cuda):
               ("fused+proj+qkv", dict(mlp_fused=2, proj_fused=1, qkv_fused=1, streams=1)),
               ("two streams", dict(mlp_fused=2, proj_fused=1, qkv_fused=0, streams=2, split_min=2)),
               ("two streams+qkv", dict(mlp_fused=2, proj_fused=1, qkv_fused=1, streams=2, split_min=2)))
-    try:
-        for c in range(16):
-            r = int(rng.choice([64, 96, 120, 168, 200, 248, 320, 400]))
-            B = int(rng.integers(1, 12))
-            m.set_resolution(r)
-            frames = torch.from_numpy(synthetic_frames(B, r, seed=2000 + c)).cuda()
-            outs = {}
-            for name, opts in routes:
-                for k, v in opts.items():
-                    dino_amd.set_option(k, v)
+    for c in range(16):
+        r = int(rng.choice([64, 96, 120, 168, 200, 248, 320, 400]))
+        B = int(rng.integers(1, 12))
+        m.set_resolution(r)
+        frames = torch.from_numpy(synthetic_frames(B, r, seed=2000 + c)).cuda()
+        outs = {}
+        for name, opts in routes:
+            with dino_amd.options(**opts):
                 lp, am = m.forward_frames(frames)
                 assert torch.isfinite(lp).all(), (name, r, B)
                 outs[name] = (lp.clone(), am.clone())
-            ref_lp, ref_am = outs["separate"]
-            for name, (lp, am) in outs.items():
-                assert float((lp - ref_lp).abs().max()) <= 0.25, (name, r, B)
-                assert float((am != ref_am).float().mean()) <= 0.02, (name, r, B)
-            assert torch.equal(outs["two streams"][0], outs["fused+proj"][0]), (r, B)
-            assert torch.equal(outs["two streams+qkv"][0], outs["fused+proj+qkv"][0]), (r, B)
-    finally:
-        for k, v in dict(mlp_fused=1, proj_fused=1, qkv_fused=0, streams=2, split_min=8).items():
-            dino_amd.set_option(k, v)
+        ref_lp, ref_am = outs["separate"]
+        for name, (lp, am) in outs.items():
+            assert float((lp - ref_lp).abs().max()) <= 0.25, (name, r, B)
+            assert float((am != ref_am).float().mean()) <= 0.02, (name, r, B)
+        assert torch.equal(outs["two streams"][0], outs["fused+proj"][0]), (r, B)
+        assert torch.equal(outs["two streams+qkv"][0], outs["fused+proj+qkv"][0]), (r, B)
 
 
 @pytest.mark.parametrize("precision,tol", [("bf16x3", 1e-3), ("bf16", 0.35)])
@@ -562,14 +541,11 @@ def test_linear_dispatch_paths_agree(cuda, precision, tol):
     m.set_resolution(480)
     frames = torch.from_numpy(synthetic_frames(8, 480, seed=91)).cuda()
     outs = {}
-    try:
+    with dino_amd.options():
         for ln, big in ((1, 1), (0, 1), (2, 1), (1, 0)):
             dino_amd.set_option("gemm_ln", ln)
             dino_amd.set_option("gemm_big", big)
             outs[(ln, big)] = m.forward_frames(frames)[0].clone()
-    finally:
-        dino_amd.set_option("gemm_ln", 1)
-        dino_amd.set_option("gemm_big", 1)
     ref = outs[(1, 1)]
     assert torch.isfinite(ref).all()
     for k, v in outs.items():
@@ -652,10 +628,9 @@ def test_two_stream_forward_is_graph_capturable(cuda):
     m, _, _ = build(2, "bf16")
     m.set_resolution(112)
     frames = torch.from_numpy(synthetic_frames(16, 112, seed=5)).cuda()
-    dino_amd.set_option("streams", 1)
-    ref = m.forward_frames(frames)[0].clone()
-    dino_amd.set_option("streams", 2)
-    try:
+    with dino_amd.options(streams=1):
+        ref = m.forward_frames(frames)[0].clone()
+    with dino_amd.options(streams=2):
         g = torch.cuda.CUDAGraph()
         s = torch.cuda.Stream()
         with torch.cuda.stream(s):
@@ -668,8 +643,6 @@ def test_two_stream_forward_is_graph_capturable(cuda):
         g.replay()
         torch.cuda.synchronize()
         assert torch.equal(out, ref)
-    finally:
-        dino_amd.set_option("streams", 2)
 
 
 def test_predict_replays_a_captured_graph(cuda, golden_dir):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import dino_amd
 from dino_amd import capi
 from oracle import dinoseg_oracle as O
 from tests.gpu_util import pack, pack_slabs, quant_like, seeded, unpack
@@ -97,15 +98,13 @@ def test_residual_gemm_small_batch_tiles(cuda, planes, M, K):
     X0 = seeded((M, N), 64)
     lib = capi.lib()
     outs = []
-    try:
+    with dino_amd.options():
         for ab in (1, 0):
             capi.check(lib.dinoseg_set_option(b"route_ab", ab))
             X = X0.clone()
             capi.check(lib.dinoseg_op_gemm(Ap.data_ptr(), M * K, K, Wp.data_ptr(), N * K, M, N, K, planes, capi.EPI_RESID,
                                            bias.data_ptr(), X.data_ptr(), None, 0, 0, S()))
             outs.append(X)
-    finally:
-        capi.check(lib.dinoseg_set_option(b"route_ab", 0))
     assert torch.equal(outs[0], outs[1])
     base = (quant_like(A, planes).double() @ quant_like(W, planes).double().t() + bias.double()).float()
     assert torch.allclose(outs[1], X0 + base, atol=3e-4 * math.sqrt(K / 64), rtol=1e-5)
@@ -134,9 +133,6 @@ def test_qkv_gemm_layout(cuda, planes, H, ntok):
     assert float((gk[:, :, :ntok] - ref[1]).abs().max()) <= tol
     assert float((gv[:, :, :ntok] - ref[2]).abs().max()) <= tol
     assert torch.all(gq[:, :, ntok:] == 0) and torch.all(gk[:, :, ntok:] == 0) and torch.all(gv[:, :, ntok:] == 0)
-
-
-ATTN_VARIANT_DEFAULT = 11 | 1024 | 65536        # kernels.h: Options::attn_variant
 
 
 def _attention_case(B, H, ntok, planes, seed, spike=False, want_lse=True):
@@ -224,16 +220,13 @@ def test_attention_kernel_variants(cuda, planes, variant):
     (bf16, the default), bit 4 = zero-reference hi+lo kernel (12 waves; measured, not the default).  Without a rescale after the first tile both bits do the same
     arithmetic in the same order as the base kernel."""
     lib = capi.lib()
-    try:
-        capi.check(lib.dinoseg_set_option(b"attn_variant", 0))
+    with dino_amd.options(attn_variant=0):
         base, ref, lse0, ref_lse = _attention_case(2, 2, 197, planes, seed=5)
         capi.check(lib.dinoseg_set_option(b"attn_variant", variant))
         got, _, lse, _ = _attention_case(2, 2, 197, planes, seed=5)
         got2, ref2, lse2, ref_lse2 = _attention_case(1, 1, 300, planes, seed=77, spike=True)     # rescale path
         got3, ref3, _, _ = _attention_case(1, 2, 3601, planes, seed=9)      # 17 valid rows in the last q-tile
         small = [_attention_case(1, 1, n, planes, seed=n) for n in (1, 33, 64, 65, 128, 129)]   # 1, 2 and 3 tiles, ragged or not
-    finally:
-        capi.check(lib.dinoseg_set_option(b"attn_variant", ATTN_VARIANT_DEFAULT))
     tol = 1.2e-2 if planes == 1 else 1e-4
     lse_tol = 6e-3 if planes == 1 else 1e-4
     # (the pipelined / zero-reference kernels (bits 2, 3: bf16 only; bit 4: the hi+lo zero-reference kernel) round differently)
@@ -270,11 +263,9 @@ def test_attention_za_is_bit_identical_to_the_compiled_kernel(cuda, fp16, mq):
                 got, ref, lse, ref_lse = _attention_case(1, 1, 300, 1, seed=77, spike=sp)
                 out.append((got, lse, ref, ref_lse))
         return out
-    try:
+    with dino_amd.options():
         base = run(11 | 512 | 4096)
         new = run(11 | 512 | 1024 | 2048 | (65536 if mq == 2 else 0))       # (bit 16: 64 queries per wave)
-    finally:
-        capi.check(lib.dinoseg_set_option(b"attn_variant", ATTN_VARIANT_DEFAULT))
     names = [f"{s}" for s in shapes] + ([f"spike {s}" for s in spikes] if not fp16 else [])
     for name, (g0, l0, ref, _), (g1, l1, _, _) in zip(names, base, new):
         assert torch.isfinite(g1).all(), name
@@ -295,7 +286,7 @@ def test_attention_za_bit_identical_at_14401_tokens(cuda, planes):
     mk = lambda sc: (torch.randn((planes, B * H * npad, 64), device="cuda", generator=g) * sc).to(torch.bfloat16).view(torch.int16)
     q, k, v = mk(0.5), mk(0.5), mk(1.0)
     outs = []
-    try:
+    with dino_amd.options():
         for variant in ((11 | 512 | 4096, 11 | 512 | 1024 | 2048, 11 | 512 | 1024 | 2048 | 65536) if planes == 1 else (11 | 16, 11 | 16 | 1024 | 2048)):
             capi.check(lib.dinoseg_set_option(b"attn_variant", variant))
             ctx = torch.zeros((planes, B * ntok, H * 64), dtype=torch.int16, device="cuda")
@@ -304,8 +295,6 @@ def test_attention_za_bit_identical_at_14401_tokens(cuda, planes):
                                                 B * ntok * H * 64, lse.data_ptr(), B, H, ntok, npad, planes, S()))
             torch.cuda.synchronize()
             outs.append((ctx, lse))
-    finally:
-        capi.check(lib.dinoseg_set_option(b"attn_variant", ATTN_VARIANT_DEFAULT))
     assert torch.isfinite(outs[0][1]).all() and bool((outs[0][0] != 0).any())
     for ctx, lse in outs[1:]:
         assert torch.equal(ctx, outs[0][0]) and torch.equal(lse, outs[0][1])
@@ -326,11 +315,9 @@ def test_attention_za_hi_lo_planes_bit_identical(cuda, fp16):
         out = [_attention_case_x3(B, H, ntok, fp16) for B, H, ntok in shapes]
         out += [_attention_case_x3(1, 1, 200, fp16, spike=sp) for sp in spikes]
         return out
-    try:
+    with dino_amd.options():
         base = run(11 | 16)
         new = run(11 | 16 | 1024 | 2048)
-    finally:
-        capi.check(lib.dinoseg_set_option(b"attn_variant", ATTN_VARIANT_DEFAULT))
     names = [f"{s}" for s in shapes] + [f"spike {s}" for s in spikes]
     for name, (g0, l0, ref, ref_lse), (g1, l1, _, _) in zip(names, base, new):
         assert torch.isfinite(g1).all(), name
@@ -367,21 +354,15 @@ def _attention_case_x3(B, H, ntok, fp16, spike=False):
         return full.reshape(-1, 64).cuda()
     lib = capi.lib()
     h16 = lambda t: t.view(torch.float16).float().sum(dim=0)
-    try:
-        capi.check(lib.dinoseg_set_option(b"op_fmt", 1 if fp16 else 0))
+    with dino_amd.options(op_fmt=int(fp16), op_v_bf16=int(fp16)):
         qp, kp = pack(padded(qs), 2), pack(padded(K), 2)
-        capi.check(lib.dinoseg_set_option(b"op_fmt", 0))
-        vp = pack(padded(V), 2)
-        capi.check(lib.dinoseg_set_option(b"op_fmt", 1 if fp16 else 0))
-        capi.check(lib.dinoseg_set_option(b"op_v_bf16", 1 if fp16 else 0))
+        with dino_amd.options(op_fmt=0):
+            vp = pack(padded(V), 2)
         ctx = torch.zeros((2, B * ntok, H * 64), dtype=torch.int16, device="cuda")
         lse = None if fp16 else torch.zeros((B, H, ntok), dtype=torch.float32, device="cuda")
         capi.check(lib.dinoseg_op_attention(qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), B * H * npad * 64, ctx.data_ptr(),
                                             B * ntok * H * 64, capi.ptr(lse), B, H, ntok, npad, 2, S()))
         torch.cuda.synchronize()
-    finally:
-        capi.check(lib.dinoseg_set_option(b"op_fmt", 0))
-        capi.check(lib.dinoseg_set_option(b"op_v_bf16", 0))
     un = h16 if fp16 else unpack
     qq = un(qp).reshape(B, H, npad, 64)[:, :, :ntok].double().cpu() / LOG2E
     kk = un(kp).reshape(B, H, npad, 64)[:, :, :ntok].double().cpu()
@@ -405,18 +386,14 @@ def _attention_case_fp16(B, H, ntok):
         full[:, :, :ntok] = x
         return full.reshape(-1, 64).cuda()
     lib = capi.lib()
-    capi.check(lib.dinoseg_set_option(b"op_fmt", 1))
-    try:
+    with dino_amd.options(op_fmt=1):
         qp, kp = pack(padded(Q), 1), pack(padded(K), 1)
-        capi.check(lib.dinoseg_set_option(b"op_fmt", 0))
-        vp = pack(padded(V), 1)
-        capi.check(lib.dinoseg_set_option(b"op_fmt", 1))
+        with dino_amd.options(op_fmt=0):
+            vp = pack(padded(V), 1)
         ctx = torch.zeros((1, B * ntok, H * 64), dtype=torch.int16, device="cuda")
         capi.check(lib.dinoseg_op_attention(qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), B * H * npad * 64, ctx.data_ptr(),
                                             B * ntok * H * 64, None, B, H, ntok, npad, 1, S()))
         torch.cuda.synchronize()
-    finally:
-        capi.check(lib.dinoseg_set_option(b"op_fmt", 0))
     h = lambda t: t.view(torch.float16).float()
     qq = h(qp).reshape(B, H, npad, 64)[:, :, :ntok].double().cpu() / LOG2E
     kk = h(kp).reshape(B, H, npad, 64)[:, :, :ntok].double().cpu()
@@ -498,18 +475,13 @@ def test_attention_key_split_for_small_grids(cuda, B, H, ntok):
     the same result up to the summation order -- one place of the bf16 output on a few elements per thousand -- and both within the
     usual bound of the fp64 reference; on the exact path (a dominant key late in the sweep) group 0 recomputes in the unsplit kernel's
     order: identical.  With an LSE output (the training forward) the keys are never split: one arithmetic at every batch size."""
-    lib = capi.lib()
-    try:
-        capi.check(lib.dinoseg_set_option(b"attn_variant", ATTN_VARIANT_DEFAULT | 512))
+    with dino_amd.options(attn_variant=dino_amd.get_option("attn_variant") | 512):
         base, ref, _, _ = _attention_case(B, H, ntok, 1, seed=ntok, want_lse=False)
         ex0 = _attention_case(1, 1, 300, 1, seed=77, spike="over", want_lse=False)
         tr0 = _attention_case(B, H, ntok, 1, seed=ntok)
-        capi.check(lib.dinoseg_set_option(b"attn_variant", ATTN_VARIANT_DEFAULT))
-        got, _, _, _ = _attention_case(B, H, ntok, 1, seed=ntok, want_lse=False)
-        ex1 = _attention_case(1, 1, 300, 1, seed=77, spike="over", want_lse=False)
-        tr1 = _attention_case(B, H, ntok, 1, seed=ntok)
-    finally:
-        capi.check(lib.dinoseg_set_option(b"attn_variant", ATTN_VARIANT_DEFAULT))
+    got, _, _, _ = _attention_case(B, H, ntok, 1, seed=ntok, want_lse=False)
+    ex1 = _attention_case(1, 1, 300, 1, seed=77, spike="over", want_lse=False)
+    tr1 = _attention_case(B, H, ntok, 1, seed=ntok)
     assert float((got - ref).abs().max()) <= 1.5e-2 and float((base - ref).abs().max()) <= 1.5e-2
     d = (got - base).abs()
     assert bool((d > 0).any()), "the split kernel was not dispatched"
@@ -529,18 +501,17 @@ def test_gemm_big_matches_small_kernel(cuda, planes, M):
     outs = []
     X0 = seeded((M, N), 34)
     for big in (0, 1, 2):          # 0: 128x128 kernel; 1: auto; 2: persistent kernel wherever it applies
-        capi.check(lib.dinoseg_set_option(b"gemm_big", big))
-        out = torch.zeros((M, N), device="cuda")
-        capi.check(lib.dinoseg_op_gemm(Ap.data_ptr(), M * K, K, Wp.data_ptr(), N * K, M, N, K, planes, capi.EPI_PLAIN,
-                                       bias.data_ptr(), out.data_ptr(), None, 0, 0, S()))
-        X = X0.clone()
-        capi.check(lib.dinoseg_op_gemm(Ap.data_ptr(), M * K, K, Wp.data_ptr(), N * K, M, N, K, planes, capi.EPI_RESID,
-                                       bias.data_ptr(), X.data_ptr(), None, 0, 0, S()))
-        g = torch.zeros((planes, M, N), dtype=torch.int16, device="cuda")
-        capi.check(lib.dinoseg_op_gemm(Ap.data_ptr(), M * K, K, Wp.data_ptr(), N * K, M, N, K, planes, capi.EPI_GELU,
-                                       bias.data_ptr(), None, g.data_ptr(), M * N, N, S()))
-        outs.append((out, X, unpack(g)))
-    capi.check(lib.dinoseg_set_option(b"gemm_big", 1))
+        with dino_amd.options(gemm_big=big):
+            out = torch.zeros((M, N), device="cuda")
+            capi.check(lib.dinoseg_op_gemm(Ap.data_ptr(), M * K, K, Wp.data_ptr(), N * K, M, N, K, planes, capi.EPI_PLAIN,
+                                           bias.data_ptr(), out.data_ptr(), None, 0, 0, S()))
+            X = X0.clone()
+            capi.check(lib.dinoseg_op_gemm(Ap.data_ptr(), M * K, K, Wp.data_ptr(), N * K, M, N, K, planes, capi.EPI_RESID,
+                                           bias.data_ptr(), X.data_ptr(), None, 0, 0, S()))
+            g = torch.zeros((planes, M, N), dtype=torch.int16, device="cuda")
+            capi.check(lib.dinoseg_op_gemm(Ap.data_ptr(), M * K, K, Wp.data_ptr(), N * K, M, N, K, planes, capi.EPI_GELU,
+                                           bias.data_ptr(), None, g.data_ptr(), M * N, N, S()))
+            outs.append((out, X, unpack(g)))
     scale = float(outs[0][0].abs().max())
     ref = (unpack(Ap).double() @ unpack(Wp).double().t() + bias.double())
     for big in (1, 2):
@@ -1102,8 +1073,7 @@ def test_gemm_rs_residual(cuda, M_, K, fp16):
     weight ring runs on across the items of the persistent walk), ragged last item (clamped rows)."""
     N = 768
     lib = capi.lib()
-    capi.check(lib.dinoseg_set_option(b"op_fmt", int(fp16)))
-    try:
+    with dino_amd.options(op_fmt=int(fp16)):
         A = seeded((M_, K), 201) + torch.arange(K, device="cuda", dtype=torch.float32)[None, :] * 1e-4
         W = seeded((N, K), 202) * 0.05 + torch.arange(N, device="cuda", dtype=torch.float32)[:, None] * 1e-5
         bias = seeded((N,), 203)
@@ -1115,8 +1085,6 @@ def test_gemm_rs_residual(cuda, M_, K, fp16):
         capi.check(lib.dinoseg_op_gemm_rs(Ap.data_ptr(), K, Wp.data_ptr(), bias.data_ptr(), M_, N, K, capi.EPI_RESID,
                                           got.data_ptr(), None, 0, None, None, None, 0, 0, 0, 0.0, S()))
         torch.cuda.synchronize()
-    finally:
-        capi.check(lib.dinoseg_set_option(b"op_fmt", 0))
     delta = Aq.double() @ Wq.double().t() + bias.double()
     want = (X.double() + delta).float()
     scale = float(delta.abs().max())
@@ -1133,8 +1101,7 @@ def test_gemm_rs_gelu(cuda, M_, fp16):
     of the one-plane modes: |error| <= 2.6e-5, below the rounding of the stored activation)."""
     N, K = 3072, 768
     lib = capi.lib()
-    capi.check(lib.dinoseg_set_option(b"op_fmt", int(fp16)))
-    try:
+    with dino_amd.options(op_fmt=int(fp16)):
         A = seeded((M_, K), 211) + torch.arange(K, device="cuda", dtype=torch.float32)[None, :] * 1e-4
         W = seeded((N, K), 212) * 0.04 + torch.arange(N, device="cuda", dtype=torch.float32)[:, None] * 1e-6
         bias = seeded((N,), 213) * 0.5
@@ -1145,8 +1112,6 @@ def test_gemm_rs_gelu(cuda, M_, fp16):
         capi.check(lib.dinoseg_op_gemm_rs(Ap.data_ptr(), K, Wp.data_ptr(), bias.data_ptr(), M_, N, K, capi.EPI_GELU, None,
                                           out.data_ptr(), N, None, None, None, 0, 0, 0, 0.0, S()))
         torch.cuda.synchronize()
-    finally:
-        capi.check(lib.dinoseg_set_option(b"op_fmt", 0))
     z = Aq.double() @ Wq.double().t() + bias.double()
     want = (0.5 * z * (1.0 + torch.erf(z / math.sqrt(2.0)))).float()
     got = out.view(torch.float16 if fp16 else torch.bfloat16).float()
@@ -1164,8 +1129,7 @@ def test_gemm_rs_qkv_layout(cuda, B, ntok, fp16):
     H, D = 12, 768
     M_, npad = B * ntok, (ntok + 63) // 64 * 64
     lib = capi.lib()
-    capi.check(lib.dinoseg_set_option(b"op_fmt", int(fp16)))
-    try:
+    with dino_amd.options(op_fmt=int(fp16)):
         A, W, bias = seeded((M_, D), 221), seeded((3 * D, D), 222) * 0.05, seeded((3 * D,), 223)
         Ap, Aq = _one_plane(A, fp16)
         Wq = _one_plane(W, fp16)[1]
@@ -1176,8 +1140,6 @@ def test_gemm_rs_qkv_layout(cuda, B, ntok, fp16):
         capi.check(lib.dinoseg_op_gemm_rs(Ap.data_ptr(), D, Wp.data_ptr(), bias.data_ptr(), M_, 3 * D, D, 4, None, None,
                                           0, q.data_ptr(), k.data_ptr(), v.data_ptr(), ntok, npad, H, qscale, S()))
         torch.cuda.synchronize()
-    finally:
-        capi.check(lib.dinoseg_set_option(b"op_fmt", 0))
     ref = (Aq.double() @ Wq.double().t() + bias.double()).float().reshape(B, ntok, 3, H, 64).permute(2, 0, 3, 1, 4)
     dt = torch.float16 if fp16 else torch.bfloat16
     gq, gk, gv = q.view(dt).float(), k.view(dt).float(), v.view(torch.bfloat16).float()
@@ -1206,8 +1168,7 @@ def test_ln_gemm_rs(cuda, B, ntok, fp16):
     W1, b1 = seeded((F_, D), 236) * 0.04, seeded((F_,), 237) * 0.5
     qscale = 0.125 * LOG2E
     dt = torch.float16 if fp16 else torch.bfloat16
-    capi.check(lib.dinoseg_set_option(b"op_fmt", int(fp16)))
-    try:
+    with dino_amd.options(op_fmt=int(fp16)):
         A16 = torch.zeros((1, M_, D), dtype=torch.int16, device="cuda")
         capi.check(lib.dinoseg_op_layernorm(X.data_ptr(), gam.data_ptr(), bet.data_ptr(), 1e-6, M_, D, A16.data_ptr(), M_ * D, 1, None, 0, ntok, S()))
         Wpq, Wp1 = _pack_rs(Wq_, 0), _pack_rs(W1, 0)
@@ -1235,8 +1196,6 @@ def test_ln_gemm_rs(cuda, B, ntok, fp16):
                                                   None, None, None, 0, 0, 0, 0.0, S()))
             torch.cuda.synchronize()
             outs[ln] = (q.view(dt).float(), k.view(dt).float(), v.view(torch.bfloat16).float(), hb.view(dt).float(), q, k, v)
-    finally:
-        capi.check(lib.dinoseg_set_option(b"op_fmt", 0))
     ulp = 2.0 ** -10 if fp16 else 2.0 ** -7
     for t in outs[True][:4]:
         assert torch.isfinite(t).all()

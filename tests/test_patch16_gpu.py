@@ -123,11 +123,8 @@ def test_two_stream_split_at_patch16_equals_one_stream(cuda, precision):
     m, _ = build(3, precision)
     frames = torch.from_numpy(synthetic_frames(32, 480, seed=9)).cuda()
     lp2, am2 = m.forward_frames(frames)                    # the default: two half-batches on two streams
-    dino_amd.set_option("streams", 1)
-    try:
+    with dino_amd.options(streams=1):
         lp1, am1 = m.forward_frames(frames)
-    finally:
-        dino_amd.set_option("streams", 2)
     torch.cuda.synchronize()
     assert lp1.shape == (32 * 900, 7)
     assert torch.equal(lp1, lp2) and torch.equal(am1, am2)
@@ -160,8 +157,7 @@ def test_patch_gather_p16(cuda, B, H, W, fmt):
     lib = capi.lib()
     G = 1024                                                # guard elements around every plane
     srcs = ((torch.from_numpy(frames).cuda(), capi.INPUT_U8_HWC), (x.cuda().contiguous(), capi.INPUT_F32_CHW))
-    dino_amd.set_option("op_fmt", fmt)
-    try:
+    with dino_amd.options(op_fmt=fmt):
         for src, kind in srcs:
             for planes in (1, 2):
                 stride = n * 768 + G
@@ -184,8 +180,6 @@ def test_patch_gather_p16(cuda, B, H, W, fmt):
                     assert float((hi + lo - want).abs().max()) <= 2.0 ** -15 * 3
                     if kind == capi.INPUT_F32_CHW:
                         assert torch.equal(hi, want.float().to(dt).double()), "hi plane is not the nearest value of the format"
-    finally:
-        dino_amd.set_option("op_fmt", 0)
 
 
 def test_patch_gather_p_at_8_is_the_hw_entry(cuda):
@@ -404,12 +398,9 @@ def test_deterministic_option_at_patch16(cuda, precision):
             m.fused_adam_step()
             losses.append(out["loss"].clone())
         return torch.stack(losses), {n: p.detach().clone() for n, p in m.named_parameters()}, g0
-    dino_amd.set_option("deterministic", 1)
-    try:
+    with dino_amd.options(deterministic=1):
         l1, p1, g1 = run(4)
         l2, p2, g2 = run(4)
-    finally:
-        dino_amd.set_option("deterministic", 0)
     assert torch.equal(l1, l2)
     for n in p1:
         assert torch.equal(g1[n], g2[n]), f"first-step gradient of {n} differs between two deterministic runs"

@@ -120,11 +120,8 @@ def test_two_stream_split_at_240x320_equals_one_stream(cuda, precision):
     m, _ = build(3, precision)
     frames = torch.from_numpy(synthetic_frames(32, 240, seed=9, w=320)).cuda()
     lp2, am2 = m.forward_frames(frames)                    # the default: two half-batches on two streams
-    dino_amd.set_option("streams", 1)
-    try:
+    with dino_amd.options(streams=1):
         lp1, am1 = m.forward_frames(frames)
-    finally:
-        dino_amd.set_option("streams", 2)
     torch.cuda.synchronize()
     assert torch.equal(lp1, lp2) and torch.equal(am1, am2)
     lp0, _ = m.forward_frames(frames[17:18])               # a frame of the second half: its own rows of the batched output

@@ -17,8 +17,6 @@ merely equal.  Batches of 2 frames: the two-stream split stays off.
 In the sequences, "R" is a refresh (load_state_dict of the same values, copied in place; "R+" an in-place add_ of a parameter to
 itself and its inverse) followed by a forward, and "then X" sets X with no refresh before the forward.
 """
-import contextlib
-
 import numpy as np
 import pytest
 import torch
@@ -30,9 +28,9 @@ from oracle import dinoseg_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-# the kernels.h defaults of every option this file sets
-DEFAULTS = {"mlp_fused": 1, "proj_fused": 1, "qkv_fused": 0, "mlp_fused4": 0, "gemm_rs": 3, "gemm_rs_ln": 1,
-            "gemm_rs_min_rows": 24000, "fp16_patch_planes": 1, "streams": 2, "split_min": 8}
+# every option this file sets: a test keeps their values in a dict that starts from what the library reads (_current)
+TRACKED = ("mlp_fused", "proj_fused", "qkv_fused", "mlp_fused4", "gemm_rs", "gemm_rs_ln", "gemm_rs_min_rows", "fp16_patch_planes",
+           "streams", "split_min")
 
 VITS = ViTConfig(n_blocks=3)
 VITB = ViTConfig(embed_dim=768, num_heads=12, n_blocks=2)
@@ -56,14 +54,8 @@ def _set(opts):
         dino_amd.set_option(k, v)
 
 
-@contextlib.contextmanager
-def library_options(**opts):
-    """The given options for the body; the kernels.h defaults of every option in DEFAULTS on the way out."""
-    try:
-        _set(opts)
-        yield
-    finally:
-        _set(DEFAULTS)
+def _current():
+    return {k: dino_amd.get_option(k) for k in TRACKED}
 
 
 def _tensors(sd):
@@ -129,18 +121,15 @@ def _oracle(cfg, frames_np, key):
     return _ORACLE[(cfg, key)]
 
 
-def fresh(cfg, precision, frames_np, key, opts, restore):
-    """Output of a fresh model whose first refresh and forward run under `opts` (then `restore` is set again); the first time an
+def fresh(cfg, precision, frames_np, key, opts):
+    """Output of a fresh model whose first refresh and forward run under `opts` (in a scope of their own); the first time an
     option set is seen, the output is also checked against the oracle."""
     k = (cfg, precision, key, tuple(sorted(opts.items())))
     if k not in _FRESH:
-        _set(opts)
-        try:
+        with dino_amd.options(**opts):
             m = _model(cfg, precision, _weights(cfg))
             lp, am = _forward(m, torch.from_numpy(frames_np).cuda())
             m._release()
-        finally:
-            _set(restore)
         ref = _oracle(cfg, frames_np, key)
         err = float((lp - ref).abs().max())
         flips = float((am != ref.argmax(1)).float().mean())
@@ -149,7 +138,7 @@ def fresh(cfg, precision, frames_np, key, opts, restore):
               f"flips {flips:.4f}")
         assert torch.isfinite(lp).all()
         if tol is None:
-            tol = 0.4 * float((fresh(cfg, "bf16", frames_np, key, opts, restore)[0] - ref).abs().max())
+            tol = 0.4 * float((fresh(cfg, "bf16", frames_np, key, opts)[0] - ref).abs().max())
         assert err <= tol, (opts, err, tol)
         assert max_flips is None or flips <= max_flips, (opts, flips)
         _FRESH[k] = (lp, am)
@@ -164,10 +153,10 @@ def run_sequence(cfg, precision, base, steps, B=2, r=240, seed=31):
     frames_np = _frames(B, r, seed)
     key = (B, r, seed)
     frames = torch.from_numpy(frames_np).cuda()
-    cur = dict(DEFAULTS, **base)
+    cur = dict(_current(), **base)
     snap = None
     met = {}
-    with library_options(**cur):
+    with dino_amd.options(**cur):
         m = _model(cfg, precision, sd)
         for i, (kind, opts) in enumerate(steps):
             _set(opts)
@@ -180,7 +169,7 @@ def run_sequence(cfg, precision, base, steps, B=2, r=240, seed=31):
                 assert kind == "then" and snap is not None
             lp, am = _forward(m, frames)
             want = contract(snap, cur)
-            ref_lp, ref_am = fresh(cfg, precision, frames_np, key, want, cur)
+            ref_lp, ref_am = fresh(cfg, precision, frames_np, key, want)
             assert torch.equal(lp, ref_lp) and torch.equal(am, ref_am), \
                 (f"step {i} ({kind} {opts}): max |dlogp| {float((lp - ref_lp).abs().max()):.3e} against a fresh model with {want}")
             met.setdefault(tuple(sorted(want.items())), lp)
@@ -251,8 +240,8 @@ def test_gemm_rs_ln_off_then_buffer_grows(cuda, precision):
     sd = _weights(cfg)
     frames_np = _frames(2, 240, 31)
     frames = torch.from_numpy(frames_np).cuda()
-    cur = dict(DEFAULTS, gemm_rs_min_rows=1)
-    with library_options(**cur):
+    cur = dict(_current(), gemm_rs_min_rows=1)
+    with dino_amd.options(**cur):
         m = _model(cfg, precision, sd)
         _forward(m, frames)
         _set({"gemm_rs_ln": 0})
@@ -266,12 +255,12 @@ def test_gemm_rs_ln_off_then_buffer_grows(cuda, precision):
         lp, am = _forward(m, frames)
         assert _generation(m) > gen
         want = dict(cur)
-        ref_lp, ref_am = fresh(cfg, precision, frames_np, (2, 240, 31), want, cur)
+        ref_lp, ref_am = fresh(cfg, precision, frames_np, (2, 240, 31), want)
         assert torch.equal(lp, ref_lp) and torch.equal(am, ref_am)
         _set({"gemm_rs_ln": 1})
         cur["gemm_rs_ln"] = 1
         lp, am = _forward(m, frames)
-        ref_lp, ref_am = fresh(cfg, precision, frames_np, (2, 240, 31), want, cur)
+        ref_lp, ref_am = fresh(cfg, precision, frames_np, (2, 240, 31), want)
         assert torch.equal(lp, ref_lp) and torch.equal(am, ref_am)
         m._release()
 
@@ -284,7 +273,7 @@ def test_hi_lo_modes_ignore_the_one_plane_options_across_refreshes(cuda, precisi
     cfg = VITS
     sd = _weights(cfg)
     frames = torch.from_numpy(_frames(2, 240, 31)).cuda()
-    with library_options(**DEFAULTS):
+    with dino_amd.options():
         m = _model(cfg, precision, sd)
         lp0, am0 = _forward(m, frames)
         gen0 = _generation(m)
@@ -310,27 +299,25 @@ def test_predict_graph_follows_a_refresh_that_moves_the_copies(cuda, before, aft
     sd = _weights(cfg)
     frame = _frames(1, 480, 37)[0]
 
-    def eager(opts, restore):
-        _set(opts)
-        try:
+    def eager(opts):
+        with dino_amd.options(**opts):
             ref = _model(cfg, "fp16", sd)
             ref.predict_graph = False
             out = ref.predict(frame)
             ref._release()
-        finally:
-            _set(restore)
         return out
 
-    cur = dict(DEFAULTS, **before)
-    with library_options(**cur):
-        want0 = eager(cur, cur)
+    cur = dict(_current(), **before)
+    with dino_amd.options(**cur):
+        want0 = eager(cur)
         m = _model(cfg, "fp16", sd)
         a = m.predict(frame)
         graph0 = m._pred_graphs[480]["graph"]
         assert np.array_equal(a, want0)
         assert np.array_equal(m.predict(frame), want0) and m._pred_graphs[480]["graph"] is graph0
+        _set(after)
         cur.update(after)
-        want1 = eager(cur, cur)
+        want1 = eager(cur)
         m.load_state_dict(_tensors(sd))                       # in place: the next call refreshes under the new options
         b = m.predict(frame)
         graph1 = m._pred_graphs[480]["graph"]
@@ -350,10 +337,10 @@ def test_fc1_wider_than_gemm_rs_runs_layernorm_and_the_regular_gemm(cuda, precis
     0.44 % flips (3 and 2), 7.96e-2 / 0.50 % (0)."""
     cfg = VITB_R6
     frames_np = _frames(2, 240, 31)
-    cur = dict(DEFAULTS, gemm_rs_min_rows=1)
-    with library_options(**cur):
-        both = fresh(cfg, precision, frames_np, (2, 240, 31), dict(cur), cur)
-        only_qkv = fresh(cfg, precision, frames_np, (2, 240, 31), dict(cur, gemm_rs=2), cur)
-        no_rs = fresh(cfg, precision, frames_np, (2, 240, 31), dict(cur, gemm_rs=0), cur)
+    cur = dict(_current(), gemm_rs_min_rows=1)
+    with dino_amd.options(**cur):
+        both = fresh(cfg, precision, frames_np, (2, 240, 31), dict(cur))
+        only_qkv = fresh(cfg, precision, frames_np, (2, 240, 31), dict(cur, gemm_rs=2))
+        no_rs = fresh(cfg, precision, frames_np, (2, 240, 31), dict(cur, gemm_rs=0))
     assert torch.equal(both[0], only_qkv[0]) and torch.equal(both[1], only_qkv[1])
     assert not torch.equal(both[0], no_rs[0])          # (qkv did run on gemm_rs)

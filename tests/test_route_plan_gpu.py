@@ -16,7 +16,6 @@ test -- by running this file's body against that commit's build (the Python surf
 which prints the table below.  tools/route_digest.py runs the same cases and prints a digest of every output, for a byte comparison
 of two builds.
 """
-import contextlib
 import os
 import sys
 
@@ -32,15 +31,11 @@ from dino_amd import DINOSeg, ViTConfig, procedural_state_dict  # noqa: E402
 from dino_amd.weights import synthetic_frames  # noqa: E402
 from oracle import dinoseg_oracle as O  # noqa: E402
 from tests import arch_util as A  # noqa: E402
+from tests.gpu_util import route_options  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 PRECISIONS = ["bf16x3", "fp16x3", "bf16", "fp16"]
 WIDE_TAG, WIDE_PRECISIONS = "Br2", ["bf16", "fp16"]
-# kernels.h: Options
-OPTION_DEFAULTS = {"gemm_ln": 1, "gemm_big": 1, "mlp_fused": 1, "proj_fused": 1, "qkv_fused": 0, "qkv_fused3": 1, "qkv_fused4": 1,
-                   "mlp_fused4": 0, "gemm_rs": 3, "gemm_rs_ln": 1, "gemm_rs_min_rows": 24000, "streams": 2, "split_min": 8,
-                   "deterministic": 0}
-REFRESH_OPTIONS = ("mlp_fused4", "gemm_rs", "gemm_rs_ln")      # which packed copies exist: read by dinoseg_refresh_weights
 
 
 def small_routes(precision):
@@ -62,23 +57,6 @@ def small_routes(precision):
 
 def wide_routes():
     return [(f"gemm_rs_ln={ln},gemm_rs={rs}", {"gemm_rs_min_rows": 1, "gemm_rs_ln": ln, "gemm_rs": rs}) for ln in (1, 0) for rs in (1, 2, 3, 7)]
-
-
-@contextlib.contextmanager
-def options(model, **kw):
-    """The given options for the body (after a refresh where one of them is read there), the kernels.h defaults on the way out."""
-    refresh = any(k in REFRESH_OPTIONS for k in kw)
-    try:
-        for k, v in kw.items():
-            dino_amd.set_option(k, v)
-        if refresh:
-            model.invalidate_weights()
-        yield
-    finally:
-        for k in kw:
-            dino_amd.set_option(k, OPTION_DEFAULTS[k])
-        if refresh:
-            model.invalidate_weights()
 
 
 def small_model(precision):
@@ -130,7 +108,7 @@ def counted(m, call):
 
 def run_cases(kind, precision):
     """yields (case id, outputs, counts) of one model: kind 'small', 'wide' or 'side'"""
-    with options(None, streams=1):
+    with route_options(streams=1):
         if kind == "side":
             m = small_model(precision)
             for name, call in side_paths(m, small_frames()):
@@ -140,7 +118,7 @@ def run_cases(kind, precision):
         m, frames, routes = (small_model(precision), small_frames(), small_routes(precision)) if kind == "small" else \
                             (wide_model(precision), wide_frames(), wide_routes())
         for name, opts in routes:
-            with options(m, **opts):
+            with route_options(m, **opts):
                 out, counts = counted(m, lambda: m.forward_frames(frames))
             yield f"{kind}/{precision}/{name}", out, counts
 
@@ -246,6 +224,23 @@ def test_launch_counts_per_route(cuda, kind, precision):
         assert counts == EXPECTED[case], (case, counts, EXPECTED[case])
         seen += 1
     assert seen == sum(1 for k in EXPECTED if k.startswith(f"{kind}/{precision}/"))
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16x3"])
+def test_route_options_restore_the_forward(cuda, precision):
+    """After a route_options scope that switched three routes (one of them read at the refresh), the forward is bit for bit the one
+    from before it and every option of the library reads what it read before."""
+    m, frames = small_model(precision), small_frames()[:1]
+    names = dino_amd.option_names()
+    before = {k: dino_amd.get_option(k) for k in names}
+    logp0, amax0 = (t.clone() for t in m.forward_frames(frames))
+    with route_options(m, gemm_ln=0, mlp_fused=2, gemm_rs=0):
+        assert (dino_amd.get_option("gemm_ln"), dino_amd.get_option("mlp_fused"), dino_amd.get_option("gemm_rs")) == (0, 2, 0)
+        m.forward_frames(frames)
+    logp1, amax1 = m.forward_frames(frames)
+    torch.cuda.synchronize()
+    assert torch.equal(logp1, logp0) and torch.equal(amax1, amax0)
+    assert {k: dino_amd.get_option(k) for k in names} == before
 
 
 if __name__ == "__main__":

@@ -415,17 +415,16 @@ def test_side_stream_weight_gradients_equal_one_stream(cuda):
     the caller's stream.  Same kernels on the same operands: tensors written by plain stores (all weights) are bit-identical,
     atomically summed ones (biases, LayerNorm gains) agree to summation order; repeated steps are stable (no race on the buffers
     the side stream reads: dXp, G)."""
+    import dino_amd
     cfg = ViTConfig(n_blocks=3)
     m, sd = build(cfg, precision="bf16")
     m.unfreeze_bb()
     frames = torch.from_numpy(synthetic_frames(4, 240, seed=141)).cuda()
     labels = torch.from_numpy(synthetic_labels(4, 900, cfg.n_classes, seed=142)).cuda()
-    lib = capi.lib()
-    try:
-        capi.check(lib.dinoseg_set_option(b"train_streams", 1))
+    with dino_amd.options(train_streams=1):
         m.fused_training_step((frames, labels), 0)
         one = {k: p.grad.clone() for k, p in m.named_parameters()}
-        capi.check(lib.dinoseg_set_option(b"train_streams", 2))
+    with dino_amd.options(train_streams=2):
         for rep in range(3):
             m.fused_training_step((frames, labels), 0)
             torch.cuda.synchronize()
@@ -434,8 +433,6 @@ def test_side_stream_weight_gradients_equal_one_stream(cuda):
                     assert torch.equal(p.grad, one[k]), (k, rep)
                 else:
                     assert float((p.grad - one[k]).abs().max()) <= 2e-5 * (float(one[k].abs().max()) + 1e-12), (k, rep)
-    finally:
-        capi.check(lib.dinoseg_set_option(b"train_streams", 2))
 
 
 # ------------------------------------------------------------------------------------------------ round 4 additions
@@ -546,12 +543,9 @@ def test_deterministic_option_makes_the_fine_tune_step_bit_reproducible(cuda, pr
             m.fused_adam_step()
             losses.append(out["loss"].clone())
         return torch.stack(losses), {n: p.detach().clone() for n, p in m.named_parameters()}, g0
-    dino_amd.set_option("deterministic", 1)
-    try:
+    with dino_amd.options(deterministic=1):
         l1, p1, g1 = run(10)
         l2, p2, g2 = run(10)
-    finally:
-        dino_amd.set_option("deterministic", 0)
     assert torch.equal(l1, l2), (l1 - l2).abs().max()
     for n in p1:
         assert torch.equal(g1[n], g2[n]), f"first-step gradient of {n} differs between two deterministic runs"
@@ -583,12 +577,9 @@ def test_deterministic_bias_only_layers_on_the_side_stream(cuda):
                 p.requires_grad_(False)
         out = m.fused_training_step((fr, lb), 0)
         return out["loss"].clone(), {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
-    dino_amd.set_option("deterministic", 1)
-    try:
+    with dino_amd.options(deterministic=1):
         l1, g1 = run()
         l2, g2 = run()
-    finally:
-        dino_amd.set_option("deterministic", 0)
     assert torch.equal(l1, l2)
     assert any(n.endswith("attn.qkv.bias") for n in g1) and not any(n.endswith("attn.qkv.weight") for n in g1)
     for n in g1:
@@ -652,9 +643,7 @@ def test_partial_freezes_leave_the_other_gradients_unchanged(cuda, streams):
         "block 1 and the head": lambda n, p: n.startswith("dino.blocks.1.") or n.startswith("clf."),
         "cls, pos and patch embedding": lambda n, p: n in ("dino.cls_token", "dino.pos_embed") or n.startswith("dino.patch_embed."),
     }
-    dino_amd.set_option("deterministic", 1)
-    dino_amd.set_option("train_streams", streams)
-    try:
+    with dino_amd.options(deterministic=1, train_streams=streams):
         m, batch = _freeze_case()
         base = _step_with(m, batch, lambda n, p: True)
         assert len(base) == len(list(m.named_parameters()))
@@ -662,9 +651,6 @@ def test_partial_freezes_leave_the_other_gradients_unchanged(cuda, streams):
             got = _step_with(m, batch, trainable)
             assert set(got) == {n for n, p in m.named_parameters() if trainable(n, p)}
             _assert_same_gradients(got, base, lambda n: n[:-len("bias")] + "weight" not in got, f"{tag} [streams {streams}]")
-    finally:
-        dino_amd.set_option("deterministic", 0)
-        dino_amd.set_option("train_streams", 2)
 
 
 @pytest.mark.parametrize("streams", [1, 2])
@@ -672,9 +658,7 @@ def test_unbinding_a_gradient_really_unbinds_it(cuda, streams):
     """requires_grad_(False) after a step: the next step neither writes nor zeroes the buffers that were bound for those
     parameters (a sentinel left in them survives), and the gradients still bound equal the first step's."""
     import dino_amd
-    dino_amd.set_option("deterministic", 1)
-    dino_amd.set_option("train_streams", streams)
-    try:
+    with dino_amd.options(deterministic=1, train_streams=streams):
         m, batch = _freeze_case()
         base = _step_with(m, batch, lambda n, p: True)
         old = {n: p.grad for n, p in m.named_parameters() if _is_block_weight(n, p)}      # the buffers the library holds
@@ -687,6 +671,3 @@ def test_unbinding_a_gradient_really_unbinds_it(cuda, streams):
             assert bool((g == 12345.0).all()), f"{n}: the unbound gradient buffer was written"
         assert set(got) == set(base) - set(old)
         _assert_same_gradients(got, base, lambda n: n[:-len("bias")] + "weight" not in got, f"block weights unbound [streams {streams}]")
-    finally:
-        dino_amd.set_option("deterministic", 0)
-        dino_amd.set_option("train_streams", 2)

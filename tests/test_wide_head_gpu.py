@@ -39,8 +39,7 @@ def _wide_case(C, K, ld, M, fmt, seed):
     Wc = seeded((C, K), seed + 1) * (1.5 / K ** 0.5)
     b = seeded((C,), seed + 2)
     cp = (C + 31) // 32 * 32
-    capi.check(capi.lib().dinoseg_set_option(b"op_fmt", code))
-    try:
+    with dino_amd.options(op_fmt=code):
         xp = _pack(x, fmt, M, ld)
         wp = _pack(Wc, fmt, cp, ld)
         logp = torch.full((M, C), float("nan"), device="cuda")
@@ -48,8 +47,6 @@ def _wide_case(C, K, ld, M, fmt, seed):
         capi.check(capi.lib().dinoseg_op_head_wide(xp.data_ptr(), M * ld, ld, M, K, wp.data_ptr(), cp * ld, b.data_ptr(), C,
                                                    logp.data_ptr(), am.data_ptr(), S()))
         torch.cuda.synchronize()
-    finally:
-        capi.check(capi.lib().dinoseg_set_option(b"op_fmt", 0))
     return x, Wc, b, xp, logp, am
 
 
@@ -80,13 +77,10 @@ def test_head_wide_op_against_fp64(cuda, fmt, K, ld, C):
             code = FMTS[fmt][0]
             lp0 = torch.full((M, C), float("nan"), device="cuda")
             am0 = torch.full((M,), -1, dtype=torch.int32, device="cuda")
-            capi.check(capi.lib().dinoseg_set_option(b"op_fmt", code))
-            try:
+            with dino_amd.options(op_fmt=code):
                 capi.check(capi.lib().dinoseg_op_head_final(xp.data_ptr(), M * ld, ld, M, K, Wc.data_ptr(), b.data_ptr(), C,
                                                             lp0.data_ptr(), am0.data_ptr(), S()))
                 torch.cuda.synchronize()
-            finally:
-                capi.check(capi.lib().dinoseg_set_option(b"op_fmt", 0))
             # (the narrow kernel multiplies the fp32 classifier: the wide one's classifier rounding, eps relative, comes on top)
             assert float((lp0 - logp).abs().max()) <= bound + 2.0 * eps * mag
             assert torch.equal(am0[clear], am[clear])
@@ -151,13 +145,10 @@ def test_two_stream_forward_at_150_classes(cuda):
     m, _, _ = _model("mlp", "bf16x3", n_blocks=2)
     m.set_resolution(64)
     frames = torch.from_numpy(synthetic_frames(16, 64, seed=9)).cuda()
-    dino_amd.set_option("streams", 1)
-    try:
+    with dino_amd.options(streams=1):
         ref, ram = (t.clone() for t in m.forward_frames(frames))
         dino_amd.set_option("streams", 2)           # (16 frames: above the default split_min of 8)
         out, am = m.forward_frames(frames)
-    finally:
-        dino_amd.set_option("streams", 2)
     assert torch.equal(out, ref) and torch.equal(am, ram)
 
 
@@ -239,11 +230,8 @@ def test_deterministic_step_at_150_classes(cuda):
         m.fused_adam_step()
         out2 = m.fused_training_step((frames, labels), 1)
         return out["loss"].clone(), out2["loss"].clone(), {k: p.grad.clone() for k, p in m.named_parameters()}
-    dino_amd.set_option("deterministic", 1)
-    try:
+    with dino_amd.options(deterministic=1):
         a, b = run(), run()
-    finally:
-        dino_amd.set_option("deterministic", 0)
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
     for k in a[2]:
         assert torch.equal(a[2][k], b[2][k]), k

@@ -39,7 +39,7 @@ def block_weight(n, p):
 
 
 # name: (config, precision, frame rows, frame columns, train_streams, which parameters train, through torch.autograd or "dense" = the
-# fused step on pixel labels of the frame's size[, options set for the case and reset to their defaults (OPTION_DEFAULTS) after it])
+# fused step on pixel labels of the frame's size[, options set for the case only])
 CASES = {
     "vits8 bf16": (S8, "bf16", 64, 64, 2, "all", False),
     "vits8 bf16x3": (S8, "bf16x3", 64, 64, 2, "all", False),
@@ -62,7 +62,6 @@ CASES = {
     "splitk_tiles=1": (S8, "bf16x3", 64, 64, 2, "all", False, {"splitk_tiles": 1}),      # the two ends of the weight gradients' slice count
     "route_ab=4": (S8, "bf16x3", 64, 64, 2, "all", False, {"route_ab": 4}),
 }
-OPTION_DEFAULTS = {"gemm_ln": 1, "splitk_tiles": 512, "route_ab": 0}
 
 
 def sha(t):
@@ -70,17 +69,11 @@ def sha(t):
 
 
 def run(cfg, prec, H, W, streams, train, autograd, opts={}):
-    for k, v in opts.items():
-        dino_amd.set_option(k, v)
-    try:
-        return run_case(cfg, prec, H, W, streams, train, autograd)
-    finally:
-        for k in opts:
-            dino_amd.set_option(k, OPTION_DEFAULTS[k])
+    with dino_amd.options(deterministic=1, train_streams=streams, **opts):
+        return run_case(cfg, prec, H, W, train, autograd)
 
 
-def run_case(cfg, prec, H, W, streams, train, autograd):
-    dino_amd.set_option("train_streams", streams)
+def run_case(cfg, prec, H, W, train, autograd):
     sd = procedural_state_dict(cfg)
     m = DINOSeg(head=cfg.head, n_blocks=cfg.n_blocks, n_classes=cfg.n_classes, precision=prec, arch=cfg, optimizer=torch.optim.Adam, lr=1e-3)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
@@ -113,13 +106,10 @@ def run_case(cfg, prec, H, W, streams, train, autograd):
     return out
 
 
-dino_amd.set_option("deterministic", 1)
 res = {}
 for name, case in CASES.items():
     res[name] = run(*case)
     print(name, len(res[name]), "digests", flush=True)
-dino_amd.set_option("deterministic", 0)
-dino_amd.set_option("train_streams", 2)
 os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
 json.dump(res, open(sys.argv[1], "w"), indent=1, sort_keys=True)
 print("ok", len(res), "cases")

@@ -10,6 +10,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
+import dino_amd  # noqa: E402
 from dino_amd import capi  # noqa: E402
 
 LOG2E = 1.4426950408889634
@@ -32,6 +33,7 @@ def rand_bf16(shape):
     return (torch.randn(shape, device="cuda") * 0.5).to(torch.bfloat16).view(torch.int16)
 
 
+@dino_amd.options()          # whatever the body sets is put back on return
 def bench_gemm(quick=True):
     lib = capi.lib()
     B, ntok, D = 32, 3601, 384
@@ -64,10 +66,9 @@ def bench_gemm(quick=True):
                 tf = 2.0 * M * N * K / (ms * 1e-3) / 1e12
                 print(f"{name:5s} N={N:5d} K={K:5d} kernel={('small', 'auto', 'big')[big]:8s} dbg={dbg} "
                       f"(skip epilogue={dbg & 1}, skip loads={(dbg >> 1) & 1}): {ms * 1e3:8.1f} us  {tf:7.1f} TFLOP/s", flush=True)
-    lib.dinoseg_set_option(b"gemm_big", 1)
-    lib.dinoseg_set_option(b"gemm_dbg", 0)
 
 
+@dino_amd.options()          # whatever the body sets is put back on return
 def bench_gemm_vitb():
     """the persistent kernel on ViT-B/8's shapes (16 frames @480: 57 616 rows), bf16, with the timing ablations"""
     lib = capi.lib()
@@ -88,10 +89,9 @@ def bench_gemm_vitb():
             tf = 2.0 * M * N * K / (ms * 1e-3) / 1e12
             print(f"vitb {name:5s} N={N:5d} K={K:5d} skip_epilogue={dbg & 1} skip_loads={dbg >> 1}: {ms * 1e3:8.1f} us  {tf:7.1f} TFLOP/s", flush=True)
         del A, W, X, O
-    lib.dinoseg_set_option(b"gemm_big", 1)
-    lib.dinoseg_set_option(b"gemm_dbg", 0)
 
 
+@dino_amd.options()          # whatever the body sets is put back on return
 def bench_gemm_planes2():
     """bf16x3 (hi + lo planes): the 128x128 kernel against the 128x384 configuration of the persistent kernel"""
     lib = capi.lib()
@@ -115,8 +115,6 @@ def bench_gemm_planes2():
                 print(f"{name:5s} planes=2 N={N:5d} K={K:5d} kernel={('small', 'auto', 'big')[big]:6s} skip_epilogue={dbg & 1} skip_loads={dbg >> 1}: "
                       f"{ms * 1e3:8.1f} us  {tf:7.1f} TFLOP/s ({3 * tf:7.1f} MFMA-equivalent)", flush=True)
         del A, W, X, O
-    lib.dinoseg_set_option(b"gemm_big", 1)
-    lib.dinoseg_set_option(b"gemm_dbg", 0)
 
 
 def bench_lngemm():
@@ -160,11 +158,11 @@ def bench_lngemm():
                 capi.check(lib.dinoseg_op_ln_gemm(X.data_ptr(), gam.data_ptr(), bet.data_ptr(), 1e-6, Ws.data_ptr(), N * D, bias.data_ptr(), M, N,
                                                   D, planes, epi, capi.ptr(out), M * N, q.data_ptr(), k.data_ptr(), vt.data_ptr(),
                                                   B * H * npad * 64, ntok, npad, H, 0.125 * LOG2E, None, None, capi.stream_ptr()))
-            def ablate(bits):
+            def ablate(bits, off=dino_amd.get_option("gemm_dbg")):
                 def f():
                     lib.dinoseg_set_option(b"gemm_dbg", bits)
                     fused()
-                    lib.dinoseg_set_option(b"gemm_dbg", 0)
+                    lib.dinoseg_set_option(b"gemm_dbg", off)
                 return f
             cases = [("LN", ln), ("GEMM", gemm), ("LN+GEMM", two), ("fused", fused)]
             if os.environ.get("LNGEMM_ONLY_FUSED"):
@@ -186,6 +184,7 @@ def bench_lngemm():
 ATTN_VARIANTS = os.environ.get("ATTN_VARIANTS", "11").split(",")        # "<attn_variant>" or "<attn_variant>:<attn_dbg>"
 
 
+@dino_amd.options()          # whatever the body sets is put back on return
 def bench_attn():
     """Interleaved A/B rounds in one process (clocks drift by +-10 % between back-to-back measurements)."""
     lib = capi.lib()
@@ -219,10 +218,6 @@ def bench_attn():
             t = sorted(times[name][1:])
             print(f"attention B={B} ntok={ntok} planes={planes} {name:18s}: min {t[0] * 1e3:7.1f} us  median {t[len(t) // 2] * 1e3:7.1f} us  "
                   f"{fl / (t[len(t) // 2] * 1e-3) / 1e12:6.1f} TFLOP/s", flush=True)
-    for kk, vv in base.items():
-        lib.dinoseg_set_option(kk.encode(), vv)
-    lib.dinoseg_set_option(b"attn_dbg", 0)
-    lib.dinoseg_set_option(b"op_fmt", 0)
 
 
 if __name__ == "__main__":

@@ -55,10 +55,9 @@ for c in range(cases):
                   ("two streams", dict(gemm_big=1, gemm_ln=1, streams=2, split_min=2, mlp_fused=1, qkv_fused3=1)))
         tol, flip_tol = (1.5e-3, 0.003) if prec == "bf16x3" else (3e-4, 0.001)
     for name, opts in routes:
-        for k, v in opts.items():
-            dino_amd.set_option(k, v)
-        lp, am = m.forward_frames(frames)
-        torch.cuda.synchronize()
+        with dino_amd.options(**opts):
+            lp, am = m.forward_frames(frames)
+            torch.cuda.synchronize()
         assert torch.isfinite(lp).all(), (name, r, B)
         outs[name] = (lp.clone(), am.clone())
     ref = outs["separate"][0]
@@ -77,6 +76,4 @@ for c in range(cases):
     if single:
         assert torch.equal(outs["two streams+qkv"][0], outs["fused+proj+qkv"][0]), ("two streams + qkv differ", r, B)
     print(line, flush=True)
-for k, v in dict(mlp_fused=1, proj_fused=1, qkv_fused=0, streams=2, split_min=8, gemm_big=1, gemm_ln=1, mlp_fused4=0, qkv_fused3=1).items():
-    dino_amd.set_option(k, v)
 print(f"{cases} cases, worst |dlogp| between routes {worst:.3f}")

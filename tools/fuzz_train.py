@@ -21,9 +21,9 @@ for prec in ("bf16", "bf16x3"):
         lb = torch.from_numpy(synthetic_labels(B, n, cfg.n_classes, seed=400 + c)).cuda()
         gs = {}
         for ts in (1, 2):
-            dino_amd.set_option("train_streams", ts)
-            out = m.fused_training_step((fr, lb), 0)
-            torch.cuda.synchronize()
+            with dino_amd.options(train_streams=ts):
+                out = m.fused_training_step((fr, lb), 0)
+                torch.cuda.synchronize()
             gs[ts] = {k: p.grad.clone() for k, p in m.named_parameters()}
             assert torch.isfinite(out["loss"])
         worst = 0.0
@@ -33,5 +33,4 @@ for prec in ("bf16", "bf16x3"):
             worst = max(worst, d)
         print(prec, "r", r, "B", B, "loss %.4f" % float(out["loss"]), "worst rel grad diff 1 vs 2 streams %.2e" % worst, flush=True)
         assert worst <= 1e-4
-dino_amd.set_option("train_streams", 2)
 print("ok")

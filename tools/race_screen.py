@@ -6,6 +6,7 @@ import os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
+import dino_amd
 from dino_amd import capi
 from gpu_util import pack, pack_slabs, quant_like, seeded, unpack
 lib = capi.lib()
@@ -46,7 +47,6 @@ for (M, N, K) in [(115232, 384, 384), (115232, 1536, 384), (28808, 384, 1536), (
         if planes == 2 and M * N > 60_000_000:
             continue
         Ap, Wp = pack(A, planes), pack(W, planes)
-        capi.check(lib.dinoseg_set_option(b"gemm_big", 2))
         X0 = seeded((M, N), 4)
         out = torch.zeros((M, N), device="cuda")
         g = torch.zeros((planes, M, N), dtype=torch.int16, device="cuda")
@@ -57,18 +57,18 @@ for (M, N, K) in [(115232, 384, 384), (115232, 1536, 384), (28808, 384, 1536), (
             capi.check(lib.dinoseg_op_gemm(Ap.data_ptr(), M * K, K, Wp.data_ptr(), N * K, M, N, K, planes, epi, bias.data_ptr(),
                                            out.data_ptr() if epi != capi.EPI_GELU else None, g.data_ptr() if epi == capi.EPI_GELU else None,
                                            M * N, N, S()))
-        screen(f"gemm_big {ename:7s} M={M} N={N} K={K}", run, lambda: [g] if epi == capi.EPI_GELU else [out])
+        with dino_amd.options(gemm_big=2):
+            screen(f"gemm_big {ename:7s} M={M} N={N} K={K}", run, lambda: [g] if epi == capi.EPI_GELU else [out])
         # agreement with the 128x128 kernel
         big = (unpack(g) if epi == capi.EPI_GELU else out).clone()
-        capi.check(lib.dinoseg_set_option(b"gemm_big", 0))
-        run(); torch.cuda.synchronize()
+        with dino_amd.options(gemm_big=0):
+            run(); torch.cuda.synchronize()
         small = unpack(g) if epi == capi.EPI_GELU else out
         err = float((big - small).abs().max()) / max(float(small.abs().max()), 1e-6)
         tol = (2.0 ** -7 if planes == 1 else 2.0 ** -14) if epi == capi.EPI_GELU else 3e-5
         print(f"    vs 128x128 kernel: rel max diff {err:.2e} {'OK' if err <= tol else 'MISMATCH'}", flush=True)
         bad += err > tol
     del A, W, Ap, Wp
-capi.check(lib.dinoseg_set_option(b"gemm_big", 1))
 
 # LayerNorm-fused A-stationary GEMM (gemm_ln.hip): private LDS-DMA rings with counted vmcnt, inline-asm LDS reads with counted
 # lgkmcnt, two barriers per panel; also against LayerNorm + the 128x128 kernel on the same operands
@@ -96,10 +96,9 @@ for (Bq, ntok, planes) in [(32, 3601, 1), (8, 3601, 2), (3, 197, 1), (1, 65, 2),
                                                 ntok, S()))
             Wp = pack(W, planes)
             ref = torch.zeros_like(out)
-            capi.check(lib.dinoseg_set_option(b"gemm_big", 0))
-            capi.check(lib.dinoseg_op_gemm(A.data_ptr(), M * D, D, Wp.data_ptr(), N * D, M, N, D, planes, epi, bias.data_ptr(), None,
-                                           ref.data_ptr(), M * N, N, S()))
-            capi.check(lib.dinoseg_set_option(b"gemm_big", 1))
+            with dino_amd.options(gemm_big=0):
+                capi.check(lib.dinoseg_op_gemm(A.data_ptr(), M * D, D, Wp.data_ptr(), N * D, M, N, D, planes, epi, bias.data_ptr(), None,
+                                               ref.data_ptr(), M * N, N, S()))
             err = float((unpack(out) - unpack(ref)).abs().max()) / max(float(unpack(ref).abs().max()), 1e-6)
             tol = 2.0 ** -6 if planes == 1 else 2.0 ** -13
             print(f"    vs LayerNorm + 128x128 kernel: rel max diff {err:.2e} {'OK' if err <= tol else 'MISMATCH'}", flush=True)
@@ -109,21 +108,20 @@ import test_ops_gpu as T
 # (round 5: 11 | 1024 [| 65536] = the assembly tile loop of attention_za.hip, 32 / 64 queries per wave; | 2048 = at every grid size;
 #  planes = 2 with bits 4 / 10 = its hi + lo body)
 for variant in (3, 11, 11 | 1024 | 2048, 11 | 1024 | 2048 | 65536, 11 | 16 | 1024 | 2048):
-  capi.check(lib.dinoseg_set_option(b"attn_variant", variant))
-  for (B, H, ntok, planes) in [(32, 6, 3601, 1), (2, 6, 3601, 2), (4, 2, 197, 1), (3, 3, 64, 1), (1, 1, 129, 2), (8, 6, 14401, 1)]:
-      npad = (ntok + 63) // 64 * 64
-      q = (torch.randn((planes, B, H, npad, 64), device="cuda") * 0.5).to(torch.bfloat16).view(torch.int16)
-      k = (torch.randn((planes, B, H, npad, 64), device="cuda") * 0.5).to(torch.bfloat16).view(torch.int16)
-      v = (torch.randn((planes, B, H, npad, 64), device="cuda") * 0.5).to(torch.bfloat16).view(torch.int16)
-      k[..., ntok:, :] = 0; v[..., ntok:, :] = 0
-      ctx = torch.zeros((planes, B * ntok, H * 64), dtype=torch.int16, device="cuda")
-      lse = torch.zeros((B, H, ntok), device="cuda")
+    with dino_amd.options(attn_variant=variant):
+        for (B, H, ntok, planes) in [(32, 6, 3601, 1), (2, 6, 3601, 2), (4, 2, 197, 1), (3, 3, 64, 1), (1, 1, 129, 2), (8, 6, 14401, 1)]:
+            npad = (ntok + 63) // 64 * 64
+            q = (torch.randn((planes, B, H, npad, 64), device="cuda") * 0.5).to(torch.bfloat16).view(torch.int16)
+            k = (torch.randn((planes, B, H, npad, 64), device="cuda") * 0.5).to(torch.bfloat16).view(torch.int16)
+            v = (torch.randn((planes, B, H, npad, 64), device="cuda") * 0.5).to(torch.bfloat16).view(torch.int16)
+            k[..., ntok:, :] = 0; v[..., ntok:, :] = 0
+            ctx = torch.zeros((planes, B * ntok, H * 64), dtype=torch.int16, device="cuda")
+            lse = torch.zeros((B, H, ntok), device="cuda")
 
-      def run():
-          capi.check(lib.dinoseg_op_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), B * H * npad * 64, ctx.data_ptr(),
-                                              B * ntok * H * 64, lse.data_ptr(), B, H, ntok, npad, planes, S()))
-      screen(f"attention variant {variant} B={B} H={H} N={ntok} planes={planes}", run, lambda: [ctx, lse])
-capi.check(lib.dinoseg_set_option(b"attn_variant", 11 | 1024 | 65536))
+            def run():
+                capi.check(lib.dinoseg_op_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), B * H * npad * 64, ctx.data_ptr(),
+                                                    B * ntok * H * 64, lse.data_ptr(), B, H, ntok, npad, planes, S()))
+            screen(f"attention variant {variant} B={B} H={H} N={ntok} planes={planes}", run, lambda: [ctx, lse])
 
 # round 6: the one-wave-per-SIMD fused launches (three-slot LDS-DMA ring shared by four waves, counted vmcnt over pieces, row loads and stores in ONE
 # in-order queue, counted lgkmcnt over the fragment reads, M0 set once per four pieces) and the row-stationary GEMMs (same ring)
@@ -170,22 +168,21 @@ for (Bq, ntok, fp16) in [(32, 3601, True), (11, 3601, False), (3, 130, True), (1
     del c, ctx_pl, x3, q3, k3, v3, x4, Wp4, Wp4t, q4, k4, v4
 
 for (M_, fp16) in [(57616, True), (24001, False), (300, True)]:
-    capi.check(lib.dinoseg_set_option(b"op_fmt", int(fp16)))
-    K = 768
-    Ap, _ = T._one_plane(seeded((M_, K), 61) * 0.7, fp16)
-    for name, N, kind, epi in (("fc1 gelu", 3072, 0, capi.EPI_GELU), ("proj resid", 768, 1, capi.EPI_RESID)):
-        W, bias = seeded((N, K), 62) * 0.05, seeded((N,), 63) * 0.3
-        Wp = T._pack_rs(W, kind)
-        X0 = seeded((M_, N), 64) if epi == capi.EPI_RESID else None
-        xo = torch.zeros((M_, N), device="cuda") if epi == capi.EPI_RESID else None
-        o16 = torch.zeros((M_, N), dtype=torch.int16, device="cuda") if epi == capi.EPI_GELU else None
+    with dino_amd.options(op_fmt=int(fp16)):
+        K = 768
+        Ap, _ = T._one_plane(seeded((M_, K), 61) * 0.7, fp16)
+        for name, N, kind, epi in (("fc1 gelu", 3072, 0, capi.EPI_GELU), ("proj resid", 768, 1, capi.EPI_RESID)):
+            W, bias = seeded((N, K), 62) * 0.05, seeded((N,), 63) * 0.3
+            Wp = T._pack_rs(W, kind)
+            X0 = seeded((M_, N), 64) if epi == capi.EPI_RESID else None
+            xo = torch.zeros((M_, N), device="cuda") if epi == capi.EPI_RESID else None
+            o16 = torch.zeros((M_, N), dtype=torch.int16, device="cuda") if epi == capi.EPI_GELU else None
 
-        def runrs():
-            if xo is not None:
-                xo.copy_(X0)
-            capi.check(lib.dinoseg_op_gemm_rs(Ap.data_ptr(), K, Wp.data_ptr(), bias.data_ptr(), M_, N, K, epi, None if xo is None else xo.data_ptr(),
-                                              None if o16 is None else o16.data_ptr(), N if o16 is not None else 0, None, None, None, 0, 0, 0, 0.0, S()))
-        screen(f"gemm_rs {name} M={M_} fp16={fp16}", runrs, lambda: [xo if xo is not None else o16])
-capi.check(lib.dinoseg_set_option(b"op_fmt", 0))
+            def runrs():
+                if xo is not None:
+                    xo.copy_(X0)
+                capi.check(lib.dinoseg_op_gemm_rs(Ap.data_ptr(), K, Wp.data_ptr(), bias.data_ptr(), M_, N, K, epi, None if xo is None else xo.data_ptr(),
+                                                  None if o16 is None else o16.data_ptr(), N if o16 is not None else 0, None, None, None, 0, 0, 0, 0.0, S()))
+            screen(f"gemm_rs {name} M={M_} fp16={fp16}", runrs, lambda: [xo if xo is not None else o16])
 print("RACE SCREEN", "CLEAN" if bad == 0 else f"FAILED ({bad})")
 sys.exit(1 if bad else 0)

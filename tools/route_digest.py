@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import dino_amd  # noqa: E402
 from dino_amd.weights import synthetic_labels  # noqa: E402
 from tests import test_route_plan_gpu as T  # noqa: E402
+from tests.gpu_util import route_options  # noqa: E402
 
 
 def digest(t):
@@ -32,9 +33,9 @@ for kind, precision in T.ALL_CASES:
         show(case, out)
 for precision in T.PRECISIONS:
     m, frames = T.small_model(precision), T.small_frames()
-    with T.options(m, streams=1):
+    with route_options(m, streams=1):
         show(f"segment/{precision}", m.segment(frames, size=(100, 100), want_logp=True))
-    with T.options(m, streams=2, split_min=2):
+    with route_options(m, streams=2, split_min=2):
         show(f"split/{precision}", m.forward_frames(frames))
         show(f"split-segment/{precision}", m.segment(frames, size=(100, 100), want_logp=True))
 labels = torch.from_numpy(synthetic_labels(2, 64, 7, seed=6)).cuda()
@@ -42,7 +43,7 @@ for precision in ("bf16", "bf16x3"):
     for gemm_ln in (0, 1):
         m = T.small_model(precision)
         m.unfreeze_bb()
-        with T.options(m, deterministic=1, gemm_ln=gemm_ln):
+        with route_options(m, deterministic=1, gemm_ln=gemm_ln):
             out = m.fused_training_step((T.small_frames(), labels), 0)
             torch.cuda.synchronize()
             show(f"train/{precision}/gemm_ln={gemm_ln}/loss", [out["loss"], out["probs"]])

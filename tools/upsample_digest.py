@@ -55,14 +55,11 @@ for shape, name in zip(D.SHAPES, D.IDS):
     show(f"upsample_argmax/{name}", ("labels", "dense"), D.run_op(logp, *shape))
     show(f"upsample_argmax/{name}/labels-only", ("labels",), D.run_op(logp, *shape, want_dense=False)[:1])
 
-dino_amd.set_option("deterministic", 1)
-try:
+with dino_amd.options(deterministic=1):
     for i, (shape, name) in enumerate(zip(L.SHAPES, L.IDS)):
         logp, t = L.random_case(shape, seed=100 + i)
         loss, dlogp, nv = L.run_op(logp.cuda(), t.cuda(), shape, ignore=255 if shape[3] <= 255 else -100)
         show(f"upsample_nll/{name}", ("loss", "n_valid", "dL"), (loss, nv, dlogp))
-finally:
-    dino_amd.set_option("deterministic", 0)
 
 for case, name in list(zip(ensemble_util.CASES, ensemble_util.IDS)) + [(ensemble_util.LARGE_LDS_CASE, "B1-C5-40x70-K8-identity")]:
     logps = [lp.cuda() for lp in ensemble_util.random_views(case)]
