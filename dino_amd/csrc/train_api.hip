@@ -187,7 +187,11 @@ static int ensure_train_workspace(dinoseg_handle* h, const TrainLayout& L, int B
     DSEG_TRY(grow_device_buffer(h->tws, h->tws_bytes, L.total, s));
     if (grows) h->tws_B = -1;
     if (h->tws_B != B || h->tws_H != Hf || h->tws_W != Wf) {
-        for (int l = 0; l < h->cfg.n_blocks; ++l)   // Q/K/V pad rows must be zero (never written afterwards)
+        // pad rows (include/dinoseg.h, dinoseg_op_attention and dinoseg_op_attention_bwd): rows ntok..npad of q, k and v are read with the
+        // 64-row tiles they share with real rows and must hold FINITE values -- any finite values, zero is not required (the forward and
+        // the backward mask a pad key and give a pad query probability 0; 0 x finite = 0, 0 x Inf is not).  Fresh memory may hold
+        // anything: zero Q/K/V once per layout (never written afterwards).
+        for (int l = 0; l < h->cfg.n_blocks; ++l)
             DSEG_CHECK_HIP(hipMemsetAsync(h->tws + L.Q + l * L.blk_stride, 0, L.LSE - L.Q, s));
         DSEG_CHECK_HIP(hipMemsetAsync(h->tws + L.ACC, 0, 256, s));
         h->tws_B = B;

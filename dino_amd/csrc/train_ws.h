@@ -21,7 +21,7 @@ struct TrainLayout {
     size_t Xin, A1, Q, K, V, LSE, CTX, Xmid, A2, HPRE, HB, blk_stride;
     size_t Xfin, PATCH, FEAT, H1, H2, LOGP, DZ;
     size_t dX, dA, dXp, G, dCTX, T1, T2, NLSE, NDEL, DPOS, SINK, ACC, SPLITK, DET;
-    size_t zero_begin, zero_end;      // Q/K/V of every block (pad rows must be zero)
+    size_t zero_begin, zero_end;      // Q/K/V of every block (pad rows must be FINITE, zero is not required: fresh memory is zeroed once)
     size_t total;
     long a_plane, qkv_plane, f_plane, feat_plane, h1_plane, h2_plane, dz_plane, patch_plane, g_plane, t_plane;
     size_t t2_bytes;

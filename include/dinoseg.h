@@ -1018,7 +1018,23 @@ int dinoseg_op_head_wide(const void* in, int64_t in_plane, int32_t ld, int32_t M
 
 /* flash-attention backward: q,k,v as the forward; dO, O: ctx-layout planes [planes][B*ntok][heads*64]; lse from the
  * forward; scratch: 2*B*heads*npad floats; dqkv out: planes [planes][B*ntok][3*heads*64] (gradient of the qkv
- * projection output, Q|K|V columns). */
+ * projection output, Q|K|V columns).  npad % 64 == 0, npad >= ntok, planes 1 or 2 (else -1, nothing is launched).
+ * Pad rows: rows ntok..npad of q, k and v are read with the 64-row tiles they share with real rows and must hold FINITE values -- any
+ * finite values, zero is not required.  A pad key is masked (dQ) or never stored (dK, dV); a pad query has -lse = -inf, probability 0,
+ * and 0 x finite = 0: dqkv carries the bits of the run on zero pad rows (tests/test_backward_containment_gpu.py); a NaN or Inf
+ * there may reach it (0 x Inf).  dO and O have no pad rows; no row at or beyond B*ntok is read.
+ * scratch needs no initialisation: all 2*B*heads*npad floats are written before they are read (-lse | -inf, then -delta | 0), and
+ * nothing outside them.  The plane strides qkv_plane, o_plane (shared by dO and O) and dqkv_plane may exceed the minimum; dqkv rows have
+ * no stride of their own (3*heads*64 elements).  Nothing but dqkv[p][row < B*ntok][col] and the scratch is written.
+ * Exactness: the kernels compute delta = sum dO O, P = 2^(q.k - lse), dS = P (dO.v - delta), dQ = 0.125 dS.k, dK = ln2 dS^T.q,
+ * dV = P^T.dO from their inputs alone.  On inputs whose scores and lse are integers, whose v, dO and O are small integers and whose
+ * sums fit 24 bits, dQ and dV carry the round-to-nearest-even planes of 0.125 * sum and of the sum, bit for bit on both planes, with P
+ * and dS rounded to the planes (hi = RNE, lo = RNE of the rest) and hi.hi + hi.lo + lo.hi per product.  dK = float32(sum) * float32(ln 2):
+ * on one plane the RNE plane of that product, bit for bit; on two planes within the planes' half ulp (2^-17 relative) plus 2^-23 of the
+ * exact product -- its lo plane is rounded from the exact product where the compiler contracts the split's multiply and subtract, from
+ * the fp32 product where it does not, and either is a correct split.  (tests/test_attention_bwd_probes_gpu.py::test_probe,
+ * ::test_probes_on_the_8_wave_dq_route; the construction and what it can see: tests/attention_bwd_probe_util.py,
+ * tests/test_attention_bwd_probes_cpu.py.) */
 int dinoseg_op_attention_bwd(const void* q, const void* k, const void* v, int64_t qkv_plane, const void* dO, const void* O,
                              int64_t o_plane, const float* lse, float* scratch, void* dqkv, int64_t dqkv_plane, int32_t B,
                              int32_t heads, int32_t ntok, int32_t npad, int32_t planes, void* stream);

@@ -129,8 +129,9 @@ def soft_bits(ntok: int):
     return list(range(nb - ns, nb))
 
 
-def build(probe, B, H, ntok, n=0, s=1, t=0, rot=0, planes=1, v_fp16=False, lo=None, seed=0) -> Case:
-    """One probe at shift c = 0 (shifted() derives the others).  lo: None, "k" or "q" (hi + lo routes, selector and weights only)."""
+def build(probe, B, H, ntok, n=0, s=1, t=0, rot=0, planes=1, v_fp16=False, lo=None, seed=0, expect=True) -> Case:
+    """One probe at shift c = 0 (shifted() derives the others).  lo: None, "k" or "q" (hi + lo routes, selector and weights only).
+    expect = False: the operands alone (tests/attention_bwd_probe_util.py takes Q and K from here and has expectations of its own)."""
     assert probe in PROBES and 1 <= ntok <= 1 << NBITS and math.gcd(s, ntok) == 1
     assert lo is None or (planes == 2 and probe in ("selector", "weights"))
     npad = (ntok + 63) // 64 * 64
@@ -176,7 +177,8 @@ def build(probe, B, H, ntok, n=0, s=1, t=0, rot=0, planes=1, v_fp16=False, lo=No
             q[ntok:] = q[0]
     c = Case(probe, B, H, ntok, npad, Q, K, V, None, None, None, None, None, None, dims, sh_d, Q[0, 0, :ntok, sh_d].copy(),
              {"pi": pis, "kind": kind, "nh": nh, "n": n, "code": code, "lo": lo, "planes": planes, "v_fp16": v_fp16})
-    _expect(c)
+    if expect:
+        _expect(c)
     return c
 
 

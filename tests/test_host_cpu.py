@@ -57,6 +57,23 @@ def test_backward_op_entries_refuse_bad_shapes_without_gpu():
     assert "bad shape g=28 D=384 oh=0 ow=60" in capi.last_error()
 
 
+def test_attention_backward_entry_refuses_bad_shapes_without_gpu():
+    """dinoseg_op_attention_bwd: npad must be a multiple of 64 and at least ntok, planes 1 or 2 -- refused before any launch."""
+    lib = capi.lib()
+    fake = 256      # never dereferenced: every call below is refused on the host
+
+    def call(ntok, npad, planes):
+        return lib.dinoseg_op_attention_bwd(fake, fake, fake, 2 * npad * 64, fake, fake, ntok * 128, fake, fake, fake, ntok * 384, 1, 2, ntok,
+                                            npad, planes, None)
+    assert call(65, 100, 1) == -1
+    assert "attention_bwd: npad=100 must be a multiple of 64 and >= ntok=65" in capi.last_error()
+    assert call(65, 64, 2) == -1
+    assert "attention_bwd: npad=64 must be a multiple of 64 and >= ntok=65" in capi.last_error()
+    for planes in (0, 3):
+        assert call(65, 128, planes) == -1
+        assert "attention_bwd: planes must be 1 or 2" in capi.last_error()
+
+
 def test_helper_op_entries_refuse_bad_arguments_without_gpu():
     """The stand-alone entries of the helper kernels refuse null pointers and negative sizes on the host, with a message."""
     lib = capi.lib()
