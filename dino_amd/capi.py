@@ -86,6 +86,10 @@ SIGNATURES = {
     "dinoseg_op_pack": (C.c_int, [_fp, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _vp]),
     "dinoseg_op_gemm": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _vp, _i64, _i32, _vp]),
     "dinoseg_op_qkv_gemm": (C.c_int, [_vp, _i64, _vp, _i64, _fp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _i64, _vp]),
+    # the patch-embedding GEMM and the training forward's residual / GELU epilogues on their own (tests/test_gemm_probes_gpu.py)
+    "dinoseg_op_patch_gemm": (C.c_int, [_vp, _vp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp, _vp]),
+    "dinoseg_op_gemm_train": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _vp, _i64, _i32, _vp, _i64,
+                                        _vp]),
     "dinoseg_op_ln_gemm_slab_elems": (_i64, [_i32, _i32, _i32]),
     "dinoseg_op_pack_slabs": (C.c_int, [_fp, _i32, _i32, _i32, _vp, _vp]),
     "dinoseg_op_ln_gemm": (C.c_int, [_fp, _fp, _fp, _f32, _vp, _i64, _fp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64,

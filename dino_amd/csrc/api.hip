@@ -913,6 +913,67 @@ extern "C" int dinoseg_op_qkv_gemm(const void* A, int64_t a_plane, const void* W
     g.fmt = options().op_fmt;
     g.q = reinterpret_cast<bf16_t*>(q); g.k = reinterpret_cast<bf16_t*>(k); g.v = reinterpret_cast<bf16_t*>(v);
     g.qkv_plane = qkv_plane; g.ntok = ntok; g.npad = npad; g.heads = heads; g.dmodel = D; g.qscale = qscale;
+    g.v_bf16 = options().op_v_bf16;
+    return launch_gemm(g, reinterpret_cast<hipStream_t>(stream));
+}
+
+// the shape rules of launch_gemm_small (gemm.hip), for the entries below that name their own refusals
+static bool gemm_small_shape_ok(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t planes) {
+    return M > 0 && N > 0 && K > 0 && N % 128 == 0 && K % 64 == 0 && lda >= K && lda % 8 == 0 && (planes == 1 || planes == 2);
+}
+
+extern "C" int dinoseg_op_patch_gemm(const void* A, const void* Wp, const float* bias, const float* pos, int32_t B, int32_t n_patches,
+                                     int32_t N, int32_t K, int32_t planes, float* X_out, void* stream) {
+    if (!A || !Wp || !bias || !pos || !X_out) {
+        dinoseg_set_error("dinoseg_op_patch_gemm: null pointer");
+        return -1;
+    }
+    if (B <= 0 || n_patches <= 0 || (int64_t)B * n_patches > INT32_MAX || !gemm_small_shape_ok(B * n_patches, N, K, K, planes)) {
+        dinoseg_set_error("dinoseg_op_patch_gemm: unsupported shape B=%d n_patches=%d N=%d K=%d planes=%d (need N%%128==0, K%%64==0)", B, n_patches,
+                          N, K, planes);
+        return -1;
+    }
+    GemmParams g = {};
+    g.A = reinterpret_cast<const bf16_t*>(A); g.a_plane = (long)B * n_patches * K; g.lda = K;
+    g.W = reinterpret_cast<const bf16_t*>(Wp); g.w_plane = (long)N * K;
+    g.M = B * n_patches; g.N = N; g.K = K; g.planes = planes; g.epi = EPI_PATCH; g.bias = bias;
+    g.fmt = options().op_fmt;
+    g.out_f32 = X_out; g.ldo_f32 = N;
+    g.pos = pos; g.n_patches = n_patches;
+    return launch_gemm(g, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_gemm_train(const void* A, int64_t a_plane, int32_t lda, const void* Wp, int64_t w_plane, int32_t M, int32_t N,
+                                     int32_t K, int32_t planes, int32_t epi, const float* bias, const float* resid, float* out_f32,
+                                     void* out_bf16, int64_t out_plane, int32_t ldo, void* aux_out, int64_t aux_plane, void* stream) {
+    if (epi != EPI_RESID && epi != EPI_GELU) {
+        dinoseg_set_error("dinoseg_op_gemm_train: epi must be 1 (residual) or 2 (GELU)");
+        return -1;
+    }
+    if (!A || !Wp || (epi == EPI_RESID && (!resid || !out_f32 || resid == out_f32)) || (epi == EPI_GELU && (!out_bf16 || !aux_out))) {
+        dinoseg_set_error("dinoseg_op_gemm_train: epi 1 needs resid and out_f32 (two buffers), epi 2 needs out_bf16 and aux_out");
+        return -1;
+    }
+    if (!gemm_small_shape_ok(M, N, K, lda, planes) || (epi == EPI_GELU && (ldo < N || ldo % 8 != 0))) {
+        dinoseg_set_error("dinoseg_op_gemm_train: unsupported shape M=%d N=%d K=%d lda=%d ldo=%d planes=%d (need N%%128==0, K%%64==0)", M, N, K, lda,
+                          ldo, planes);
+        return -1;
+    }
+    if (epi == EPI_GELU && options().op_fmt != FMT_BF16) {
+        dinoseg_set_error("dinoseg_op_gemm_train: the pre-activation planes (aux_out) are bf16 only");
+        return -1;
+    }
+    GemmParams g = {};
+    g.A = reinterpret_cast<const bf16_t*>(A); g.a_plane = a_plane; g.lda = lda;
+    g.W = reinterpret_cast<const bf16_t*>(Wp); g.w_plane = w_plane;
+    g.M = M; g.N = N; g.K = K; g.planes = planes; g.epi = epi; g.bias = bias;
+    g.fmt = options().op_fmt;
+    if (epi == EPI_RESID) {
+        g.resid = resid; g.out_f32 = out_f32; g.ldo_f32 = N;
+    } else {
+        g.out_bf16 = reinterpret_cast<bf16_t*>(out_bf16); g.out_plane = out_plane; g.ldo = ldo;
+        g.aux_out = reinterpret_cast<bf16_t*>(aux_out); g.aux_plane = aux_plane;
+    }
     return launch_gemm(g, reinterpret_cast<hipStream_t>(stream));
 }
 

@@ -848,10 +848,27 @@ int dinoseg_op_gemm(const void* A, int64_t a_plane, int32_t lda, const void* W, 
                     int64_t out_plane, int32_t ldo, void* stream);
 
 /* attn.qkv GEMM with the head-scatter epilogue (vision_transformer.py:82): Q (times qscale), K, V, each
- * [planes][B,H,npad,64]; M = B*ntok rows. */
+ * [planes][B,H,npad,64]; M = B*ntok rows.  With fp16 hi + lo planes (option "op_fmt" 1, planes 2) option "op_v_bf16" 1 writes V as
+ * bf16 hi + lo planes, the form dinoseg_op_attention reads under the same option (the forward's default parity mode at large batches). */
 int dinoseg_op_qkv_gemm(const void* A, int64_t a_plane, const void* W, int64_t w_plane, const float* bias, int32_t B,
                         int32_t ntok, int32_t npad, int32_t heads, int32_t planes, float qscale, void* q, void* k,
                         void* v, int64_t qkv_plane, void* stream);
+
+/* The patch-embedding GEMM (the conv of vision_transformer.py:153,157 as a GEMM, + bias + position rows, :224-235):
+ *     X_out[b (n_patches + 1) + 1 + p, :] = A[b n_patches + p, :] . W^T + bias + pos[1 + p, :]
+ * A: planes x [B n_patches][K] (the patch-gather matrix), W: planes x [N][K], both in the format of option "op_fmt"; bias fp32 [N];
+ * pos fp32 [n_patches + 1][N]; X_out fp32 [B (n_patches + 1)][N].  The CLS rows b (n_patches + 1) are not written.  N % 128 == 0,
+ * K % 64 == 0. */
+int dinoseg_op_patch_gemm(const void* A, const void* W, const float* bias, const float* pos, int32_t B, int32_t n_patches, int32_t N,
+                          int32_t K, int32_t planes, float* X_out, void* stream);
+
+/* dinoseg_op_gemm as dinoseg_train_forward launches it.  epi 1: out_f32 = resid + A W^T + bias with resid != out_f32 (attn.proj and
+ * mlp.fc2 read the residual stream of one buffer and write the next); epi 2: out_bf16 planes = GELU(z), z = A W^T + bias, and
+ * aux_out planes [planes][M][ldo] (plane stride aux_plane) = z itself, kept for the backward's gelu' -- bf16 operands only.
+ * N % 128 == 0, K % 64 == 0, lda % 8 == 0 (the 128 x 128 kernel). */
+int dinoseg_op_gemm_train(const void* A, int64_t a_plane, int32_t lda, const void* W, int64_t w_plane, int32_t M, int32_t N, int32_t K,
+                          int32_t planes, int32_t epi, const float* bias, const float* resid, float* out_f32, void* out_bf16,
+                          int64_t out_plane, int32_t ldo, void* aux_out, int64_t aux_plane, void* stream);
 
 /* Slab-major bf16 copy of an fp32 weight W [N][K] for dinoseg_op_ln_gemm (dst holds dinoseg_op_ln_gemm_slab_elems(N, K, planes)
  * bf16 elements; -1 = unsupported shape): [column tile][k-step][plane][rows][32 k], pre-swizzled, zero padded. */

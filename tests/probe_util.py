@@ -1,11 +1,12 @@
-"""Probe builders and per-element bounds for tests/test_forward_probes_gpu.py and tests/test_gelu_formula_cpu.py.
+"""Probe builders and per-element bounds for tests/test_forward_probes_gpu.py, tests/test_gemm_probes_gpu.py, tests/test_gemm_probes_cpu.py
+and tests/test_gelu_formula_cpu.py.
 
 The fused forward launches (mlp_fused2/3/4.hip, the GELU epilogues of gemm*.hip) round their intermediate results to 16 bits at points
 that their own fp32 noise moves, so on random data they can only be held to a bound scaled by the largest output.  A probe isolates one
 stage with weights that make every OTHER stage exact (W = 0 with the probe in the bias, 0 / 1 selector matrices, rows of +-1 whose
 LayerNorm is exactly +-1, operands that are exact in the 16-bit format): what is left is one stage against fp64, element by element.
 
-Nothing here touches the GPU: the formulas are restated in fp64 numpy, the bounds are derived from the instruction sequences the
+Nothing here launches a kernel: the formulas are restated in fp64 numpy, the bounds are derived from the instruction sequences the
 kernels run (docstrings below) and are never fitted to an output.
 """
 from __future__ import annotations
@@ -263,3 +264,189 @@ def sum_bound(abs_terms_sum: np.ndarray, n_terms: int, extra: int = 8) -> np.nda
     sum behave as a random walk, sqrt(n) U with overwhelming probability, and the factor 4 is that margin -- the same constant form
     tests/test_backward_ops_gpu.py uses.  `extra` covers the bias, the residual add and the final roundings.)"""
     return (4.0 * math.sqrt(n_terms) + extra) * U * abs_terms_sum
+
+
+# ------------------------------------------------------------------------------------------------ shared by the probe files
+# (tests/test_forward_probes_gpu.py: the fused launches; tests/test_gemm_probes_gpu.py: the stand-alone GEMMs)
+GEMMS = ("gemm-1", "gemm-2", "gemm_big-1", "gemm_big-2", "ln_gemm-1", "ln_gemm-2", "gemm_rs-1", "ln_gemm_rs-1")
+GEMM_BIG_OPTION = {"gemm": 0, "gemm_big": 2}      # option "gemm_big" that sends dinoseg_op_gemm / dinoseg_op_qkv_gemm to gemm.hip / gemm_big.hip (other routes: 1, the default)
+NAN16 = 0x7FC1        # a NaN in both 16-bit formats: what the pad rows hold before the launch
+
+
+def planes_of(kind):
+    return 2 if kind.endswith("3") or kind.endswith("-2") else 1
+
+
+def unplane(t, fp16):
+    """int16 planes [planes, ...] -> fp64 [planes, ...] on the host"""
+    return t.view(tdtype(fp16)).to(torch.float64).cpu().numpy()
+
+
+def stored(v, fp16, planes, sat=True):
+    """the value the format holds for fp32 v: RNE (after the fp16 clamp), or hi + lo"""
+    v = np.asarray(v, dtype=np.float32)
+    if fp16 and sat:
+        v = np.clip(v, -FP16_MAX, FP16_MAX)
+    if planes == 1:
+        return rne(v, fp16)
+    hi, lo = split(v, fp16)
+    return hi + lo
+
+
+def exact_operand(shape, seed, fp16, planes, lo, hi, signed=True):
+    """seeded fp32 values the kernel's operand planes hold exactly: six significant bits on one plane; on two planes hi (six bits) + lo (six bits,
+    |lo| < ulp(hi) / 4), which is its own hi + lo split.  Returns (value fp64, lo part fp64 -- zero on one plane)."""
+    v = exact_in_format(shape, seed, fp16, lo, hi, signed).astype(np.float64)
+    if planes == 1:
+        return v, np.zeros_like(v)
+    g = np.random.default_rng(seed + 1000)
+    e = np.floor(np.log2(np.abs(v)))
+    m6 = 1.0 + g.integers(0, 32, shape) / 32.0
+    lo_part = m6 * 2.0 ** (e - (13 if fp16 else 10)) * np.where(g.integers(0, 2, shape) == 0, 1.0, -1.0)
+    full = v + lo_part
+    h2, l2 = split(full.astype(np.float32), fp16)
+    assert (full.astype(np.float32).astype(np.float64) == full).all() and (h2 == v).all() and (l2 == lo_part).all()
+    return full, lo_part
+
+
+def banded(shape, tile=HT, ntiles=F // HT):
+    """mask [384, 1536]: output column d multiplies hidden tile d mod 48 only -- each tile's products stand alone in eight columns, so what one
+    k-step loses is not buried under the rounding bound of the other 47"""
+    d = np.arange(shape[0])[:, None]
+    j = np.arange(shape[1])[None, :]
+    return (j // tile) == (d % ntiles)
+
+
+KSL = 32      # W1 row j is non-zero on the k-slice [32 (j mod 12), 32 (j mod 12) + 32): every slice of fc1's k-loop carries 128 hidden units alone
+
+
+def block_sparse_w1(rows, seed, width=D):
+    """[rows, width]: +-{1, 1.25, 1.5, 1.75} on one 32-wide k-slice per row, zero elsewhere (exact in every format, and so are all partial sums)"""
+    g = np.random.default_rng(seed)
+    w = np.zeros((rows, width), dtype=np.float32)
+    nsl = width // KSL
+    for j in range(rows):
+        k0 = KSL * (j % nsl)
+        w[j, k0:k0 + KSL] = (1.0 + g.integers(0, 4, KSL) / 4.0) * np.where(g.integers(0, 2, KSL) == 0, 1.0, -1.0)
+    return w
+
+
+def ln_fc1_case(M, eps, fp16, planes, rows=F, seed=501, offset=64.0, width=D):
+    """X [M, width] of +-1, W1, b1 and the fp64 pre-activation z with its bound.  With eps = 0 the LayerNorm of a row is the row; with eps = 1e-6 it
+    is the row times rstd = 1 / sqrt(1 + 1e-6), which one plane rounds back to +-1 and two planes carry to 2^-17 / 2^-22.
+    |sum| <= 32 x 1.75 = 56, so with b1 = 64 every z lies in [8, 120]: from 8 on the GELU returns z itself, and half an ulp of bf16 is at most 0.25."""
+    X = sign_rows(M, seed, width=width)
+    W1 = block_sparse_w1(rows, seed + 1, width=width)
+    b1 = np.full(rows, offset, dtype=np.float32)
+    prod = X.astype(np.float64) @ W1.astype(np.float64).T
+    rstd = 1.0 / math.sqrt(1.0 + eps)
+    sabs = np.abs(W1).sum(axis=1).astype(np.float64)
+    if planes == 1:
+        a, a_err = 1.0, 4.0 * U                                   # RNE(rstd) = 1 in bf16 and fp16; the kernel's fp32 statistics are exact on +-1 rows
+    else:
+        a, a_err = rstd, (2.0 ** -22 if fp16 else 2.0 ** -17) + 4.0 * U
+    z = a * prod + b1.astype(np.float64)[None, :]
+    zerr = sum_bound(np.abs(b1).astype(np.float64) + sabs, width)[None, :] + a_err * sabs[None, :]
+    return X, W1, b1, z, zerr
+
+
+# ------------------------------------------------------------------------------------------------ the checks of tests/test_gemm_probes_gpu.py
+# (here, so that tests/test_gemm_probes_cpu.py can run them on an fp32 emulation of a correct GEMM and on mutants of it)
+LOG2E = 1.4426950408889634
+QS = float(np.float32(0.125 * LOG2E))      # the Q scale of the forward: 1 / sqrt(64) times log2 e, as the kernels hold it
+FMT_IDS = {False: "bf16", True: "fp16"}
+KSTEP = {"gemm": 64, "gemm_big": 32, "gemm_cstat": 64}      # the k-step of a kernel's K loop: BK in gemm.hip, big::BK in gemm_big.hip, a pair of 32-wide k-tiles in gemm_cstat (nk2 = K / 64)
+WIDTH = {"gemm": 384, "gemm_big": 384, "ln_gemm": 384, "gemm_rs": 768, "ln_gemm_rs": 768}      # K of probes G2: the kernel's width
+LN_ROUTES = ("ln_gemm", "ln_gemm_rs")
+EPI_GELU, EPI_RELU = 2, 3                  # (dino_amd.capi, restated: this module does not load the library)
+
+
+def g2_formats(kind):
+    """ln_gemm on two planes is bf16 only (dinoseg_op_ln_gemm)"""
+    return (False,) if kind == "ln_gemm-2" else (False, True)
+
+
+def g2_widths(kind):
+    """N: 1536, and for gemm_bstat the edges of gemm_rs_supported (N % 64 == 0, N >= 128, 4 N <= 16 KiB)"""
+    return (1536, 128, 192, 4096) if kind.split("-")[0] in ("gemm_rs", "ln_gemm_rs") else (1536,)
+
+
+def g2_eps(kind):
+    return (0.0, 1e-6) if kind.split("-")[0] in LN_ROUTES else (0.0,)
+
+
+# ReLU where the entry has it (dinoseg_op_gemm; gemm.hip refuses it for one fp16 plane: "the inference epilogues only")
+G2_CASES = [(k, f, e) for k in GEMMS for f in g2_formats(k) for e in (EPI_GELU, EPI_RELU)
+            if e == EPI_GELU or (k.split("-")[0] in ("gemm", "gemm_big") and (k, f) != ("gemm-1", True))]
+G2_MS = (77, 673)
+# (kind, heads the kernel's *_supported accepts, formats as (fp16, v_bf16)): dmodel % 128 == 0 in gemm.hip, % 384 in gemm_big.hip, K = 384 in
+# gemm_ln*.hip, dmodel = 768 in gemm_rs.hip
+QKV_KINDS = [("gemm-1", (2, 6, 12), ((False, 0), (True, 0))), ("gemm-2", (2, 6, 12), ((False, 0), (True, 0), (True, 1))),
+             ("gemm_big-1", (6, 12), ((False, 0), (True, 0))), ("gemm_big-2", (6, 12), ((False, 0), (True, 0), (True, 1))),
+             ("ln_gemm-1", (6,), ((False, 0), (True, 0))), ("ln_gemm-2", (6,), ((False, 0),)),
+             ("gemm_rs-1", (12,), ((False, 0), (True, 0))), ("ln_gemm_rs-1", (12,), ((False, 0), (True, 0)))]
+G3_CASES = [(k, H, f, vb) for k, hs, fs in QKV_KINDS for H in hs for f, vb in fs]
+G3_SHAPES = ((1, 77), (3, 130), (2, 257))
+
+
+def v_is_fp16(fp16, planes, v_bf16):
+    """V is bf16 on one plane whatever the operand format; on fp16 hi + lo planes it is fp16 unless op_v_bf16 asks for bf16"""
+    return bool(fp16 and planes == 2 and not v_bf16)
+
+
+def within(name, err, bound):
+    """|err| <= bound per element (numpy arrays or torch tensors); prints the worst |err| / bound and returns it"""
+    bound = bound + 0.0 * err
+    assert bool((abs(err) < float("inf")).all()), f"{name}: a result is not finite"
+    r = err / bound
+    i = int(r.argmax())
+    at = tuple(int(x) for x in np.unravel_index(i, tuple(err.shape)))
+    w = float(r.reshape(-1)[i])
+    print(f"{name}: worst |err| / bound {w:.3f} (|err| {float(err.reshape(-1)[i]):.3e}) at {at}")
+    assert bool((err <= bound).all()), (name, at, float(err.reshape(-1)[i]), float(bound.reshape(-1)[i]))
+    return w
+
+
+def accum_reference(A, A_lo, W, W_lo, K):
+    """G1: A W^T in fp64 on the operands the kernel multiplies (numpy or torch, [M, K] and [N, K]) without the lo x lo products the two-plane
+    kernels leave out, and sum_bound of the K products of each element"""
+    return A @ W.T - A_lo @ W_lo.T, sum_bound(abs(A) @ abs(W).T, K)
+
+
+def add_bound(*terms):
+    """4 U (|x| + |b| + ...): a residual, bias or position add is one rounded add and the value the sum starts from or ends in (another)"""
+    return 4.0 * U * sum(abs(t) for t in terms)
+
+
+def check_patch(name, out, ref, bound):
+    """out [B, n + 1, N] (NaN before the launch): the CLS rows still NaN, the patch rows within the bound"""
+    assert bool((out[:, 0] != out[:, 0]).all()), f"{name}: a CLS row was written"
+    return within(name, abs(out[:, 1:] - ref), bound)
+
+
+def check_stored(name, o, z, zerr, W, fp16, planes):
+    """G2: o [planes, M, N] fp64 = the stored planes; their sum is fmt(z) within half_ulp(|z| + zerr) + zerr and one number of the format.
+    2 bound <= min |W != 0|: one dropped or duplicated product cannot pass."""
+    h = o.sum(axis=0)
+    bound = half_ulp(np.abs(z) + zerr, fp16, planes) + zerr
+    assert (2.0 * bound <= np.abs(W[W != 0]).min()).all(), float(bound.max())
+    w = within(name, np.abs(h - z), bound)
+    assert bool(representable(torch.from_numpy(h).float(), fp16, planes).all()), f"{name}: a stored value is not a number of the format"
+    return w
+
+
+def check_qkv(name, q, k, v, z, zerr, fp16, planes, v_fp16, B, ntok, H, qs=QS):
+    """G3, test_layernorm_qkv_tails' check: z, zerr [M, 3 dm] (numpy); q, k, v int16 planes [planes, B, H, npad, 64] (torch), NAN16 in the pad rows
+    before the launch.  q = fmt(z qs), k = fmt(z), v = fmt_v(z) per element; 2 bound <= 1 (qs for Q) <= min |W != 0|."""
+    lay = lambda a: a.reshape(B, ntok, 3, H, 64).transpose(2, 0, 3, 1, 4)
+    z, zerr = lay(z), lay(np.broadcast_to(zerr, z.shape))
+    top = 0.0
+    for nm, t, f16, want, werr in (("q", q, fp16, z[0] * qs, zerr[0] * qs + U * np.abs(z[0] * qs)), ("k", k, fp16, z[1], zerr[1]),
+                                   ("v", v, v_fp16, z[2], zerr[2])):
+        g = unplane(t, f16)[:, :, :, :ntok].sum(axis=0)
+        bound = half_ulp(np.abs(want) + werr, f16, planes) + werr
+        assert (2.0 * bound <= (qs if nm == "q" else 1.0)).all(), (nm, float(bound.max()))
+        top = max(top, within(f"{name} {nm}", np.abs(g - want), bound))
+        assert bool(representable(torch.from_numpy(g).float(), f16, planes).all()), f"{name} {nm}: a stored value is not a number of the format"
+        assert bool((t[:, :, :, ntok:] == NAN16).all()), f"{name} {nm}: pad rows were written"
+    return top

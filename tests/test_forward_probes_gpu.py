@@ -1,4 +1,14 @@
-"""Stage-by-stage probes of the fused forward kernels: gemm.hip, gemm_big.hip, gemm_ln.hip, gemm_ln12.hip, gemm_rs.hip, mlp_fused2/3/4.hip.
+"""Stage-by-stage probes of the fused forward kernels mlp_fused2/3/4.hip (every probe), and of the 16-bit epilogues of the stand-alone GEMMs gemm.hip,
+gemm_big.hip, gemm_ln.hip, gemm_ln12.hip and gemm_rs.hip with W = 0 (probes 1, 2 and 6 only: the K loop of those kernels adds nothing here).
+
+Which probe reaches which kernel:
+  probes 1, 2, 6    mlp_fused2/3/4.hip (FUSED) and the GELU / ReLU epilogues of the eight GEMMS kinds (W = 0, the probe in the bias; probe 6 also
+                    through the fc1 product of gemm_ln12.hip, gemm_ln.hip and gemm_rs.hip's LayerNorm route, and the Q / K / V stores of the qkv tails,
+                    gemm_ln12.hip and gemm_rs.hip)
+  probes 3, 4       mlp_fused2/3/4.hip only
+  probe 5           mlp_fused2/3/4.hip and their qkv tails (TAILS) only
+The K loops and the scatter epilogues of the stand-alone GEMMs are held per element by tests/test_gemm_probes_gpu.py (probes G1 to G3), with the
+builders this file shares with it through tests/probe_util.py.
 
 tests/test_ops_gpu.py and tests/test_fp16_gpu.py hold these launches to one bound scaled by the largest output, on seeded normal data: the
 16-bit roundings inside a fused launch sit at points its own fp32 noise moves.  Here every stage but one is made EXACT by the weights
@@ -35,6 +45,7 @@ import torch
 
 from dino_amd import capi, options
 from tests import probe_util as P
+from tests.probe_util import GEMMS, NAN16, banded, block_sparse_w1, exact_operand, ln_fc1_case, planes_of, stored, unplane      # (shared with test_gemm_probes_gpu.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -43,7 +54,6 @@ D, F = P.D, P.F
 LOG2E = 1.4426950408889634
 MS = (33, 77, 129, 673)
 FUSED = ("mlp2", "proj2", "mlp3", "proj3", "mlp4", "proj4")
-GEMMS = ("gemm-1", "gemm-2", "gemm_big-1", "gemm_big-2", "ln_gemm-1", "ln_gemm-2", "gemm_rs-1", "ln_gemm_rs-1")
 # Does the GELU output of the launch saturate at the fp16 range?  mlp_fused3.hip does (OP_SAT).  mlp_fused2.hip and mlp_fused4.hip pack it with
 # the plain pack2<FMT>: an fp16 pre-activation beyond 65504 becomes inf there and 0 x inf = NaN spreads along the row.  The saturating pack was
 # built and measured (profiles/fused_gelu_saturation_ab.md: -0.46 % frames/s on the headline, outside the parent's spread) and not kept; the limit
@@ -63,10 +73,6 @@ def i16(*shape):
     return torch.zeros(shape, dtype=torch.int16, device="cuda")
 
 
-def planes_of(kind):
-    return 2 if kind.endswith("3") or kind.endswith("-2") else 1
-
-
 def one_plane(x, fp16):
     return x.to(P.tdtype(fp16)).contiguous().view(torch.int16)
 
@@ -75,11 +81,6 @@ def two_planes(x, fp16):
     dt = P.tdtype(fp16)
     hi = x.to(dt)
     return torch.stack([hi, (x - hi.float()).to(dt)]).contiguous().view(torch.int16)
-
-
-def unplane(t, fp16):
-    """int16 planes [planes, ...] -> fp64 [planes, ...] on the host"""
-    return t.view(P.tdtype(fp16)).to(torch.float64).cpu().numpy()
 
 
 def pre_err(kind, fp16):
@@ -183,17 +184,6 @@ def check_gelu_values(name, h, x, fp16, planes, erf, perr, residual=0.0, fused3=
     assert (h[big] == want).all(), (name, x[big][h[big] != want][:4], h[big][h[big] != want][:4])
 
 
-def stored(v, fp16, planes, sat=True):
-    """the value the format holds for fp32 v: RNE (after the fp16 clamp), or hi + lo"""
-    v = np.asarray(v, dtype=np.float32)
-    if fp16 and sat:
-        v = np.clip(v, -P.FP16_MAX, P.FP16_MAX)
-    if planes == 1:
-        return P.rne(v, fp16)
-    hi, lo = P.split(v, fp16)
-    return hi + lo
-
-
 @pytest.mark.parametrize("fp16", [False, True], ids=["bf16", "fp16"])
 @pytest.mark.parametrize("kind", FUSED)
 def test_gelu_probe_fused(cuda, kind, fp16):
@@ -223,7 +213,7 @@ def run_epilogue(kind, fp16, M, bias, epi=capi.EPI_GELU, X=None, W=None):
     route, planes = kind.split("-")[0], planes_of(kind)
     N = bias.numel()
     out = i16(planes, M, N)
-    with options(op_fmt=fp16, gemm_big={"gemm": 0, "gemm_big": 2}.get(route, 1)):
+    with options(op_fmt=fp16, gemm_big=P.GEMM_BIG_OPTION.get(route, 1)):
         if route in ("gemm", "gemm_big"):
             K = 64
             A, Wz = i16(planes, M, K), i16(planes, N, K)
@@ -324,30 +314,6 @@ def test_store_rounding_epilogues(cuda, kind, fp16, epi):
 
 
 # ------------------------------------------------------------------------------------------------ probe 3: fc2 accumulation
-def exact_operand(shape, seed, fp16, planes, lo, hi, signed=True):
-    """seeded fp32 values the kernel's operand planes hold exactly: six significant bits on one plane; on two planes hi (six bits) + lo (six bits,
-    |lo| < ulp(hi) / 4), which is its own hi + lo split.  Returns (value fp64, lo part fp64 -- zero on one plane)."""
-    v = P.exact_in_format(shape, seed, fp16, lo, hi, signed).astype(np.float64)
-    if planes == 1:
-        return v, np.zeros_like(v)
-    g = np.random.default_rng(seed + 1000)
-    e = np.floor(np.log2(np.abs(v)))
-    m6 = 1.0 + g.integers(0, 32, shape) / 32.0
-    lo_part = m6 * 2.0 ** (e - (13 if fp16 else 10)) * np.where(g.integers(0, 2, shape) == 0, 1.0, -1.0)
-    full = v + lo_part
-    h2, l2 = P.split(full.astype(np.float32), fp16)
-    assert (full.astype(np.float32).astype(np.float64) == full).all() and (h2 == v).all() and (l2 == lo_part).all()
-    return full, lo_part
-
-
-def banded(shape, tile=P.HT, ntiles=F // P.HT):
-    """mask [384, 1536]: output column d multiplies hidden tile d mod 48 only -- each tile's products stand alone in eight columns, so what one
-    k-step loses is not buried under the rounding bound of the other 47"""
-    d = np.arange(shape[0])[:, None]
-    j = np.arange(shape[1])[None, :]
-    return (j // tile) == (d % ntiles)
-
-
 @pytest.mark.parametrize("M", [77, 673, 128 * 300 + 19])
 @pytest.mark.parametrize("fp16", [False, True], ids=["bf16", "fp16"])
 @pytest.mark.parametrize("kind", FUSED)
@@ -399,39 +365,6 @@ def test_projection(cuda, kind, fp16, M):
 
 
 # ------------------------------------------------------------------------------------------------ probe 5: LayerNorm + fc1
-KSL = 32      # W1 row j is non-zero on the k-slice [32 (j mod 12), 32 (j mod 12) + 32): every slice of fc1's k-loop carries 128 hidden units alone
-
-
-def block_sparse_w1(rows, seed, width=D):
-    """[rows, width]: +-{1, 1.25, 1.5, 1.75} on one 32-wide k-slice per row, zero elsewhere (exact in every format, and so are all partial sums)"""
-    g = np.random.default_rng(seed)
-    w = np.zeros((rows, width), dtype=np.float32)
-    nsl = width // KSL
-    for j in range(rows):
-        k0 = KSL * (j % nsl)
-        w[j, k0:k0 + KSL] = (1.0 + g.integers(0, 4, KSL) / 4.0) * np.where(g.integers(0, 2, KSL) == 0, 1.0, -1.0)
-    return w
-
-
-def ln_fc1_case(M, eps, fp16, planes, rows=F, seed=501, offset=64.0):
-    """X [M, 384] of +-1, W1, b1 and the fp64 pre-activation z with its bound.  With eps = 0 the LayerNorm of a row is the row; with eps = 1e-6 it
-    is the row times rstd = 1 / sqrt(1 + 1e-6), which one plane rounds back to +-1 and two planes carry to 2^-17 / 2^-22.
-    |sum| <= 32 x 1.75 = 56, so with b1 = 64 every z lies in [8, 120]: from 8 on the GELU returns z itself, and half an ulp of bf16 is at most 0.25."""
-    X = P.sign_rows(M, seed)
-    W1 = block_sparse_w1(rows, seed + 1)
-    b1 = np.full(rows, offset, dtype=np.float32)
-    prod = X.astype(np.float64) @ W1.astype(np.float64).T
-    rstd = 1.0 / math.sqrt(1.0 + eps)
-    sabs = np.abs(W1).sum(axis=1).astype(np.float64)
-    if planes == 1:
-        a, a_err = 1.0, 4.0 * P.U                                   # RNE(rstd) = 1 in bf16 and fp16; the kernel's fp32 statistics are exact on +-1 rows
-    else:
-        a, a_err = rstd, (2.0 ** -22 if fp16 else 2.0 ** -17) + 4.0 * P.U
-    z = a * prod + b1.astype(np.float64)[None, :]
-    zerr = P.sum_bound(np.abs(b1).astype(np.float64) + sabs, D)[None, :] + a_err * sabs[None, :]
-    return X, W1, b1, z, zerr
-
-
 @pytest.mark.parametrize("eps", [0.0, 1e-6])
 @pytest.mark.parametrize("fp16", [False, True], ids=["bf16", "fp16"])
 @pytest.mark.parametrize("kind", FUSED)
@@ -514,7 +447,6 @@ def test_fp16_saturation_epilogues(cuda, kind, epi):
 
 
 # ------------------------------------------------------------------------------------------------ probe 5, the qkv tails
-NAN16 = 0x7FC1        # a NaN in both 16-bit formats: what the pad rows hold before the launch
 TAILS = [("tail2", False, 0), ("tail2", True, 0), ("tail3", False, 0), ("tail3", True, 0), ("tail3", True, 1), ("tail4", False, 0), ("tail4", True, 0)]
 
 
