@@ -155,6 +155,13 @@ SIGNATURES = {
     "dinoseg_op_guide_cells": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _i32, _fp, _vp]),
     "dinoseg_op_upsample_guided": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _fp, _fp, _vp]),
     "dinoseg_forward_guided_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _fp, _i32, _i32, _i32, _f64, _f64, _fp, _fp, _fp, _fp, _vp]),
+    # image-guided iterative label refinement (PAMR): the scratch size (host only), the seed from labels (kind 0) or scores (kind 1), the
+    # passes and the labels, all of it behind the forward
+    "dinoseg_refine_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "dinoseg_op_refine_seed": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp]),
+    "dinoseg_op_refine_iterate": (C.c_int, [_fp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _f64, _i32, _fp, _fp, _vp]),
+    "dinoseg_forward_refined_hw": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _fp, _i32, _i32, _f64, C.POINTER(_i32), _i32, _f64, _i32,
+                                             _fp, _vp, _fp, _fp, _vp]),
     # pixel-resolution training loss: upsample + cross-entropy + its gradient, alone and as the fine-tune step on pixel labels
     "dinoseg_op_upsample_nll_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "dinoseg_op_upsample_nll": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _i32, _fp, _fp, _fp, _fp, _vp, _vp]),

@@ -600,6 +600,20 @@ extern "C" int dinoseg_op_upsample_guided(const float* logp, const uint8_t* guid
                                   labels_out, dense_out, reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int64_t dinoseg_refine_scratch_bytes(int32_t B, int32_t C, int32_t OH, int32_t OW) { return refine_scratch_bytes(B, C, OH, OW); }
+
+extern "C" int dinoseg_op_refine_seed(const void* seed, int32_t kind, int32_t B, int32_t C, int32_t OH, int32_t OW, int32_t hp, int32_t wp,
+                                      double gain, void* scratch, void* stream) {
+    return launch_refine_seed("dinoseg_op_refine_seed", seed, kind, B, C, OH, OW, hp, wp, gain, scratch, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_refine_iterate(const uint8_t* guide, void* scratch, int32_t B, int32_t C, int32_t OH, int32_t OW,
+                                         const int32_t* dilations, int32_t n_dil, double sigma, int32_t iters, int32_t* labels_out,
+                                         float* dense_out, void* stream) {
+    return launch_refine_iterate("dinoseg_op_refine_iterate", guide, scratch, B, C, OH, OW, dilations, n_dil, sigma, iters, labels_out,
+                                 dense_out, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int64_t dinoseg_op_upsample_ensemble_scratch_bytes(int32_t K, int32_t B, int32_t OH, int32_t OW) {
     return upsample_ensemble_scratch_bytes(K, B, OH, OW);
 }

@@ -506,6 +506,35 @@ extern "C" int dinoseg_forward_guided_hw(dinoseg_handle* h, const void* x, int32
                                   dense_out, s);
 }
 
+extern "C" int dinoseg_forward_refined_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W,
+                                          const uint8_t* guide, int32_t OH, int32_t OW, double gain, const int32_t* dilations, int32_t n_dil,
+                                          double sigma, int32_t iters, float* logp_out, void* scratch, int32_t* labels_out, float* dense_out,
+                                          void* stream) {
+    const char* who = "dinoseg_forward_refined_hw";
+    if (!h || !x || B <= 0) {
+        dinoseg_set_error("%s: bad argument (null handle or frames, or B=%d)", who, B);
+        return -1;
+    }
+    if (!guide || !logp_out || !scratch || (!labels_out && !dense_out)) {
+        dinoseg_set_error("%s: null pointer (guide, logp_out, scratch, and at least one of labels_out / dense_out, are required)", who);
+        return -1;
+    }
+    if (!frame_ok(H, W, h->cfg.patch)) {
+        set_resolution_error(h->cfg.patch);
+        return -1;
+    }
+    const int hp = H / h->cfg.patch, wp = W / h->cfg.patch, C = h->cfg.n_classes;
+    if (refine_seed_check(who, REFINE_SEED_SCORES, B, C, OH, OW, hp, wp, gain)) return -1;
+    if (refine_iterate_check(who, B, C, OH, OW, dilations, n_dil, sigma, iters, nullptr)) return -1;
+    ForwardRequest rq;
+    rq.logp_out = logp_out;
+    DSEG_TRY(forward_split(h, x, x_kind, B, H, W, rq, stream));
+    DeviceGuard guard(h);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    DSEG_TRY(launch_refine_seed(who, logp_out, REFINE_SEED_SCORES, B, C, OH, OW, hp, wp, gain, scratch, s));
+    return launch_refine_iterate(who, guide, scratch, B, C, OH, OW, dilations, n_dil, sigma, iters, labels_out, dense_out, s);
+}
+
 extern "C" int dinoseg_forward(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t r, float* logp_out,
                                int32_t* argmax_out, int32_t tap_block, float* tap_out, void* stream) {
     return dinoseg_forward_hw(h, x, x_kind, B, r, r, logp_out, argmax_out, tap_block, tap_out, stream);

@@ -314,6 +314,27 @@ int upsample_guided_check(const char* who, int B, int hp, int wp, int C, int OH,
                           UpGuidedPlan* plan);
 int launch_upsample_guided(const char* who, const float* logp, const uint8_t* guide, const uint32_t* cells, int B, int hp, int wp, int C, int OH, int OW,
                            int radius, double sigma_spatial, double sigma_range, int32_t* labels, float* dense, hipStream_t s);
+// Image-guided iterative label refinement (refine.hip; the rule: include/dinoseg.h, dinoseg_op_refine_iterate): PAMR passes over a state
+// [B, C, OH, OW] that ping-pongs between the halves of scratch [2][B, C, OH, OW], guided by the uint8 frame guide [B, OH, OW, 3].
+// launch_refine_seed writes half 0 from int32 labels [B, OH, OW] (one-hot) or fp32 scores [B, hp*wp, C] (bilinear enlargement, then
+// softmax(gain v)); launch_refine_iterate runs `iters` passes, one launch each, and writes labels int32 [B, OH, OW] and / or the final
+// state dense fp32 [B, C, OH, OW].  No atomics.  The checks are the host-side refusals alone (-1 and a message starting with `who`);
+// refine_iterate_check also plans the launch.
+constexpr int REFINE_SEED_LABELS = 0, REFINE_SEED_SCORES = 1;
+constexpr int REFINE_MAX_C = 256, REFINE_MAX_DIL = 6, REFINE_MAX_DILATION = 24, REFINE_MAX_ITERS = 64, REFINE_MAX_SIDE = 1 << 14;
+struct RefinePlan {
+    int tiles_x, tiles_y, CC, plane_words;
+    size_t lds_bytes;
+    float k;
+};
+long long refine_scratch_bytes(int B, int C, int OH, int OW);
+int refine_seed_check(const char* who, int kind, int B, int C, int OH, int OW, int hp, int wp, double gain);
+int launch_refine_seed(const char* who, const void* seed, int kind, int B, int C, int OH, int OW, int hp, int wp, double gain, void* scratch,
+                       hipStream_t s);
+int refine_iterate_check(const char* who, int B, int C, int OH, int OW, const int32_t* dilations, int n_dil, double sigma, int iters,
+                         RefinePlan* plan);
+int launch_refine_iterate(const char* who, const uint8_t* guide, void* scratch, int B, int C, int OH, int OW, const int32_t* dilations,
+                          int n_dil, double sigma, int iters, int32_t* labels, float* dense, hipStream_t s);
 // Pixel-resolution training loss (upsample_loss.hip): loss = F.cross_entropy(that upsample of logp, labels int64 [B, OH, OW]) with the
 // mean over the valid pixels (0 <= label < C; ignore_index and -100 skipped, anything else skipped and flags[0] |= 1), and dlogp
 // [B, hp*wp, C] = d loss / d logp (nullable: loss only), without a [B, C, OH, OW] tensor.  dlogp is a gather in a fixed order (no

@@ -175,6 +175,85 @@ def guide_plan(patch: int, x: torch.Tensor, guide, size):
     return kind, B, H, W, OH, OW
 
 
+REFINE_DILATIONS = (1, 2, 4, 8, 12, 24)     # PAMR's
+REFINE_MAX_SIDE = 1 << 14
+
+
+def refine_params(gain=1.0, iters=10, dilations=REFINE_DILATIONS, sigma=0.1):
+    """The validated (gain, iters, dilations, sigma) of a refinement (include/dinoseg.h, dinoseg_op_refine_iterate): gain positive
+    and finite, iters an integer in 0..64, 1 to 6 strictly ascending integer dilations in 1..24, sigma in [1e-3, 1e3]."""
+    try:
+        gain, sigma = float(gain), float(sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"gain and sigma must be numbers, got {gain!r} and {sigma!r}") from None
+    with np.errstate(over="ignore", under="ignore"):
+        gain32 = float(np.float32(gain))            # (the library multiplies by the fp32 value)
+    if not (math.isfinite(gain) and gain > 0.0 and math.isfinite(gain32) and gain32 > 0.0):
+        raise ValueError(f"gain must be positive and finite (in fp32 too), got {gain}")
+    if not (math.isfinite(sigma) and 1e-3 <= sigma <= 1e3):
+        raise ValueError(f"sigma must be in [1e-3, 1e3], got {sigma}")
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 0 <= int(iters) <= 64:
+        raise ValueError(f"iters must be an integer in 0..64, got {iters!r}")
+    try:
+        dil = tuple(dilations)
+    except TypeError:
+        raise ValueError(f"dilations must be a sequence of integers, got {dilations!r}") from None
+    if not 1 <= len(dil) <= 6:
+        raise ValueError(f"dilations takes 1 to 6 entries, got {len(dil)}")
+    if any(isinstance(d, bool) or not isinstance(d, (int, np.integer)) or not 1 <= int(d) <= 24 for d in dil):
+        raise ValueError(f"every dilation must be an integer in 1..24, got {dil}")
+    dil = tuple(int(d) for d in dil)
+    if any(b <= a for a, b in zip(dil, dil[1:])):
+        raise ValueError(f"dilations must ascend strictly, got {dil}")
+    return gain, int(iters), dil, sigma
+
+
+def refine_plan(seed, guide, n_classes=None, grid=None, gain=1.0, iters=10, dilations=REFINE_DILATIONS, sigma=0.1):
+    """The checks of ``DINOSeg.refine`` without a device: (kind, B, C, OH, OW, hp, wp, gain, iters, dilations, sigma).  kind 0: an
+    integer label map [B, OH, OW] at the guide's size with ``n_classes``; kind 1: fp32 scores [B, n, C] with ``grid=(hp, wp)``,
+    n == hp * wp, no larger than the guide.  Every ``ValueError`` is raised here, before any device use."""
+    if not isinstance(guide, torch.Tensor) or guide.dtype != torch.uint8 or guide.dim() != 4 or guide.shape[3] != 3:
+        raise ValueError(f"expected a uint8 guide [B,OH,OW,3], got {getattr(guide, 'dtype', type(guide).__name__)} "
+                         f"{tuple(getattr(guide, 'shape', ()))}")
+    B, OH, OW = (int(v) for v in guide.shape[:3])
+    if B < 1:
+        raise ValueError("empty batch")
+    if not (1 <= OH <= REFINE_MAX_SIDE and 1 <= OW <= REFINE_MAX_SIDE):
+        raise ValueError(f"the guide's size {(OH, OW)} must be in 1..{REFINE_MAX_SIDE} per side")
+    if not isinstance(seed, torch.Tensor):
+        raise ValueError(f"expected a seed tensor, got {type(seed).__name__}")
+    hp = wp = 0
+    if seed.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        kind = 0
+        if seed.dim() != 3 or tuple(seed.shape) != (B, OH, OW):
+            raise ValueError(f"expected seed labels [B={B}, {OH}, {OW}] (the guide's size), got {tuple(seed.shape)}")
+        if n_classes is None:
+            raise ValueError("a label seed needs n_classes")
+        if grid is not None:
+            raise ValueError("grid belongs to a scores seed; a label seed is at the guide's size")
+        C = n_classes
+    elif seed.dtype == torch.float32:
+        kind = 1
+        if seed.dim() != 3 or seed.shape[0] != B:
+            raise ValueError(f"expected seed scores [B={B}, n, C], got {tuple(seed.shape)}")
+        if grid is None:
+            raise ValueError("a scores seed needs grid=(hp, wp)")
+        hp, wp = _pair(grid, "grid")
+        if hp < 1 or wp < 1 or hp * wp != seed.shape[1]:
+            raise ValueError(f"grid {(hp, wp)} does not hold the seed's {seed.shape[1]} rows")
+        if OH < hp or OW < wp:
+            raise ValueError(f"the guide's size {(OH, OW)} is smaller than the grid {(hp, wp)}")
+        C = int(seed.shape[2])
+        if n_classes is not None and int(n_classes) != C:
+            raise ValueError(f"n_classes={n_classes} differs from the seed's {C} columns")
+    else:
+        raise ValueError(f"expected an integer label map [B,OH,OW] or fp32 scores [B,n,C], got {seed.dtype}")
+    if isinstance(C, bool) or not isinstance(C, (int, np.integer)) or not 1 <= int(C) <= 256:
+        raise ValueError(f"n_classes must be an integer in 1..256, got {C!r}")
+    gain, iters, dil, sigma = refine_params(gain, iters, dilations, sigma)
+    return kind, B, int(C), OH, OW, hp, wp, gain, iters, dil, sigma
+
+
 def multiscale_plan(patch: int, H: int, W: int, scales, flip: bool, size):
     """The views of ``segment_multiscale`` on H x W frames: ([(H_k, W_k, flip_k)] scale-major, the unflipped view first; their
     count K; the output's (OH, OW))."""

@@ -19,8 +19,8 @@ from torch import nn
 
 from . import capi
 from .dense_plan import (_pair, components_plan, context_frames, dense_mode, frame_layout, guide_plan, guided_params, kmeans_plan, label_size,
-                         maskcut_plan, multiscale_plan, ncut_plan, ncut_start, out_size, propagate_plan, resolution_message, sample_indices,
-                         view_sizes, window_origins, window_plan)  # noqa: F401  (view_sizes, window_origins: re-exported)
+                         maskcut_plan, multiscale_plan, ncut_plan, ncut_start, out_size, propagate_plan, refine_params, refine_plan,
+                         resolution_message, sample_indices, view_sizes, window_origins, window_plan)  # noqa: F401  (view_sizes, window_origins: re-exported)
 from .preprocess import resize_linear_u8
 from .weights import VIT_B8, VIT_B16, VIT_S8, VIT_S16, ViTConfig
 
@@ -634,6 +634,70 @@ class DINOSeg(nn.Module):
         nearest-neighbour enlargement.  ``want_logp=True`` also returns the averaged log-probabilities (fp32 [B,C,OH,OW]).  The
         defaults are a starting point: their effect on mIoU has not been measured on any dataset.  Inference only."""
         return self._guided(x, guide, size, guided_params(True, radius, sigma_spatial, sigma_range), want_logp)[:2]
+
+    # ---- image-guided iterative label refinement (PAMR passes at pixel resolution: csrc/refine.hip) ----
+    def _refine_buffers(self, B: int, nc: int, OH: int, OW: int, want_probs: bool):
+        """(scratch fp32 [2, B, C, OH, OW], labels int32 [B,OH,OW], probs fp32 [B,C,OH,OW] or None) on the model's device."""
+        nbytes = capi.lib().dinoseg_refine_scratch_bytes(B, nc, OH, OW)
+        if nbytes < 0:
+            raise capi.DinosegError(capi.last_error())
+        scratch = torch.empty((nbytes // 4,), dtype=torch.float32, device=self.device)
+        labels = torch.empty((B, OH, OW), dtype=torch.int32, device=self.device)
+        probs = torch.empty((B, nc, OH, OW), dtype=torch.float32, device=self.device) if want_probs else None
+        return scratch, labels, probs
+
+    @torch.no_grad()
+    def refine(self, seed: torch.Tensor, guide: torch.Tensor, n_classes: Optional[int] = None, grid=None, gain: float = 1.0,
+               iters: int = 10, dilations=(1, 2, 4, 8, 12, 24), sigma: float = 0.1, want_probs: bool = False):
+        """Image-guided iterative refinement (PAMR, Araslanov & Roth 2020) of a coarse result -> (labels int32 [B,OH,OW], probs
+        fp32 [B,C,OH,OW] or None).  ``seed`` is an integer label map [B,OH,OW] at the guide's size with ``n_classes`` (the labels
+        of ``segment*``, ``cluster``, ``ncut``, ``discover_all``, ``propagate``, or hand labels; a label outside [0, n_classes)
+        is void and takes what its neighbours give), or fp32 scores [B,n,C] on a patch grid ``grid=(hp, wp)`` (log-probs,
+        ``cluster``'s scores), enlarged bilinearly and turned into ``softmax(gain * v)``.  ``guide`` is a uint8 image [B,OH,OW,3].
+        Every pass averages the state over 8 taps per dilation with weights ``exp(-|colour difference| / (3 sigma std))``, std the
+        guide's local deviation per channel, so label boundaries move onto the image's edges (the rule: include/dinoseg.h,
+        dinoseg_op_refine_iterate).  A pixel no mass reached is labelled -1.  Uses no model weight.  The defaults are PAMR's; their
+        effect on mIoU has not been measured on any dataset."""
+        kind, B, nc, OH, OW, hp, wp, gain, iters, dil, sigma = refine_plan(seed, guide, n_classes, grid, gain, iters, dilations, sigma)
+        self._require_gpu()
+        guide = guide.to(self.device).contiguous()
+        seed = seed.to(self.device)
+        seed = (seed.to(torch.int32) if kind == 0 else seed).contiguous()
+        scratch, labels, probs = self._refine_buffers(B, nc, OH, OW, want_probs)
+        lib, s = capi.lib(), self._stream()
+        capi.check(lib.dinoseg_op_refine_seed(seed.data_ptr(), kind, B, nc, OH, OW, hp, wp, gain, scratch.data_ptr(), s))
+        capi.check(lib.dinoseg_op_refine_iterate(guide.data_ptr(), scratch.data_ptr(), B, nc, OH, OW, (C.c_int32 * len(dil))(*dil),
+                                                 len(dil), sigma, iters, labels.data_ptr(), capi.ptr(probs), s))
+        return labels, probs
+
+    @torch.no_grad()
+    def segment_refined(self, x: torch.Tensor, guide: Optional[torch.Tensor] = None, size=None, gain: float = 1.0, iters: int = 10,
+                        dilations=(1, 2, 4, 8, 12, 24), sigma: float = 0.1, want_probs: bool = False):
+        """``segment`` followed by ``refine`` in one library call: the forward, then the refinement seeded from its own
+        log-probs (``softmax(gain * bilinear enlargement)``) -> (labels int32 [B,OH,OW], probs fp32 [B,C,OH,OW] or None).  The guide
+        rules are ``segment_guided``'s: a uint8 ``guide`` [B,OH,OW,3] at the output's size, or none for uint8 frames, which then
+        guide themselves (resized when ``size`` is not their own); fp32 frames without a guide raise ``ValueError``.  Inference
+        only; the effect on mIoU has not been measured on any dataset."""
+        gain, iters, dil, sigma = refine_params(gain, iters, dilations, sigma)
+        kind, B, H, W, OH, OW = guide_plan(self.cfg.patch, x, guide, size)
+        if OH > (1 << 14) or OW > (1 << 14):
+            raise ValueError(f"size {(OH, OW)} exceeds the refinement's 16384 per side")
+        self._require_gpu()
+        x = self._to_device(x, kind)
+        if guide is not None:
+            guide = guide.to(self.device).contiguous()
+        elif (OH, OW) == (H, W):
+            guide = x
+        else:
+            guide = self._resize_view(x, kind, OH, OW)
+        self._sync_weights()
+        hp, wp = H // self.cfg.patch, W // self.cfg.patch
+        logp = torch.empty((B * hp * wp, self.cfg.n_classes), dtype=torch.float32, device=x.device)
+        scratch, labels, probs = self._refine_buffers(B, self.cfg.n_classes, OH, OW, want_probs)
+        capi.check(capi.lib().dinoseg_forward_refined_hw(self._handle, x.data_ptr(), kind, B, H, W, guide.data_ptr(), OH, OW, gain,
+                                                         (C.c_int32 * len(dil))(*dil), len(dil), sigma, iters, logp.data_ptr(),
+                                                         scratch.data_ptr(), labels.data_ptr(), capi.ptr(probs), self._stream()))
+        return labels, probs
 
     # ---- multi-scale + flip ensemble at pixel resolution (csrc/upsample_ensemble.hip) ----
     def _resize_view(self, x: torch.Tensor, kind: int, Hk: int, Wk: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -234,6 +234,63 @@ int dinoseg_forward_guided_hw(dinoseg_handle* h, const void* x, int32_t x_kind, 
                               int32_t OH, int32_t OW, int32_t radius, double sigma_spatial, double sigma_range, float* logp_out,
                               uint32_t* cells_scratch, int32_t* labels_out, float* dense_out, void* stream);
 
+/* ---- image-guided iterative label refinement at pixel resolution: PAMR (pixel-adaptive mask refinement, Araslanov & Roth, CVPR 2020).
+ * A state P [B, C, OH, OW] is averaged `iters` times over dilated neighbours whose weights fall with the guide's colour difference in
+ * units of the local standard deviation, so mass spreads inside a region and stops at the image's edges.  A pure gather in a fixed tap
+ * order: no atomics, nothing that grows as N^2, two runs agree bit for bit ----
+ *
+ *   guide     : uint8 [B, OH, OW, 3] at the state's size; 1 <= OH, OW <= 2^14
+ *   state P   : fp32 [B, C, OH, OW], 1 <= C <= 256, in half 0 of scratch [2][B, C, OH, OW] (dinoseg_refine_scratch_bytes)
+ *   dilations : host array d_1 < ... < d_M, 1 <= M <= 6, each in 1..24 (PAMR's: 1, 2, 4, 8, 12, 24)
+ *   sigma     : in [1e-3, 1e3] (PAMR's constant: 0.1);  iters in 0..64
+ * With S = 9 M, the constant k = log2(e) sqrt(S (S - 1)) / (3 sigma) is computed on the host in fp64 and rounded once to fp32; the rule
+ * is in terms of the rounded value.  All coordinates and colour differences are integers.
+ *
+ * 1. Taps.  Per dilation d the 8 offsets (dy, dx) in {-d, 0, d}^2 without (0, 0); order: dilation ascending, then dy ascending, then dx
+ *    ascending; T = 8 M taps.  A tap's coordinates are clamped to the frame (replicate border), so a tap may be the pixel itself.
+ * 2. Local deviation.  Per pixel and guide channel, over the S samples -- the 9 clamped positions of every dilation, the centre counting
+ *    M times -- the integer sums s1 = sum g, s2 = sum g^2 and Nv = S s2 - s1^2 (exact in int32, <= 1.9e8).  r = 0 when Nv == 0 (every
+ *    |difference| of that channel is then 0 too); otherwise r = k / sqrt(float(Nv)): the conversion, the square root and the quotient
+ *    each correctly rounded to fp32.  This is log2(e) / (3 sigma std) with the unbiased standard deviation of the samples.
+ * 3. Weights.  e_t = -(a_R r_R + a_G r_G + a_B r_B): a_R r_R rounded, then fmaf in channel order, a = the integer absolute difference
+ *    between the guide at the pixel and at the tap.  e_max = the maximum over taps; w_t = exp2(e_t - e_max), the difference rounded to
+ *    fp32, exp2 to one ulp.  The largest weight is exactly 1, so W = sum of w_t in tap order >= 1.
+ * 4. Pass.  acc_k = sum over taps of fmaf(w_t, P_k(q_t), acc) from 0 in tap order;  P'_k = acc_k (1 / W), the reciprocal correctly
+ *    rounded, once per pixel.
+ * 5. Result.  After the last pass labels = the FIRST maximum of P_k over k; if that maximum is not > 0 the label is -1 (no mass
+ *    reached the pixel).  iters = 0 labels the seed.
+ * Consequences: a constant guide gives all weights exactly 1 and a pass is plain fp32 additions in tap order times the rounded 1 / T;
+ * iters = n in one call equals n calls with iters = 1, each from the state the one before returned, bit for bit; the labels-only call
+ * writes the labels of the call that also returns the state.
+ *
+ * dinoseg_op_refine_seed: one launch that writes half 0 of scratch.
+ *   kind 0: seed = int32 labels [B, OH, OW]; the one-hot state of C classes.  A label outside [0, C) (255, -100) gives an all-zero
+ *           pixel, which takes what its neighbours give.  hp, wp and gain are ignored.
+ *   kind 1: seed = fp32 scores [B, hp*wp, C], OH >= hp, OW >= wp: the bilinear enlargement v of dinoseg_op_upsample_argmax (its dense
+ *           values bit for bit), then per pixel g_k = gain v_k (rounded), m = max g_k, x_k = exp(g_k - m) by v_exp_f32 of (g_k - m)
+ *           log2(e), s = sum of x_k in class order, P_k = x_k (1 / s) with the reciprocal correctly rounded.  gain > 0 and finite; 1
+ *           makes the head's log-probs seed their own probabilities.
+ * dinoseg_op_refine_iterate: `iters` passes from half 0, one launch each, ping-pong between the halves; the last pass writes labels_out
+ *   int32 [B, OH, OW] and, when given, the final state dense_out fp32 [B, C, OH, OW] (at least one is required; dense_out must not
+ *   alias scratch).  Afterwards the scratch's contents are unspecified; half 0 is read, so seed again (or copy a state into half 0)
+ *   before the next call.
+ * Refused on the host (-1, a message naming the entry) before anything is launched: null pointers; kind outside {0, 1}; B < 1; C, n_dil,
+ * a dilation, sigma, gain, iters or sizes out of range; dilations not strictly ascending; every shape dinoseg_op_upsample_argmax
+ * refuses (kind 1); a tile footprint (64 + 2 d_M) x (32 + 2 d_M), clamped to the frame, of which two planes do not fit the LDS (no
+ * accepted dilation reaches that).  Stream-ordered, no host synchronisation, no allocation. */
+int64_t dinoseg_refine_scratch_bytes(int32_t B, int32_t C, int32_t OH, int32_t OW);
+int dinoseg_op_refine_seed(const void* seed, int32_t kind, int32_t B, int32_t C, int32_t OH, int32_t OW, int32_t hp, int32_t wp, double gain,
+                           void* scratch, void* stream);
+int dinoseg_op_refine_iterate(const uint8_t* guide, void* scratch, int32_t B, int32_t C, int32_t OH, int32_t OW, const int32_t* dilations,
+                              int32_t n_dil, double sigma, int32_t iters, int32_t* labels_out, float* dense_out, void* stream);
+/* dinoseg_forward_hw into the caller's logp_out [B*n, n_classes] (required), then dinoseg_op_refine_seed (kind 1, gain) from it into
+ * scratch and dinoseg_op_refine_iterate for the whole batch on the caller's stream (under the two-stream split: behind the join).  For
+ * uint8 frames with OH x OW == H x W, guide may alias x.  Everything the launches would refuse is refused before the forward enqueues
+ * anything.  Stream-ordered, capturable, no host synchronisation, no allocation. */
+int dinoseg_forward_refined_hw(dinoseg_handle* h, const void* x, int32_t x_kind, int32_t B, int32_t H, int32_t W, const uint8_t* guide,
+                               int32_t OH, int32_t OW, double gain, const int32_t* dilations, int32_t n_dil, double sigma, int32_t iters,
+                               float* logp_out, void* scratch, int32_t* labels_out, float* dense_out, void* stream);
+
 /* ---- pixel-resolution training loss (what ViT segmenters train on: F.cross_entropy(F.interpolate(scores, size=mask.shape,
  * mode="bilinear", align_corners=False), mask, ignore_index=255)), without the [B, C, OH, OW] transient ----
  *
