@@ -2,7 +2,7 @@
 import contextlib
 
 from .augment import Augmenter, augment_table, draw_reference_augment  # noqa: F401
-from .dinoseg import ClusterResult, ComponentsResult, DINOSeg, DiscoverResult, LabelPropagator, MaskCutResult, NcutResult, context_frames, dense_nll_loss, get_transforms, ncut_start, sample_indices, view_sizes, window_origins  # noqa: F401
+from .dinoseg import ClusterResult, ComponentsResult, DINOSeg, DiscoverResult, KnnResult, LabelPropagator, MaskCutResult, MemoryBank, NcutResult, context_frames, dense_nll_loss, get_transforms, ncut_start, sample_indices, view_sizes, window_origins  # noqa: F401
 from .weights import VIT_B8, VIT_B16, VIT_S8, VIT_S16, ViTConfig, procedural_state_dict  # noqa: F401
 
 

@@ -181,6 +181,12 @@ SIGNATURES = {
     "dinoseg_op_label_cells": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _vp]),
     "dinoseg_propagate_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "dinoseg_op_propagate": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _fp, _fp, _fp, _vp, _vp]),
+    # k-NN label retrieval from a memory bank of labelled patch features: the scratch size and the library's number of bank ranges
+    # (host only), one call = the scores launch over (query tiles, ranges) and the merge launch
+    "dinoseg_knn_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "dinoseg_knn_splits": (_i32, [_i32, _i32, _i32]),
+    "dinoseg_op_knn_labels": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _f64, _i32, _fp, _fp, _fp, _vp,
+                                        _vp]),
     # spherical k-means over patch features: the scratch size (host only), centroid rows -> unit rows + planes, one assignment pass
     # (scores on request, objective and moved slots), one centroid update
     "dinoseg_kmeans_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),

@@ -676,6 +676,17 @@ extern "C" int dinoseg_op_propagate(const void* target_planes, const void* const
                             reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int64_t dinoseg_knn_scratch_bytes(int32_t N, int32_t M, int32_t k, int32_t splits) { return knn_scratch_bytes(N, M, k, splits); }
+
+extern "C" int32_t dinoseg_knn_splits(int32_t N, int32_t M, int32_t k) { return knn_splits(N, M, k); }
+
+extern "C" int dinoseg_op_knn_labels(const void* query_planes, int32_t B, int32_t n, const void* bank_planes, int64_t M, int64_t bank_rows,
+                                     const void* bank_labels, int32_t label_kind, int32_t D, int32_t C, int32_t k, double tau,
+                                     int32_t splits, float* seg_out, int32_t* topk_idx, float* topk_w, void* scratch, void* stream) {
+    return launch_knn_labels(query_planes, B, n, bank_planes, M, bank_rows, bank_labels, label_kind, D, C, k, tau, splits, seg_out,
+                             topk_idx, topk_w, scratch, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int64_t dinoseg_kmeans_scratch_bytes(int32_t B, int32_t n, int32_t K, int32_t D) { return kmeans_scratch_bytes(B, n, K, D); }
 
 extern "C" int dinoseg_op_kmeans_init(const float* rows, int32_t K, int32_t D, int32_t normalize, float* centroids, void* planes,

@@ -402,6 +402,18 @@ int launch_propagate(const void* target_planes, const void* const* ctx_planes, c
                      int D, int C, int radius, int k, double tau, float* seg_out, int32_t* topk_idx, float* topk_w, void* scratch,
                      hipStream_t s);
 
+// Few-shot segmentation: k-NN label retrieval from a flat bank of labelled patch features (knn.hip; the rule: include/dinoseg.h,
+// dinoseg_op_knn_labels).  Queries are the planes of launch_normalize_tokens for B frames of n cells; the bank is planes
+// [2][bank_rows][D] with M live rows and soft fp32 [bank_rows, C] (kind 0) or hard uint8 [bank_rows] (kind 1) labels.
+// launch_knn_labels: the scores launch (one workgroup per 64 queries and bank range, per-query lists of k in LDS) and the merge launch
+// (the ranges' lists, weights, gathers).  knn_splits: the library's number of ranges; knn_scratch_bytes: 8 S N k (splits 0 = the
+// library's choice); both host only, -1 for refusable arguments.  No atomics; every refusal is on the host.
+int knn_splits(int N, int M, int k);
+long long knn_scratch_bytes(int N, int M, int k, int splits);
+int launch_knn_labels(const void* query_planes, int B, int n, const void* bank_planes, long long M, long long bank_rows,
+                      const void* bank_labels, int label_kind, int D, int C, int k, double tau, int splits, float* seg_out,
+                      int32_t* topk_idx, float* topk_w, void* scratch, hipStream_t s);
+
 // Spherical k-means over patch features (kmeans.hip; the rule: include/dinoseg.h, dinoseg_op_kmeans_assign).  Points are the planes of
 // launch_normalize_tokens for B frames of n cells, clustered jointly; centroids are fp32 [K, D] rows plus planes [2][K][D].
 // launch_kmeans_init: fp32 rows -> (unit) fp32 rows and their planes.  launch_kmeans_assign: the assign launch (scores on MFMAs, the

@@ -1,5 +1,5 @@
-// The split-plane pair walk of the feature-space operators, shared by propagate.hip (propagate_scores_kernel), kmeans.hip
-// (kmeans_assign_kernel) and ncut.hip (ncut_graph_kernel), and the small pieces of the unit-row planes they all read: ONE copy of
+// The split-plane pair walk of the feature-space operators, shared by propagate.hip (propagate_scores_kernel), knn.hip
+// (knn_scores_kernel), kmeans.hip (kmeans_assign_kernel) and ncut.hip (ncut_graph_kernel), and the small pieces of the unit-row planes they all read: ONE copy of
 // the staging, the slice order and the fragment reads, so all of them form <x_q, x_k> by the same arithmetic bit for bit.
 //
 // The family's geometry: one workgroup of 4 waves owns 64 query rows and walks key rows in blocks of 64.  Rows are unit rows scaled
@@ -22,6 +22,17 @@ constexpr float PAIR_UNSCALE = 0x1p-20f;        // planes carry 2^10 x: products
 
 // the total order of the selections: score descending, index ascending
 __device__ __forceinline__ bool better(float s, int i, float s2, int i2) { return s > s2 || (s == s2 && i < i2); }
+
+// (score, g) as one unsigned key whose order is the total order: larger = earlier.  0 = no candidate.
+__device__ __forceinline__ unsigned long long prp_key(float s, int g) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, s);
+    const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)o << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)g);
+}
+__device__ __forceinline__ float prp_key_score(unsigned long long key) {
+    const uint32_t o = (uint32_t)(key >> 32);
+    return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
 
 // v = hi + lo in fp16 (v: a unit row's component scaled by 2^10, so that lo stays clear of the fp16 subnormals)
 struct UnitSplit {

@@ -200,17 +200,6 @@ __global__ __launch_bounds__(256) void propagate_scores_kernel(const uint16_t* _
     }
 }
 
-// (score, g) as one unsigned key whose order is the total order: larger = earlier.  0 = no candidate.
-__device__ __forceinline__ unsigned long long prp_key(float s, int g) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, s);
-    const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)o << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)g);
-}
-__device__ __forceinline__ float prp_key_score(unsigned long long key) {
-    const uint32_t o = (uint32_t)(key >> 32);
-    return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
-
 __global__ __launch_bounds__(256) void propagate_merge_kernel(const float* __restrict__ cand_s, const int* __restrict__ cand_g, PrpCtx ctx,
                                                               int n, int n_ctx, int k, int C, float a, float* __restrict__ seg_out,
                                                               int32_t* __restrict__ topk_idx, float* __restrict__ topk_w) {

@@ -386,6 +386,104 @@ def propagate_plan(patch: int, frames: torch.Tensor, first, n_classes=None, n_co
     return PropagatePlan(kind, int(T), int(H), int(W), hp, wp, C, seed, n_context, radius, topk, temperature, OH, OW, chunk)
 
 
+# ---- few-shot segmentation: k-NN label retrieval from a memory bank (include/dinoseg.h: dinoseg_op_knn_labels) ----
+KNN_MAX_K = 16
+KNN_MAX_ROWS = 1 << 24
+
+
+class KnnPlan(NamedTuple):
+    """What a ``segment_knn`` call was asked for, validated: the frames' layout, the patch grid, the bank's live rows and classes,
+    the rule's parameters and the output size."""
+    kind: int
+    B: int
+    H: int
+    W: int
+    hp: int
+    wp: int
+    M: int
+    C: int
+    topk: int
+    temperature: float
+    OH: int
+    OW: int
+    chunk: int
+    n_blocks: int
+
+
+def _temperature(temperature) -> float:
+    try:
+        temperature = float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError(f"temperature must be a positive number, got {temperature!r}") from None
+    if not (math.isfinite(temperature) and temperature > 0.0):
+        raise ValueError(f"temperature must be finite and positive, got {temperature}")
+    return temperature
+
+
+def knn_plan(patch: int, embed_dim: int, x: torch.Tensor, bank_size: int, bank_dim: int, bank_classes: int, bank_blocks: int,
+             n_blocks=None, topk=10, temperature=0.1, size=None, chunk=32) -> KnnPlan:
+    """The shape and parameter checks of ``DINOSeg.segment_knn`` without a device.  ``x`` is the batch (uint8 [B,H,W,3] or fp32
+    [B,3,H,W], H and W multiples of the patch size); ``bank_size``, ``bank_dim``, ``bank_classes`` and ``bank_blocks`` are the
+    bank's live rows, row width, classes and the ``n_blocks`` its features were taken after; ``n_blocks=None`` is the bank's.
+    Every ``ValueError`` is raised here, before any device use."""
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"expected the frames as a tensor, uint8 [B,H,W,3] or fp32 [B,3,H,W], got {type(x).__name__}")
+    kind, B, H, W = frame_layout(x, patch, multiple=True, one_patch=True, non_empty=True)
+    hp, wp = H // patch, W // patch
+    topk = _int_in(topk, 1, KNN_MAX_K, "topk")
+    chunk = _int_in(chunk, 1, 1 << 20, "chunk")
+    temperature = _temperature(temperature)
+    if int(bank_size) < 1:
+        raise ValueError("the memory bank is empty: add labelled frames first")
+    if int(bank_dim) != int(embed_dim):
+        raise ValueError(f"the memory bank holds rows of width {bank_dim}, the model's embed_dim is {embed_dim}")
+    if n_blocks is not None and int(n_blocks) != int(bank_blocks):
+        raise ValueError(f"the memory bank was filled with n_blocks = {bank_blocks}, the call asks for n_blocks = {n_blocks}")
+    try:
+        OH, OW = out_size(size, (H, W))
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be a pair (OH, OW), got {size!r}") from None
+    if OH < hp or OW < wp:
+        raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(hp, wp)}")
+    return KnnPlan(kind, int(B), int(H), int(W), hp, wp, int(bank_size), int(bank_classes), topk, temperature, OH, OW, chunk,
+                   int(bank_blocks))
+
+
+class BankAddPlan(NamedTuple):
+    """What a ``MemoryBank.add`` call was asked for, validated: the frames' layout, the patch grid, the labels' size and kind
+    (0 = uint8, 1 = int64, as ``dinoseg_op_label_cells``), the cells kept per frame and the rows the call adds."""
+    kind: int
+    B: int
+    hp: int
+    wp: int
+    OH: int
+    OW: int
+    mask_kind: int
+    per_frame: int
+    rows: int
+    seed: int
+
+
+def bank_add_plan(patch: int, frames: torch.Tensor, labels: torch.Tensor, per_frame=None, seed=0, room: int = KNN_MAX_ROWS) -> BankAddPlan:
+    """The checks of ``MemoryBank.add`` without a device: ``frames`` as in ``knn_plan``, ``labels`` integer [B, OH, OW] at least as
+    large as the patch grid, ``per_frame`` the cells kept per frame (``None``: all), ``room`` the rows the bank can still take."""
+    if not isinstance(frames, torch.Tensor):
+        raise ValueError(f"expected the frames as a tensor, uint8 [B,H,W,3] or fp32 [B,3,H,W], got {type(frames).__name__}")
+    kind, B, H, W = frame_layout(frames, patch, multiple=True, one_patch=True, non_empty=True)
+    hp, wp = H // patch, W // patch
+    if not isinstance(labels, torch.Tensor) or labels.is_floating_point() or labels.dtype == torch.bool:
+        raise ValueError(f"labels must be integer pixel labels [B, OH, OW], got {getattr(labels, 'dtype', type(labels).__name__)}")
+    OH, OW = label_size(labels, B)
+    if OH < hp or OW < wp:
+        raise ValueError(f"pixel labels of {(OH, OW)} are smaller than the patch grid {(hp, wp)}")
+    per_frame = hp * wp if per_frame is None else _int_in(per_frame, 1, hp * wp, "per_frame")
+    seed = _int_in(seed, -(1 << 62), 1 << 62, "seed")
+    rows = int(B) * per_frame
+    if rows > room:
+        raise ValueError(f"the call adds {rows} rows, the memory bank has room for {room}")
+    return BankAddPlan(kind, int(B), hp, wp, OH, OW, 0 if labels.dtype == torch.uint8 else 1, per_frame, rows, seed)
+
+
 # ---- unsupervised segmentation: spherical k-means over patch features (include/dinoseg.h: dinoseg_op_kmeans_assign) ----
 KMEANS_MAX_K = 256             # the class limit of dinoseg_op_upsample_argmax
 

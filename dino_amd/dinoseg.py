@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import capi
-from .dense_plan import (_pair, components_plan, context_frames, dense_mode, frame_layout, guide_plan, guided_params, kmeans_plan, label_size,
+from .dense_plan import (_pair, bank_add_plan, components_plan, context_frames, dense_mode, frame_layout, guide_plan, guided_params, kmeans_plan, knn_plan, label_size,
                          maskcut_plan, multiscale_plan, ncut_plan, ncut_start, out_size, propagate_plan, refine_params, refine_plan,
                          resolution_message, sample_indices, view_sizes, window_origins, window_plan)  # noqa: F401  (view_sizes, window_origins: re-exported)
 from .preprocess import resize_linear_u8
@@ -847,6 +847,50 @@ class DINOSeg(nn.Module):
                 if want_seg:
                     seg[t].copy_(seg_t)
         return labels, seg
+
+    # ---- few-shot segmentation: k-NN label retrieval from a memory bank (csrc/knn.hip) ----
+    @torch.no_grad()
+    def segment_knn(self, x: torch.Tensor, bank: "MemoryBank", topk: int = 10, temperature: float = 0.1, size=None, chunk: int = 32,
+                    want_seg: bool = False, want_idx: bool = False, n_blocks: Optional[int] = None) -> "KnnResult":
+        """Few-shot segmentation by nearest neighbours in a ``MemoryBank`` of labelled patch features (the k-NN evaluation of the
+        DINO paper made dense; the in-context protocol of Hummingbird): ``x`` uint8 [B,H,W,3] or fp32 [B,3,H,W], H and W multiples
+        of the patch size -> ``KnnResult(labels int32 [B,OH,OW], seg fp32 [B,n,C] or None, idx int32 [B,n,k] or None)``.  Every
+        cell takes the ``topk`` most similar live rows of the bank (cosine of the final-norm patch tokens after the bank's
+        ``n_blocks`` blocks; the lower row on an exact tie) and averages their labels with weights ``exp((s - s_max) /
+        temperature)`` (the rule: include/dinoseg.h, dinoseg_op_knn_labels); the bilinear enlargement of that soft map to ``size``
+        (default the frames' own) with the first maximum gives ``labels``.  The [B n, M] score matrix is never formed.  The
+        backbone runs in batches of ``chunk`` frames, each followed by one operator call and one enlargement; ``B = 1`` is the
+        camera's streaming form.  ``n_blocks``, when given, must be the bank's.  No training and no head weight: a row added to
+        the bank takes effect in the next call.  Inference only."""
+        if not isinstance(bank, MemoryBank):
+            raise ValueError(f"bank must be a MemoryBank, got {type(bank).__name__}")
+        plan = knn_plan(self.cfg.patch, self.cfg.embed_dim, x, bank.size, bank.dim, bank.n_classes, bank.n_blocks, n_blocks, topk,
+                        temperature, size, chunk)
+        self._require_gpu()
+        x = self._to_device(x, plan.kind)
+        lib, n, D, k = capi.lib(), plan.hp * plan.wp, self.cfg.embed_dim, plan.topk
+        labels = torch.empty((plan.B, plan.OH, plan.OW), dtype=torch.int32, device=self.device)
+        seg = torch.empty((plan.B if want_seg else min(plan.chunk, plan.B), n, plan.C), dtype=torch.float32, device=self.device)
+        idx = torch.empty((plan.B, n, k), dtype=torch.int32, device=self.device) if want_idx else None
+        planes = torch.empty((min(plan.chunk, plan.B), 2, n, D), dtype=torch.float16, device=self.device)
+        scratch = None
+        for c0 in range(0, plan.B, plan.chunk):
+            tokens = self.features(x[c0:c0 + plan.chunk], plan.n_blocks)
+            Bc = tokens.shape[0]
+            nbytes = lib.dinoseg_knn_scratch_bytes(Bc * n, plan.M, k, 0)
+            if nbytes < 0:
+                raise capi.DinosegError(f"dinoseg_knn_scratch_bytes refused N = {Bc * n}, M = {plan.M}, k = {k}")
+            if scratch is None or scratch.numel() < nbytes:
+                scratch = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+            seg_c = seg[c0:c0 + Bc] if want_seg else seg[:Bc]
+            capi.check(lib.dinoseg_op_normalize_tokens(tokens.data_ptr(), Bc, n, D, planes.data_ptr(), self._stream()))
+            capi.check(lib.dinoseg_op_knn_labels(planes.data_ptr(), Bc, n, bank.planes.data_ptr(), plan.M, bank.capacity,
+                                                 bank.labels.data_ptr(), 1 if bank.hard else 0, D, plan.C, k, plan.temperature, 0,
+                                                 seg_c.data_ptr(), capi.ptr(idx[c0:] if want_idx else None), None, scratch.data_ptr(),
+                                                 self._stream()))
+            capi.check(lib.dinoseg_op_upsample_argmax(seg_c.data_ptr(), Bc, plan.hp, plan.wp, plan.C, plan.OH, plan.OW,
+                                                      labels[c0:].data_ptr(), None, self._stream()))
+        return KnnResult(labels, seg if want_seg else None, idx)
 
     # ---- unsupervised segmentation: spherical k-means over patch features (csrc/kmeans.hip) ----
     def _point_planes(self, x: torch.Tensor, plan, n_blocks: int) -> torch.Tensor:
@@ -1895,6 +1939,97 @@ class LabelPropagator:
         labels = torch.empty((p.OH, p.OW), dtype=torch.int32, device=self.model.device)
         seg = self._runner.step(self.model.features(self.model._to_device(x, kind), self.n_blocks), labels)
         return labels, (seg.clone() if self.want_seg else None)
+
+
+# --------------------------------------------------------------------------- few-shot segmentation (k-NN from a memory bank)
+class KnnResult(NamedTuple):
+    """What ``DINOSeg.segment_knn`` returns: pixel labels int32 [B, OH, OW], and when asked for the soft map fp32 [B, n, C] and the
+    selected bank rows int32 [B, n, k] in rank order (-1 beyond min(k, bank.size))."""
+    labels: torch.Tensor
+    seg: Optional[torch.Tensor]
+    idx: Optional[torch.Tensor]
+
+
+class MemoryBank:
+    """A flat bank of labelled patch features for ``DINOSeg.segment_knn``: ``MemoryBank(model, n_classes, capacity, hard=False,
+    n_blocks=0)`` allocates, once, the unit rows as fp16 hi + lo planes [2, capacity, D] and the label store (soft fp32 [capacity,
+    n_classes], or with ``hard=True`` one uint8 per row, 255 = void, hence at most 255 classes); rows 0 .. ``size`` - 1 are live.
+    ``add`` fills it in place, ``clear`` empties it, ``state_dict`` / ``load_state_dict`` carry it bit for bit (with ``frames``, the
+    number of frames added, which ``per_frame`` seeds count from).  Rows are never evicted or replaced."""
+
+    def __init__(self, model: DINOSeg, n_classes: int, capacity: int, hard: bool = False, n_blocks: int = 0):
+        for what, v, hi in (("n_classes", n_classes, 256), ("capacity", capacity, 1 << 24)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= hi:
+                raise ValueError(f"{what} must be an integer in 1..{hi}, got {v!r}")
+        if isinstance(n_blocks, bool) or not isinstance(n_blocks, (int, np.integer)) or not 0 <= n_blocks <= model.cfg.n_blocks:
+            raise ValueError(f"n_blocks must be an integer in 0..{model.cfg.n_blocks}, got {n_blocks!r}")
+        if hard and int(n_classes) > 255:
+            raise ValueError("a hard bank stores void as 255, so it holds at most 255 classes; use soft labels for 256")
+        model._require_gpu()
+        self.model, self.n_classes, self.capacity, self.hard, self.n_blocks = model, int(n_classes), int(capacity), bool(hard), int(n_blocks)
+        self.dim = model.cfg.embed_dim
+        self.planes = torch.zeros((2, self.capacity, self.dim), dtype=torch.float16, device=model.device)
+        self.labels = torch.full((self.capacity,), 255, dtype=torch.uint8, device=model.device) if self.hard else \
+            torch.zeros((self.capacity, self.n_classes), dtype=torch.float32, device=model.device)
+        self.size = 0
+        self.frames = 0                             # frames added so far: frame i of the bank draws its cells from seed + i
+
+    def clear(self) -> None:
+        self.size = 0
+        self.frames = 0
+
+    @torch.no_grad()
+    def add(self, frames: torch.Tensor, labels: torch.Tensor, per_frame: Optional[int] = None, seed: int = 0) -> int:
+        """Add labelled frames: ``frames`` uint8 [B,H,W,3] or fp32 [B,3,H,W] (any H x W of patch multiples; frames of different
+        shapes go in separate calls), ``labels`` integer [B,OH,OW] at least as large as the patch grid (a label outside [0,
+        n_classes) such as 255 or -100 is void) -> the number of rows added.  A cell's row is its unit patch feature
+        (``features`` after the bank's ``n_blocks``, ``dinoseg_op_normalize_tokens``) and its label the class shares of its pixels
+        (``dinoseg_op_label_cells``); a hard bank keeps the first maximum of the shares, 255 where all are zero.  ``per_frame=m``
+        keeps m cells per frame, those of ``sample_indices(n, m, seed + i)`` for the i-th frame the bank has seen, in that order.
+        A call that would overflow ``capacity`` raises ``ValueError`` and adds nothing."""
+        model = self.model
+        p = bank_add_plan(model.cfg.patch, frames, labels, per_frame, seed, self.capacity - self.size)
+        x = model._to_device(frames, p.kind)
+        y = labels.to(device=model.device, dtype=torch.uint8 if p.mask_kind == 0 else torch.int64).contiguous()
+        lib, n, D, C_ = capi.lib(), p.hp * p.wp, self.dim, self.n_classes
+        planes = torch.empty((2, n, D), dtype=torch.float16, device=model.device)
+        seg = torch.empty((n, C_), dtype=torch.float32, device=model.device)
+        classes = torch.arange(C_, device=model.device)
+        for c0 in range(0, p.B, 32):
+            tokens = model.features(x[c0:c0 + 32], self.n_blocks)
+            for i in range(tokens.shape[0]):
+                b = c0 + i
+                capi.check(lib.dinoseg_op_normalize_tokens(tokens[i].data_ptr(), 1, n, D, planes.data_ptr(), model._stream()))
+                capi.check(lib.dinoseg_op_label_cells(y[b].data_ptr(), p.mask_kind, p.OH, p.OW, p.hp, p.wp, C_, seg.data_ptr(),
+                                                      model._stream()))
+                keep = slice(None) if p.per_frame == n else sample_indices(n, p.per_frame, p.seed + self.frames).to(model.device)
+                at = slice(self.size, self.size + p.per_frame)
+                self.planes[:, at] = planes[:, keep]
+                rows = seg[keep]
+                if self.hard:
+                    top = rows.max(dim=1, keepdim=True).values
+                    first = torch.where(rows == top, classes, C_).min(dim=1).values        # the first maximum
+                    self.labels[at] = torch.where(top[:, 0] > 0, first, 255).to(torch.uint8)
+                else:
+                    self.labels[at] = rows
+                self.size += p.per_frame
+                self.frames += 1
+        return p.rows
+
+    def state_dict(self) -> dict:
+        return {"planes": self.planes.clone(), "labels": self.labels.clone(), "size": self.size, "frames": self.frames,
+                "n_classes": self.n_classes, "hard": self.hard, "n_blocks": self.n_blocks}
+
+    def load_state_dict(self, state: dict) -> None:
+        planes, labels = state["planes"], state["labels"]
+        same = (int(state["n_classes"]), bool(state["hard"]), int(state["n_blocks"])) == (self.n_classes, self.hard, self.n_blocks)
+        if not same or tuple(planes.shape) != tuple(self.planes.shape) or planes.dtype != self.planes.dtype or \
+                tuple(labels.shape) != tuple(self.labels.shape) or labels.dtype != self.labels.dtype or \
+                not 0 <= int(state["size"]) <= self.capacity:
+            raise ValueError("the state is not that of a bank with this one's capacity, width, n_classes, hard and n_blocks")
+        self.planes.copy_(planes)
+        self.labels.copy_(labels)
+        self.size, self.frames = int(state["size"]), int(state.get("frames", 0))
 
 
 # --------------------------------------------------------------------------- unsupervised segmentation (spherical k-means)

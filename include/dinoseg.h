@@ -490,6 +490,52 @@ int dinoseg_op_propagate(const void* target_planes, const void* const* ctx_plane
                          int32_t hp, int32_t wp, int32_t D, int32_t C, int32_t radius, int32_t k, double tau, float* seg_out,
                          int32_t* topk_idx, float* topk_w, void* scratch, void* stream);
 
+/* ---- few-shot segmentation: k-NN label retrieval from a memory bank of labelled patch features (the k-NN evaluation of the DINO paper
+ * made dense; the in-context scene understanding protocol of Hummingbird), without the [N, M] score matrix.  No reference counterpart:
+ * the reference trains its head.  knn.hip.  The definitions are those of the propagation section above; only what differs is stated.
+ *
+ * Notation: B query frames of n cells, N = B n queries, query i = frame i / n, cell i % n; a bank of bank_rows rows of which the first
+ * M are live (1 <= M <= bank_rows <= 2^24), so that a bank is filled in place up to its capacity; D the embedding width (a multiple
+ * of 64 in 64 .. 8192); C classes, 1 .. 256; k in 1 .. 16; tau > 0; E = (D + 16) 2^-24.
+ *
+ * 1. Rows.  Query planes [B][2][n][D] as dinoseg_op_normalize_tokens writes them.  Bank planes [2][bank_rows][D]: the same format with
+ *    one "frame" of bank_rows rows, the lo plane bank_rows D elements after the hi plane.  Rows M .. bank_rows - 1 (planes and labels)
+ *    are never read.
+ * 2. Labels.  label_kind 0: soft fp32 [bank_rows, C].  label_kind 1: hard uint8 [bank_rows]; a value >= C is void: a void row is a
+ *    neighbour like any other (it is selected, its weight counts in W) and adds to no class, the convention of dinoseg_op_label_cells.
+ * 3. Candidates.  Every live row g in 0 .. M-1 is a candidate of every query: no neighbourhood test.  The score is step 2 of the
+ *    propagation rule exactly (lo.hi + hi.lo + hi.hi in one fp32 chain on v_mfma_f32_32x32x16_f16, D in ascending slices of 64, -0
+ *    taken as +0, a function of the two rows alone, |s - the fp64 value| <= E).
+ * 4. Selection.  The first K' = min(k, M) candidates in the total order (score descending, then g ascending).
+ * 5. Weights and value.  Steps 4 and 5 of the propagation rule: w_i = exp2((s_i - s_0) a), a = log2(e) / tau rounded once on the host,
+ *    W = sum w_i in rank order, V[c] = (sum_i w_i labels[g_i, c]) (1 / W) by fmaf in rank order from 0.  Hard labels:
+ *    V[c] = (the sum of the w_i with label_i == c, in rank order) (1 / W).  seg_out[i, :] = V, fp32 [N, C].
+ * 6. Pixel labels: dinoseg_op_upsample_argmax applied to seg_out, unchanged.
+ *
+ * dinoseg_op_knn_labels: steps 3 - 5 in two launches.  Scores: the grid is (ceil(N / 64), S); a workgroup takes 64 consecutive queries
+ * and one of S contiguous bank ranges, walks it in key blocks of 64 and keeps each query's list of k (score, g) in LDS; its merged
+ * list goes to the scratch [S][N][k].  With nblk = ceil(M / 64) key blocks, range s is the blocks floor(s nblk / S) ..
+ * floor((s + 1) nblk / S) - 1, i.e. rows 64 floor(s nblk / S) .. min(64 floor((s + 1) nblk / S), M) - 1: whole blocks, never empty,
+ * the last one clipped at M.  Merge: one wave per query merges the S lists under the total order (S k <= 256 keys), forms the weights
+ * and does the k gathers (soft rows) or k compares per class (hard labels).  No atomics, no synchronisation between workgroups,
+ * nothing of size N M is written; two runs agree bit for bit.
+ * splits: 0 = the library's choice, dinoseg_knn_splits(N, M, k) = min(cap, max(1, min(ceil(512 / ceil(N / 64)), nblk / 4))) with
+ * cap = min(16, 256 / k, nblk): two workgroups for each of the 256 compute units where the query tiles alone give fewer, and ranges of
+ * at least 4 key blocks.  Any S in 1 .. cap is accepted.  The order is total, so the outputs are bit-identical for every S.
+ * scratch: dinoseg_knn_scratch_bytes(N, M, k, splits) bytes of device memory (8 S N k, S resolved as above; host only, -1 for
+ * refusable arguments; dinoseg_knn_splits likewise).  Optional outputs: topk_idx int32 [N, k] (g in rank order, -1 beyond K') and
+ * topk_w fp32 [N, k] (w_i / W, 0 beyond K').
+ * Refused on the host (-1, the message names the entry) before anything is launched: null pointers (the two optional outputs apart);
+ * C outside 1 .. 256; k outside 1 .. 16; splits outside 0 .. cap; a label_kind other than 0 / 1; D not a multiple of 64 or above
+ * 8192; M or bank_rows outside 1 <= M <= bank_rows <= 2^24; non-positive B or n, n above 2^24, B n above 2^31 - 256; tau not finite
+ * or not positive; planes not 16-byte aligned.  Stream-ordered, no host synchronisation, no allocation. */
+#define DINOSEG_KNN_MAX_K 16
+int64_t dinoseg_knn_scratch_bytes(int32_t N, int32_t M, int32_t k, int32_t splits);
+int32_t dinoseg_knn_splits(int32_t N, int32_t M, int32_t k);
+int dinoseg_op_knn_labels(const void* query_planes, int32_t B, int32_t n, const void* bank_planes, int64_t M, int64_t bank_rows,
+                          const void* bank_labels, int32_t label_kind, int32_t D, int32_t C, int32_t k, double tau, int32_t splits,
+                          float* seg_out, int32_t* topk_idx, float* topk_w, void* scratch, void* stream);
+
 /* ---- unsupervised segmentation: spherical k-means over patch features (the k-means baseline of STEGO and of "Deep ViT Features as
  * Dense Visual Descriptors": cluster the patch tokens of a batch or clip, get segments whose ids mean the same in every frame).  No
  * reference counterpart: the reference trains on hand-labelled frames.  kmeans.hip.
