@@ -395,6 +395,8 @@ int launch_augment(const uint8_t* frames, const void* masks, int mask_kind, int 
 // launch_propagate: one target frame from n_ctx <= 16 context frames (host arrays of device pointers, by value to the kernels): the
 // scores launch (one workgroup per query tile and context frame, per-query lists of k in LDS) and the merge launch (weights, gathers).
 // scratch: propagate_scratch_bytes (8 n_ctx n k; -1 for refusable arguments).  No atomics; every refusal is on the host.
+// The top-k selection of both launches -- lists, total order, 4-way merge, wave select, weights, topk outputs, scratch layout, the
+// checks of D, C, k and tau -- is select_common.h, one copy for this operator and launch_knn_labels.
 int launch_normalize_tokens(const float* tokens, int B, int n, int D, void* planes, hipStream_t s);
 int launch_label_cells(const void* labels, int mask_kind, int OH, int OW, int hp, int wp, int C, float* seg, hipStream_t s);
 long long propagate_scratch_bytes(int hp, int wp, int n_ctx, int k);
@@ -406,8 +408,9 @@ int launch_propagate(const void* target_planes, const void* const* ctx_planes, c
 // dinoseg_op_knn_labels).  Queries are the planes of launch_normalize_tokens for B frames of n cells; the bank is planes
 // [2][bank_rows][D] with M live rows and soft fp32 [bank_rows, C] (kind 0) or hard uint8 [bank_rows] (kind 1) labels.
 // launch_knn_labels: the scores launch (one workgroup per 64 queries and bank range, per-query lists of k in LDS) and the merge launch
-// (the ranges' lists, weights, gathers).  knn_splits: the library's number of ranges; knn_scratch_bytes: 8 S N k (splits 0 = the
-// library's choice); both host only, -1 for refusable arguments.  No atomics; every refusal is on the host.
+// (the ranges' lists, weights, gathers), the selection being select_common.h's.  knn_splits: the library's number of ranges;
+// knn_scratch_bytes: 8 S N k (splits 0 = the library's choice); both host only, -1 for refusable arguments.  No atomics; every
+// refusal is on the host.
 int knn_splits(int N, int M, int k);
 long long knn_scratch_bytes(int N, int M, int k, int splits);
 int launch_knn_labels(const void* query_planes, int B, int n, const void* bank_planes, long long M, long long bank_rows,

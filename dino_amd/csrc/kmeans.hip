@@ -336,10 +336,7 @@ bool km_shape_ok(long long B, long long n, int K, int D) {
 }
 
 int km_shape_check(const char* who, int B, int n, int K, int D) {
-    if (D < 64 || D % 64 != 0 || D > 8192) {
-        dinoseg_set_error("%s: width D = %d (a multiple of 64 up to 8192)", who, D);
-        return -1;
-    }
+    if (pair_width_check(who, D)) return -1;
     if (K < 1 || K > DINOSEG_KMEANS_MAX_K) {
         dinoseg_set_error("%s: K = %d centroids (1 <= K <= %d)", who, K, DINOSEG_KMEANS_MAX_K);
         return -1;

@@ -181,10 +181,7 @@ int nc_launch_graph(const char* who, int max_cells, const void* planes, int B, i
         dinoseg_set_error("%s: null pointer", who);
         return -1;
     }
-    if (D < 64 || D % 64 != 0 || D > 8192) {
-        dinoseg_set_error("%s: width D = %d (a multiple of 64 up to 8192)", who, D);
-        return -1;
-    }
+    if (pair_width_check(who, D)) return -1;
     if (nc_cells_check(who, B, n, max_cells, NC_FITS) || nc_grid_check(who, B, n)) return -1;
     if (!std::isfinite(tau) || !(tau > -1.0 && tau < 1.0)) {
         dinoseg_set_error("%s: tau = %g (finite, inside (-1, 1))", who, tau);

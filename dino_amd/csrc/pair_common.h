@@ -1,6 +1,7 @@
 // The split-plane pair walk of the feature-space operators, shared by propagate.hip (propagate_scores_kernel), knn.hip
-// (knn_scores_kernel), kmeans.hip (kmeans_assign_kernel) and ncut.hip (ncut_graph_kernel), and the small pieces of the unit-row planes they all read: ONE copy of
-// the staging, the slice order and the fragment reads, so all of them form <x_q, x_k> by the same arithmetic bit for bit.
+// (knn_scores_kernel), kmeans.hip (kmeans_assign_kernel) and ncut.hip (ncut_graph_kernel), and the small pieces of the unit-row planes
+// they all read: ONE copy of the staging, the slice order and the fragment reads, so all of them form <x_q, x_k> by the same arithmetic
+// bit for bit.  What propagate.hip and knn.hip do with the scores -- the top-k selection -- is select_common.h, on top of this header.
 //
 // The family's geometry: one workgroup of 4 waves owns 64 query rows and walks key rows in blocks of 64.  Rows are unit rows scaled
 // by 2^10 and split into fp16 hi + lo planes (split_unit); a plane's row is D halves, D a multiple of 64.  Per block and 64-wide
@@ -20,19 +21,17 @@ constexpr int PAIR_STAGE = 32768;               // the four panes: 64 rows x 128
 constexpr int PAIR_QHI = 0, PAIR_QLO = 8192, PAIR_KHI = 16384, PAIR_KLO = 24576;
 constexpr float PAIR_UNSCALE = 0x1p-20f;        // planes carry 2^10 x: products are 2^20 <x_q, x_k>
 
+// the widths the walk takes: whole slices of 64 halves, a row offset inside int
+inline int pair_width_check(const char* who, int D) {
+    if (D < 64 || D % 64 != 0 || D > 8192) {
+        dinoseg_set_error("%s: width D = %d (a multiple of 64 up to 8192)", who, D);
+        return -1;
+    }
+    return 0;
+}
+
 // the total order of the selections: score descending, index ascending
 __device__ __forceinline__ bool better(float s, int i, float s2, int i2) { return s > s2 || (s == s2 && i < i2); }
-
-// (score, g) as one unsigned key whose order is the total order: larger = earlier.  0 = no candidate.
-__device__ __forceinline__ unsigned long long prp_key(float s, int g) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, s);
-    const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)o << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)g);
-}
-__device__ __forceinline__ float prp_key_score(unsigned long long key) {
-    const uint32_t o = (uint32_t)(key >> 32);
-    return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
 
 // v = hi + lo in fp16 (v: a unit row's component scaled by 2^10, so that lo stays clear of the fp16 subnormals)
 struct UnitSplit {

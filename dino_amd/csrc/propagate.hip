@@ -10,24 +10,18 @@
 //                             pixel: a broadcast), integer counts, no atomics; seg_0 = count / pixels of the cell.
 //   propagate_scores_kernel   one workgroup (4 waves) per (8 x 8 query tile, context frame).  The tile's key window is the tile widened
 //                             by R cells and clipped to the grid (32 x 32 keys at R = 12), walked in blocks of 64 keys by the family's
-//                             pair walk (pair_common.h); wave (qh, kh) multiplies keys 32 kh .. by queries 32 qh .. : lo.hi + hi.lo +
-//                             hi.hi into one accumulator.  Every (key, query) element of an MFMA goes through the same arithmetic, so
-//                             a score depends on the two rows alone.  A lane owns one query and 16 keys of the block: the
-//                             neighbourhood test in integers, then an insertion into the lane's own sorted list of k (score, g) in
-//                             LDS ([slot][thread]: conflict-free), gated by the list's last entry in registers.  At the end 64
-//                             threads merge the 4 lists of their query (4-way, the total order) into the scratch: [n_ctx][n][k]
-//                             scores and indices.  LDS: 32 KiB + 2 KiB k <= 64 KiB; no atomics; every loop bound is a function of
-//                             the shapes.
-//   propagate_merge_kernel    one wave per query: the n_ctx k <= 256 candidates sit 4 to a lane as 64-bit keys (order-preserving score
-//                             bits, then ~g), k rounds of a wave maximum select rank 0 .. K'-1; weights, W, 1 / W are wave-uniform;
-//                             lanes stride the C classes with k gathers and fmaf each.
+//                             pair walk (pair_common.h); wave (qh, kh) multiplies keys 32 kh .. by queries 32 qh .. .  Every (key,
+//                             query) element of an MFMA goes through the same arithmetic, so a score depends on the two rows alone.
+//                             A lane owns one query and 16 keys of the block: the neighbourhood test in integers, then the key is a
+//                             candidate for the selection of select_common.h (the slice body, the per-lane lists of k (score, g) in
+//                             LDS, the 4-way merge into the scratch: [n_ctx][n][k] scores, then indices).  LDS: 32 KiB + 2 KiB k <=
+//                             64 KiB; no atomics; every loop bound is a function of the shapes.
+//   propagate_merge_kernel    one wave per query: the wave select of select_common.h over the n_ctx k <= 256 candidates; lanes
+//                             stride the C classes with k gathers and fmaf each.
 #include "../../include/dinoseg.h"
 #include "common.h"
 #include "kernels.h"
-#include "pair_common.h"
-
-#include <climits>
-#include <cmath>
+#include "select_common.h"
 
 namespace dseg {
 
@@ -35,7 +29,7 @@ namespace {
 
 constexpr int PRP_TILE = 8;                     // query tile side, 64 queries
 constexpr int PRP_MAX_SIDE = 4096;              // grid side: n <= 2^24, 16 n < 2^31
-constexpr int PRP_EMPTY = INT_MAX;              // g of an empty list slot (score -inf): after every candidate in the total order
+static_assert(DINOSEG_PROPAGATE_MAX_K <= SEL_MAX_K, "the selection's k");
 
 __global__ __launch_bounds__(256) void normalize_tokens_kernel(const float* __restrict__ tokens, long long rows, int n, int D,
                                                                uint16_t* __restrict__ planes) {
@@ -94,8 +88,6 @@ struct PrpCtx {
 __global__ __launch_bounds__(256) void propagate_scores_kernel(const uint16_t* __restrict__ tq, PrpCtx ctx, int hp, int wp, int D, int R,
                                                                int k, int tiles_x, float* __restrict__ cand_s, int* __restrict__ cand_g) {
     extern __shared__ __attribute__((aligned(16))) char prp_lds[];
-    float* ls = reinterpret_cast<float*>(prp_lds + PAIR_STAGE);          // [k][256] scores of the lanes' lists, best first
-    int* lg = reinterpret_cast<int*>(prp_lds + PAIR_STAGE + k * 1024);   // [k][256] their global indices
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
     const int qh = wave >> 1, kh = wave & 1;
     const int n = hp * wp, ci = blockIdx.y;
@@ -107,14 +99,7 @@ __global__ __launch_bounds__(256) void propagate_scores_kernel(const uint16_t* _
     const int nkb = (nkeys + 63) >> 6;
     const uint16_t* kp = ctx.planes[ci];
 
-    for (int s = 0; s < k; ++s) {
-        ls[s * 256 + tid] = -INFINITY;
-        lg[s * 256 + tid] = PRP_EMPTY;
-    }
-    float* my_ls = ls + tid;                                            // the lane's own list: slot s at [s * 256]
-    int* my_lg = lg + tid;
-    float thr_s = -INFINITY;                                            // the list's last entry: what a candidate must beat
-    int thr_g = PRP_EMPTY;
+    SelLists lists = sel_lists(prp_lds, k);
 
     // the lane's query in the selection
     const int qi = qh * 32 + lr, qr = r0 + (qi >> 3), qc = c0 + (qi & 7);
@@ -135,15 +120,8 @@ __global__ __launch_bounds__(256) void propagate_scores_kernel(const uint16_t* _
     };
 
     f32x16 acc;
-    auto zero = [&]() {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    };
-    auto slice = [&](bf16x8 qhi, bf16x8 qlo, bf16x8 khi, bf16x8 klo) {
-        acc = mfma32f<FMT_FP16>(klo, qhi, acc);
-        acc = mfma32f<FMT_FP16>(khi, qlo, acc);
-        acc = mfma32f<FMT_FP16>(khi, qhi, acc);
-    };
+    auto zero = [&]() { sel_zero(acc); };
+    auto slice = [&](bf16x8 qhi, bf16x8 qlo, bf16x8 khi, bf16x8 klo) { sel_slice(acc, qhi, qlo, khi, klo); };
     // the block's scores: register r of this lane is key acc_row(r, lh) of the wave's half, query lr
     auto select = [&](int kb) {
         if (!qvalid) return;
@@ -153,49 +131,17 @@ __global__ __launch_bounds__(256) void propagate_scores_kernel(const uint16_t* _
             if (w >= nkeys) continue;
             const int wr = w / ww, kr = wr0 + wr, kc = wc0 + (w - wr * ww);
             if (abs(kr - qr) > R || abs(kc - qc) > R) continue;
-            const float s = acc[r] * PAIR_UNSCALE + 0.f;                // (+ 0: a negative zero becomes the positive one)
-            const int g = ci * n + kr * wp + kc;
-            if (!better(s, g, thr_s, thr_g)) continue;
-            int pos = k - 1;                                            // the last entry leaves
-            while (pos > 0) {
-                const float ps = my_ls[(pos - 1) * 256];
-                const int pg = my_lg[(pos - 1) * 256];
-                if (!better(s, g, ps, pg)) break;
-                my_ls[pos * 256] = ps;
-                my_lg[pos * 256] = pg;
-                --pos;
-            }
-            my_ls[pos * 256] = s;
-            my_lg[pos * 256] = g;
-            thr_s = my_ls[(k - 1) * 256];
-            thr_g = my_lg[(k - 1) * 256];
+            sel_insert(lists, sel_score(acc[r]), ci * n + kr * wp + kc);
         }
     };
     pair_walk(prp_lds, tq, (size_t)n * D, qrow, kp, (size_t)n * D, nkb, D >> 6, key_row, [](int) {}, zero, slice, select);
     __syncthreads();
-    // 4-way merge of the query's lists (waves (qh, 0) and (qh, 1), both lane halves) under the total order
+    // thread q merges the lists of the tile's query q into the frame's slots of the scratch
     if (tid < 64) {
-        const int q = tid, r = r0 + (q >> 3), c = c0 + (q & 7);
+        const int r = r0 + (tid >> 3), c = c0 + (tid & 7);
         if (r < hp && c < wp) {
-            const int t0 = ((q >> 5) * 2) * 64 + (q & 31), t1 = t0 + 32, t2 = t0 + 64, t3 = t0 + 96;
-            int p0 = 0, p1 = 0, p2 = 0, p3 = 0;
             const size_t out = ((size_t)ci * n + (size_t)r * wp + c) * k;
-            for (int i = 0; i < k; ++i) {
-                // (a list's head index reaches k only after k picks from it: the loop has ended by then)
-                float bs = ls[p0 * 256 + t0];
-                int bg = lg[p0 * 256 + t0], which = 0;
-                const float s1 = ls[p1 * 256 + t1], s2 = ls[p2 * 256 + t2], s3 = ls[p3 * 256 + t3];
-                const int g1 = lg[p1 * 256 + t1], g2 = lg[p2 * 256 + t2], g3 = lg[p3 * 256 + t3];
-                if (better(s1, g1, bs, bg)) { bs = s1; bg = g1; which = 1; }
-                if (better(s2, g2, bs, bg)) { bs = s2; bg = g2; which = 2; }
-                if (better(s3, g3, bs, bg)) { bs = s3; bg = g3; which = 3; }
-                p0 += which == 0;
-                p1 += which == 1;
-                p2 += which == 2;
-                p3 += which == 3;
-                cand_s[out + i] = bs;
-                cand_g[out + i] = bg == PRP_EMPTY ? -1 : bg;
-            }
+            sel_merge4(lists, tid, cand_s + out, cand_g + out);
         }
     }
 }
@@ -203,66 +149,22 @@ __global__ __launch_bounds__(256) void propagate_scores_kernel(const uint16_t* _
 __global__ __launch_bounds__(256) void propagate_merge_kernel(const float* __restrict__ cand_s, const int* __restrict__ cand_g, PrpCtx ctx,
                                                               int n, int n_ctx, int k, int C, float a, float* __restrict__ seg_out,
                                                               int32_t* __restrict__ topk_idx, float* __restrict__ topk_w) {
-    __shared__ float sel_w[4][DINOSEG_PROPAGATE_MAX_K];
-    __shared__ int sel_g[4][DINOSEG_PROPAGATE_MAX_K];
+    __shared__ SelPicks picks;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q = blockIdx.x * 4 + wave;
-    const bool valid = q < n;
-    int kept = 0;
-    float W = 0.f;
-    if (valid) {
-        unsigned long long key[4];
-        const int ncand = n_ctx * k;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = lane + 64 * j;
-            key[j] = 0;
-            if (e < ncand) {
-                const int ci = e / k, i = e - ci * k;
-                const size_t at = ((size_t)ci * n + q) * k + i;
-                const int g = cand_g[at];
-                if (g >= 0) key[j] = prp_key(cand_s[at], g);
-            }
-        }
-        float s0 = 0.f;
-        for (int i = 0; i < k; ++i) {
-            unsigned long long m = key[0];
-#pragma unroll
-            for (int j = 1; j < 4; ++j) m = key[j] > m ? key[j] : m;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const unsigned long long other = __shfl_xor(m, o);
-                m = other > m ? other : m;
-            }
-            if (m == 0) break;                                          // K' = i candidates in all (wave-uniform)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) key[j] = key[j] == m ? 0 : key[j];   // (g is unique: exactly one slot of one lane)
-            const float s = prp_key_score(m);
-            if (i == 0) s0 = s;
-            const float w = __builtin_amdgcn_exp2f((s - s0) * a);
-            W += w;
-            if (lane == 0) {
-                sel_w[wave][i] = w;
-                sel_g[wave][i] = (int)(0xFFFFFFFFu - (uint32_t)m);
-            }
-            kept = i + 1;
-        }
-    }
+    const SelSum sum = sel_wave_select(cand_s, cand_g, n_ctx, n, q, k, a, picks, [](int, int) {});
     __syncthreads();
-    if (!valid) return;
-    const float inv = __fdiv_rn(1.f, W);
+    if (q >= n) return;
+    const float inv = sel_inv(sum.W);
     for (int c = lane; c < C; c += 64) {
         float v = 0.f;
-        for (int i = 0; i < kept; ++i) {
-            const int g = sel_g[wave][i], ci = g / n, j = g - ci * n;
-            v = __builtin_fmaf(sel_w[wave][i], ctx.segs[ci][(size_t)j * C + c], v);
+        for (int i = 0; i < sum.kept; ++i) {
+            const int g = picks.g[wave][i], ci = g / n, j = g - ci * n;
+            v = __builtin_fmaf(picks.w[wave][i], ctx.segs[ci][(size_t)j * C + c], v);
         }
         seg_out[(size_t)q * C + c] = v * inv;
     }
-    if (lane < k) {
-        if (topk_idx) topk_idx[(size_t)q * k + lane] = lane < kept ? sel_g[wave][lane] : -1;
-        if (topk_w) topk_w[(size_t)q * k + lane] = lane < kept ? sel_w[wave][lane] * inv : 0.f;
-    }
+    sel_write_topk(picks, sum.kept, inv, q, k, topk_idx, topk_w);
 }
 
 int prp_grid_check(const char* who, int hp, int wp) {
@@ -328,7 +230,7 @@ long long propagate_scratch_bytes(int hp, int wp, int n_ctx, int k) {
     if (hp < 1 || wp < 1 || hp > PRP_MAX_SIDE || wp > PRP_MAX_SIDE || n_ctx < 1 || n_ctx > DINOSEG_PROPAGATE_MAX_CONTEXT || k < 1 ||
         k > DINOSEG_PROPAGATE_MAX_K)
         return -1;
-    return (long long)n_ctx * hp * wp * k * 8;                          // fp32 scores, then int32 indices, [n_ctx][n][k] each
+    return sel_scratch_bytes(n_ctx, (long long)hp * wp, k);
 }
 
 int launch_propagate(const void* target_planes, const void* const* ctx_planes, const float* const* ctx_segs, int n_ctx, int hp, int wp,
@@ -361,41 +263,21 @@ int launch_propagate(const void* target_planes, const void* const* ctx_planes, c
         return -1;
     }
     if (prp_grid_check(who, hp, wp)) return -1;
-    if (D < 64 || D % 64 != 0 || D > 8192) {
-        dinoseg_set_error("%s: width D = %d (a multiple of 64 up to 8192)", who, D);
-        return -1;
-    }
-    if (C < 1 || C > 256) {
-        dinoseg_set_error("%s: C = %d classes (1 <= C <= 256)", who, C);
-        return -1;
-    }
-    if (k < 1 || k > DINOSEG_PROPAGATE_MAX_K) {
-        dinoseg_set_error("%s: k = %d (1 <= k <= %d)", who, k, DINOSEG_PROPAGATE_MAX_K);
-        return -1;
-    }
+    if (sel_shape_check(who, D, C, k, DINOSEG_PROPAGATE_MAX_K)) return -1;
     if (radius < 0) {
         dinoseg_set_error("%s: radius %d (>= 0)", who, radius);
         return -1;
     }
-    if (!(std::isfinite(tau) && tau > 0.0)) {
-        dinoseg_set_error("%s: temperature %g (finite and positive)", who, tau);
-        return -1;
-    }
-    const float a = (float)(1.4426950408889634074 / tau);
-    if (!std::isfinite(a)) {
-        dinoseg_set_error("%s: temperature %g is too small (log2(e) / tau exceeds fp32)", who, tau);
-        return -1;
-    }
+    float a;
+    if (sel_temperature(who, tau, &a)) return -1;
     const int n = hp * wp;
     const int R = radius > PRP_MAX_SIDE ? PRP_MAX_SIDE : radius;         // (beyond the grid's side the window is the whole grid)
     const int tiles_x = (wp + PRP_TILE - 1) / PRP_TILE, tiles_y = (hp + PRP_TILE - 1) / PRP_TILE;
-    float* cand_s = reinterpret_cast<float*>(scratch);
-    int* cand_g = reinterpret_cast<int*>(cand_s + (size_t)n_ctx * n * k);
-    const size_t lds = PAIR_STAGE + (size_t)k * 2048;
-    hipLaunchKernelGGL(propagate_scores_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n_ctx), dim3(256), lds, s,
-                       reinterpret_cast<const uint16_t*>(target_planes), ctx, hp, wp, D, R, k, tiles_x, cand_s, cand_g);
+    const SelScratch c = sel_scratch(scratch, n_ctx, n, k);
+    hipLaunchKernelGGL(propagate_scores_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n_ctx), dim3(256), sel_lds_bytes(k), s,
+                       reinterpret_cast<const uint16_t*>(target_planes), ctx, hp, wp, D, R, k, tiles_x, c.cand_s, c.cand_g);
     DSEG_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(propagate_merge_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, cand_s, cand_g, ctx, n, n_ctx, k, C, a,
+    hipLaunchKernelGGL(propagate_merge_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, c.cand_s, c.cand_g, ctx, n, n_ctx, k, C, a,
                        seg_out, topk_idx, topk_w);
     DSEG_CHECK_HIP(hipGetLastError());
     return 0;

@@ -13,23 +13,12 @@ from tests import arch_util as A
 from tests import knn_util as K
 from tests import pair_probe_util as PP
 from tests import propagate_util as P
+from tests.test_propagate_gpu import by_key, dev, normalize, run_propagate
 
 pytestmark = pytest.mark.gpu
 S = capi.stream_ptr
 TAU = K.TAU
 UNDECIDED_CAP = 0.04
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a)).cuda()
-
-
-def normalize(tokens):
-    """tokens: device fp32 [B, 1 + n, D] -> planes fp16 [B, 2, n, D]"""
-    B, n1, D = tokens.shape
-    planes = torch.empty((B, 2, n1 - 1, D), dtype=torch.float16, device="cuda")
-    capi.check(capi.lib().dinoseg_op_normalize_tokens(tokens.data_ptr(), B, n1 - 1, D, planes.data_ptr(), S()))
-    return planes
 
 
 def scratch_bytes(N, M, k, splits):
@@ -72,12 +61,6 @@ def reference(i):
     B, n, M, rows, D, C, k, kind = K.CASES[i]
     qp, bp, labels = device_case(i)
     return K.knn_host(qp.cpu().numpy(), bp.cpu().numpy(), M, labels.cpu().numpy(), kind, C, k, TAU)
-
-
-def by_key(g, v):
-    """rows of v reordered by ascending g (a selection as a set with its values)"""
-    order = np.argsort(g, axis=1, kind="stable")
-    return np.take_along_axis(g, order, axis=1), np.take_along_axis(v, order, axis=1)
 
 
 @pytest.mark.parametrize("i", range(len(K.CASES)), ids=K.case_id)
@@ -179,6 +162,36 @@ def test_exact_ties_go_to_the_lower_row(cuda, k):
         assert np.array_equal(idx[clear], g_host[clear]), "with clear gaps even the rank order is the host's"
         bar = P.value_bar(D, k, TAU, 1.0)
         assert np.abs(seg[clear].astype(np.float64) - V_host[clear]).max() <= bar
+
+
+@pytest.mark.parametrize("splits", [1, None], ids=["one", "cap"])
+@pytest.mark.parametrize("n_ctx,k", [(1, 1), (2, 5), (3, 16)])
+def test_whole_frame_propagation_is_knn_over_the_context_rows(cuda, n_ctx, k, splits):
+    """With the whole frame as neighbourhood, dinoseg_op_propagate is dinoseg_op_knn_labels over the context frames' rows laid end to
+    end: g = ci n + cell is the bank row, the stacked segs are the soft labels, and order, weights and gather are one piece of code
+    (csrc/select_common.h).  seg_out, topk_idx and topk_w agree as bits, at one range and at the most the bank allows.  9 x 11 cells:
+    a ragged second query tile here, ragged 8 x 8 tiles there, two key blocks per frame.  Context frame 1 is a copy of frame 0, so
+    every query meets exact ties, which both break towards the lower index."""
+    hp, wp, D, C, R = 9, 11, 64, 7, 12
+    n = hp * wp
+    M = n_ctx * n
+    rng = np.random.default_rng(470 + n_ctx)
+    tok_c = rng.standard_normal((n_ctx, n + 1, D)).astype(np.float32)
+    if n_ctx >= 2:
+        tok_c[1] = tok_c[0]
+    tq = normalize(dev(rng.standard_normal((1, n + 1, D)).astype(np.float32)))       # [1, 2, n, D]: knn's query planes as they are
+    cp = normalize(dev(tok_c))                                                       # [n_ctx, 2, n, D]
+    segs = dev(rng.random((n_ctx, n, C)).astype(np.float32))
+    bank = cp.permute(1, 0, 2, 3).reshape(2, M, D).contiguous()                      # the hi planes of all frames, then the lo planes
+    want = run_propagate(tq[0], [cp[c] for c in range(n_ctx)], [segs[c] for c in range(n_ctx)], hp, wp, R, k, tau=TAU)
+    got = run_knn(tq, bank, M, segs.view(M, C), C, k, tau=TAU, splits=splits or K.split_cap(M, k))
+    for name, a, b in zip(("seg_out", "topk_idx", "topk_w"), got[:3], want):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), name
+    if n_ctx >= 2:                                                      # the ties were met: a twin follows its lower copy at once
+        idx = got[1].cpu().numpy()
+        assert not np.any((idx[:, 0] >= n) & (idx[:, 0] < 2 * n))
+        low = idx[:, 0] < n
+        assert low.any() and np.array_equal(idx[low, 1], idx[low, 0] + n)
 
 
 def test_integer_planes_select_and_score_exactly(cuda):

@@ -1,12 +1,13 @@
-"""GPU box: a sha256 of every output of the feature-space operators (csrc/propagate.hip, kmeans.hip, ncut.hip, ncut_split.hip) on
-seeded inputs, one line per output, for a byte comparison of two builds of the library (a change to the shared pair walk of
-csrc/pair_common.h or to the pass pieces of csrc/ncut_common.h must not move a bit):
+"""GPU box: a sha256 of every output of the feature-space operators (csrc/propagate.hip, knn.hip, kmeans.hip, ncut.hip,
+ncut_split.hip) on seeded inputs, one line per output, for a byte comparison of two builds of the library (a change to the shared pair
+walk of csrc/pair_common.h, to the selection of csrc/select_common.h or to the pass pieces of csrc/ncut_common.h must not move a bit):
     DINOSEG_LIB=<build A>/libdinoseg_hip.so python tools/feature_digest.py > a.txt
     python tools/feature_digest.py > b.txt && cmp a.txt b.txt
-The shapes and inputs are the CASES of tests/test_propagate_gpu.py, CASES x KINDS of tests/test_kmeans_gpu.py and PARAMS of
-tests/test_ncut_gpu.py, and one ragged shape for the two row kernels; the whole run takes a few seconds.
+The shapes and inputs are the CASES of tests/test_propagate_gpu.py and tests/knn_util.py, CASES x KINDS of tests/test_kmeans_gpu.py
+and PARAMS of tests/test_ncut_gpu.py, and one ragged shape for the two row kernels; the whole run takes a few seconds.
   normalize_tokens   planes; kmeans_init: centroids, planes (with and without the normalisation)
   propagate          the candidate scores and indices left in the scratch, seg, topk_idx, topk_w
+  knn_labels         the same five, at the library's number of ranges (splits 0) and at one range
   kmeans_assign      assign, best, scores, objective, moved and the tile records left in the scratch
   kmeans_update      centroids, planes, counts and the partial sums and counts left in the scratch
   ncut_graph         words, degree
@@ -20,7 +21,9 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tests import knn_util as KU  # noqa: E402
 from tests import test_kmeans_gpu as K  # noqa: E402
+from tests import test_knn_gpu as KN  # noqa: E402
 from tests import test_ncut_gpu as NC  # noqa: E402
 from tests import test_ncut_split_gpu as NS  # noqa: E402
 from tests import test_propagate_gpu as P  # noqa: E402
@@ -58,6 +61,20 @@ for i, case in enumerate(P.CASES):
     seg, idx, w = P.run_propagate(tq, cp, sg, hp, wp, R, k, out=out)
     cand = out[3].view(torch.int32).view(2, n_ctx, n, k)                # fp32 scores, then int32 indices
     show(f"propagate/{ident(case)}", ("cand_scores", "cand_idx", "seg", "topk_idx", "topk_w"), (cand[0], cand[1], seg, idx, w))
+
+# ------------------------------------------------------------------------------------------------ k-NN retrieval
+for i, case in enumerate(KU.CASES):
+    B, n, M, rows, D, C, k, kind = case
+    N = B * n
+    qp, bp, labels = KN.device_case(i)
+    for splits in (0, 1):
+        out = (torch.empty((N, C), dtype=torch.float32, device="cuda"), torch.empty((N, k), dtype=torch.int32, device="cuda"),
+               torch.empty((N, k), dtype=torch.float32, device="cuda"),
+               torch.zeros((KN.scratch_bytes(N, M, k, splits),), dtype=torch.uint8, device="cuda"))
+        seg, idx, w, scratch = KN.run_knn(qp, bp, M, labels, C, k, splits=splits, out=out)
+        cand = scratch.view(torch.int32).view(2, -1, N, k)              # fp32 scores, then int32 indices, [S][N][k] each
+        show(f"knn_labels/{ident(case)}/splits{splits}", ("cand_scores", "cand_idx", "seg", "topk_idx", "topk_w"),
+             (cand[0], cand[1], seg, idx, w))
 
 # ------------------------------------------------------------------------------------------------ k-means
 for i, case in enumerate(K.CASES):
