@@ -2,7 +2,8 @@
 import contextlib
 
 from .augment import Augmenter, augment_table, draw_reference_augment  # noqa: F401
-from .dinoseg import ClusterResult, ComponentsResult, DINOSeg, DiscoverResult, KnnResult, LabelPropagator, MaskCutResult, MemoryBank, NcutResult, context_frames, dense_nll_loss, get_transforms, ncut_start, sample_indices, view_sizes, window_origins  # noqa: F401
+from .dinoseg import ClusterResult, ComponentsResult, DINOSeg, DiscoverResult, KnnResult, LabelPropagator, MaskCutResult, MemoryBank, NcutResult, PCAFitter, context_frames, dense_nll_loss, get_transforms, ncut_start, sample_indices, view_sizes, window_origins  # noqa: F401
+from .pca import FeaturePCA, pca_solve  # noqa: F401
 from .weights import VIT_B8, VIT_B16, VIT_S8, VIT_S16, ViTConfig, procedural_state_dict  # noqa: F401
 
 
@@ -47,4 +48,4 @@ def options(**kw):
                 set_option(key, value)
 
 
-__all__ = ["DINOSeg", "ClusterResult", "NcutResult", "ComponentsResult", "DiscoverResult", "MaskCutResult", "LabelPropagator", "context_frames", "Augmenter", "augment_table", "draw_reference_augment", "dense_nll_loss", "get_transforms", "ncut_start", "sample_indices", "view_sizes", "window_origins", "ViTConfig", "VIT_S8", "VIT_B8", "VIT_S16", "VIT_B16", "procedural_state_dict", "set_option", "get_option", "options"]
+__all__ = ["DINOSeg", "ClusterResult", "NcutResult", "ComponentsResult", "DiscoverResult", "MaskCutResult", "LabelPropagator", "PCAFitter", "FeaturePCA", "pca_solve", "context_frames", "Augmenter", "augment_table", "draw_reference_augment", "dense_nll_loss", "get_transforms", "ncut_start", "sample_indices", "view_sizes", "window_origins", "ViTConfig", "VIT_S8", "VIT_B8", "VIT_S16", "VIT_B16", "procedural_state_dict", "set_option", "get_option", "options"]

@@ -187,6 +187,13 @@ SIGNATURES = {
     "dinoseg_knn_splits": (_i32, [_i32, _i32, _i32]),
     "dinoseg_op_knn_labels": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _f64, _i32, _fp, _fp, _fp, _vp,
                                         _vp]),
+    # PCA of patch features: the scratch size and the number of row ranges (host only), the streaming moments (two launches), the
+    # projection into the token layout, the three-colour map
+    "dinoseg_pca_scratch_bytes": (_i64, [_i32, _i32, _i32]),
+    "dinoseg_pca_ranges": (_i32, [_i64, _i32]),
+    "dinoseg_op_token_moments": (C.c_int, [_fp, _vp, _i32, _i32, _i32, _fp, _vp, _vp, _vp, _vp, _vp]),
+    "dinoseg_op_pca_project": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _fp, _fp, _i32, _fp, _vp]),
+    "dinoseg_op_pca_colour": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _fp, _fp, _vp, _i32, _i32, _vp, _vp]),
     # spherical k-means over patch features: the scratch size (host only), centroid rows -> unit rows + planes, one assignment pass
     # (scores on request, objective and moved slots), one centroid update
     "dinoseg_kmeans_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),

@@ -687,6 +687,28 @@ extern "C" int dinoseg_op_knn_labels(const void* query_planes, int32_t B, int32_
                              topk_idx, topk_w, scratch, reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int64_t dinoseg_pca_scratch_bytes(int32_t B, int32_t n, int32_t D) { return pca_scratch_bytes(B, n, D); }
+
+extern "C" int32_t dinoseg_pca_ranges(int64_t rows, int32_t D) {
+    return rows >= 1 && rows <= (1ll << 31) - 256 && D >= 64 && D <= 1024 && D % 64 == 0 ? pca_ranges(rows, D) : -1;
+}
+
+extern "C" int dinoseg_op_token_moments(const float* tokens, const uint8_t* keep, int32_t B, int32_t n, int32_t D, const float* shift,
+                                        double* sum, double* outer, int64_t* count, void* scratch, void* stream) {
+    return launch_token_moments(tokens, keep, B, n, D, shift, sum, outer, reinterpret_cast<long long*>(count), scratch,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_pca_project(const float* tokens, int32_t B, int32_t n, int32_t D, const float* mean, const float* basis,
+                                      const float* scale, int32_t q, float* out, void* stream) {
+    return launch_pca_project(tokens, B, n, D, mean, basis, scale, q, out, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dinoseg_op_pca_colour(const float* comps, int32_t B, int32_t hp, int32_t wp, int32_t q, const float* lo, const float* inv,
+                                     const uint8_t* keep, int32_t OH, int32_t OW, uint8_t* rgb, void* stream) {
+    return launch_pca_colour(comps, B, hp, wp, q, lo, inv, keep, OH, OW, rgb, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int64_t dinoseg_kmeans_scratch_bytes(int32_t B, int32_t n, int32_t K, int32_t D) { return kmeans_scratch_bytes(B, n, K, D); }
 
 extern "C" int dinoseg_op_kmeans_init(const float* rows, int32_t K, int32_t D, int32_t normalize, float* centroids, void* planes,

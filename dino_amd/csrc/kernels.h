@@ -417,6 +417,21 @@ int launch_knn_labels(const void* query_planes, int B, int n, const void* bank_p
                       const void* bank_labels, int label_kind, int D, int C, int k, double tau, int splits, float* seg_out,
                       int32_t* topk_idx, float* topk_w, void* scratch, hipStream_t s);
 
+// PCA of patch features (pca.hip; the rules: include/dinoseg.h, dinoseg_op_token_moments).  Tokens are fp32 [B, 1 + n, D] as
+// dinoseg_features_hw writes them, the CLS row skipped.  launch_token_moments: the partials launch (one wave per (tile pair or sum
+// tile, range) on the fp32-input MFMA) and the finalising launch (ranges added in order in fp64, the mirror written, the accumulators
+// added to).  pca_ranges: R(B n, D); pca_scratch_bytes: 4 R (4096 pairs + D + 1), host only, -1 for refusable arguments.
+// launch_pca_project: centred rows times basis^T into the token layout [B, 1 + n, q], the CLS rows zero.  launch_pca_colour: three
+// components -> scaled, enlarged with the family's tile walk, clamped, uint8 [B, OH, OW, 3].  No atomics; every refusal is on the host.
+int pca_ranges(long long N, int D);
+long long pca_scratch_bytes(int B, int n, int D);
+int launch_token_moments(const float* tokens, const uint8_t* keep, int B, int n, int D, const float* shift, double* sum, double* outer,
+                         long long* count, void* scratch, hipStream_t s);
+int launch_pca_project(const float* tokens, int B, int n, int D, const float* mean, const float* basis, const float* scale, int q, float* out,
+                       hipStream_t s);
+int launch_pca_colour(const float* comps, int B, int hp, int wp, int q, const float* lo, const float* inv, const uint8_t* keep, int OH,
+                      int OW, uint8_t* rgb, hipStream_t s);
+
 // Spherical k-means over patch features (kmeans.hip; the rule: include/dinoseg.h, dinoseg_op_kmeans_assign).  Points are the planes of
 // launch_normalize_tokens for B frames of n cells, clustered jointly; centroids are fp32 [K, D] rows plus planes [2][K][D].
 // launch_kmeans_init: fp32 rows -> (unit) fp32 rows and their planes.  launch_kmeans_assign: the assign launch (scores on MFMAs, the

@@ -421,10 +421,11 @@ def _temperature(temperature) -> float:
 
 
 def knn_plan(patch: int, embed_dim: int, x: torch.Tensor, bank_size: int, bank_dim: int, bank_classes: int, bank_blocks: int,
-             n_blocks=None, topk=10, temperature=0.1, size=None, chunk=32) -> KnnPlan:
+             n_blocks=None, topk=10, temperature=0.1, size=None, chunk=32, project=None) -> KnnPlan:
     """The shape and parameter checks of ``DINOSeg.segment_knn`` without a device.  ``x`` is the batch (uint8 [B,H,W,3] or fp32
     [B,3,H,W], H and W multiples of the patch size); ``bank_size``, ``bank_dim``, ``bank_classes`` and ``bank_blocks`` are the
     bank's live rows, row width, classes and the ``n_blocks`` its features were taken after; ``n_blocks=None`` is the bank's.
+    ``project`` is the bank's ``FeaturePCA`` when it has one: its rows then have the projection's width, not the model's.
     Every ``ValueError`` is raised here, before any device use."""
     if not isinstance(x, torch.Tensor):
         raise ValueError(f"expected the frames as a tensor, uint8 [B,H,W,3] or fp32 [B,3,H,W], got {type(x).__name__}")
@@ -435,7 +436,11 @@ def knn_plan(patch: int, embed_dim: int, x: torch.Tensor, bank_size: int, bank_d
     temperature = _temperature(temperature)
     if int(bank_size) < 1:
         raise ValueError("the memory bank is empty: add labelled frames first")
-    if int(bank_dim) != int(embed_dim):
+    if project is not None:
+        pca_projection(project, embed_dim, "the memory bank's projection", bank=True, blocks=bank_blocks)
+        if int(bank_dim) != project.q:
+            raise ValueError(f"the memory bank holds rows of width {bank_dim}, its projection has {project.q} components")
+    elif int(bank_dim) != int(embed_dim):
         raise ValueError(f"the memory bank holds rows of width {bank_dim}, the model's embed_dim is {embed_dim}")
     if n_blocks is not None and int(n_blocks) != int(bank_blocks):
         raise ValueError(f"the memory bank was filled with n_blocks = {bank_blocks}, the call asks for n_blocks = {n_blocks}")
@@ -705,3 +710,101 @@ def maskcut_plan(patch: int, x: torch.Tensor, max_objects=3, tau=0.2, eps=1e-5, 
     if plan.hp > COMPONENTS_MAX_SIDE or plan.wp > COMPONENTS_MAX_SIDE:
         raise ValueError(f"the patch grid {(plan.hp, plan.wp)} exceeds {COMPONENTS_MAX_SIDE} (COMPONENTS_MAX_SIDE) along a side")
     return MaskCutPlan(plan, max_objects, int(connectivity))
+
+
+# ---- PCA of patch features (include/dinoseg.h: dinoseg_op_token_moments, dinoseg_op_pca_project, dinoseg_op_pca_colour) ----
+PCA_MAX_Q = 256                # include/dinoseg.h: DINOSEG_PCA_MAX_Q, the components dinoseg_op_pca_project takes
+PCA_MAX_SIDE = 16384           # an output side of dinoseg_op_pca_colour
+
+
+class PcaPlan(NamedTuple):
+    """What a PCA call (``PCAFitter.update``, ``pca_fit``, ``pca_project``, ``pca_map``, a projected ``MemoryBank``) was asked for,
+    validated: the frames' layout, the patch grid, the components, whether a ``keep`` mask came, the blocks the features are taken
+    after, the chunk, the output size and the colour range (``None``: the call's own minimum / maximum)."""
+    kind: int
+    B: int
+    H: int
+    W: int
+    hp: int
+    wp: int
+    q: int
+    keep: bool
+    n_blocks: int
+    chunk: int
+    OH: int
+    OW: int
+    lo: Optional[Tuple[float, float, float]]
+    hi: Optional[Tuple[float, float, float]]
+
+
+def _colour_range(v, what: str) -> Optional[Tuple[float, float, float]]:
+    if v is None:
+        return None
+    try:
+        if isinstance(v, (torch.Tensor, np.ndarray)):
+            v = v.tolist()
+        vals = [float(v)] * 3 if isinstance(v, (int, float)) else [float(t) for t in v]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a number or three numbers, got {v!r}") from None
+    if len(vals) != 3 or not all(math.isfinite(t) for t in vals):
+        raise ValueError(f"{what} must be a finite number or three of them, got {v!r}")
+    return (vals[0], vals[1], vals[2])
+
+
+def pca_projection(pca, embed_dim: int, what: str = "pca", bank: bool = False, blocks=None):
+    """The checks of a fitted projection handed to a call: a ``FeaturePCA`` of the model's width with at most ``PCA_MAX_Q``
+    components; for a memory bank (``bank``) a number of components that is a multiple of 64, the width the similarity operators
+    take; ``blocks``, when given, must be the projection's ``n_blocks``."""
+    from .pca import FeaturePCA
+    if not isinstance(pca, FeaturePCA):
+        raise ValueError(f"{what} must be a FeaturePCA, got {type(pca).__name__}")
+    if pca.dim != int(embed_dim):
+        raise ValueError(f"{what} was fitted on features of width {pca.dim}, the model's embed_dim is {embed_dim}")
+    if not 1 <= pca.q <= PCA_MAX_Q:
+        raise ValueError(f"{what} has {pca.q} components, the projection takes 1..{PCA_MAX_Q}")
+    if bank and pca.q % 64 != 0:
+        raise ValueError(f"a memory bank's projection needs a number of components that is a multiple of 64, got q = {pca.q}")
+    if blocks is not None and int(blocks) != pca.n_blocks:
+        raise ValueError(f"{what} was fitted with n_blocks = {pca.n_blocks}, the call asks for n_blocks = {blocks}")
+    return pca
+
+
+def pca_plan(patch: int, embed_dim: int, max_blocks: int, x: torch.Tensor, q=None, keep=None, n_blocks=0, chunk=32, pca=None,
+             size=None, lo=None, hi=None, colour: bool = False) -> PcaPlan:
+    """The shape and parameter checks of the PCA calls without a device.  ``x`` is the batch (uint8 [B,H,W,3] or fp32 [B,3,H,W], H
+    and W multiples of the patch size).  Fitting: ``q`` components (1 .. min(``PCA_MAX_Q``, ``embed_dim``); ``None`` for an
+    ``update``, which takes none), ``keep`` a bool / uint8 [B, n] mask, ``n_blocks`` in 0 .. ``max_blocks``.  Projecting: ``pca`` a
+    ``FeaturePCA`` of the model's width, ``n_blocks`` ``None`` or the projection's.  ``colour``: at least three components, ``size``
+    at least the patch grid with sides up to ``PCA_MAX_SIDE``, ``lo`` / ``hi`` ``None`` or finite numbers.  Every ``ValueError`` is
+    raised here, before any device use."""
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"expected the frames as a tensor, uint8 [B,H,W,3] or fp32 [B,3,H,W], got {type(x).__name__}")
+    kind, B, H, W = frame_layout(x, patch, multiple=True, one_patch=True, non_empty=True)
+    hp, wp = H // patch, W // patch
+    n = hp * wp
+    chunk = _int_in(chunk, 1, 1 << 20, "chunk")
+    if pca is not None:
+        pca_projection(pca, embed_dim, blocks=n_blocks)
+        n_blocks, q = pca.n_blocks, pca.q
+    else:
+        n_blocks = _int_in(n_blocks, 0, int(max_blocks), "n_blocks")
+        if q is not None:
+            q = _int_in(q, 1, min(PCA_MAX_Q, int(embed_dim)), "q")
+    if keep is not None:
+        if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != (B, n):
+            raise ValueError(f"keep must be a bool or uint8 mask [B = {B}, n = {n}], got "
+                             f"{getattr(keep, 'dtype', type(keep).__name__)} {tuple(getattr(keep, 'shape', ()))}")
+    try:
+        OH, OW = out_size(size, (H, W))
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be a pair (OH, OW), got {size!r}") from None
+    if colour:
+        if q is None or q < 3:
+            raise ValueError(f"a colour map needs at least 3 components, the projection has {q}")
+        if OH < hp or OW < wp:
+            raise ValueError(f"size {(OH, OW)} is smaller than the patch grid {(hp, wp)}")
+        if OH > PCA_MAX_SIDE or OW > PCA_MAX_SIDE:
+            raise ValueError(f"size {(OH, OW)} exceeds {PCA_MAX_SIDE} along a side")
+    lo, hi = _colour_range(lo, "lo"), _colour_range(hi, "hi")
+    return PcaPlan(kind, int(B), int(H), int(W), hp, wp, 0 if q is None else int(q), keep is not None, int(n_blocks), chunk, OH, OW,
+                   lo, hi)

@@ -19,8 +19,9 @@ from torch import nn
 
 from . import capi
 from .dense_plan import (_pair, bank_add_plan, components_plan, context_frames, dense_mode, frame_layout, guide_plan, guided_params, kmeans_plan, knn_plan, label_size,
-                         maskcut_plan, multiscale_plan, ncut_plan, ncut_start, out_size, propagate_plan, refine_params, refine_plan,
+                         maskcut_plan, multiscale_plan, ncut_plan, ncut_start, out_size, pca_plan, pca_projection, propagate_plan, refine_params, refine_plan,
                          resolution_message, sample_indices, view_sizes, window_origins, window_plan)  # noqa: F401  (view_sizes, window_origins: re-exported)
+from .pca import FeaturePCA, pca_solve
 from .preprocess import resize_linear_u8
 from .weights import VIT_B8, VIT_B16, VIT_S8, VIT_S16, ViTConfig
 
@@ -860,22 +861,24 @@ class DINOSeg(nn.Module):
         temperature)`` (the rule: include/dinoseg.h, dinoseg_op_knn_labels); the bilinear enlargement of that soft map to ``size``
         (default the frames' own) with the first maximum gives ``labels``.  The [B n, M] score matrix is never formed.  The
         backbone runs in batches of ``chunk`` frames, each followed by one operator call and one enlargement; ``B = 1`` is the
-        camera's streaming form.  ``n_blocks``, when given, must be the bank's.  No training and no head weight: a row added to
-        the bank takes effect in the next call.  Inference only."""
+        camera's streaming form.  ``n_blocks``, when given, must be the bank's.  A bank built with ``project`` has its
+        ``FeaturePCA`` applied to the tokens (``dinoseg_op_pca_project``) before they are normalised, and the search runs at the
+        projection's width.  No training and no head weight: a row added to the bank takes effect in the next call.  Inference
+        only."""
         if not isinstance(bank, MemoryBank):
             raise ValueError(f"bank must be a MemoryBank, got {type(bank).__name__}")
         plan = knn_plan(self.cfg.patch, self.cfg.embed_dim, x, bank.size, bank.dim, bank.n_classes, bank.n_blocks, n_blocks, topk,
-                        temperature, size, chunk)
+                        temperature, size, chunk, bank.project)
         self._require_gpu()
         x = self._to_device(x, plan.kind)
-        lib, n, D, k = capi.lib(), plan.hp * plan.wp, self.cfg.embed_dim, plan.topk
+        lib, n, D, k = capi.lib(), plan.hp * plan.wp, bank.dim, plan.topk
         labels = torch.empty((plan.B, plan.OH, plan.OW), dtype=torch.int32, device=self.device)
         seg = torch.empty((plan.B if want_seg else min(plan.chunk, plan.B), n, plan.C), dtype=torch.float32, device=self.device)
         idx = torch.empty((plan.B, n, k), dtype=torch.int32, device=self.device) if want_idx else None
         planes = torch.empty((min(plan.chunk, plan.B), 2, n, D), dtype=torch.float16, device=self.device)
         scratch = None
         for c0 in range(0, plan.B, plan.chunk):
-            tokens = self.features(x[c0:c0 + plan.chunk], plan.n_blocks)
+            tokens = bank._rows(self.features(x[c0:c0 + plan.chunk], plan.n_blocks), n)
             Bc = tokens.shape[0]
             nbytes = lib.dinoseg_knn_scratch_bytes(Bc * n, plan.M, k, 0)
             if nbytes < 0:
@@ -891,6 +894,77 @@ class DINOSeg(nn.Module):
             capi.check(lib.dinoseg_op_upsample_argmax(seg_c.data_ptr(), Bc, plan.hp, plan.wp, plan.C, plan.OH, plan.OW,
                                                       labels[c0:].data_ptr(), None, self._stream()))
         return KnnResult(labels, seg if want_seg else None, idx)
+
+    # ---- PCA of patch features: moments, projection, colour map (csrc/pca.hip; the solve: pca.py) ----
+    @torch.no_grad()
+    def pca_fit(self, x: torch.Tensor, q: int = 3, keep: Optional[torch.Tensor] = None, n_blocks: int = 0, chunk: int = 32) -> FeaturePCA:
+        """The PCA of the patch features of ``x`` (uint8 [B,H,W,3] or fp32 [B,3,H,W], H and W multiples of the patch size): the
+        ``q`` leading components of the final-norm patch tokens after ``n_blocks`` blocks (0 = all), over the cells ``keep`` (bool /
+        uint8 [B, n]) keeps -> ``FeaturePCA``.  Exactly one ``PCAFitter`` fed ``x`` in batches of ``chunk`` frames: the moments
+        are accumulated on the device (``dinoseg_op_token_moments``), the [D, D] eigen-problem is solved on the host
+        (``pca_solve``).  Nothing of the size of the features leaves the device.  Inference only."""
+        pca_plan(self.cfg.patch, self.cfg.embed_dim, self.cfg.n_blocks, x, q, keep, n_blocks, chunk)
+        fitter = PCAFitter(self, n_blocks)
+        fitter.update(x, keep, chunk)
+        return fitter.solve(q)
+
+    def _pca_components(self, x: torch.Tensor, plan, pca: FeaturePCA, whiten: bool) -> torch.Tensor:
+        """The projection of every frame in the token layout fp32 [B, 1 + n, q] (the CLS rows zero): the backbone in batches of 32
+        frames, each projected into its slice of one buffer."""
+        n = plan.hp * plan.wp
+        mean, basis, scale = pca.on(self.device)
+        out = torch.empty((plan.B, n + 1, pca.q), dtype=torch.float32, device=self.device)
+        for c0 in range(0, plan.B, 32):
+            tokens = self.features(x[c0:c0 + 32], plan.n_blocks)
+            capi.check(capi.lib().dinoseg_op_pca_project(tokens.data_ptr(), tokens.shape[0], n, pca.dim, mean.data_ptr(), basis.data_ptr(),
+                                                         scale.data_ptr() if whiten else None, pca.q, out[c0:].data_ptr(),
+                                                         self._stream()))
+        return out
+
+    @torch.no_grad()
+    def pca_project(self, x: torch.Tensor, pca: FeaturePCA, whiten: bool = False, n_blocks: Optional[int] = None) -> torch.Tensor:
+        """The patch features of ``x`` projected onto a fitted ``FeaturePCA``: fp32 [B, n, q], ``(f - mean) @ basis.T`` in fp32
+        (the rule: include/dinoseg.h, dinoseg_op_pca_project), divided by the components' standard deviations with ``whiten``.  The
+        result is a view past the zero CLS rows of the token layout [B, 1 + n, q].  ``n_blocks``, when given, must be the
+        projection's.  Inference only."""
+        plan = pca_plan(self.cfg.patch, self.cfg.embed_dim, self.cfg.n_blocks, x, n_blocks=n_blocks, pca=pca)
+        self._require_gpu()
+        return self._pca_components(self._to_device(x, plan.kind), plan, pca, bool(whiten))[:, 1:]
+
+    @torch.no_grad()
+    def pca_map(self, x: torch.Tensor, pca: FeaturePCA, size=None, keep: Optional[torch.Tensor] = None, lo=None, hi=None) -> torch.Tensor:
+        """The three-colour map of the first three components (the DINO / DINOv2 figure): uint8 [B, OH, OW, 3], ``size`` default
+        the frames' own.  Per component ``t = (v - lo) / (hi - lo)`` is enlarged bilinearly, clamped to [0, 1] and rounded to a
+        byte in one launch (the rule: include/dinoseg.h, dinoseg_op_pca_colour); a pixel whose nearest cell ``keep`` (bool / uint8
+        [B, n]) drops is black.  ``lo`` / ``hi`` ``None`` take the call's minimum / maximum of each component over the kept cells
+        (the demo's behaviour: one reduction over [B, n, 3]); a camera passes fixed numbers (one, or three) for colours that stay
+        stable over time.  The scale is ``1 / (hi - lo)`` in fp32, and 0 -- a channel of zeros -- where ``hi <= lo``.
+        Inference only."""
+        plan = pca_plan(self.cfg.patch, self.cfg.embed_dim, self.cfg.n_blocks, x, keep=keep, n_blocks=None, pca=pca, size=size, lo=lo, hi=hi, colour=True)
+        self._require_gpu()
+        comps = self._pca_components(self._to_device(x, plan.kind), plan, pca, False)
+        keep_u8 = None if keep is None else keep.to(device=self.device, dtype=torch.uint8).contiguous()
+        lo_t, inv_t = self._pca_range(comps, keep_u8, plan.lo, plan.hi)
+        rgb = torch.empty((plan.B, plan.OH, plan.OW, 3), dtype=torch.uint8, device=self.device)
+        capi.check(capi.lib().dinoseg_op_pca_colour(comps.data_ptr(), plan.B, plan.hp, plan.wp, pca.q, lo_t.data_ptr(), inv_t.data_ptr(),
+                                                    capi.ptr(keep_u8), plan.OH, plan.OW, rgb.data_ptr(), self._stream()))
+        return rgb
+
+    def _pca_range(self, comps: torch.Tensor, keep_u8: Optional[torch.Tensor], lo, hi):
+        """(lo, inv) fp32 [3] on the device for ``dinoseg_op_pca_colour``: the given numbers, or the minimum / maximum of components
+        0 .. 2 over the kept cells; ``inv = 1 / (hi - lo)`` in fp32, 0 where ``hi <= lo`` or nothing is kept."""
+        if lo is None or hi is None:
+            v = comps[:, 1:, :3]
+            if keep_u8 is not None:
+                kept = keep_u8.bool().unsqueeze(-1)
+                v_lo, v_hi = torch.where(kept, v, float("inf")), torch.where(kept, v, float("-inf"))
+            else:
+                v_lo = v_hi = v
+        lo_t = v_lo.amin(dim=(0, 1)) if lo is None else torch.tensor(lo, dtype=torch.float32, device=self.device)
+        hi_t = v_hi.amax(dim=(0, 1)) if hi is None else torch.tensor(hi, dtype=torch.float32, device=self.device)
+        span = hi_t - lo_t
+        ok = torch.isfinite(span) & (span > 0) & torch.isfinite(lo_t)
+        return torch.where(ok, lo_t, 0.0).contiguous(), torch.where(ok, 1.0 / span, 0.0).contiguous()
 
     # ---- unsupervised segmentation: spherical k-means over patch features (csrc/kmeans.hip) ----
     def _point_planes(self, x: torch.Tensor, plan, n_blocks: int) -> torch.Tensor:
@@ -1941,6 +2015,69 @@ class LabelPropagator:
         return labels, (seg.clone() if self.want_seg else None)
 
 
+# --------------------------------------------------------------------------- PCA of patch features (streaming fit)
+class PCAFitter:
+    """The streaming fit of a PCA of patch features: ``PCAFitter(model, n_blocks=0)``, any number of ``update(frames, keep=None,
+    chunk=32)`` calls (frames uint8 [B,H,W,3] or fp32 [B,3,H,W], any H x W of patch multiples per call; ``keep`` bool / uint8
+    [B, n]) and ``solve(q)`` -> ``FeaturePCA``.  The state is the device accumulators of ``dinoseg_op_token_moments``: ``sum`` fp64
+    [D], ``outer`` fp64 [D, D], ``count`` int64 and the fp32 ``shift`` [D]; no token outlives its chunk.  The shift is fixed by
+    the first chunk that has a kept row: the fp32 column mean of its kept rows, from a sums-only moments call (null shift, null
+    outer) and one small read.  This is the shifted-data algorithm: the solve's ``sum sum^T / count`` then removes a small
+    remainder, not the features' large common mean."""
+
+    def __init__(self, model: DINOSeg, n_blocks: int = 0):
+        if isinstance(n_blocks, bool) or not isinstance(n_blocks, (int, np.integer)) or not 0 <= n_blocks <= model.cfg.n_blocks:
+            raise ValueError(f"n_blocks must be an integer in 0..{model.cfg.n_blocks}, got {n_blocks!r}")
+        self.model, self.n_blocks = model, int(n_blocks)
+        self.shift = self.sum = self.outer = self.count = None
+        self._scratch = None
+
+    def _moments(self, tokens, keep, n, shift, sum_, outer, count) -> None:
+        lib, D, Bc = capi.lib(), self.model.cfg.embed_dim, tokens.shape[0]
+        nbytes = lib.dinoseg_pca_scratch_bytes(Bc, n, D)
+        if nbytes < 0:
+            raise capi.DinosegError(f"dinoseg_pca_scratch_bytes refused B = {Bc}, n = {n}, D = {D}")
+        if self._scratch is None or self._scratch.numel() < nbytes:
+            self._scratch = torch.empty((nbytes,), dtype=torch.uint8, device=self.model.device)
+        capi.check(lib.dinoseg_op_token_moments(tokens.data_ptr(), capi.ptr(keep), Bc, n, D, capi.ptr(shift), sum_.data_ptr(),
+                                                capi.ptr(outer), count.data_ptr(), self._scratch.data_ptr(), self.model._stream()))
+
+    @torch.no_grad()
+    def update(self, frames: torch.Tensor, keep: Optional[torch.Tensor] = None, chunk: int = 32) -> int:
+        """Add the kept patch rows of ``frames`` to the moments -> the number of rows taken (``keep`` is counted where it lives: a
+        host mask costs no device synchronisation, a device mask one small read)."""
+        model = self.model
+        plan = pca_plan(model.cfg.patch, model.cfg.embed_dim, model.cfg.n_blocks, frames, keep=keep, n_blocks=self.n_blocks, chunk=chunk)
+        model._require_gpu()
+        x = model._to_device(frames, plan.kind)
+        dev, D, n = model.device, model.cfg.embed_dim, plan.hp * plan.wp
+        keep_u8 = None if keep is None else keep.to(device=dev, dtype=torch.uint8).contiguous()
+        taken = plan.B * n if keep is None else int(keep.ne(0).sum().item())
+        if self.sum is None:
+            self.sum = torch.zeros((D,), dtype=torch.float64, device=dev)
+            self.outer = torch.zeros((D, D), dtype=torch.float64, device=dev)
+            self.count = torch.zeros((1,), dtype=torch.int64, device=dev)
+        for c0 in range(0, plan.B, plan.chunk):
+            tokens = model.features(x[c0:c0 + plan.chunk], self.n_blocks)
+            keep_c = None if keep_u8 is None else keep_u8[c0:c0 + plan.chunk]
+            if self.shift is None:
+                s0 = torch.zeros((D,), dtype=torch.float64, device=dev)
+                n0 = torch.zeros((1,), dtype=torch.int64, device=dev)
+                self._moments(tokens, keep_c, n, None, s0, None, n0)
+                rows = int(n0.item())                                                   # the one small read
+                if rows == 0:
+                    continue
+                self.shift = (s0 / rows).to(torch.float32)
+            self._moments(tokens, keep_c, n, self.shift, self.sum, self.outer, self.count)
+        return taken
+
+    def solve(self, q: int) -> FeaturePCA:
+        """The ``FeaturePCA`` of the rows taken so far (``pca_solve`` on the accumulators read back)."""
+        if self.shift is None:
+            raise ValueError("a PCA needs at least 2 rows, got count = 0")
+        return pca_solve(self.sum.cpu(), self.outer.cpu(), int(self.count.item()), self.shift.cpu(), int(q), self.n_blocks)
+
+
 # --------------------------------------------------------------------------- few-shot segmentation (k-NN from a memory bank)
 class KnnResult(NamedTuple):
     """What ``DINOSeg.segment_knn`` returns: pixel labels int32 [B, OH, OW], and when asked for the soft map fp32 [B, n, C] and the
@@ -1955,9 +2092,13 @@ class MemoryBank:
     n_blocks=0)`` allocates, once, the unit rows as fp16 hi + lo planes [2, capacity, D] and the label store (soft fp32 [capacity,
     n_classes], or with ``hard=True`` one uint8 per row, 255 = void, hence at most 255 classes); rows 0 .. ``size`` - 1 are live.
     ``add`` fills it in place, ``clear`` empties it, ``state_dict`` / ``load_state_dict`` carry it bit for bit (with ``frames``, the
-    number of frames added, which ``per_frame`` seeds count from).  Rows are never evicted or replaced."""
+    number of frames added, which ``per_frame`` seeds count from).  Rows are never evicted or replaced.  ``project``, a
+    ``FeaturePCA`` whose number of components is a multiple of 64 and whose ``n_blocks`` is the bank's, makes the rows the unit
+    PROJECTED features: ``dim`` is then its ``q``, ``add`` and ``segment_knn`` project the tokens before they normalise them, and
+    the state carries the projection.  Without it every call runs the launches it ran before."""
 
-    def __init__(self, model: DINOSeg, n_classes: int, capacity: int, hard: bool = False, n_blocks: int = 0):
+    def __init__(self, model: DINOSeg, n_classes: int, capacity: int, hard: bool = False, n_blocks: int = 0,
+                 project: Optional[FeaturePCA] = None):
         for what, v, hi in (("n_classes", n_classes, 256), ("capacity", capacity, 1 << 24)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= hi:
                 raise ValueError(f"{what} must be an integer in 1..{hi}, got {v!r}")
@@ -1965,9 +2106,12 @@ class MemoryBank:
             raise ValueError(f"n_blocks must be an integer in 0..{model.cfg.n_blocks}, got {n_blocks!r}")
         if hard and int(n_classes) > 255:
             raise ValueError("a hard bank stores void as 255, so it holds at most 255 classes; use soft labels for 256")
+        if project is not None:
+            pca_projection(project, model.cfg.embed_dim, "project", bank=True, blocks=int(n_blocks))
         model._require_gpu()
         self.model, self.n_classes, self.capacity, self.hard, self.n_blocks = model, int(n_classes), int(capacity), bool(hard), int(n_blocks)
-        self.dim = model.cfg.embed_dim
+        self.project = project
+        self.dim = model.cfg.embed_dim if project is None else project.q
         self.planes = torch.zeros((2, self.capacity, self.dim), dtype=torch.float16, device=model.device)
         self.labels = torch.full((self.capacity,), 255, dtype=torch.uint8, device=model.device) if self.hard else \
             torch.zeros((self.capacity, self.n_classes), dtype=torch.float32, device=model.device)
@@ -1977,6 +2121,17 @@ class MemoryBank:
     def clear(self) -> None:
         self.size = 0
         self.frames = 0
+
+    def _rows(self, tokens: torch.Tensor, n: int) -> torch.Tensor:
+        """The rows the bank compares, in the token layout: the backbone's tokens, or with ``project`` their projection
+        (``dinoseg_op_pca_project``: fp32 [B, 1 + n, q], the CLS rows zero)."""
+        if self.project is None:
+            return tokens
+        mean, basis, _ = self.project.on(self.model.device)
+        out = torch.empty((tokens.shape[0], n + 1, self.dim), dtype=torch.float32, device=self.model.device)
+        capi.check(capi.lib().dinoseg_op_pca_project(tokens.data_ptr(), tokens.shape[0], n, self.project.dim, mean.data_ptr(),
+                                                     basis.data_ptr(), None, self.dim, out.data_ptr(), self.model._stream()))
+        return out
 
     @torch.no_grad()
     def add(self, frames: torch.Tensor, labels: torch.Tensor, per_frame: Optional[int] = None, seed: int = 0) -> int:
@@ -1996,7 +2151,7 @@ class MemoryBank:
         seg = torch.empty((n, C_), dtype=torch.float32, device=model.device)
         classes = torch.arange(C_, device=model.device)
         for c0 in range(0, p.B, 32):
-            tokens = model.features(x[c0:c0 + 32], self.n_blocks)
+            tokens = self._rows(model.features(x[c0:c0 + 32], self.n_blocks), n)
             for i in range(tokens.shape[0]):
                 b = c0 + i
                 capi.check(lib.dinoseg_op_normalize_tokens(tokens[i].data_ptr(), 1, n, D, planes.data_ptr(), model._stream()))
@@ -2017,8 +2172,11 @@ class MemoryBank:
         return p.rows
 
     def state_dict(self) -> dict:
-        return {"planes": self.planes.clone(), "labels": self.labels.clone(), "size": self.size, "frames": self.frames,
-                "n_classes": self.n_classes, "hard": self.hard, "n_blocks": self.n_blocks}
+        state = {"planes": self.planes.clone(), "labels": self.labels.clone(), "size": self.size, "frames": self.frames,
+                 "n_classes": self.n_classes, "hard": self.hard, "n_blocks": self.n_blocks}
+        if self.project is not None:
+            state["project"] = self.project.state_dict()
+        return state
 
     def load_state_dict(self, state: dict) -> None:
         planes, labels = state["planes"], state["labels"]
@@ -2027,6 +2185,14 @@ class MemoryBank:
                 tuple(labels.shape) != tuple(self.labels.shape) or labels.dtype != self.labels.dtype or \
                 not 0 <= int(state["size"]) <= self.capacity:
             raise ValueError("the state is not that of a bank with this one's capacity, width, n_classes, hard and n_blocks")
+        if ("project" in state) != (self.project is not None):
+            raise ValueError("the state and this bank do not agree on whether the rows are projected")
+        if self.project is not None:
+            project = pca_projection(FeaturePCA.from_state_dict(state["project"]), self.model.cfg.embed_dim, "the state's projection",
+                                     bank=True, blocks=self.n_blocks)
+            if project.q != self.dim:
+                raise ValueError(f"the state's projection has {project.q} components, this bank's rows have width {self.dim}")
+            self.project = project
         self.planes.copy_(planes)
         self.labels.copy_(labels)
         self.size, self.frames = int(state["size"]), int(state.get("frames", 0))

@@ -536,6 +536,64 @@ int dinoseg_op_knn_labels(const void* query_planes, int32_t B, int32_t n, const 
                           const void* bank_labels, int32_t label_kind, int32_t D, int32_t C, int32_t k, double tau, int32_t splits,
                           float* seg_out, int32_t* topk_idx, float* topk_w, void* scratch, void* stream);
 
+/* ---- PCA of patch features: streaming moments, projection onto a basis and the three-colour feature map (the DINO / DINOv2 figure;
+ * the dimensionality reduction STEGO, "Deep ViT Features" and Hummingbird put in front of clustering and retrieval).  No reference
+ * counterpart.  pca.hip.  The eigen-decomposition is the host's (dino_amd.pca_solve); these are the three device operators around it.
+ *
+ * Notation: tokens are fp32 [B][1 + n][D] as dinoseg_features_hw writes them; row 0 of every frame is the CLS row and is skipped, as
+ * dinoseg_op_normalize_tokens skips it.  D is a multiple of 64 in 64 .. 1024.  Patch row p = b n + c (frame b, cell c), p in
+ * 0 .. N - 1, N = B n.  Every product sum is v_mfma_f32_32x32x2_f32, which is bit for bit the fp32 fmaf chain in k order, so the
+ * rules below are exact to restate.
+ *
+ * dinoseg_op_token_moments: the sufficient statistics of a PCA, added to the caller's accumulators so that a data set is fitted chunk
+ * by chunk.
+ *   keep  : uint8 [B][n], nullable; a row with keep == 0 does not take part.   shift : fp32 [D], nullable = zeros.
+ *   sum   : fp64 [D];   outer : fp64 [D][D], nullable (sums and count only);   count : int64 [1].  All three are ADDED to.
+ * 1. The point.  c_p[d] = fp32(x_p[d] - shift[d]): one fp32 subtraction.  A row that is not kept has c_p = +0 in every column.
+ * 2. Ranges.  ALL N patch rows, kept or not, are cut by position into R ranges of L = ceil(N / R) consecutive rows: range r is
+ *    rows r L .. min((r + 1) L, N) - 1 (trailing ranges may be empty).  R = dinoseg_pca_ranges(N, D) =
+ *    max(1, min(64, ceil(N / 128), ceil(2048 / P))) with T = D / 64 column tiles and P = T (T + 1) / 2 tile pairs: a function of N
+ *    and D alone, never of the mask, so no compaction pass is needed.
+ * 3. Partials.  Per range, part_outer[d][e] = the fp32 chain acc = fmaf(c_p[d], c_p[e], acc) over the range's rows in ascending
+ *    order from +0 (rows not kept add +0 products); part_sum[d] = the fp32 chain acc = acc + c_p[d] likewise.  Only tile pairs
+ *    with d / 64 <= e / 64 are computed.
+ * 4. Totals.  total = the partials added in range order in fp64 from 0; outer[d][e] += total for d <= e, and the SAME total is added
+ *    to outer[e][d]: an outer that starts symmetric stays exactly symmetric.  sum[d] += its total.  count += the kept rows (exact).
+ * Bounds, per element: |outer's increment - exact sum_p c_p[d] c_p[e]| <= (L + 16) 2^-24 sum_p |c_p[d] c_p[e]|, and
+ * |sum's increment - exact| <= (L + 16) 2^-24 sum_p |c_p[d]|.  No atomics, no synchronisation between workgroups beyond the two
+ * kernel boundaries; two runs agree bit for bit.  scratch: dinoseg_pca_scratch_bytes(B, n, D) = 4 R (4096 P + D + 1) bytes (host only,
+ * -1 for refusable arguments; dinoseg_pca_ranges likewise): the ranges' partials, nothing of size N D.
+ *
+ * dinoseg_op_pca_project: y[p][j] = the fp32 chain acc = fmaf(fp32(x_p[d] - mean[d]), basis[j][d], acc) over d ascending from +0,
+ * multiplied once by scale[j] when scale is given (whitening).
+ *   mean : fp32 [D];  basis : fp32 [q][D], q in 1 .. 256;  scale : fp32 [q], nullable;  out : fp32 [B][1 + n][q], the token layout
+ * with row 0 of every frame written as zeros, so that dinoseg_op_normalize_tokens(out, B, n, q, ...) takes it unchanged when q is a
+ * multiple of 64 and dinoseg_op_pca_colour reads it.  A row's result depends on that row alone: B frames in one call or one by one
+ * agree bit for bit.  |y - the fp64 value| <= (D + 16) 2^-24 sum_d |c[d] basis[j][d]|, times |scale[j]| when scale is given.
+ *
+ * dinoseg_op_pca_colour: components 0 .. 2 of comps (fp32 [B][1 + hp wp][q], q >= 3, as dinoseg_op_pca_project writes them) to
+ * rgb uint8 [B][OH][OW][3] in one launch, 3 bytes per pixel written, no [B, 3, OH, OW] fp32 tensor.
+ *   lo, inv : fp32 [3] on the device;  keep : uint8 [B][hp wp], nullable.
+ * Per cell and channel t = (v - lo_c) inv_c, one subtraction and one multiplication in fp32; t is enlarged bilinearly with the exact
+ * integer coordinates and the arithmetic of dinoseg_op_upsample_argmax (a + (b - a) lambda by fmaf along x, then along y); then
+ * t = min(max(t, 0), 1) (a NaN becomes 0), byte = (uint8) rintf(255 t) (ties to even).  A pixel whose nearest cell
+ * ((oy hp) / OH, (ox wp) / OW), the rule of dinoseg_op_guide_cells, is not kept becomes (0, 0, 0).  OH >= hp, OW >= wp, sides up to
+ * 16384.  Two runs agree bit for bit.
+ *
+ * Refused on the host (-1, the message names the entry) before anything is launched: null required pointers; D not a multiple of 64
+ * in 64 .. 1024; q outside 1 .. 256, or below 3 for the colour entry; non-positive sizes; B n above 2^31 - 256; an output smaller
+ * than the grid or a side above 16384; tokens, shift, mean, basis or scratch not 16-byte aligned; sum, outer or count not 8-byte
+ * aligned; scale, out, comps, lo or inv not 4-byte aligned.  Stream-ordered, no host synchronisation, no allocation. */
+#define DINOSEG_PCA_MAX_Q 256
+int64_t dinoseg_pca_scratch_bytes(int32_t B, int32_t n, int32_t D);
+int32_t dinoseg_pca_ranges(int64_t rows, int32_t D);
+int dinoseg_op_token_moments(const float* tokens, const uint8_t* keep, int32_t B, int32_t n, int32_t D, const float* shift, double* sum,
+                             double* outer, int64_t* count, void* scratch, void* stream);
+int dinoseg_op_pca_project(const float* tokens, int32_t B, int32_t n, int32_t D, const float* mean, const float* basis, const float* scale,
+                           int32_t q, float* out, void* stream);
+int dinoseg_op_pca_colour(const float* comps, int32_t B, int32_t hp, int32_t wp, int32_t q, const float* lo, const float* inv,
+                          const uint8_t* keep, int32_t OH, int32_t OW, uint8_t* rgb, void* stream);
+
 /* ---- unsupervised segmentation: spherical k-means over patch features (the k-means baseline of STEGO and of "Deep ViT Features as
  * Dense Visual Descriptors": cluster the patch tokens of a batch or clip, get segments whose ids mean the same in every frame).  No
  * reference counterpart: the reference trains on hand-labelled frames.  kmeans.hip.
